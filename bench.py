@@ -12,7 +12,10 @@ The learned FlowFormer layers are not part of the step (their source and weights
 N > 1: one process per GPU (torch.distributed / RCCL), each rank owns independent sequence(s) (weak scaling);
 the only collective is one all_gather of the per-frame poses (+ timestamps + track lengths) at the end of the timed region.
 
-Besides the contract's fields the JSON line carries
+A plain run (``--gpus 1 --steps N --warmup W``) sets up, warms up, times the N steps and prints the line: metric, value, unit,
+higher_is_better, dtype, ms_per_step, the host figures of the timed pass and the configuration.  ``--dump-outputs DIR`` also writes
+what the last timed step computed (poses, solver info, keypoints, lookup tokens) as DIR/<name>.npy.  Everything else is measured only
+with ``--full``, which fills these fields of the line (null without it):
   roofline      dominant kernel (cost-volume GEMM): algorithmic FLOPs / HIP-event launch time, measured on its stream
   cpu_baseline  oracle/pipeline.py (torch-CPU ops shaped like the reference) on a bounded sample, N = 1 only
   parity        free-running HIP track vs the oracle's on the same frames: keypoints, per-frame pose diff, RTE
@@ -43,6 +46,7 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0
 PEAK_HBM_GBS = 8000.0
 MIN_TIMED_LAUNCHES = 200       # the roofline average is taken over at least this many GEMM launches
 RAMP_SECONDS = 1.5             # untimed sustained load before the contract's warm-up: clocks ramp, queues are created
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together
 
 
 def parse_args():
@@ -94,6 +98,12 @@ def parse_args():
     ap.add_argument("--share-gpu", action="store_true",
                     help="TEST ONLY (N > 1 ranks on a 1-GPU box): every rank drives device 0 and the collectives run over gloo — real kernels, real gather_tracks, real "
                          "core pinning, no RCCL; the line is marked and its value is not a scaling measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also measure and check everything else: HIP events around the volume GEMM (roofline, timeline), the other "
+                         "volume precisions, CPU baseline + parity, Fast-mode, configs[4], decoder-loop, patch-embedding, per-kernel, plugin-path and "
+                         "end-to-end legs (each still switchable by its own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--dry-collectives", action="store_true",
                     help="CPU-only plumbing check of the N-rank launch path: gloo backend, no kernels, synthetic tracks through the "
                          "same barrier / gather_tracks / max-over-ranks code; the line it prints is marked and is NOT a measurement")
@@ -149,6 +159,47 @@ def dry_collectives(args, rank, world) -> None:
                           "dry_collectives": True, "ranks_seen": dist.get_world_size(), "rank_ids": ids, "gather_ok": bool(ok),
                           "track_lengths": [int(x) for x in lengths]}), flush=True)
     dist.destroy_process_group()
+
+
+def last_step_outputs(res, hot) -> dict:
+    """What a caller of the timed path holds after its last step (``res``: that step's result, a list of them for lanes > 1): per lane
+    the optimised pose (fp32 and fp64), the LM solve's {loss, steps, rejects, loss0}, the surviving observation count and the selected
+    keypoints (concatenated in lane order; ``n_selected`` splits them), and the window-lookup tokens of the step's last decoder iteration."""
+    import numpy as np
+
+    lanes = res if isinstance(res, list) else [res]
+
+    def f64(t, n):
+        return np.full(n, np.nan) if t is None else t.detach().double().cpu().numpy().reshape(n)
+
+    kps = [np.zeros((0, 2)) if r.kp0_uv is None else r.kp0_uv.cpu().double().numpy().reshape(-1, 2) for r in lanes]
+    out = {"pose": np.stack([r.pose.detach().float().cpu().numpy().reshape(7) for r in lanes]),
+           "pose_f64": np.stack([f64(r.pose_f64, 7) for r in lanes]),
+           "solver_info": np.stack([f64(r.info, 4) for r in lanes]),
+           "n_valid": np.concatenate([f64(r.n_valid, 1) for r in lanes]),
+           "n_selected": np.array([float(len(k)) for k in kps]),
+           "keypoints_uv": np.concatenate(kps)}
+    if hot.last_tokens is not None:
+        out["lookup_tokens"] = hot.last_tokens.float().cpu().numpy()
+    return out
+
+
+def write_outputs(out_dir: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """``out_dir/<name>.npy`` per array: float32 stays float32, everything else becomes float64.  Smallest first, each may take an equal
+    share of what is left of ``budget``; an array larger than its share is replaced by a fixed sample of its flattened elements (the same
+    seeded indices in every run, so two runs stay comparable element for element)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].nbytes)
+    left = budget
+    for i, (name, a) in enumerate(items):
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        cap = max(left - 128 * (len(items) - i), 0) // (len(items) - i) // a.itemsize      # (128 bytes: the .npy header)
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes + 128
 
 
 def volume_work(lanes, n_q, C, esz, osz=4):
@@ -776,8 +827,9 @@ def main():
     last_period: dict = {}
     last_region: dict = {}
 
-    def measure(lanes, steps, warmup, seed, with_events, precision=None, fast=False):
-        """W untimed + K timed steps of an L-lane pipe.  Returns (elapsed s, poses, per-launch GEMM ms, launches in region)."""
+    def measure(lanes, steps, warmup, seed, with_events, precision=None, fast=False, dump_dir=None):
+        """W untimed + K timed steps of an L-lane pipe.  Returns (elapsed s, poses, per-launch GEMM ms, launches in region).
+        ``dump_dir``: write the last timed step's outputs there (:func:`last_step_outputs`)."""
         batches = lane_batches(lanes, fast)
         hot = make_pipe(lanes, seed, precision, fast=fast)
         torch.manual_seed(seed)  # the selector consumes the global CPU generator (reference behaviour) when lanes == 1
@@ -790,10 +842,18 @@ def main():
         if not args.no_ramp:   # untimed sustained load: the driver's short runs (--steps 20) would otherwise sample cold clocks
             t_end = time.perf_counter() + RAMP_SECONDS
             while time.perf_counter() < t_end:
-                for _ in hot.run(batches[(t_idx + k) % args.pool] for k in range(24)):
+                for _ in hot.run(batches[(t_idx + k) % args.pool] for k in range(args.pool)):
                     pass
-                t_idx += 24
+                t_idx += args.pool
                 torch.cuda.synchronize()
+            # the ramp's length is wall-clock bound: restart the sequence where initialize() left it (whole passes over the pool, so the
+            # previous frame is the initial one again; pose prior and permutation generators reset) - the warm-up and timed steps then
+            # compute the same values in every run with the same arguments (--dump-outputs)
+            hot.pose = torch.tensor([0, 0, 0, 0, 0, 0, 1.0], device=dev)
+            torch.manual_seed(seed)
+            if getattr(hot, "_native_seeds", False):
+                seeds = (ops.C.c_uint64 * lanes)(*[seed + l for l in range(lanes)])
+                ops.L.check(hot._lib.mv_frame_pipe_seed_lanes(hot._pipe, seeds), "mv_frame_pipe_seed_lanes")
         shape = (steps, 7) if lanes == 1 else (steps, lanes, 7)
         poses = torch.zeros(shape, dtype=torch.float32, device=dev)
         stamps = torch.arange(steps, dtype=torch.int64, device=dev) * 33_333_333   # synthetic 30 Hz frame timestamps (ns)
@@ -829,7 +889,8 @@ def main():
         # software-pipelined stream (frame t+1's frontend is queued before frame t's host randperm); K full run_pairs
         trace = []   # host time of every finished step (one perf_counter per step: where a hiccup inside the ~3.4 ms region sat is part of the line)
         h0 = (getattr(hot, "host_issue_s", 0.0), getattr(hot, "host_wait_s", 0.0), getattr(hot, "host_frames", 0))
-        for _ in hot.run((batches[(t_idx + k) % args.pool] for k in range(steps)), pose_sink=poses):
+        last = None
+        for last in hot.run((batches[(t_idx + k) % args.pool] for k in range(steps)), pose_sink=poses):
             trace.append(time.perf_counter() - t0)
         t_run = time.perf_counter() - t0
         last_host.clear()
@@ -851,6 +912,9 @@ def main():
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         gc.enable()
+        if dump_dir is not None:      # now: the result's buffers are views that the next two frames of this pipe recycle
+            write_outputs(dump_dir, last_step_outputs(last, hot))
+        del last
         last_region.clear()
         if trace:
             gaps = [b - a for a, b in zip([0.0] + trace[:-1], trace)]
@@ -919,8 +983,10 @@ def main():
         return elapsed, all_poses, ms, min(steps, len(ms))
 
     # ---- per-launch HIP events around the dominant kernel for the Python driver (launch stream = torch's current stream)
+    # the HIP events around the dominant kernel (roofline, timeline) are part of --full: a plain run times the steps alone
+    with_events = args.full and not args.no_kernel_events
     vol_events = []
-    if not native and not args.no_kernel_events:
+    if not native and with_events:
         orig_corr_volume = ops.corr_volume
 
         def timed_corr_volume(*a, **k):
@@ -933,7 +999,8 @@ def main():
 
         ops.corr_volume = timed_corr_volume
 
-    elapsed, main_poses, ms, in_region = measure(args.lanes, args.steps, args.warmup, 1234 + rank, not args.no_kernel_events)
+    elapsed, main_poses, ms, in_region = measure(args.lanes, args.steps, args.warmup, 1234 + rank, with_events,
+                                                 dump_dir=args.dump_outputs if rank == 0 else None)
     # every rank's gathered track: finite and not the zero padding (a rank that tracked nothing would show up here, not in `value`)
     rank_tracks_finite = [bool(torch.isfinite(main_poses[r]).all() and float(main_poses[r, :, 3:].abs().sum()) > 0) for r in range(main_poses.shape[0])]
     del main_poses
@@ -1031,7 +1098,7 @@ def main():
 
     # ---- the other volume precisions beside the default line: same stream, same step definition
     other_legs = None
-    if rank == 0 and world == 1 and native and args.feat_dtype == "f32" and args.volume_precision in ("f16x2", "bf16x3", "exact") and args.exact_steps > 0:
+    if args.full and rank == 0 and world == 1 and native and args.feat_dtype == "f32" and args.volume_precision in ("f16x2", "bf16x3", "exact") and args.exact_steps > 0:
         other_legs = {}
         what = {"exact": "v_mfma_f32_32x32x2_f32, bitwise an fmaf chain (the round-2 default)",
                 "bf16x3": "three bf16 pieces per operand, six products (corr_volume_split_stream<bf16x3>)",
@@ -1054,7 +1121,7 @@ def main():
 
     # ---- CPU baseline (oracle pipeline, torch-CPU ops shaped like the reference) on a bounded sample + free-running parity
     cpu_baseline = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import metrics, se3
         from oracle.pipeline import OracleHotPath
 
@@ -1168,7 +1235,7 @@ def main():
     # (Runs BEFORE the configs[4] leg: on this HIP stack a one-lane pipe — three normal-priority streams + one high-priority — created after a batched pipe —
     # two + two — has been destroyed maps two of its streams onto one hardware queue and runs 3.7x slower: 2.3 k instead of 8.4 k frames/s, profiles/r06_fast_mode.log.)
     fast_mode = None
-    if (rank == 0 and world == 1 and native and args.fast_mode_steps > 0 and args.lanes == 1 and (H, W) == (480, 640) and args.feat_dtype == "f32"
+    if (args.full and rank == 0 and world == 1 and native and args.fast_mode_steps > 0 and args.lanes == 1 and (H, W) == (480, 640) and args.feat_dtype == "f32"
             and C in (128, 256)):
         try:
             ef1 = measure(1, args.fast_mode_steps, 10, 2468, False, fast=True)[0]
@@ -1185,7 +1252,7 @@ def main():
 
     # ---- configs[4]: batch-32 frames per GPU (B = 64 pairs per GEMM) — a short second measurement, N = 1 only
     config4 = None
-    if rank == 0 and world == 1 and native and args.config4_steps > 0 and args.lanes == 1 and (H, W) == (480, 640):
+    if args.full and rank == 0 and world == 1 and native and args.config4_steps > 0 and args.lanes == 1 and (H, W) == (480, 640):
         e4, _, ms4, in4 = measure(32, args.config4_steps, 10, 4321, not args.no_kernel_events)
         config4 = {"workload": "configs[4]: batch-32 640x480 frames per GPU = 32 lanes, one cost-volume GEMM of B = 64 pairs per step",
                    "value": round(32 * args.config4_steps / e4, 2), "unit": "stereo frames/s", "steps": args.config4_steps, "warmup": 10,
@@ -1198,7 +1265,7 @@ def main():
     # ---- decoder-loop harness: the same lookups / upsamplings issued BETWEEN real PyTorch-ROCm kernels (GRU, convolutions,
     # attention of a stand-in network with the reference's loop structure, covhead.py:85-135) instead of back to back
     decoder_loop = None
-    if rank == 0 and world == 1 and not args.no_decoder_leg and args.lanes == 1 and args.feat_dtype == "f32" and args.layout == "chw":
+    if args.full and rank == 0 and world == 1 and not args.no_decoder_leg and args.lanes == 1 and args.feat_dtype == "f32" and args.layout == "chw":
         try:
             from tools.decoder_harness import DecoderLoopHarness
 
@@ -1238,18 +1305,18 @@ def main():
 
     # what RCCL actually connected: world size as the process group reports it + every rank's device (one all_gather of 2 ints)
     patch_embed = None
-    if rank == 0 and world == 1 and not args.no_decoder_leg and args.lanes == 1 and args.feat_dtype == "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_decoder_leg and args.lanes == 1 and args.feat_dtype == "f32":
         try:
             patch_embed = patch_embed_leg(ops, ops.corr_volume(frames[0].fmap1, frames[0].fmap2, layout=args.layout), dev)
         except Exception as e:  # noqa: BLE001 - a measurement leg must not take the benchmark line down
             patch_embed = {"error": repr(e)[:300]}
     kernels = plugin_path = None
-    if rank == 0 and world == 1 and not args.no_decoder_leg and args.lanes == 1:
+    if args.full and rank == 0 and world == 1 and not args.no_decoder_leg and args.lanes == 1:
         try:
             kernels = kernels_leg(ops, frames, cam, args, dev, roofline, patch_embed, n_q, C)
         except Exception as e:  # noqa: BLE001 - a measurement leg must not take the benchmark line down
             kernels = {"error": repr(e)[:300]}
-    if rank == 0 and world == 1 and args.lanes == 1 and args.plugin_frames > 0 and not args.no_cpu_baseline and args.feat_dtype == "f32":
+    if args.full and rank == 0 and world == 1 and args.lanes == 1 and args.plugin_frames > 0 and not args.no_cpu_baseline and args.feat_dtype == "f32":
         try:
             plugin_path = plugin_path_leg(cam, cfr, args.plugin_frames, args.graph)
             if plugin_path and "error" not in plugin_path and cpu_baseline and cpu_baseline.get("parts"):
@@ -1257,7 +1324,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             plugin_path = {"error": repr(e)[:300]}
     end_to_end = None
-    if rank == 0 and world == 1 and args.end_to_end_frames > 0 and args.lanes == 1 and (H, W) == (480, 640) and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.end_to_end_frames > 0 and args.lanes == 1 and (H, W) == (480, 640) and not args.no_cpu_baseline:
         try:
             end_to_end = end_to_end_leg(args.end_to_end_frames)
         except Exception as e:  # noqa: BLE001 - a measurement leg must not take the benchmark line down

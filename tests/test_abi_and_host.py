@@ -318,6 +318,34 @@ def test_bench_roofline_object_contract():
             assert abs(r["achieved"] - b16 / 1e-4 / 1e9) < 0.02 * r["achieved"] and r["unit"] == "GB/s"
 
 
+def test_bench_dump_outputs_budget_and_sampling(tmp_path):
+    """`bench.py --dump-outputs`: float32 arrays stay float32, others become float64; small arrays are written whole; an array beyond the
+    64 MB budget is replaced by a sample whose indices are the same in every run; all files together stay within the budget."""
+    import importlib.util
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_dump_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(5)
+    arrays = {"pose": rng.standard_normal((32, 7)).astype(np.float32), "keypoints_uv": rng.integers(0, 640, (6000, 2)),
+              "lookup_tokens": rng.standard_normal((64, 81, 60, 80), dtype=np.float32)}     # 99.5 MB: the 32-lane token buffer
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["keypoints_uv.npy", "lookup_tokens.npy", "pose.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BUDGET_BYTES == 64 * 10 ** 6
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert got["pose"].dtype == np.float32 and np.array_equal(got["pose"], arrays["pose"])
+    assert got["keypoints_uv"].dtype == np.float64 and np.array_equal(got["keypoints_uv"], arrays["keypoints_uv"])
+    tok = got["lookup_tokens"]
+    assert tok.dtype == np.float32 and tok.ndim == 1 and 0.9 * 16e6 < tok.size < arrays["lookup_tokens"].size
+    assert np.isin(tok[:1000], arrays["lookup_tokens"]).all()                         # a sample of the array, not other values
+    assert np.array_equal(tok, np.load(tmp_path / "b" / "lookup_tokens.npy"))          # the same sample in every run
+
+
 def test_tiled_slice_cells_host_arithmetic():
     """`mv_tiled_slice_cells(H, W)` (include/macvo_hip.h): cells of one tiled fp16 volume slice = ceil(H / 4) tile rows of W / 4 tiles of 16 cells — the slice
     height padded to a multiple of 4; 0 where the tiling does not apply (W % 4 != 0).  Pure host arithmetic: callers size operand 2 and the volume with it."""

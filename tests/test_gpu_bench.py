@@ -28,7 +28,7 @@ def test_bench_under_torch_distributed_run_world_1(gpu):
         port = so.getsockname()[1]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3", "--no-cpu-baseline"] + QUICK
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3", "--full", "--no-cpu-baseline"] + QUICK
     d = _line(subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env))
     assert d["n_gpus"] == 1 and d["ranks_seen"] == 1 and d["rank_devices"] == [0]          # the process group was RCCL with one rank
     assert d["steps"] == 12 and d["warmup"] == 3 and d["value"] > 0 and d["scaling"] == "weak"
@@ -40,7 +40,7 @@ def test_bench_under_torch_distributed_run_world_1(gpu):
 
 @pytest.mark.gpu
 def test_bench_line_parity_covers_the_kernels_it_times(gpu):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--cpu-frames", "6", "--parity-frames", "6",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--full", "--cpu-frames", "6", "--parity-frames", "6",
            "--reference-frames", "6"] + QUICK
     d = _line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT))
     par = d["parity"]
@@ -107,7 +107,7 @@ def test_bench_eight_ranks_sharing_the_gpu(gpu):
 def test_bench_fast_mode_line_checks_the_fp16_cell_kernels(gpu):
     """ADVICE r4: with ``--feat-dtype f16 --layout hwc --volume-store encoder`` the pipe runs corr_volume_h_stream<out16> and the lookup on fp16 cells;
     the line's parity block must exercise THOSE kernels (the pipe's own fp16 volume buffer and token buffer), with the fp16 bar, not the fp32 ones."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--cpu-frames", "2", "--parity-frames", "2", "--reference-frames", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--full", "--cpu-frames", "2", "--parity-frames", "2", "--reference-frames", "0",
            "--feat-dtype", "f16", "--layout", "hwc", "--volume-store", "encoder"] + QUICK
     d = _line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT))
     vl = d["parity"]["volume_and_lookups"]
@@ -121,7 +121,7 @@ def test_bench_fast_mode_line_checks_the_fp16_cell_kernels(gpu):
 def test_bench_line_carries_a_roofline_per_kernel(gpu):
     """`kernels{}` — one entry per SURVEY §8(d) kernel, measured alone (HIP events, back to back) in the run itself, with the
     algorithmic bytes / FLOPs the fractions are computed from — and the patch-embedding leg with its Fast-mode (16-bit in / out) form."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--no-cpu-baseline", "--no-ramp", "--exact-steps", "0", "--config4-steps", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-ramp", "--exact-steps", "0", "--config4-steps", "0",
            "--fast-mode-steps", "20", "--pool", "6", "--end-to-end-frames", "0", "--plugin-frames", "0"]
     d = _line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT))
     fm = d["fast_mode"]                                                  # the Fast-mode leg: fp16 features, tiled fp16-stored volume, one lane and 32
@@ -139,3 +139,34 @@ def test_bench_line_carries_a_roofline_per_kernel(gpu):
     pe = d["patch_embed"]
     assert pe["parity"]["within_bar"] and pe["fast_mode"]["tokens_equal_fp32_form_rounded_once"] and pe["fast_mode"]["hbm_GB_per_frame"] <= 0.2
     assert d["decoder_loop"]["hip_us_interleaved"]["convex_upsample"] < 25
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_the_same_outputs(gpu, tmp_path):
+    """A plain run is the headline alone (no HIP events, no extra legs: those are --full), ``--steps`` is the number of timed steps and
+    ``ms_per_step`` their mean; ``--dump-outputs`` writes the last timed step's outputs, identical in two runs with the same arguments
+    although the untimed clock ramp before the warm-up lasts a wall-clock time, not a number of frames."""
+    import numpy as np
+
+    lines = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3", "--pool", "6",
+               "--dump-outputs", str(tmp_path / d)]
+        lines.append(_line(subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)))
+    for d in lines:
+        assert d["steps"] == 12 and d["warmup"] == 3 and d["value"] > 0 and d["higher_is_better"] is True and d["unit"] == "stereo frames/s"
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1) < 1e-3                       # one lane: frames/s x ms per step
+        assert d["dtype"].startswith("f32 via f16x2")
+        for k in ("roofline", "timeline", "other_precisions", "cpu_baseline", "parity", "config4", "fast_mode", "decoder_loop", "patch_embed",
+                  "kernels", "plugin_path", "end_to_end"):
+            assert d[k] is None, k
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert files == ["keypoints_uv.npy", "lookup_tokens.npy", "n_selected.npy", "n_valid.npy", "pose.npy", "pose_f64.npy", "solver_info.npy"]
+    got = {f[:-4]: (np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in files}
+    for name, (a, b) in got.items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b, equal_nan=True), name
+    n_sel = got["n_selected"][0]
+    assert n_sel.shape == (1,) and n_sel[0] > 0 and got["keypoints_uv"][0].shape == (int(n_sel[0]), 2)
+    assert np.isfinite(got["pose"][0]).all() and got["lookup_tokens"][0].shape == (2, 81, 60, 80)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
