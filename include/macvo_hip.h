@@ -350,6 +350,32 @@ int mv_match_cov_pair(const float* depth_map0, const float* kp_uv0, float* flow_
                       float* flow_cov1, double* out_cov1, const mvMatchCovParams* params /* host */, int N,
                       mvStream_t stream);
 
+/* The other observation-covariance models of ICovariance2to3 (Module/Covariance/Project2to3.py), selected by `cov.obs.type:`.
+ *   MV_COV_MATCH  MatchCovariance (:113-191) — exactly mv_match_cov
+ *   MV_COV_GMM    GaussianMixtureCovariance (:194-262) + gaussian_mixture_mean_var (Utility/Math.py:66-93): the K x K patch is gathered
+ *                 from the depth map AND the dense depth-variance map (depth_cov_map, required), the normalised Gaussian weights below
+ *                 1e-3 are zeroed and the rest renormalised; mean = sum p z, var = (sum p (c + z^2) - mean^2) / 2 (the reference's /2),
+ *                 NO min_depth_cov clamp; flow_cov[:, :2] is clamped in place; use_patch_var = 0 -> var = depth_cov.  Every weight below
+ *                 the threshold -> NaN row (0 / 0), as in the reference.
+ *   MV_COV_NONE   NoCovariance (:48-57): the fp64 identity; flow_cov is NOT clamped (read, written back unchanged).
+ * modifiers: an ordered chain of up to 4 steps packed 4 bits per step, innermost (first applied) in bits 0-3, 0 = end of chain:
+ *   MV_COVMOD_DIAG       Modifier_Diagonalize (:281-301): off-diagonal entries := 0
+ *   MV_COVMOD_NORMALIZE  Modifier_Normalize (:305-323): cov /= det(cov) (the determinant itself, as the reference computes it)
+ * both applied in fp64 to the camera-frame covariance, before R cov R^T (MACVO.py:241-281).
+ * out_stats [N, 2] fp32 = (mean depth, variance) for MATCH / GMM, NaN for NONE. */
+enum { MV_COV_MATCH = 0, MV_COV_GMM = 1, MV_COV_NONE = 2 };
+enum { MV_COVMOD_DIAG = 1, MV_COVMOD_NORMALIZE = 2 };
+
+int mv_obs_cov(int model, int32_t modifiers, const float* depth_map, const float* depth_cov_map, const float* kp_uv,
+               float* flow_cov, const float* depth_cov, const double* rot, const mvMatchCovParams* params /* host */, int N,
+               double* out_cov, double* out_cov_rot, float* out_stats, mvStream_t stream);
+
+/* mv_match_cov_pair_lanes with a model and a modifier chain (use_patch_var = 1; depth_cov_map0/1 required for MV_COV_GMM). */
+int mv_obs_cov_pair_lanes(int model, int32_t modifiers, const float* depth_map0, const float* depth_cov_map0, const float* kp_uv0,
+                          float* flow_cov0, const double* rot0, double* out_cov0, double* out_cov_rot0, const float* depth_map1,
+                          const float* depth_cov_map1, const float* kp_uv1, float* flow_cov1, double* out_cov1,
+                          const mvMatchCovParams* params /* host */, int lanes, const int32_t* n_live, int cap, mvStream_t stream);
+
 /* -------------------------------------------------------------------------------------------
  * A17-A22  covariance-weighted two-frame pose-graph solve, batched over independent problems.
  * Replaces TwoFrame_PGO._optimize (Module/Optimization/TwoFramePGO/Optimizer.py:81-102), the residual
@@ -670,6 +696,8 @@ typedef struct {
     float min_flow_cov_sq, min_depth_cov, filter_min_depth;
     float map_max_depth, map_max_depth_cov;   /* MappingPointSelector: z < map_max_depth, sigma_z^2 < map_max_depth_cov (KeypointSelector.py:87-100) */
     mvLMParams lm;
+    int32_t cov_model;         /* MV_COV_* of all three covariance calls of a frame (both observation sets and the mapping tail); 0 = MatchCovariance */
+    int32_t cov_modifiers;     /* modifier chain of mv_obs_cov; 0 = none */
 } mvFramePipeConfig;
 
 /* what the learned layers hand over for one estimate_pair (device pointers, fp32 unless noted) */

@@ -7,7 +7,8 @@ Layout
   interfaces.py    mirror of the reference's plugin interfaces (IFrontend, IKeypointSelector,
                    ICovariance2to3, IOptimizer, SubclassRegistry, ConfigTestable)
   plugins.py       drop-in plugin classes (HIP_CovAwareSelector(_NoDepth), HIP_MappingPointSelector,
-                   HIP_MatchCovariance, HIP_TwoFrame_PGO, ...)
+                   HIP_MatchCovariance, HIP_GaussianMixtureCovariance, HIP_NoCovariance,
+                   HIP_Modifier_Diagonalize / _Normalize, HIP_TwoFrame_PGO, ...)
   pipeline.py      the per-frame hot path in the reference's call order (Odometry/MACVO.py:173-311)
   distributed.py   one process per GPU, sequence sharding, RCCL pose gather
 

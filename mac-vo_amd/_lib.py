@@ -18,7 +18,9 @@ MV_VOL_ENC16 = 16
 MV_LAYOUT_CHW, MV_LAYOUT_HWC = 0, 1
 MV_KP_NODEPTH, MV_KP_FULL, MV_KP_MAPPING = 0, 1, 2
 MV_GRAPH_ICP, MV_GRAPH_REPROJ, MV_GRAPH_DISP = 0, 1, 2
-ABI_VERSION = 5
+MV_COV_MATCH, MV_COV_GMM, MV_COV_NONE = 0, 1, 2
+MV_COVMOD_DIAG, MV_COVMOD_NORMALIZE = 1, 2
+ABI_VERSION = 6
 MV_MAX_LANES = 64        # include/macvo_hip.h
 
 
@@ -55,7 +57,8 @@ class mvFramePipeConfig(C.Structure):
         "kp_kernel_size", "kp_mask_width", "num_point", "edgewidth", "min_num_point", "graph_type", "filters",
         "cov_kernel_size", "mapping", "map_num_point", "map_mask_width", "async_backend")] + [(n, C.c_float) for n in (
         "fx", "fy", "cx", "cy", "baseline", "bl_fx", "bl_fx_sq", "match_cov_default", "max_match_cov", "max_depth_cov",
-        "max_depth", "min_flow_cov_sq", "min_depth_cov", "filter_min_depth", "map_max_depth", "map_max_depth_cov")] + [("lm", mvLMParams)]
+        "max_depth", "min_flow_cov_sq", "min_depth_cov", "filter_min_depth", "map_max_depth", "map_max_depth_cov")] + [("lm", mvLMParams)] + [
+        (n, C.c_int32) for n in ("cov_model", "cov_modifiers")]
 
 
 class mvMapStores(C.Structure):
@@ -122,6 +125,8 @@ SIGNATURES = {
                               C.c_float, _P, _P, _P, _P, _P, _P, _P]),
     "mv_match_cov": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(mvMatchCovParams), C.c_int, _P, _P, _P, _P]),
     "mv_match_cov_pair": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(mvMatchCovParams), C.c_int, _P]),
+    "mv_obs_cov": (C.c_int, [C.c_int, C.c_int32, _P, _P, _P, _P, _P, _P, C.POINTER(mvMatchCovParams), C.c_int, _P, _P, _P, _P]),
+    "mv_obs_cov_pair_lanes": (C.c_int, [C.c_int, C.c_int32] + [_P] * 12 + [C.POINTER(mvMatchCovParams), C.c_int, _P, C.c_int, _P]),
     "mv_lm_default_params": (None, [C.POINTER(mvLMParams)]),
     "mv_pgo_solve": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int,
                                C.POINTER(mvLMParams), _P, _P, _P, _P]),

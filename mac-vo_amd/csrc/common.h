@@ -94,6 +94,33 @@ static inline int mv_launch_status() {
 
 static inline int mv_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// modifier chain of mv_obs_cov (MV_COVMOD_*): 4 bits per step, innermost first, 0 = end; at most 4 steps, nothing after the end
+static inline bool mv_cov_modifiers_ok(int32_t m) {
+    bool ended = false;
+    for (int s = 0; s < 8; ++s) {
+        const int k = (int)(((uint32_t)m >> (4 * s)) & 15u);
+        if (k == 0) { ended = true; continue; }
+        if (ended || s >= 4 || (k != MV_COVMOD_DIAG && k != MV_COVMOD_NORMALIZE)) return false;
+    }
+    return true;
+}
+
+// The fused backend front (frontend_ops.hip) with the frame driver's covariance model: mv_backend_front_lanes /
+// mv_backend_front_draw_lanes + (cov_model, cov_modifiers) of mv_obs_cov; depth_cov0 / depth_cov1 (sdd0 / sdd1) must be given for MV_COV_GMM.
+int mv_backend_front_cov_lanes(int cov_model, int32_t cov_modifiers, const int32_t* cand, size_t cand_lane_stride, const int64_t* perm_dev,
+                               const int64_t* perm_host, int lanes, const int32_t* n_live, int cap, const float* match_flow, const float* match_cov,
+                               const float* depth0, const float* disp0, const float* sdisp0, const float* sdd0, const float* depth1, const float* disp1,
+                               const float* sdisp1, const float* sdd1, int edge, float match_cov_default, const mvMatchCovParams* cov_params,
+                               int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
+                               float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream);
+int mv_backend_front_cov_draw_lanes(int cov_model, int32_t cov_modifiers, const int32_t* cand, size_t cand_lane_stride, const int32_t* count_dev,
+                                    int count_stride, const uint32_t* state_in, uint32_t* state_out, int num_point, int lanes, int cap,
+                                    const float* match_flow, const float* match_cov, const float* depth0, const float* disp0, const float* sdisp0,
+                                    const float* sdd0, const float* depth1, const float* disp1, const float* sdisp1, const float* sdd1, int edge,
+                                    float match_cov_default, const mvMatchCovParams* cov_params, int64_t* out_perm, int32_t* out_live,
+                                    int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
+                                    float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream);
+
 // ---- wave-level reductions (64 lanes, butterfly so every lane ends with the result) ----
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

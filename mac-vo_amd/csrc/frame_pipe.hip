@@ -420,6 +420,7 @@ static int check_config(const mvFramePipeConfig* c) {
     MV_CHECK_ARG(!c->volume_split || c->volume_split == MV_VOL_ENC16 || c->feat_dtype == MV_F32);
     MV_CHECK_ARG(c->volume_split != MV_VOL_ENC16 || (c->feat_dtype == MV_F16 && c->radius == 4));   // (the lookup reads fp16 cells)
     MV_CHECK_ARG(!(c->volume_split == 2 || c->volume_split == 3) || c->layout == MV_LAYOUT_HWC);   // (the packed form takes either layout)
+    MV_CHECK_ARG(c->cov_model >= MV_COV_MATCH && c->cov_model <= MV_COV_NONE && mv_cov_modifiers_ok(c->cov_modifiers));
     return MV_OK;
 }
 
@@ -1211,13 +1212,13 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     mvMatchCovParams cp{c.H, c.W, c.cov_kernel_size, 1, c.fx, c.fy, c.cx, c.cy, c.min_flow_cov_sq, c.min_depth_cov};
     if (j.device) {
         // device-driven frame: the front launch draws the permutation itself (count and generator in device memory) and publishes the live-row count
-        MV_TRY(mv_backend_front_draw_lanes(p->cand[pd.cand], (size_t)p->plane, p->count[pd.cand], 4, p->rp_state[g & 1], p->rp_state[(g + 1) & 1], c.num_point,
-                                           L, cap, m1.match_flow, m1.match_cov, m0.depth, m0.disparity, m0.disparity_cov, m0.depth_cov, m1.depth, m1.disparity,
+        MV_TRY(mv_backend_front_cov_draw_lanes(c.cov_model, c.cov_modifiers, p->cand[pd.cand], (size_t)p->plane, p->count[pd.cand], 4, p->rp_state[g & 1],
+                                           p->rp_state[(g + 1) & 1], c.num_point, L, cap, m1.match_flow, m1.match_cov, m0.depth, m0.disparity, m0.disparity_cov, m0.depth_cov, m1.depth, m1.disparity,
                                            m1.disparity_cov, m1.depth_cov, c.edgewidth, c.match_cov_default, &cp, b.perm, b.live_dev, b.kp0, b.kp0f, b.kp1,
                                            b.inbound, b.vals, b.sigma0, b.sigma1, b.pos_Tc, b.cov0, b.cov1, s));
     } else if (fused) {
         // gather + track + back-projection + both covariance models + observation filters = ONE launch
-        MV_TRY(mv_backend_front_lanes(p->cand[pd.cand], (size_t)p->plane, b.perm, perm_in_args ? p->h_perm[ps] : nullptr, L, n_sel, cap,
+        MV_TRY(mv_backend_front_cov_lanes(c.cov_model, c.cov_modifiers, p->cand[pd.cand], (size_t)p->plane, b.perm, perm_in_args ? p->h_perm[ps] : nullptr, L, n_sel, cap,
                                       m1.match_flow, m1.match_cov, m0.depth, m0.disparity, m0.disparity_cov, m0.depth_cov, m1.depth, m1.disparity,
                                       m1.disparity_cov, m1.depth_cov, c.edgewidth, c.match_cov_default, &cp, b.kp0, b.kp0f, b.kp1, b.inbound, b.vals,
                                       b.sigma0, b.sigma1, b.pos_Tc, b.cov0, b.cov1, s));
@@ -1232,8 +1233,8 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
                                  c.cx, c.cy, b.kp0, b.kp0f, b.kp1, b.inbound, b.vals, b.sigma0, b.sigma1, b.pos_Tc, s));
     }
     if (!fused) {
-        MV_TRY(mv_match_cov_pair_lanes(m0.depth, b.kp0f, b.sigma0, nullptr, b.cov0, nullptr, m1.depth, b.kp1, b.sigma1, b.cov1, &cp,
-                                       L, n_sel, cap, s));
+        MV_TRY(mv_obs_cov_pair_lanes(c.cov_model, c.cov_modifiers, m0.depth, m0.depth_cov, b.kp0f, b.sigma0, nullptr, b.cov0, nullptr, m1.depth,
+                                     m1.depth_cov, b.kp1, b.sigma1, b.cov1, &cp, L, n_sel, cap, s));
         MV_TRY(mv_obs_filter_lanes(b.inbound, b.cov0, b.cov1, b.vals, c.filters, c.filter_min_depth, c.max_depth, L, n_sel, cap,
                                    b.valid, b.n_valid, s));
     }
@@ -1540,7 +1541,8 @@ extern "C" int mv_frame_pipe_map_points(mvFramePipe* p, const int64_t* perm_host
                              p->pose[p->prior_slot], c.match_cov_default, p->mp_uvf, p->mp_d, p->mp_sdd, p->mp_sigma, p->mp_Tc, p->mp_Tw,
                              image_dev ? p->mp_color : nullptr, s));
         mvMatchCovParams cp{c.H, c.W, c.cov_kernel_size, 1, c.fx, c.fy, c.cx, c.cy, c.min_flow_cov_sq, c.min_depth_cov};
-        MV_TRY(mv_match_cov(m0.depth, p->mp_uvf, p->mp_sigma, p->mp_sdd, nullptr, &cp, n_sel, p->mp_cov, nullptr, nullptr, s));
+        MV_TRY(mv_obs_cov(c.cov_model, c.cov_modifiers, m0.depth, m0.depth_cov, p->mp_uvf, p->mp_sigma, p->mp_sdd, nullptr, &cp, n_sel, p->mp_cov,
+                          nullptr, nullptr, s));   // the same ObsCovModel (MACVO.py:324)
     }
     if (stores) {   // map_points.push + frame2map.add (also for n_sel == 0: the reference adds the empty range), behind the frame's registration
         MV_TRY(mv_map_append_points(stores, n_sel, p->mp_Tw, p->mp_cov, image_dev ? p->mp_color : nullptr, s));

@@ -309,6 +309,7 @@ struct DrawArgs {
     const uint32_t* state_in;  // [lanes, mvrp::MT_STRIDE]
     uint32_t* state_out;       // [lanes, mvrp::MT_STRIDE], != state_in
     int k;                     // num_point
+    int32_t cov_mods;          // the covariance modifier chain of backend_front_kernel<., ., true> (any PM; in what was padding)
     int64_t* out_perm;         // [lanes, cap]
     int32_t* out_live;         // [lanes, 2]: selected keypoints = min(count, k), candidate count
 };
@@ -317,7 +318,9 @@ struct DrawLds {
     int32_t head[mvrp::NBUCKET];
     int32_t out[mvrp::MAX_HEAD];
 };
-template <int PM>   // where the permutation comes from: 0 device memory, 1 the kernel arguments, 2 drawn here
+// MODEL / MODS: the frame driver's covariance model (mv_obs_cov; <MV_COV_MATCH, false> = MatchCovariance as before).  GMM reads the dense
+// depth-variance maps the tracking already takes (a.sdd0 / a.sdd1).
+template <int PM, int MODEL = MV_COV_MATCH, bool MODS = false>   // PM: where the permutation comes from: 0 device memory, 1 the kernel arguments, 2 drawn here
 __global__ __launch_bounds__(256) void backend_front_kernel(const int32_t* __restrict__ cand, size_t cand_lane_stride, const int64_t* __restrict__ perm,
                                                             PermArg pa, int cap, mvLaneCounts cnt, int64_t* out_uv, TrackArgs a, float fx, float fy,
                                                             float cx, float cy, float* pos_Tc, const float* depth_map0, const float* depth_map1,
@@ -379,8 +382,30 @@ __global__ __launch_bounds__(256) void backend_front_kernel(const int32_t* __res
         }
         const mvcov::CovSet S{set ? depth_map1 : depth_map0, nullptr, set ? a.out_sigma1 : a.out_sigma0, nullptr, nullptr, set ? out_cov1 : out_cov0,
                               nullptr, nullptr};
-        mvcov::match_cov_wave_vals(S, cp, cap, pl, n, u, v, suu, svv, suv);
+        if constexpr (MODEL == MV_COV_MATCH && !MODS)
+            mvcov::match_cov_wave_vals(S, cp, cap, pl, n, u, v, suu, svv, suv);
+        else
+            mvcov::match_cov_wave_vals<MODEL, MODS>(S, cp, cap, pl, n, u, v, suu, svv, suv, da.cov_mods, set ? a.sdd1 : a.sdd0);
     }
+}
+
+// one backend_front_kernel<PM, model, modifiers?> launch
+template <int PM, typename... Args>
+void launch_backend_front(int model, int32_t mods, dim3 grid, hipStream_t st, DrawArgs da, Args... args) {
+    const bool m = mods != 0;
+    da.cov_mods = mods;
+    if (model == MV_COV_MATCH && !m)
+        hipLaunchKernelGGL((backend_front_kernel<PM>), grid, dim3(256), 0, st, args..., da);
+    else if (model == MV_COV_MATCH)
+        hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_MATCH, true>), grid, dim3(256), 0, st, args..., da);
+    else if (model == MV_COV_GMM && !m)
+        hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_GMM, false>), grid, dim3(256), 0, st, args..., da);
+    else if (model == MV_COV_GMM)
+        hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_GMM, true>), grid, dim3(256), 0, st, args..., da);
+    else if (!m)
+        hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_NONE, false>), grid, dim3(256), 0, st, args..., da);
+    else
+        hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_NONE, true>), grid, dim3(256), 0, st, args..., da);
 }
 
 }  // namespace
@@ -478,7 +503,20 @@ extern "C" int mv_backend_front_lanes(const int32_t* cand, size_t cand_lane_stri
                                       const float* sdisp1, const float* sdd1, int edge, float match_cov_default, const mvMatchCovParams* cov_params,
                                       int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
                                       float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream) {
+    return mv_backend_front_cov_lanes(MV_COV_MATCH, 0, cand, cand_lane_stride, perm_dev, perm_host, lanes, n_live, cap, match_flow, match_cov, depth0,
+                                      disp0, sdisp0, sdd0, depth1, disp1, sdisp1, sdd1, edge, match_cov_default, cov_params, out_kp0_uv, out_kp0,
+                                      out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1, out_pos_Tc, out_cov0, out_cov1, stream);
+}
+
+int mv_backend_front_cov_lanes(int cov_model, int32_t cov_modifiers, const int32_t* cand, size_t cand_lane_stride, const int64_t* perm_dev,
+                               const int64_t* perm_host, int lanes, const int32_t* n_live, int cap, const float* match_flow, const float* match_cov,
+                               const float* depth0, const float* disp0, const float* sdisp0, const float* sdd0, const float* depth1, const float* disp1,
+                               const float* sdisp1, const float* sdd1, int edge, float match_cov_default, const mvMatchCovParams* cov_params,
+                               int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
+                               float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream) {
     MV_CHECK_ARG(cov_params && edge >= 0);
+    MV_CHECK_ARG(cov_model >= MV_COV_MATCH && cov_model <= MV_COV_NONE && mv_cov_modifiers_ok(cov_modifiers));
+    MV_CHECK_ARG(cov_model != MV_COV_GMM || (sdd0 && sdd1));
     const mvMatchCovParams cp = *cov_params;
     MV_CHECK_ARG(cp.H > 0 && cp.W > 0 && cp.kernel_size >= 1 && (cp.kernel_size & 1) && cp.use_patch_var);
     if (cp.kernel_size > mvcov::MAX_K) return MV_ERR_UNSUPPORTED;
@@ -491,21 +529,21 @@ extern "C" int mv_backend_front_lanes(const int32_t* cand, size_t cand_lane_stri
                  out_sigma0 && out_sigma1 && out_pos_Tc && out_cov0 && out_cov1);
     const TrackArgs ta{match_flow, match_cov, depth0, disp0, sdisp0, sdd0, depth1, disp1, sdisp1, sdd1, cp.H, cp.W, edge, match_cov_default,
                        out_kp0, out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1};
-    const dim3 grid(mv_ceil_div(n_max, 4), 2, lanes), block(256);
+    const dim3 grid(mv_ceil_div(n_max, 4), 2, lanes);
     if (perm_host && lanes == 1 && n_max <= 256) {     // the permutation rides in the kernel arguments
         PermArg pa;
         for (int i = 0; i < n_max; ++i) {
             MV_CHECK_ARG(perm_host[i] >= 0 && perm_host[i] <= 0x7fffffffLL);
             pa.idx[i] = (int32_t)perm_host[i];
         }
-        hipLaunchKernelGGL(backend_front_kernel<1>, grid, block, 0, (hipStream_t)stream, cand, cand_lane_stride, nullptr, pa, cap, c, out_kp0_uv, ta,
-                           cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp, DrawArgs{});
+        launch_backend_front<1>(cov_model, cov_modifiers, grid, (hipStream_t)stream, DrawArgs{}, cand, cand_lane_stride, (const int64_t*)nullptr, pa, cap, c,
+                                out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
     } else {
         MV_CHECK_ARG(perm_dev);
         PermArg pa;
         pa.idx[0] = 0;
-        hipLaunchKernelGGL(backend_front_kernel<0>, grid, block, 0, (hipStream_t)stream, cand, cand_lane_stride, perm_dev, pa, cap, c, out_kp0_uv, ta,
-                           cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp, DrawArgs{});
+        launch_backend_front<0>(cov_model, cov_modifiers, grid, (hipStream_t)stream, DrawArgs{}, cand, cand_lane_stride, perm_dev, pa, cap, c, out_kp0_uv, ta,
+                                cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
     }
     return mv_launch_status();
 }
@@ -519,7 +557,22 @@ extern "C" int mv_backend_front_draw_lanes(const int32_t* cand, size_t cand_lane
                                            const mvMatchCovParams* cov_params, int64_t* out_perm, int32_t* out_live, int64_t* out_kp0_uv, float* out_kp0,
                                            float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0, float* out_sigma1, float* out_pos_Tc,
                                            double* out_cov0, double* out_cov1, mvStream_t stream) {
+    return mv_backend_front_cov_draw_lanes(MV_COV_MATCH, 0, cand, cand_lane_stride, count_dev, count_stride, state_in, state_out, num_point, lanes, cap,
+                                           match_flow, match_cov, depth0, disp0, sdisp0, sdd0, depth1, disp1, sdisp1, sdd1, edge, match_cov_default,
+                                           cov_params, out_perm, out_live, out_kp0_uv, out_kp0, out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1,
+                                           out_pos_Tc, out_cov0, out_cov1, stream);
+}
+
+int mv_backend_front_cov_draw_lanes(int cov_model, int32_t cov_modifiers, const int32_t* cand, size_t cand_lane_stride, const int32_t* count_dev,
+                                    int count_stride, const uint32_t* state_in, uint32_t* state_out, int num_point, int lanes, int cap,
+                                    const float* match_flow, const float* match_cov, const float* depth0, const float* disp0, const float* sdisp0,
+                                    const float* sdd0, const float* depth1, const float* disp1, const float* sdisp1, const float* sdd1, int edge,
+                                    float match_cov_default, const mvMatchCovParams* cov_params, int64_t* out_perm, int32_t* out_live,
+                                    int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
+                                    float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream) {
     MV_CHECK_ARG(cov_params && edge >= 0 && lanes >= 1 && lanes <= MV_MAX_LANES && cap >= 1 && num_point >= 0 && num_point <= cap && count_stride >= 1);
+    MV_CHECK_ARG(cov_model >= MV_COV_MATCH && cov_model <= MV_COV_NONE && mv_cov_modifiers_ok(cov_modifiers));
+    MV_CHECK_ARG(cov_model != MV_COV_GMM || (sdd0 && sdd1));
     const mvMatchCovParams cp = *cov_params;
     MV_CHECK_ARG(cp.H > 0 && cp.W > 0 && cp.kernel_size >= 1 && (cp.kernel_size & 1) && cp.use_patch_var);
     if (cp.kernel_size > mvcov::MAX_K || num_point > mvrp::MAX_HEAD) return MV_ERR_UNSUPPORTED;
@@ -527,12 +580,12 @@ extern "C" int mv_backend_front_draw_lanes(const int32_t* cand, size_t cand_lane
                  out_kp0_uv && out_kp1 && out_inbound && out_vals && out_sigma0 && out_sigma1 && out_pos_Tc && out_cov0 && out_cov1);
     const TrackArgs ta{match_flow, match_cov, depth0, disp0, sdisp0, sdd0, depth1, disp1, sdisp1, sdd1, cp.H, cp.W, edge, match_cov_default,
                        out_kp0, out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1};
-    const dim3 grid(mv_ceil_div(num_point > 0 ? num_point : 1, 4), 2, lanes), block(256);   // (num_point == 0: workgroup (0, 0, l) still advances the generator)
+    const dim3 grid(mv_ceil_div(num_point > 0 ? num_point : 1, 4), 2, lanes);   // (num_point == 0: workgroup (0, 0, l) still advances the generator)
     PermArg pa;
     pa.idx[0] = 0;
-    const DrawArgs da{count_dev, count_stride, state_in, state_out, num_point, out_perm, out_live};
-    hipLaunchKernelGGL(backend_front_kernel<2>, grid, block, 0, (hipStream_t)stream, cand, cand_lane_stride, nullptr, pa, cap, mvLaneCounts{}, out_kp0_uv, ta,
-                       cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp, da);
+    const DrawArgs da{count_dev, count_stride, state_in, state_out, num_point, 0, out_perm, out_live};
+    launch_backend_front<2>(cov_model, cov_modifiers, grid, (hipStream_t)stream, da, cand, cand_lane_stride, (const int64_t*)nullptr, pa, cap, mvLaneCounts{},
+                            out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
     return mv_launch_status();
 }
 

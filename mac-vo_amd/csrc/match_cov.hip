@@ -13,6 +13,10 @@
 // b-fastest over the lanes so each wave-wide load covers ~2 contiguous 124-B patch rows; taps and weights
 // stay in registers (16 each for K = 31); three butterfly reductions (sum k, sum w*z, sum w*(z-mu)^2);
 // lane 0 assembles the 3x3 in fp32 with the reference's op order, widens to fp64 and rotates.
+//
+// mv_obs_cov / mv_obs_cov_pair_lanes: GaussianMixtureCovariance (Project2to3.py:194-262), NoCovariance (:48-57) and the
+// Modifier_Diagonalize / Modifier_Normalize chain (:281-323) on the same wave layout (obs_cov_kernel<MODEL, MODS>).  GMM gathers
+// the dense depth-variance patch next to the depth patch (same transposed tap order) and keeps c + z^2 per tap (16 more VGPRs).
 #include "common.h"
 #include <math.h>
 #include "match_cov_dev.h"
@@ -26,6 +30,34 @@ __global__ __launch_bounds__(256) void match_cov_kernel(CovSet s0, CovSet s1, mv
     const int pl = blockIdx.z;
     if (n >= cnt.n[pl]) return;  // whole wave exits together
     match_cov_wave(blockIdx.y ? s1 : s0, p, cap, pl, n);   // the frame's two keypoint sets (kp0 on depth0, kp1 on depth1) share a launch
+}
+
+// the other models of ICovariance2to3 and the modifier chain (mv_obs_cov); match_cov_kernel stays the MatchCovariance-without-modifiers form
+template <int MODEL, bool MODS>
+__global__ __launch_bounds__(256) void obs_cov_kernel(CovSet s0, CovSet s1, mvMatchCovParams p, int cap, mvLaneCounts cnt, int32_t mods,
+                                                      const float* depth_cov_map0, const float* depth_cov_map1) {
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int pl = blockIdx.z;
+    if (n >= cnt.n[pl]) return;
+    match_cov_wave<MODEL, MODS>(blockIdx.y ? s1 : s0, p, cap, pl, n, mods, blockIdx.y ? depth_cov_map1 : depth_cov_map0);
+}
+
+int launch_obs_cov(int model, int32_t mods, dim3 grid, hipStream_t st, const CovSet& s0, const CovSet& s1, const mvMatchCovParams& p, int cap,
+                   const mvLaneCounts& c, const float* dcm0, const float* dcm1) {
+    const bool m = mods != 0;
+    if (model == MV_COV_MATCH && !m)
+        hipLaunchKernelGGL(match_cov_kernel, grid, dim3(256), 0, st, s0, s1, p, cap, c);
+    else if (model == MV_COV_MATCH)
+        hipLaunchKernelGGL((obs_cov_kernel<MV_COV_MATCH, true>), grid, dim3(256), 0, st, s0, s1, p, cap, c, mods, dcm0, dcm1);
+    else if (model == MV_COV_GMM && !m)
+        hipLaunchKernelGGL((obs_cov_kernel<MV_COV_GMM, false>), grid, dim3(256), 0, st, s0, s1, p, cap, c, mods, dcm0, dcm1);
+    else if (model == MV_COV_GMM)
+        hipLaunchKernelGGL((obs_cov_kernel<MV_COV_GMM, true>), grid, dim3(256), 0, st, s0, s1, p, cap, c, mods, dcm0, dcm1);
+    else if (!m)
+        hipLaunchKernelGGL((obs_cov_kernel<MV_COV_NONE, false>), grid, dim3(256), 0, st, s0, s1, p, cap, c, mods, dcm0, dcm1);
+    else
+        hipLaunchKernelGGL((obs_cov_kernel<MV_COV_NONE, true>), grid, dim3(256), 0, st, s0, s1, p, cap, c, mods, dcm0, dcm1);
+    return mv_launch_status();
 }
 
 }  // namespace
@@ -82,4 +114,48 @@ extern "C" int mv_match_cov_pair(const float* depth_map0, const float* kp_uv0, f
     const int32_t n = N;
     return mv_match_cov_pair_lanes(depth_map0, kp_uv0, flow_cov0, rot0, out_cov0, out_cov_rot0, depth_map1, kp_uv1, flow_cov1,
                                    out_cov1, params, 1, &n, N, stream);
+}
+
+extern "C" int mv_obs_cov(int model, int32_t modifiers, const float* depth_map, const float* depth_cov_map, const float* kp_uv, float* flow_cov,
+                          const float* depth_cov, const double* rot, const mvMatchCovParams* params, int N, double* out_cov, double* out_cov_rot,
+                          float* out_stats, mvStream_t stream) {
+    MV_CHECK_ARG(params && N >= 0 && model >= MV_COV_MATCH && model <= MV_COV_NONE && mv_cov_modifiers_ok(modifiers));
+    if (N == 0) return MV_OK;
+    MV_CHECK_ARG(depth_map && kp_uv && flow_cov && out_cov);
+    const mvMatchCovParams p = *params;
+    MV_CHECK_ARG(p.H > 0 && p.W > 0 && p.kernel_size >= 1 && (p.kernel_size & 1));
+    if (p.kernel_size > MAX_K) return MV_ERR_UNSUPPORTED;
+    MV_CHECK_ARG(p.use_patch_var || depth_cov);
+    MV_CHECK_ARG(model != MV_COV_GMM || depth_cov_map);
+    MV_CHECK_ARG(!out_cov_rot || rot);
+    const CovSet s0{depth_map, kp_uv, flow_cov, depth_cov, rot, out_cov, out_cov_rot, out_stats};
+    mvLaneCounts c{};
+    c.n[0] = N;
+    return launch_obs_cov(model, modifiers, dim3(mv_ceil_div(N, 4), 1, 1), (hipStream_t)stream, s0, s0, p, N, c, depth_cov_map, depth_cov_map);
+}
+
+extern "C" int mv_obs_cov_pair_lanes(int model, int32_t modifiers, const float* depth_map0, const float* depth_cov_map0, const float* kp_uv0,
+                                     float* flow_cov0, const double* rot0, double* out_cov0, double* out_cov_rot0, const float* depth_map1,
+                                     const float* depth_cov_map1, const float* kp_uv1, float* flow_cov1, double* out_cov1,
+                                     const mvMatchCovParams* params, int lanes, const int32_t* n_live, int cap, mvStream_t stream) {
+    MV_CHECK_ARG(model >= MV_COV_MATCH && model <= MV_COV_NONE && mv_cov_modifiers_ok(modifiers));
+    MV_CHECK_ARG(params && lanes >= 1 && lanes <= MV_MAX_LANES && n_live && cap >= 0);
+    mvLaneCounts c{};
+    int n_max = 0;
+    for (int l = 0; l < lanes; ++l) {
+        MV_CHECK_ARG(n_live[l] >= 0 && n_live[l] <= cap);
+        c.n[l] = n_live[l];
+        n_max = n_live[l] > n_max ? n_live[l] : n_max;
+    }
+    if (n_max == 0) return MV_OK;
+    MV_CHECK_ARG(depth_map0 && kp_uv0 && flow_cov0 && out_cov0 && depth_map1 && kp_uv1 && flow_cov1 && out_cov1);
+    MV_CHECK_ARG(model != MV_COV_GMM || (depth_cov_map0 && depth_cov_map1));
+    const mvMatchCovParams p = *params;
+    MV_CHECK_ARG(p.H > 0 && p.W > 0 && p.kernel_size >= 1 && (p.kernel_size & 1) && p.use_patch_var);
+    if (p.kernel_size > MAX_K) return MV_ERR_UNSUPPORTED;
+    MV_CHECK_ARG(!out_cov_rot0 || rot0);
+    const CovSet s0{depth_map0, kp_uv0, flow_cov0, nullptr, rot0, out_cov0, out_cov_rot0, nullptr};
+    const CovSet s1{depth_map1, kp_uv1, flow_cov1, nullptr, nullptr, out_cov1, nullptr, nullptr};
+    return launch_obs_cov(model, modifiers, dim3(mv_ceil_div(n_max, 4), 2, lanes), (hipStream_t)stream, s0, s1, p, cap, c, depth_cov_map0,
+                          depth_cov_map1);
 }

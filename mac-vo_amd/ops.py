@@ -642,6 +642,107 @@ def match_cov_pair(depth0: torch.Tensor, kp0_uv: torch.Tensor, sigma0: torch.Ten
     return c0, c0w, c1
 
 
+COV_MODELS = {"match": L.MV_COV_MATCH, "gmm": L.MV_COV_GMM, "none": L.MV_COV_NONE}
+COV_MODIFIERS = {"diag": L.MV_COVMOD_DIAG, "normalize": L.MV_COVMOD_NORMALIZE}
+
+
+def cov_modifier_chain(modifiers) -> int:
+    """``("diag", "normalize", ...)`` (innermost first, at most 4) -> the packed int32 chain of ``mv_obs_cov``."""
+    mods = tuple(modifiers)
+    if len(mods) > 4:
+        raise ValueError(f"at most 4 covariance modifiers, got {mods}")
+    chain = 0
+    for i, m in enumerate(mods):
+        if m not in COV_MODIFIERS:
+            raise ValueError(f"unknown covariance modifier {m!r} (one of {sorted(COV_MODIFIERS)})")
+        chain |= COV_MODIFIERS[m] << (4 * i)
+    return chain
+
+
+def _cov_model(model: str) -> int:
+    if model not in COV_MODELS:
+        raise ValueError(f"unknown covariance model {model!r} (one of {sorted(COV_MODELS)})")
+    return COV_MODELS[model]
+
+
+def obs_cov(model: str, depth_map: torch.Tensor, kp_uv: torch.Tensor, flow_cov: torch.Tensor, depth_cov: torch.Tensor | None,
+            fx: float, fy: float, cx: float, cy: float, depth_cov_map: torch.Tensor | None = None, modifiers=(),
+            kernel_size: int = 31, min_flow_cov: float = 0.25, min_depth_cov: float = 0.05, use_patch_var: bool = True,
+            rot: torch.Tensor | None = None, want_stats: bool = False):
+    """The observation-covariance models of ``ICovariance2to3`` (Project2to3.py): ``model`` "match" (MatchCovariance = :func:`match_cov`),
+    "gmm" (GaussianMixtureCovariance: needs ``depth_cov_map`` = ``depth_est.cov``) or "none" (NoCovariance), followed by the modifier
+    chain ``modifiers`` ("diag" = Modifier_Diagonalize, "normalize" = Modifier_Normalize; innermost first) on the camera-frame
+    covariance.  ``flow_cov [N,3]`` is clamped IN PLACE by "match" / "gmm", left as it is by "none".  Returns like :func:`match_cov`."""
+    lib = L.load()
+    m, chain = _cov_model(model), cov_modifier_chain(modifiers)
+    depth_map = _req(depth_map, torch.float32, "depth_map")
+    H, W = depth_map.shape[-2:]
+    if kp_uv.dtype != torch.float32:
+        kp_uv = kp_uv.to(torch.float32)
+    kp_uv = _req(kp_uv, torch.float32, "kp_uv")
+    if flow_cov.dtype != torch.float32 or not flow_cov.is_contiguous() or not flow_cov.is_cuda:
+        raise L.MacvoHipError("obs_cov: flow_cov must be a contiguous float32 GPU tensor (it is clamped in place)")
+    if m == L.MV_COV_GMM and depth_cov_map is None:
+        raise L.MacvoHipError("obs_cov: the gaussian-mixture model needs depth_cov_map (depth_est.cov)")
+    N = kp_uv.shape[0]
+    dev = depth_map.device
+    dcm = None if depth_cov_map is None else _req(depth_cov_map, torch.float32, "depth_cov_map")
+    dc = None if depth_cov is None else _req(depth_cov, torch.float32, "depth_cov")
+    r = None if rot is None else _req(rot.to(dev), torch.float64, "rot")
+    out = torch.empty((N, 3, 3), dtype=torch.float64, device=dev)
+    out_rot = torch.empty((N, 3, 3), dtype=torch.float64, device=dev) if r is not None else None
+    stats = torch.empty((N, 2), dtype=torch.float32, device=dev) if want_stats else None
+    p = L.mvMatchCovParams(H, W, kernel_size, int(use_patch_var or dc is None), fx, fy, cx, cy, min_flow_cov ** 2,
+                           min_depth_cov)
+    L.check(lib.mv_obs_cov(m, chain, depth_map.data_ptr(), _ptr(dcm), kp_uv.data_ptr(), flow_cov.data_ptr(), _ptr(dc), _ptr(r),
+                           C.byref(p), N, out.data_ptr(), _ptr(out_rot), _ptr(stats), _stream()), "mv_obs_cov")
+    res = (out,)
+    if out_rot is not None:
+        res += (out_rot,)
+    if want_stats:
+        res += (stats,)
+    return res[0] if len(res) == 1 else res
+
+
+def obs_cov_pair(model: str, depth0: torch.Tensor, kp0_uv: torch.Tensor, sigma0: torch.Tensor, depth1: torch.Tensor,
+                 kp1_uv: torch.Tensor, sigma1: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
+                 depth_cov_map0: torch.Tensor | None = None, depth_cov_map1: torch.Tensor | None = None, modifiers=(),
+                 rot: torch.Tensor | None = None, kernel_size: int = 31, min_flow_cov: float = 0.25, min_depth_cov: float = 0.05,
+                 n_live: "list[int] | None" = None):
+    """Both ObsCovModel calls of a frame (MACVO.py:241-242) with the model / modifiers of :func:`obs_cov`, one launch
+    (``mv_obs_cov_pair_lanes``).  Lane-batched when the inputs carry a leading lane axis: depth ``[L, H, W]``, keypoint
+    tables ``[L, cap, .]`` and ``n_live`` (default: ``cap`` rows per lane); ``rot`` is then ``[L, 3, 3]``.
+    -> (cov0, cov0_world | None, cov1)."""
+    lib = L.load()
+    m, chain = _cov_model(model), cov_modifier_chain(modifiers)
+    d0, d1 = _req(depth0, torch.float32, "depth0"), _req(depth1, torch.float32, "depth1")
+    k0, k1 = _req(kp0_uv, torch.float32, "kp0_uv"), _req(kp1_uv, torch.float32, "kp1_uv")
+    for t_, nm in ((sigma0, "sigma0"), (sigma1, "sigma1")):
+        if t_.dtype != torch.float32 or not t_.is_contiguous() or not t_.is_cuda:
+            raise L.MacvoHipError(f"obs_cov_pair: {nm} must be a contiguous float32 GPU tensor (clamped in place)")
+    if m == L.MV_COV_GMM and (depth_cov_map0 is None or depth_cov_map1 is None):
+        raise L.MacvoHipError("obs_cov_pair: the gaussian-mixture model needs both depth_cov_map0 and depth_cov_map1")
+    H, W = d0.shape[-2:]
+    lanes = k0.shape[0] if k0.dim() == 3 else 1
+    cap = k0.shape[-2]
+    assert k1.shape == k0.shape
+    n_live = [cap] * lanes if n_live is None else [int(n) for n in n_live]
+    dev = d0.device
+    dcm0 = None if depth_cov_map0 is None else _req(depth_cov_map0, torch.float32, "depth_cov_map0")
+    dcm1 = None if depth_cov_map1 is None else _req(depth_cov_map1, torch.float32, "depth_cov_map1")
+    r = None if rot is None else _req(rot.to(dev), torch.float64, "rot")
+    lead = (lanes, cap) if k0.dim() == 3 else (cap,)
+    c0 = torch.empty(lead + (3, 3), dtype=torch.float64, device=dev)
+    c1 = torch.empty(lead + (3, 3), dtype=torch.float64, device=dev)
+    c0w = torch.empty(lead + (3, 3), dtype=torch.float64, device=dev) if r is not None else None
+    p = L.mvMatchCovParams(H, W, kernel_size, 1, fx, fy, cx, cy, min_flow_cov ** 2, min_depth_cov)
+    nl = (C.c_int32 * lanes)(*n_live)
+    L.check(lib.mv_obs_cov_pair_lanes(m, chain, d0.data_ptr(), _ptr(dcm0), k0.data_ptr(), sigma0.data_ptr(), _ptr(r), c0.data_ptr(),
+                                      _ptr(c0w), d1.data_ptr(), _ptr(dcm1), k1.data_ptr(), sigma1.data_ptr(), c1.data_ptr(), C.byref(p),
+                                      lanes, nl, cap, _stream()), "mv_obs_cov_pair_lanes")
+    return c0, c0w, c1
+
+
 # ------------------------------------------------------------------------------------------- A17-A22
 def lm_default_params() -> L.mvLMParams:
     p = L.mvLMParams()
@@ -730,8 +831,9 @@ class MapPoints:
 
 def map_points(uv: torch.Tensor, depth: torch.Tensor, depth_cov: torch.Tensor, K4: tuple, pose: torch.Tensor,
                image: torch.Tensor | None = None, match_cov_default: float = 0.25, kernel_size: int = 31,
-               min_flow_cov: float = 0.25, min_depth_cov: float = 0.05) -> MapPoints:
-    """Everything ``run_pair`` does for the dense map after the selector (MACVO.py:317-334) in two launches."""
+               min_flow_cov: float = 0.25, min_depth_cov: float = 0.05, cov_model: str = "match", cov_modifiers=()) -> MapPoints:
+    """Everything ``run_pair`` does for the dense map after the selector (MACVO.py:317-334) in two launches.  ``cov_model`` /
+    ``cov_modifiers``: the ObsCovModel of :func:`obs_cov` (MACVO.py:324 uses the same model as the keypoints)."""
     lib = L.load()
     uv = _req(uv, torch.int64, "uv")
     depth = _req(depth, torch.float32, "depth")
@@ -747,7 +849,11 @@ def map_points(uv: torch.Tensor, depth: torch.Tensor, depth_cov: torch.Tensor, K
                               *[float(k) for k in K4], pose_c.data_ptr(), float(match_cov_default), uvf.data_ptr(),
                               d.data_ptr(), sdd.data_ptr(), sig.data_ptr(), Tc.data_ptr(), Tw.data_ptr(), _ptr(col), _stream()),
             "mv_map_points")
-    cov = match_cov(depth, uvf, sig, sdd, *K4, kernel_size=kernel_size, min_flow_cov=min_flow_cov, min_depth_cov=min_depth_cov)
+    if cov_model == "match" and not tuple(cov_modifiers):
+        cov = match_cov(depth, uvf, sig, sdd, *K4, kernel_size=kernel_size, min_flow_cov=min_flow_cov, min_depth_cov=min_depth_cov)
+    else:
+        cov = obs_cov(cov_model, depth, uvf, sig, sdd, *K4, depth_cov_map=depth_cov, modifiers=cov_modifiers, kernel_size=kernel_size,
+                      min_flow_cov=min_flow_cov, min_depth_cov=min_depth_cov)
     return MapPoints(uvf, d, sdd, Tc, Tw, cov, col)
 
 

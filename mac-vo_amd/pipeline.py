@@ -105,6 +105,45 @@ class HotPathConfig:
     volume_store: str = "fp32"
     async_backend: bool | None = None    # native driver: issue a frame's backend launches from a second host thread (None: the
                                          # library's default / MV_PIPE_ASYNC_BACKEND); identical results either way
+    # observation-covariance model (`cov.obs` of the experiment YAML, Project2to3.py): "match" = MatchCovariance | "gmm" =
+    # GaussianMixtureCovariance | "none" = NoCovariance, then the modifiers "diag" (Modifier_Diagonalize) / "normalize"
+    # (Modifier_Normalize), innermost first.  cov_config_fields() maps a reference `cov.obs` block onto these two fields.
+    cov_model: str = "match"
+    cov_modifiers: tuple[str, ...] = ()
+
+
+_COV_TYPES = {"MatchCovariance": "match", "GaussianMixtureCovariance": "gmm", "NoCovariance": "none",
+              "HIP_MatchCovariance": "match", "HIP_GaussianMixtureCovariance": "gmm", "HIP_NoCovariance": "none"}
+_COV_MODIFIER_TYPES = {"Modifier_Diagonalize": "diag", "Modifier_Normalize": "normalize",
+                       "HIP_Modifier_Diagonalize": "diag", "HIP_Modifier_Normalize": "normalize"}
+
+
+def _ns_get(x, key):
+    return x[key] if isinstance(x, dict) else getattr(x, key)
+
+
+def cov_config_fields(obs) -> dict:
+    """A reference ``cov.obs`` block (``{type, args}`` as a dict or SimpleNamespace; modifiers nest their submodel in
+    ``args.type`` / ``args.args``) -> ``{"cov_model", "cov_modifiers", and the model's args}`` for :class:`HotPathConfig`.
+    ``Modifier_Normalize(Modifier_Diagonalize(MatchCovariance))`` -> ``cov_model="match", cov_modifiers=("diag", "normalize")``."""
+    mods = []
+    while _ns_get(obs, "type") in _COV_MODIFIER_TYPES:
+        mods.append(_COV_MODIFIER_TYPES[_ns_get(obs, "type")])
+        obs = _ns_get(obs, "args")
+    t = _ns_get(obs, "type")
+    if t not in _COV_TYPES:
+        raise ValueError(f"covariance model {t!r} has no HIP form (one of {sorted(set(_COV_TYPES))})")
+    out = {"cov_model": _COV_TYPES[t], "cov_modifiers": tuple(reversed(mods))}
+    args = _ns_get(obs, "args")
+    if args is not None and _COV_TYPES[t] != "none":
+        # (not the model's match_cov_default: it only stands in for an absent flow_cov, which the pipe never passes; the
+        # constant kp0 / map-point sigma is Odometry.args.match_cov_default, MACVO.py:228,322)
+        for k, f in (("kernel_size", "cov_kernel_size"), ("min_flow_cov", "min_flow_cov"), ("min_depth_cov", "min_depth_cov")):
+            try:
+                out[f] = _ns_get(args, k)
+            except (KeyError, AttributeError):
+                pass
+    return out
 
 
 @dataclass
@@ -329,9 +368,15 @@ class HotPath:
 
             tr = ops.kp_track(kp0, maps1.flow, maps1.flow_cov, maps0, maps1, c.edgewidth, c.match_cov_default)
             pos0_Tc, pos_Tw, rot = ops.backproject(tr.kp0_uv, tr.vals[0], cam.K4, self.pose, want_rot=True)
-            cov0, cov0_w, cov1 = ops.match_cov_pair(maps0.depth, tr.kp0_uv, tr.sigma0, maps1.depth, tr.kp1_uv, tr.sigma1,
-                                                    *cam.K4, rot=rot, kernel_size=c.cov_kernel_size,
-                                                    min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov)
+            if c.cov_model == "match" and not tuple(c.cov_modifiers):
+                cov0, cov0_w, cov1 = ops.match_cov_pair(maps0.depth, tr.kp0_uv, tr.sigma0, maps1.depth, tr.kp1_uv, tr.sigma1,
+                                                        *cam.K4, rot=rot, kernel_size=c.cov_kernel_size,
+                                                        min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov)
+            else:
+                cov0, cov0_w, cov1 = ops.obs_cov_pair(c.cov_model, maps0.depth, tr.kp0_uv, tr.sigma0, maps1.depth, tr.kp1_uv, tr.sigma1,
+                                                      *cam.K4, depth_cov_map0=maps0.depth_cov, depth_cov_map1=maps1.depth_cov,
+                                                      modifiers=c.cov_modifiers, rot=rot, kernel_size=c.cov_kernel_size,
+                                                      min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov)
             valid, n_valid = ops.obs_filter(tr.inbound, cov0, cov1, tr.vals, c.filters, c.filter_min_depth, self._max_depth)
 
             batch = ops.PGOBatch(
@@ -358,7 +403,8 @@ class HotPath:
                     muv = pend.cands_m.finish(c.map_num_point)
                     map_pts = ops.map_points(muv, maps0.depth, maps0.depth_cov, cam.K4, batch.init_pose, image=pend.image0,
                                              match_cov_default=c.match_cov_default, kernel_size=c.cov_kernel_size,
-                                             min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov)
+                                             min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov, cov_model=c.cov_model,
+                                             cov_modifiers=c.cov_modifiers)
                     self._map_done = torch.cuda.Event()
                     self._map_done.record(back)
         self._pgo_done = done
@@ -587,7 +633,8 @@ class NativeHotPath:
             bl_fx=bl_fx, bl_fx_sq=bl_fx ** 2, match_cov_default=c.match_cov_default, max_match_cov=c.max_match_cov,
             max_depth_cov=c.max_depth_cov, max_depth=max_depth, min_flow_cov_sq=c.min_flow_cov ** 2,
             min_depth_cov=c.min_depth_cov, filter_min_depth=c.filter_min_depth, mapping=int(c.mapping), map_num_point=c.map_num_point,
-            map_mask_width=c.map_mask_width, async_backend=0 if c.async_backend is None else (1 if c.async_backend else -1), map_max_depth=c.map_max_depth, map_max_depth_cov=c.map_max_depth_cov, lm=self.lm)
+            map_mask_width=c.map_mask_width, async_backend=0 if c.async_backend is None else (1 if c.async_backend else -1), map_max_depth=c.map_max_depth, map_max_depth_cov=c.map_max_depth_cov, lm=self.lm,
+            cov_model=ops._cov_model(c.cov_model), cov_modifiers=ops.cov_modifier_chain(c.cov_modifiers))
         nbytes = lib.mv_frame_pipe_arena_bytes(C.byref(pc))
         if nbytes == 0:
             raise L.MacvoHipError("mv_frame_pipe_arena_bytes: invalid configuration")

@@ -7,6 +7,8 @@ replace, every hot arithmetic step in the HIP kernels (``include/macvo_hip.h``).
     CovAwareSelector                          HIP_CovAwareSelector
     MappingPointSelector                      HIP_MappingPointSelector
     MatchCovariance                           HIP_MatchCovariance
+    GaussianMixtureCovariance / NoCovariance  HIP_GaussianMixtureCovariance / HIP_NoCovariance
+    Modifier_Diagonalize / Modifier_Normalize HIP_Modifier_Diagonalize / HIP_Modifier_Normalize  (fused into the kernel over a HIP model)
     TwoFrame_PGO                              HIP_TwoFrame_PGO
     FlowFormerCovFrontend                     HIP_FlowFormerCovFrontend  (network stays PyTorch; lookups + epilogue in HIP)
     CUDAGraph_FlowFormerCovFrontend           HIP_CUDAGraph_FlowFormerCovFrontend  (same, inference replayed as a hipGraph)
@@ -128,6 +130,31 @@ def _grid_select(frame, numPoint: int, mask_width: int, dev) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------------------------- covariance
+def _obs_cov_device(model: str, config, frame, kp, depth_est, depth_cov, flow_cov, rot=None, modifiers=()):
+    """One ``ops.obs_cov`` call with the reference's argument handling (Project2to3.py:124-135,205-217): a given ``flow_cov`` is clamped
+    in place (MatchCovariance / GaussianMixtureCovariance), an absent one is the constant ``match_cov_default`` sigma (unclamped)."""
+    dev = torch.device(config.device) if hasattr(config, "device") else (depth_est.depth.device if depth_est.depth.is_cuda else torch.device("cuda"))
+    n = kp.size(0)
+    has_flow_cov = flow_cov is not None
+    if has_flow_cov:
+        work = flow_cov if (flow_cov.is_cuda and flow_cov.dtype == torch.float32 and flow_cov.is_contiguous()) \
+            else flow_cov.to(dev, torch.float32).contiguous()
+    else:
+        work = torch.full((n, 3), float(getattr(config, "match_cov_default", 0.25)), dtype=torch.float32, device=dev)
+        work[:, 2] = 0.0
+    if model == "gmm":
+        assert depth_est.cov is not None
+    none = model == "none"
+    res = ops.obs_cov(model, depth_est.depth.to(dev), kp.to(dev), work, None if depth_cov is None else depth_cov.to(dev),
+                      frame.fx, frame.fy, frame.cx, frame.cy, depth_cov_map=None if depth_est.cov is None else depth_est.cov.to(dev),
+                      modifiers=modifiers, kernel_size=31 if none else config.kernel_size,
+                      min_flow_cov=config.min_flow_cov if (has_flow_cov and not none) else 0.0,
+                      min_depth_cov=0.05 if none else config.min_depth_cov, use_patch_var=(has_flow_cov or depth_cov is None), rot=rot)
+    if has_flow_cov and work is not flow_cov:
+        flow_cov.copy_(work)                                                   # keep the in-place side effect
+    return res
+
+
 class HIP_MatchCovariance(ICovariance2to3):
     """``MatchCovariance`` (Module/Covariance/Project2to3.py:113-191).  Returns ``[N,3,3]`` float64 on the CPU like the
     reference (its result is pushed straight into the CPU map, Odometry/MACVO.py:265-266) and clamps the caller's
@@ -165,6 +192,113 @@ class HIP_MatchCovariance(ICovariance2to3):
             "min_depth_cov": lambda c: _num(c) and c > 0.0,
             "device": _is_device,
         })
+
+    _cov_model = "match"      # what a HIP_Modifier_* around this class fuses into the kernel
+
+
+class HIP_GaussianMixtureCovariance(ICovariance2to3):
+    """``GaussianMixtureCovariance`` (Project2to3.py:194-262 + Utility/Math.py:66-93) on the GPU: the depth and depth-variance patches,
+    weights below 1e-3 dropped and renormalised, var = (E[c + z^2] - mean^2) / 2, no ``min_depth_cov`` clamp (reference quirks kept;
+    a row whose weights all fall below the threshold is NaN, as in the reference).  The reference's config has no ``device`` key: the
+    depth map's device is used (the GPU when it is on the CPU).  Returns CPU float64 like ``HIP_MatchCovariance``."""
+
+    _cov_model = "gmm"
+
+    def estimate(self, frame, kp, depth_est, depth_cov, flow_cov) -> torch.Tensor:
+        return self.estimate_device(frame, kp, depth_est, depth_cov, flow_cov).cpu()
+
+    def estimate_device(self, frame, kp, depth_est, depth_cov, flow_cov, rot: torch.Tensor | None = None):
+        return _obs_cov_device("gmm", self.config, frame, kp, depth_est, depth_cov, flow_cov, rot)
+
+    @classmethod
+    def is_valid_config(cls, config: SimpleNamespace | None) -> None:
+        cls._enforce_config_spec(config, {
+            "kernel_size": lambda k: isinstance(k, int) and k > 0 and (k % 2 == 1) and k <= 31,
+            "match_cov_default": lambda c: _num(c) and c > 0.0,
+            "min_flow_cov": lambda c: _num(c) and c > 0.0,
+            "min_depth_cov": lambda c: _num(c) and c > 0.0,
+        })
+
+
+class HIP_NoCovariance(ICovariance2to3):
+    """``NoCovariance`` (Project2to3.py:48-57): the float64 identity for every observation; ``flow_cov`` is left untouched."""
+
+    _cov_model = "none"
+
+    def estimate(self, frame, kp, depth_est, depth_cov, flow_cov) -> torch.Tensor:
+        return self.estimate_device(frame, kp, depth_est, depth_cov, flow_cov).cpu()
+
+    def estimate_device(self, frame, kp, depth_est, depth_cov, flow_cov, rot: torch.Tensor | None = None):
+        return _obs_cov_device("none", self.config, frame, kp, depth_est, depth_cov, flow_cov, rot)
+
+    @classmethod
+    def is_valid_config(cls, config: SimpleNamespace | None) -> None:
+        return
+
+
+class _HIPCovModifier(ICovariance2to3):
+    """A modifier (Project2to3.py:275-323): the submodule comes from the registry like the reference's.  Over a HIP model (possibly through
+    other HIP modifiers, at most 4 in all) the whole chain runs in the model's kernel, in fp64 before any rotation; over anything else
+    the reference's torch operation is applied to the submodule's result."""
+
+    _modifier = ""
+
+    def __init__(self, config: SimpleNamespace):
+        super().__init__(config)
+        self.submodule = ICovariance2to3.instantiate(config.type, config.args)
+
+    def _chain(self):
+        """(the HIP model at the bottom, modifiers innermost first) or None when the chain cannot be fused."""
+        sub = self.submodule
+        if isinstance(sub, _HIPCovModifier):
+            inner = sub._chain()
+            ch = None if inner is None else (inner[0], inner[1] + (self._modifier,))
+        elif getattr(type(sub), "_cov_model", None):
+            ch = (sub, (self._modifier,))
+        else:
+            ch = None
+        return ch if (ch is not None and len(ch[1]) <= 4) else None
+
+    def estimate(self, frame, kp, depth_est, depth_cov, flow_cov) -> torch.Tensor:
+        if self._chain() is None:
+            return self._modify(self.submodule.estimate(frame, kp, depth_est, depth_cov, flow_cov))
+        return self.estimate_device(frame, kp, depth_est, depth_cov, flow_cov).cpu()
+
+    def estimate_device(self, frame, kp, depth_est, depth_cov, flow_cov, rot: torch.Tensor | None = None):
+        ch = self._chain()
+        if ch is None:
+            raise TypeError(f"{type(self).__name__}: the submodule {type(self.submodule).__name__} is not a HIP covariance model")
+        base, mods = ch
+        return _obs_cov_device(base._cov_model, base.config, frame, kp, depth_est, depth_cov, flow_cov, rot, mods)
+
+    @classmethod
+    def is_valid_config(cls, config: SimpleNamespace | None) -> None:
+        ICovariance2to3.is_valid_config(config)
+
+
+class HIP_Modifier_Diagonalize(_HIPCovModifier):
+    """``Modifier_Diagonalize`` (Project2to3.py:281-301): the off-diagonal entries of the submodule's covariances set to zero."""
+
+    _modifier = "diag"
+
+    @staticmethod
+    def _modify(covs: torch.Tensor) -> torch.Tensor:
+        for i in range(3):
+            for j in range(3):
+                if i != j:
+                    covs[..., i, j] = 0.0
+        return covs
+
+
+class HIP_Modifier_Normalize(_HIPCovModifier):
+    """``Modifier_Normalize`` (Project2to3.py:305-323): ``cov /= det(cov)`` — the determinant itself, as the reference computes it."""
+
+    _modifier = "normalize"
+
+    @staticmethod
+    def _modify(covs: torch.Tensor) -> torch.Tensor:
+        covs /= torch.det(covs).unsqueeze(-1).unsqueeze(-1)
+        return covs
 
 
 # ----------------------------------------------------------------------------------------------- optimizer
