@@ -377,6 +377,24 @@ int mv_obs_cov_pair_lanes(int model, int32_t modifiers, const float* depth_map0,
                           const mvMatchCovParams* params /* host */, int lanes, const int32_t* n_live, int cap, mvStream_t stream);
 
 /* -------------------------------------------------------------------------------------------
+ * TartanMotionNet motion prior (Module/MotionModel.py:90-123): everything around the learned PoseNet.
+ *
+ * mv_motion_input_lanes: TartanStereoVOMotion.inference's input (StereoVO_Interface.py:177-188) for `lanes` frames in one launch:
+ *   flow  lane l at flow + l * flow_lane_stride   [2, H, W] fp32 (the temporal match flow, match01.flow)
+ *   depth lane l at depth + l * depth_lane_stride [H, W] fp32    (depth1.depth)
+ *   out   [lanes, 5, 112, 160] fp32 = cat(flow * 0.05, depth transform, intrinsic layer) after cropAndResize(x, (112, 160)):
+ *         centre crop to (112 s, 160 s), s = min(H / 112, W / 160) (an odd difference keeps one more row / column), bilinear with
+ *         align_corners = True.  Depth: reciprocal * bl_fx * 0.02, NaN -> 0, +-inf -> +-FLT_MAX, clamp(min = 0), / bl_fx / 0.005.
+ *         Intrinsic layer with the reference's swapped arguments: channel 3 = (col - cy + 0.5) / fy, channel 4 = (row - cx + 0.5) / fx.
+ *   bl_fx = frame_baseline * fx as a double, rounded once.  Requires H >= 112 and W >= 160.
+ * mv_pose_exp_compose: out[i] = prev[i] @ Exp(se3(raw[i] * pose_norm)) in fp32 (PyPose right multiplication, fp32 small-angle branch);
+ *   prev / out [n, 7] (tx ty tz qx qy qz qw), raw row i at raw + i * raw_stride (6 values), pose_norm [6] (0.13 x 3, 0.013 x 3). */
+int mv_motion_input_lanes(int lanes, int H, int W, const float* flow, long long flow_lane_stride, const float* depth,
+                          long long depth_lane_stride, float fx, float fy, float cx, float cy, float bl_fx, float* out, mvStream_t stream);
+int mv_pose_exp_compose(int n, const float* prev, const float* raw, long long raw_stride, const float* pose_norm, float* out,
+                        mvStream_t stream);
+
+/* -------------------------------------------------------------------------------------------
  * A17-A22  covariance-weighted two-frame pose-graph solve, batched over independent problems.
  * Replaces TwoFrame_PGO._optimize (Module/Optimization/TwoFramePGO/Optimizer.py:81-102), the residual
  * graphs + analytic Jacobians (Module/Optimization/TwoFramePGO/Graphs.py:33-231), LM_analytic.step
@@ -451,6 +469,25 @@ int mv_pgo_solve_posed_dev(int nprob, const int32_t* offsets, const int32_t* n_l
                            int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
                            uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
                            float* out_pose_f32, float* pose_sink, mvStream_t stream);
+/* The motion-model forms (TartanMotionNet: Odometry/MACVO.py:193-194,273-281,303-307): as mv_pgo_solve_posed / mv_pgo_solve_posed_dev, but the rows are
+ * rotated into the world frame with init_pose (the previous pose) while LM starts from start_pose [nprob, 7] (the motion-model prior); a problem with
+ * fewer than min_points valid rows returns start_pose.  The entry points above compile to the same kernels as before. */
+int mv_pgo_solve_posed_motion(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type, const float* init_pose,
+                              const float* start_pose, const float* intrinsics, const float* baseline, const float* pos_Tc, const double* cov_Tc,
+                              float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
+                              const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov,
+                              const double* obs2_covTc, int filter_flags, float filter_min_depth, float filter_max_depth,
+                              const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out, int min_points,
+                              const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32, float* pose_sink,
+                              mvStream_t stream);
+int mv_pgo_solve_posed_motion_dev(int nprob, const int32_t* offsets, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
+                                  const float* init_pose, const float* start_pose, const float* intrinsics, const float* baseline,
+                                  const float* pos_Tc, const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot,
+                                  const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp, const float* pixel2_disp_cov,
+                                  const float* pixel2_uv_cov, const double* obs2_covTc, int filter_flags, float filter_min_depth,
+                                  float filter_max_depth, const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out,
+                                  int min_points, const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32,
+                                  float* pose_sink, mvStream_t stream);
 
 /* -------------------------------------------------------------------------------------------
  * A23  PWC-Net local correlation, forward (the reference's only hand-written CUDA kernel; non-default matcher path).
@@ -698,7 +735,12 @@ typedef struct {
     mvLMParams lm;
     int32_t cov_model;         /* MV_COV_* of all three covariance calls of a frame (both observation sets and the mapping tail); 0 = MatchCovariance */
     int32_t cov_modifiers;     /* modifier chain of mv_obs_cov; 0 = none */
+    int32_t motion_model;      /* MV_MOTION_*: 0 = StaticMotionModel (the prior of a frame = the previous pose); 1 = TartanMotionNet: every tracked frame's
+                                  PoseNet input is written to MV_FB_MOTION_IN right behind its epilogue, the caller runs the PoseNet and attaches its raw
+                                  output with mv_frame_pipe_set_motion before the frame's finish; prior = previous pose @ Exp(raw * pose_norm) is the LM
+                                  start, the pose of a frame without tracked keypoints and the frame's prior in mv_frame_pipe_map_append */
 } mvFramePipeConfig;
+enum { MV_MOTION_STATIC = 0, MV_MOTION_TARTAN = 1 };
 
 /* what the learned layers hand over for one estimate_pair (device pointers, fp32 unless noted) */
 typedef struct {
@@ -725,7 +767,10 @@ enum {
     /* dense-mapping tail of the newest finished frame (mapping = 1; rows = what mv_frame_pipe_map_points was called with) */
     MV_FB_MAP_UV, MV_FB_MAP_D, MV_FB_MAP_SDD, MV_FB_MAP_TC, MV_FB_MAP_TW, MV_FB_MAP_COV /* fp64 [.,9] */, MV_FB_MAP_COLOR /* u8 [.,3] */,
     /* device-driven frame (round 6): the permutation head the front launch drew, int64 [lanes, num_point]; int32 [lanes, 2] = selected keypoints, candidates */
-    MV_FB_PERM, MV_FB_LIVE
+    MV_FB_PERM, MV_FB_LIVE,
+    /* motion_model = MV_MOTION_TARTAN: fp32 [lanes, 5, 112, 160] PoseNet input of an enqueued frame (age counts enqueued frames; valid on a stream after
+     * mv_frame_pipe_wait_motion_input); fp32 [lanes, 7] motion-model prior of a finished frame (age 0 / 1) */
+    MV_FB_MOTION_IN, MV_FB_PRIOR
 };
 
 size_t mv_frame_pipe_arena_bytes(const mvFramePipeConfig* cfg);           /* 0 = invalid configuration */
@@ -740,6 +785,12 @@ int mv_frame_pipe_set_pose(mvFramePipe* p, const float* pose7_host);      /* [la
 /* frontend half of a frame; inputs must be complete on `in_stream` (an event is recorded there) and stay untouched
  * until the frame's lookups ran.  with_selector = 0 for the very first frame. */
 int mv_frame_pipe_enqueue(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_stream, int with_selector);
+/* motion_model = MV_MOTION_TARTAN.  mv_frame_pipe_wait_motion_input: `stream` waits until the PoseNet input of the newest enqueued frame (MV_FB_MOTION_IN,
+ * age 0) is written.  mv_frame_pipe_set_motion: attaches the raw PoseNet output [lanes, 6] fp32 (device, before pose_norm) to the newest enqueued tracked
+ * frame: copied on `stream` into the pipe's slot for that frame's finish, with an event the frame's solve waits for; call it after the PoseNet's last read
+ * of MV_FB_MOTION_IN (the slot is rewritten behind that event) and before the frame's finish. */
+int mv_frame_pipe_wait_motion_input(mvFramePipe* p, mvStream_t stream);
+int mv_frame_pipe_set_motion(mvFramePipe* p, const float* motion_dev, mvStream_t stream);
 /* optional: issue the volume GEMM of the NEXT frame (the one the next mv_frame_pipe_enqueue will complete) right away; it
  * only needs fmap1 / fmap2 and a free volume buffer, so the host can queue it before it blocks on the previous frame's
  * candidate count and the GEMM stream never waits for the host.  At most one GEMM ahead. */

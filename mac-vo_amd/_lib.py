@@ -20,7 +20,8 @@ MV_KP_NODEPTH, MV_KP_FULL, MV_KP_MAPPING = 0, 1, 2
 MV_GRAPH_ICP, MV_GRAPH_REPROJ, MV_GRAPH_DISP = 0, 1, 2
 MV_COV_MATCH, MV_COV_GMM, MV_COV_NONE = 0, 1, 2
 MV_COVMOD_DIAG, MV_COVMOD_NORMALIZE = 1, 2
-ABI_VERSION = 6
+MV_MOTION_STATIC, MV_MOTION_TARTAN = 0, 1
+ABI_VERSION = 7
 MV_MAX_LANES = 64        # include/macvo_hip.h
 
 
@@ -58,7 +59,7 @@ class mvFramePipeConfig(C.Structure):
         "cov_kernel_size", "mapping", "map_num_point", "map_mask_width", "async_backend")] + [(n, C.c_float) for n in (
         "fx", "fy", "cx", "cy", "baseline", "bl_fx", "bl_fx_sq", "match_cov_default", "max_match_cov", "max_depth_cov",
         "max_depth", "min_flow_cov_sq", "min_depth_cov", "filter_min_depth", "map_max_depth", "map_max_depth_cov")] + [("lm", mvLMParams)] + [
-        (n, C.c_int32) for n in ("cov_model", "cov_modifiers")]
+        (n, C.c_int32) for n in ("cov_model", "cov_modifiers", "motion_model")]
 
 
 class mvMapStores(C.Structure):
@@ -88,7 +89,7 @@ class mvFrameInputs(C.Structure):
 FB_NAMES = ("VOLUME", "TOKENS", "DISPARITY", "DISPARITY_COV", "DEPTH", "DEPTH_COV", "MATCH_FLOW", "MATCH_COV", "CAND",
             "COUNT", "STATS", "KP0", "KP0F", "KP1", "INBOUND", "VALS", "SIGMA0", "SIGMA1", "POS_TC", "POS_TW", "ROT", "COV0",
             "COV0W", "COV1", "VALID", "NVALID", "POSE64", "INFO", "POSE", "MAP_UV", "MAP_D", "MAP_SDD", "MAP_TC", "MAP_TW", "MAP_COV",
-            "MAP_COLOR", "PERM", "LIVE")
+            "MAP_COLOR", "PERM", "LIVE", "MOTION_IN", "PRIOR")
 FB = {n: i for i, n in enumerate(FB_NAMES)}
 
 _P = C.c_void_p
@@ -127,6 +128,14 @@ SIGNATURES = {
     "mv_match_cov_pair": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(mvMatchCovParams), C.c_int, _P]),
     "mv_obs_cov": (C.c_int, [C.c_int, C.c_int32, _P, _P, _P, _P, _P, _P, C.POINTER(mvMatchCovParams), C.c_int, _P, _P, _P, _P]),
     "mv_obs_cov_pair_lanes": (C.c_int, [C.c_int, C.c_int32] + [_P] * 12 + [C.POINTER(mvMatchCovParams), C.c_int, _P, C.c_int, _P]),
+    "mv_motion_input_lanes": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_longlong, _P, C.c_longlong] + [C.c_float] * 5 + [_P, _P]),
+    "mv_pose_exp_compose": (C.c_int, [C.c_int, _P, _P, C.c_longlong, _P, _P, _P]),
+    "mv_pgo_solve_posed_motion": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int] + [_P] * 15 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int,
+                                                                                         C.POINTER(mvLMParams)] + [_P] * 5),
+    "mv_pgo_solve_posed_motion_dev": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int] + [_P] * 15 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P,
+                                                                                                         C.c_int, C.POINTER(mvLMParams)] + [_P] * 5),
+    "mv_frame_pipe_wait_motion_input": (C.c_int, [_P, _P]),
+    "mv_frame_pipe_set_motion": (C.c_int, [_P, _P, _P]),
     "mv_lm_default_params": (None, [C.POINTER(mvLMParams)]),
     "mv_pgo_solve": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int,
                                C.POINTER(mvLMParams), _P, _P, _P, _P]),

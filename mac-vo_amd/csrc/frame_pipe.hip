@@ -27,6 +27,7 @@
 // stage never overwrites data a still-running stage of another stream reads (maps x3, everything else x2) and the
 // cross-stream hazards are closed with events (see `enqueue` / `finish`).
 #include "common.h"
+#include "motion_dev.h"
 #include <atomic>
 #include <chrono>
 #include <stdio.h>
@@ -64,6 +65,7 @@ namespace {
 #define MV_MAX_PENDING 3
 #endif
 constexpr int MAX_PENDING = MV_MAX_PENDING, N_MAPS = MAX_PENDING + 2, N_CAND = MAX_PENDING + 1, N_PERM = 4, N_INEV = 8, MAX_VOL = 4, MAX_LK = 2;
+constexpr int N_MOT = 8;   // motion_model: ring of per-finish motion slots (raw PoseNet output + composed prior of finish g -> slot g % N_MOT)
 constexpr int N_BEV = 8;   // ring of per-finish backend events (finish g -> slot g % N_BEV): the device-driven frame waits for the exact finish whose reads free a slot
 
 struct Maps {
@@ -269,6 +271,19 @@ struct mvFramePipe {
     double st_enq = 0, st_enq_lookups = 0, st_enq_seg = 0, st_vol = 0, st_fin = 0, st_calls = 0;   // us inside enqueue (its lookups / its selector segment), enqueue_volume, finish_device
     bool stop;
     int async_rc;           // first error of an asynchronously issued job, reported by the next call
+    // TartanMotionNet prior (c.motion_model = MV_MOTION_TARTAN).  PoseNet input per maps slot (= per enqueued frame, written behind the frame's epilogue,
+    // read by the caller's PoseNet); raw motion and composed prior per FINISH index g (slot g % N_MOT): mv_frame_pipe_set_motion writes the raw motion on
+    // the caller's stream (e_motion_set), the finish composes prev pose @ Exp(raw * pose_norm) on the solve's stream (e_motion_used) into `prior`, which the
+    // solve starts from and mv_frame_pipe_map_append registers.  A slot is rewritten only behind the events of its previous user.
+    float* motion_in[N_MAPS];
+    hipEvent_t e_motion_in[N_MAPS], e_motion_read[N_MAPS];
+    bool motion_in_valid[N_MAPS], motion_read_valid[N_MAPS];
+    float* motion_raw[N_MOT];
+    float* prior[N_MOT];
+    float* pose_norm;       // [6] fp32
+    hipEvent_t e_motion_set[N_MOT], e_motion_used[N_MOT];
+    bool motion_used_valid[N_MOT];
+    long motion_g[N_MOT];   // finish index whose raw motion the slot holds (-1: none)
 };
 
 // cross-stream dependency; when the event has already fired no barrier packet is queued at all (every
@@ -399,6 +414,14 @@ static size_t carve(mvFramePipe* p, char* base) {
         p->mp_color = a.take<uint8_t>(3 * MP);
     }
     for (int k = 0; k < 3; ++k) p->pose[k] = a.take<float>(L * 7);
+    if (c.motion_model == MV_MOTION_TARTAN) {
+        for (int k = 0; k < N_MAPS; ++k) p->motion_in[k] = a.take<float>(L * (size_t)motion::OUT_C * motion::OUT_H * motion::OUT_W);
+        for (int k = 0; k < N_MOT; ++k) {
+            p->motion_raw[k] = a.take<float>(L * 6);
+            p->prior[k] = a.take<float>(L * 7);
+        }
+        p->pose_norm = a.take<float>(6);
+    }
     p->intr = a.take<float>(L * 4);
     p->bl = a.take<float>(L);
     p->offs = a.take<int32_t>(L + 1);
@@ -421,6 +444,7 @@ static int check_config(const mvFramePipeConfig* c) {
     MV_CHECK_ARG(c->volume_split != MV_VOL_ENC16 || (c->feat_dtype == MV_F16 && c->radius == 4));   // (the lookup reads fp16 cells)
     MV_CHECK_ARG(!(c->volume_split == 2 || c->volume_split == 3) || c->layout == MV_LAYOUT_HWC);   // (the packed form takes either layout)
     MV_CHECK_ARG(c->cov_model >= MV_COV_MATCH && c->cov_model <= MV_COV_NONE && mv_cov_modifiers_ok(c->cov_modifiers));
+    MV_CHECK_ARG(c->motion_model == MV_MOTION_STATIC || (c->motion_model == MV_MOTION_TARTAN && motion::crop_scale(c->H, c->W) >= 1));
     return MV_OK;
 }
 
@@ -473,6 +497,10 @@ extern "C" void mv_frame_pipe_destroy(mvFramePipe* p) {
     for (int k = 0; k < N_CAND; ++k) ev(p->e_cand[k]);
     for (int k = 0; k < 2; ++k) { ev(p->e_posed[k]); ev(p->e_solved[k]); }
     for (auto e : p->e_backend) ev(e);
+    for (auto e : p->e_motion_in) ev(e);
+    for (auto e : p->e_motion_read) ev(e);
+    for (auto e : p->e_motion_set) ev(e);
+    for (auto e : p->e_motion_used) ev(e);
     ev(p->e_pgo);
     for (int k = 0; k < N_CAND; ++k) ev(p->e_lk[k]);
     for (auto e : p->e_seg) ev(e);
@@ -532,6 +560,13 @@ static int create_impl(mvFramePipe* p) {
         MV_HIP(hipHostMalloc((void**)&p->h_count[k], (size_t)p->lanes * 4 * sizeof(int32_t), hipHostMallocDefault));
     }
     for (auto& e : p->e_backend) MV_HIP(mk(&e));
+    if (c.motion_model == MV_MOTION_TARTAN) {
+        for (auto& e : p->e_motion_in) MV_HIP(mk(&e));
+        for (auto& e : p->e_motion_read) MV_HIP(mk(&e));
+        for (auto& e : p->e_motion_set) MV_HIP(mk(&e));
+        for (auto& e : p->e_motion_used) MV_HIP(mk(&e));
+    }
+    for (auto& g : p->motion_g) g = -1;
     for (int k = 0; k < 2; ++k) {
         MV_HIP(mk(&p->e_posed[k]));
         MV_HIP(mk(&p->e_solved[k]));
@@ -572,6 +607,8 @@ static int create_impl(mvFramePipe* p) {
     MV_HIP(hipMemcpyAsync(p->intr, intr.data(), intr.size() * sizeof(float), hipMemcpyHostToDevice, p->s_main));
     MV_HIP(hipMemcpyAsync(p->bl, bl.data(), bl.size() * sizeof(float), hipMemcpyHostToDevice, p->s_main));
     MV_HIP(hipMemcpyAsync(p->offs, offs.data(), offs.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->s_main));
+    static const float pose_norm[6] = {0.13f, 0.13f, 0.13f, 0.013f, 0.013f, 0.013f};   // TartanStereoVONetInterface.pose_norm (StereoVO_Interface.py:51-53)
+    if (p->pose_norm) MV_HIP(hipMemcpyAsync(p->pose_norm, pose_norm, sizeof(pose_norm), hipMemcpyHostToDevice, p->s_main));
     { const char* e = getenv("MV_PIPE_FUSE_BACKEND"); p->fuse_backend = (e && atoi(e) == 0) ? 0 : 1; }
     p->time_detail = 1;
     MV_HIP(hipStreamSynchronize(p->s_main));   // the host vectors die here
@@ -805,6 +842,19 @@ static int ensure_chain_events(mvFramePipe* p, long f, int cand_slot) {
     return MV_OK;
 }
 
+// TartanMotionNet: the PoseNet input of the frame in maps slot m, behind the frame's epilogue on the segment's stream.  The slot was last read by the
+// caller's PoseNet of frame f - N_MAPS (event of its mv_frame_pipe_set_motion, recorded on the caller's thread before this segment was described).
+static int issue_motion_input(mvFramePipe* p, int m, hipStream_t s) {
+    const mvFramePipeConfig& c = p->c;
+    if (p->motion_read_valid[m]) MV_TRY(wait_if_pending(s, p->e_motion_read[m]));
+    const Maps& mp = p->maps[m];
+    MV_TRY(mv_motion_input_lanes(p->lanes, c.H, c.W, mp.match_flow, 2LL * p->plane, mp.depth, (long long)p->plane, c.fx, c.fy, c.cx, c.cy, c.bl_fx,
+                                 p->motion_in[m], s));
+    MV_HIP(hipEventRecord(p->e_motion_in[m], s));
+    p->motion_in_valid[m] = true;
+    return MV_OK;
+}
+
 static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
     const mvFramePipeConfig& c = p->c;
     const mvFrameInputs* in = &d.in;
@@ -863,6 +913,7 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
                                           p->lanes, s));
     }
     const Pending pd{m, d.maps_prev, k, with_selector, ti};
+    if (with_selector && c.motion_model == MV_MOTION_TARTAN && !(c.selector_mode == MV_KP_NODEPTH && fuse_epi && !up)) MV_TRY(issue_motion_input(p, m, s));
     if (with_selector) {
         mvKpSelectParams sp{c.H, c.W, c.selector_mode, c.kp_kernel_size, c.kp_mask_width, c.max_depth, c.max_depth_cov,
                             c.max_match_cov};
@@ -873,6 +924,7 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
                                                      mp.depth, mp.depth_cov, nullptr, mp.match_flow, mp.match_cov, nullptr,
                                                      nullptr, &sp, kp_ws, p->kp_ws_bytes, p->cand[k], p->count[k],
                                                      p->stats[k], p->lanes, s));
+            if (c.motion_model == MV_MOTION_TARTAN) MV_TRY(issue_motion_input(p, m, s));   // (the fused launch wrote the maps)
         } else if (c.selector_mode == MV_KP_NODEPTH) {
             MV_TRY(mv_kp_select_lanes(mp.match_cov, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sp, kp_ws,
                                       p->kp_ws_bytes, p->cand[k], p->count[k], p->stats[k], p->lanes, s));
@@ -1007,6 +1059,37 @@ extern "C" int mv_frame_pipe_enqueue(mvFramePipe* p, const mvFrameInputs* in, mv
     return MV_OK;
 }
 
+extern "C" int mv_frame_pipe_wait_motion_input(mvFramePipe* p, mvStream_t stream) {
+    MV_CHECK_ARG(p && p->c.motion_model == MV_MOTION_TARTAN && !p->pending.empty() && p->pending.back().f == p->n_enq - 1);
+    // the newest frame's selector segment (which writes the PoseNet input) must have been issued
+    const long sj = p->pending.back().sel_job;
+    if (sj >= 0) MV_TRY(wait_issued(p, sj + 1));
+    else MV_TRY(flush_deferred(p));
+    const int m = (int)((p->n_enq - 1) % N_MAPS);
+    MV_CHECK_ARG(p->motion_in_valid[m]);
+    MV_HIP(hipStreamWaitEvent((hipStream_t)stream, p->e_motion_in[m], 0));
+    return MV_OK;
+}
+
+extern "C" int mv_frame_pipe_set_motion(mvFramePipe* p, const float* motion_dev, mvStream_t stream) {
+    MV_CHECK_ARG(p && motion_dev && p->c.motion_model == MV_MOTION_TARTAN && !p->pending.empty() && p->pending.back().f == p->n_enq - 1);
+    const long g = p->n_fin + (long)p->pending.size() - 1;   // the finish index of the newest enqueued tracked frame
+    const int k = (int)(g % N_MOT);
+    hipStream_t s = (hipStream_t)stream;
+    // the slot's previous user, finish g - N_MOT, composed its prior on the solve's stream: that launch must have been ISSUED before its event means anything
+    if (p->motion_used_valid[k]) {
+        MV_TRY(wait_issued(p, g - N_MOT + 1));
+        MV_HIP(hipStreamWaitEvent(s, p->e_motion_used[k], 0));
+    }
+    MV_HIP(hipMemcpyAsync(p->motion_raw[k], motion_dev, (size_t)p->lanes * 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    MV_HIP(hipEventRecord(p->e_motion_set[k], s));   // recorded before the frame's finish is queued: its solve waits for it
+    p->motion_g[k] = g;
+    const int m = (int)((p->n_enq - 1) % N_MAPS);     // ... and the PoseNet's reads of this frame's input are behind this point of `stream`
+    MV_HIP(hipEventRecord(p->e_motion_read[m], s));
+    p->motion_read_valid[m] = true;
+    return MV_OK;
+}
+
 extern "C" int mv_frame_pipe_wait_candidates(mvFramePipe* p, int32_t* n_cand) {
     MV_CHECK_ARG(p && n_cand && !p->pending.empty());
     MV_TRY(selector_of_front_issued(p));
@@ -1101,6 +1184,7 @@ static int finish_host(mvFramePipe* p, const int32_t* n_sel, float* pose_sink, F
         MV_CHECK_ARG(n_sel[l] >= 0 && n_sel[l] <= c.num_point);
         n_max = n_sel[l] > n_max ? n_sel[l] : n_max;
     }
+    MV_CHECK_ARG(c.motion_model != MV_MOTION_TARTAN || p->motion_g[p->n_fin % N_MOT] == p->n_fin);   // mv_frame_pipe_set_motion for this frame first
     j.pd = p->pending.front();
     p->pending.pop_front();
     j.g = p->n_fin;
@@ -1147,11 +1231,19 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     if (n_max == 0 && p->dev_draw)
         MV_HIP(hipMemcpyAsync(p->rp_state[(g + 1) & 1], p->rp_state[g & 1], (size_t)L * (size_t)mv_randperm_state_words() * sizeof(uint32_t),
                               hipMemcpyDeviceToDevice, s));
+    const bool motion = c.motion_model == MV_MOTION_TARTAN;
+    float* const prior = motion ? p->prior[g % N_MOT] : nullptr;
+    if (motion) {   // prior = previous pose @ Exp(raw * pose_norm), on the solve's stream behind the previous solve and the caller's set_motion
+        MV_HIP(hipStreamWaitEvent(p->s_side, p->e_motion_set[g % N_MOT], 0));
+        MV_TRY(mv_pose_exp_compose(L, p->pose[j.pose_from], p->motion_raw[g % N_MOT], 6, p->pose_norm, prior, p->s_side));
+        MV_HIP(hipEventRecord(p->e_motion_used[g % N_MOT], p->s_side));
+        p->motion_used_valid[g % N_MOT] = true;
+    }
     if (n_max == 0) {   // nothing to track in any lane: the poses stay at the motion-model prior (MACVO.py:303-307)
         // The pose slots still rotate (MV_FB_POSE age a = the pose after the a-th newest finish) and the slot's events are
         // refreshed, so that everything keyed on "slot of finish g" (mv_frame_pipe_map_append, result views) sees this frame and
         // not the one two finishes back.  In-order on the side stream: behind the previous solve, no extra wait needed.
-        MV_HIP(hipMemcpyAsync(p->pose[j.pose_to], p->pose[j.pose_from], (size_t)L * 7 * sizeof(float), hipMemcpyDeviceToDevice,
+        MV_HIP(hipMemcpyAsync(p->pose[j.pose_to], motion ? prior : p->pose[j.pose_from], (size_t)L * 7 * sizeof(float), hipMemcpyDeviceToDevice,
                               p->s_side));
         if (j.pose_sink)
             MV_HIP(hipMemcpyAsync(j.pose_sink, p->pose[j.pose_to], (size_t)L * 7 * sizeof(float), hipMemcpyDeviceToDevice, p->s_side));
@@ -1256,10 +1348,24 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     if (ti >= 0) MV_HIP(hipEventRecord(p->tv6[ti], ss));
     const size_t N = (size_t)cap;
     const size_t LN = (size_t)L * N;   // value table is [11, lanes, cap]: each of its rows is one concatenated per-point column
-    if (j.device) {
+    if (j.device && motion) {
+        MV_TRY(mv_pgo_solve_posed_motion_dev(L, p->offs, b.live_dev, 2, cap, c.graph_type, pose, prior, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w,
+                                             b.rot, b.kp1, b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, c.filters, c.filter_min_depth,
+                                             c.max_depth, b.inbound, b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm, b.pose64, b.info,
+                                             p->pose[j.pose_to], j.pose_sink, ss));
+        MV_HIP(hipEventRecord(p->e_solved[k], ss));
+        MV_HIP(hipEventRecord(p->e_pgo, ss));
+    } else if (j.device) {
         MV_TRY(mv_pgo_solve_posed_dev(L, p->offs, b.live_dev, 2, cap, c.graph_type, pose, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w, b.rot, b.kp1,
                                       b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, c.filters, c.filter_min_depth, c.max_depth, b.inbound,
                                       b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm, b.pose64, b.info, p->pose[j.pose_to], j.pose_sink, ss));
+        MV_HIP(hipEventRecord(p->e_solved[k], ss));
+        MV_HIP(hipEventRecord(p->e_pgo, ss));
+    } else if (p->fuse_backend && motion) {
+        MV_TRY(mv_pgo_solve_posed_motion(L, p->offs, n_sel, cap, c.graph_type, pose, prior, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w, b.rot,
+                                         b.kp1, b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, c.mapping ? -1 : c.filters,
+                                         c.filter_min_depth, c.max_depth, b.inbound, b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm, b.pose64,
+                                         b.info, p->pose[j.pose_to], j.pose_sink, ss));
         MV_HIP(hipEventRecord(p->e_solved[k], ss));
         MV_HIP(hipEventRecord(p->e_pgo, ss));
     } else if (p->fuse_backend) {
@@ -1275,7 +1381,7 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     } else {
         MV_TRY(mv_pose_apply_lanes(pose, b.pos_Tc, b.cov0, L, n_sel, cap, b.pos_Tw, b.rot, b.cov0w, ss));
         MV_HIP(hipEventRecord(p->e_posed[k], ss));
-        MV_TRY(mv_pgo_solve(L, p->offs, c.graph_type, pose, p->intr, p->bl, b.pos_Tw, b.cov0w, b.kp1, b.vals + 4 * LN,
+        MV_TRY(mv_pgo_solve(L, p->offs, c.graph_type, motion ? prior : pose, p->intr, p->bl, b.pos_Tw, b.cov0w, b.kp1, b.vals + 4 * LN,
                             b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, b.valid, c.min_num_point, &c.lm, b.pose64, b.info,
                             p->pose[j.pose_to], ss));
         if (j.pose_sink)
@@ -1489,7 +1595,7 @@ extern "C" int mv_frame_pipe_map_append(mvFramePipe* p, const mvMapStores* store
     f.cov0 = b.cov0; f.cov1 = b.cov1; f.pos_Tw = b.pos_Tw; f.cov0_world = b.cov0w;
     f.color = color_dev;
     f.K = K_dev; f.T_BS = T_BS_dev;
-    f.prior_pose = p->pose[p->prior_slot];
+    f.prior_pose = p->c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];   // push_keyframe(frame1, est_pose) (MACVO.py:282)
     f.baseline = baseline;
     f.time_ns = time_ns;
     f.out_frame_idx = nullptr;
@@ -1731,6 +1837,9 @@ extern "C" int mv_frame_pipe_buffer(mvFramePipe* p, int which, int age, void** p
         case MV_FB_POSE: if (age > 1) break; *ptr = p->pose[(p->pose_cur + 3 - age) % 3]; *count = 7 * L; return MV_OK;
         case MV_FB_PERM: if (!b) break; *ptr = b->perm; *count = N; return MV_OK;
         case MV_FB_LIVE: if (!b || !p->dev_draw) break; *ptr = b->live_dev; *count = 2 * L; return MV_OK;
+        case MV_FB_MOTION_IN: if (c.motion_model != MV_MOTION_TARTAN || !front(N_MAPS)) break; *ptr = p->motion_in[f % N_MAPS];
+            *count = L * (size_t)motion::OUT_C * motion::OUT_H * motion::OUT_W; return MV_OK;
+        case MV_FB_PRIOR: if (c.motion_model != MV_MOTION_TARTAN || !back()) break; *ptr = p->prior[g % N_MOT]; *count = 7 * L; return MV_OK;
         case MV_FB_MAP_UV: if (!c.mapping || age) break; *ptr = p->mp_uvf; *count = 2 * (size_t)p->mp_rows; return MV_OK;
         case MV_FB_MAP_D: if (!c.mapping || age) break; *ptr = p->mp_d; *count = (size_t)p->mp_rows; return MV_OK;
         case MV_FB_MAP_SDD: if (!c.mapping || age) break; *ptr = p->mp_sdd; *count = (size_t)p->mp_rows; return MV_OK;

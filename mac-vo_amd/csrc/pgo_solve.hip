@@ -34,6 +34,7 @@
 // in speculative rounds — score against it as before.  A build reduces 28 values instead of 55.
 // Problems with more points than threads (and the one-wave throughput variant's > 64) keep the full 55-value build.
 #include "common.h"
+#include <type_traits>
 #include "pgo_math.h"
 #include "pose_apply_dev.h"
 #include "obs_filter_dev.h"
@@ -185,8 +186,19 @@ __device__ __forceinline__ void reduce_many(double* __restrict__ v, double* __re
     }
 }
 
-template <int GT, int NW>
-__global__ __launch_bounds__(64 * NW) void pgo_solve_kernel(PgoArgs a, mvLMParams lm) {
+// NWM = waves per problem (NW), + PGO_MOTION for the motion-model form (mv_pgo_solve_posed_motion*): LM starts from start_pose instead of init_pose
+// (which still rotates the rows into the world frame), and a problem below min_points returns start_pose.  The other instantiations keep their
+// names and their argument block (PgoArgs), so their code does not change.
+constexpr int PGO_MOTION = 64;
+struct PgoMotionArgs : PgoArgs {
+    const float* start_pose;
+};
+
+template <int GT, int NWM>
+__global__ __launch_bounds__(64 * (NWM % PGO_MOTION)) void pgo_solve_kernel(typename std::conditional<(NWM >= PGO_MOTION), PgoMotionArgs, PgoArgs>::type a,
+                                                                           mvLMParams lm) {
+    constexpr int NW = NWM % PGO_MOTION;
+    constexpr bool MOTION = NWM >= PGO_MOTION;
     constexpr int PGO_THREADS = 64 * NW;
     __shared__ double red_tab[NW][NRED];
     __shared__ __attribute__((aligned(16))) double red_fin[NW == 4 ? NRED + 1 : 1];
@@ -234,10 +246,12 @@ __global__ __launch_bounds__(64 * NW) void pgo_solve_kernel(PgoArgs a, mvLMParam
     }
 
     Pose P;
+    const float* start = a.init_pose;
+    if constexpr (MOTION) start = a.start_pose;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) P.t[k] = (double)a.init_pose[7 * prob + k];
+    for (int k = 0; k < 3; ++k) P.t[k] = (double)start[7 * prob + k];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) P.q[k] = (double)a.init_pose[7 * prob + 3 + k];
+    for (int k = 0; k < 4; ++k) P.q[k] = (double)start[7 * prob + 3 + k];
     pose_finish(P);
 
     PointData<GT> mine;
@@ -554,6 +568,7 @@ __global__ __launch_bounds__(64 * NW) void pgo_solve_kernel(PgoArgs a, mvLMParam
     }
 }
 
+
 }  // namespace
 
 #ifdef MV_PGO_STAMPS
@@ -589,6 +604,7 @@ struct PoseApplyArgs {   // mv_pgo_solve_posed's extra arguments (all null for t
     const float* vals = nullptr;
     uint8_t* valid_out = nullptr;
     int32_t* count_out = nullptr;
+    const float* start_pose = nullptr;   // mv_pgo_solve_posed_motion(_dev): the LM start (init_pose then only rotates the rows)
 };
 
 static int pgo_solve_impl(int nprob, const int32_t* offsets, int graph_type, const float* init_pose,
@@ -604,6 +620,7 @@ static int pgo_solve_impl(int nprob, const int32_t* offsets, int graph_type, con
     PgoArgs a{offsets, init_pose, intrinsics, baseline, pos_Tw, cov_Tw, pixel2_uv, pixel2_d, pixel2_disp,
               pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, out_pose, out_info, out_pose_f32, 1};
     a.pose_sink = pa.pose_sink;
+    MV_CHECK_ARG(!pa.start_pose || (pa.pos_Tc && nprob < 512));   // (the motion kernel is the 4-wave form)
     if (pa.pos_Tc) {
         MV_CHECK_ARG(nprob <= MV_MAX_LANES && (pa.n_live || pa.live_dev));
         a.live_dev = pa.live_dev;
@@ -643,7 +660,8 @@ static int pgo_solve_impl(int nprob, const int32_t* offsets, int graph_type, con
     const bool wide = nprob < 512;
     dim3 grid(nprob), block(wide ? 256 : 64);
 #define MV_PGO(G)                                                                             \
-    if (wide) hipLaunchKernelGGL((pgo_solve_kernel<G, 4>), grid, block, 0, s, a, *params);    \
+    if (pa.start_pose) hipLaunchKernelGGL((pgo_solve_kernel<G, 4 + PGO_MOTION>), grid, block, 0, s, PgoMotionArgs{a, pa.start_pose}, *params); \
+    else if (wide) hipLaunchKernelGGL((pgo_solve_kernel<G, 4>), grid, block, 0, s, a, *params);    \
     else hipLaunchKernelGGL((pgo_solve_kernel<G, 1>), grid, block, 0, s, a, *params)
     switch (graph_type) {
         case MV_GRAPH_ICP:
@@ -675,6 +693,14 @@ extern "C" int mv_pgo_solve(int nprob, const int32_t* offsets, int graph_type, c
                           pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, params, out_pose, out_info, out_pose_f32,
                           PoseApplyArgs{nullptr, nullptr, nullptr, nullptr, nullptr}, stream);
 }
+
+static int solve_posed(int nprob, const int32_t* offsets, const int32_t* n_live, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
+                       const float* init_pose, const float* start_pose, const float* intrinsics, const float* baseline, const float* pos_Tc,
+                       const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
+                       const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
+                       int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
+                       uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
+                       float* out_pose_f32, float* pose_sink, mvStream_t stream);
 
 extern "C" int mv_pgo_solve_posed(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type, const float* init_pose,
                                   const float* intrinsics, const float* baseline, const float* pos_Tc, const double* cov_Tc,
@@ -715,4 +741,57 @@ extern "C" int mv_pgo_solve_posed_dev(int nprob, const int32_t* offsets, const i
     }
     return pgo_solve_impl(nprob, offsets, graph_type, init_pose, intrinsics, baseline, pos_Tw, cov_Tw, pixel2_uv, pixel2_d, pixel2_disp,
                           pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, params, out_pose, out_info, out_pose_f32, pa, stream);
+}
+
+// The motion-model forms (TartanMotionNet, MACVO.py:193-194,273-281,303-307): the rows are rotated into the world frame with init_pose (the previous
+// pose), LM starts from start_pose (the prior), a problem below min_points returns start_pose.  pgo_solve_kernel<G, 4, true>; the entry points above
+// keep their instantiations.
+static int solve_posed(int nprob, const int32_t* offsets, const int32_t* n_live, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
+                       const float* init_pose, const float* start_pose, const float* intrinsics, const float* baseline, const float* pos_Tc,
+                       const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
+                       const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
+                       int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
+                       uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
+                       float* out_pose_f32, float* pose_sink, mvStream_t stream) {
+    MV_CHECK_ARG(pos_Tc && pos_Tw && start_pose && (n_live || (n_live_dev && n_live_stride >= 1)) && (!cov_Tc || cov_Tw));
+    MV_CHECK_ARG(nprob < 512);
+    PoseApplyArgs pa{pos_Tc, cov_Tc, out_rot, pose_sink, n_live};
+    pa.live_dev = n_live_dev;
+    pa.live_stride = n_live_dev ? n_live_stride : 0;
+    pa.start_pose = start_pose;
+    if (filter_flags >= 0) {
+        pa.filter_flags = filter_flags; pa.filter_min_depth = filter_min_depth; pa.filter_max_depth = filter_max_depth; pa.cap = cap;
+        pa.inbound = inbound; pa.vals = vals; pa.valid_out = valid; pa.count_out = count_out;
+    }
+    return pgo_solve_impl(nprob, offsets, graph_type, init_pose, intrinsics, baseline, pos_Tw, cov_Tw, pixel2_uv, pixel2_d, pixel2_disp,
+                          pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, params, out_pose, out_info, out_pose_f32, pa, stream);
+}
+
+extern "C" int mv_pgo_solve_posed_motion(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type, const float* init_pose,
+                                         const float* start_pose, const float* intrinsics, const float* baseline, const float* pos_Tc, const double* cov_Tc,
+                                         float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
+                                         const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov,
+                                         const double* obs2_covTc, int filter_flags, float filter_min_depth, float filter_max_depth,
+                                         const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out, int min_points,
+                                         const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32, float* pose_sink,
+                                         mvStream_t stream) {
+    MV_CHECK_ARG(n_live);
+    return solve_posed(nprob, offsets, n_live, nullptr, 0, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw,
+                       out_rot, pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, filter_flags, filter_min_depth,
+                       filter_max_depth, inbound, vals, valid, count_out, min_points, params, out_pose, out_info, out_pose_f32, pose_sink, stream);
+}
+
+extern "C" int mv_pgo_solve_posed_motion_dev(int nprob, const int32_t* offsets, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
+                                             const float* init_pose, const float* start_pose, const float* intrinsics, const float* baseline,
+                                             const float* pos_Tc, const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot,
+                                             const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp, const float* pixel2_disp_cov,
+                                             const float* pixel2_uv_cov, const double* obs2_covTc, int filter_flags, float filter_min_depth,
+                                             float filter_max_depth, const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out,
+                                             int min_points, const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32,
+                                             float* pose_sink, mvStream_t stream) {
+    MV_CHECK_ARG(n_live_dev);
+    return solve_posed(nprob, offsets, nullptr, n_live_dev, n_live_stride, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc,
+                       pos_Tw, cov_Tw, out_rot, pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, filter_flags,
+                       filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params, out_pose, out_info, out_pose_f32,
+                       pose_sink, stream);
 }

@@ -14,7 +14,7 @@ the light-weight mirrors below, which keep the reference's contract:
   (``Module/Frontend/Matching.py:21-40``);
 * the abstract methods of ``IFrontend`` (``Module/Frontend/Frontend.py:38-118``), ``IKeypointSelector``
   (``Module/KeypointSelector.py:17-48``), ``ICovariance2to3`` (``Module/Covariance/Project2to3.py:16-44``) and
-  ``IOptimizer`` (``Module/Optimization/Interface.py:40-241``).
+  ``IOptimizer`` (``Module/Optimization/Interface.py:40-241``), ``IMotionModel`` (``Module/MotionModel.py:16-42``).
 """
 from __future__ import annotations
 
@@ -118,6 +118,7 @@ if USING_REFERENCE:  # pragma: no cover
     IKeypointSelector = _RefModule.IKeypointSelector
     ICovariance2to3 = _RefModule.ICovariance2to3
     IOptimizer = _RefModule.IOptimizer
+    IMotionModel = _RefModule.IMotionModel
     GraphInput, GraphOutput = _RefGraphInput, _RefGraphOutput
 else:
 
@@ -200,6 +201,18 @@ else:
 
         @abstractmethod
         def select_point(self, frame, numPoint: int, depth0_est, depth1_est, match_est) -> torch.Tensor: ...
+
+    class IMotionModel(ABC, ConfigurablePlugin):
+        """Module/MotionModel.py:16-42: the initial guess of the incoming frame's pose under the global frame."""
+
+        def __init__(self, config: SimpleNamespace):
+            self.config = config
+
+        @abstractmethod
+        def predict(self, frame, flow: torch.Tensor | None, depth: torch.Tensor | None): ...
+
+        @abstractmethod
+        def update(self, pose) -> None: ...
 
     class ICovariance2to3(ABC, ConfigurablePlugin):
         def __init__(self, config: SimpleNamespace):

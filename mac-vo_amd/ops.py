@@ -878,3 +878,64 @@ def obs_filter(inbound: torch.Tensor | None, cov1: torch.Tensor | None, cov2: to
     L.check(lib.mv_obs_filter(_ptr(_u8(inbound)), _ptr(c1), _ptr(c2), _ptr(vv), flags, min_depth, max_depth, N,
                               valid.data_ptr(), count.data_ptr(), _stream()), "mv_obs_filter")
     return valid, count
+
+
+# ---------------------------------------------------------------------------------------------- TartanMotionNet motion prior
+MOTION_IN_SHAPE = (5, 112, 160)                                   # the PoseNet input of one frame (StereoVO_Interface.py:179)
+POSE_NORM = (0.13, 0.13, 0.13, 0.013, 0.013, 0.013)               # TartanStereoVONetInterface.pose_norm (StereoVO_Interface.py:51-53)
+_pose_norm_dev: dict = {}
+
+
+def pose_norm(device) -> torch.Tensor:
+    """``pose_norm`` as the fp32 device tensor the reference multiplies with (cached per device)."""
+    dev = torch.device(device)
+    t = _pose_norm_dev.get(dev)
+    if t is None:
+        t = _pose_norm_dev[dev] = torch.tensor(POSE_NORM, dtype=torch.float32, device=dev)
+    return t
+
+
+def motion_input(flow: torch.Tensor, depth: torch.Tensor, fx: float, fy: float, cx: float, cy: float, baseline: float,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """TartanStereoVOMotion.inference's PoseNet input (StereoVO_Interface.py:177-188) in one launch (``mv_motion_input_lanes``):
+    temporal flow ``[2,H,W]`` / ``[1,2,H,W]`` or per lane ``[L,2,H,W]`` and depth ``[H,W]`` / ``[1,1,H,W]`` / ``[L,1,H,W]`` / ``[L,H,W]``
+    -> ``[L,5,112,160]`` fp32.  ``fx, fy, cx, cy, baseline`` are the frame's Python floats (``meta.fx``, ``meta.frame_baseline``...);
+    the intrinsic layer keeps the reference's swapped (height, width) arguments."""
+    lib = L.load()
+    flow = _req(flow, torch.float32, "flow")
+    depth = _req(depth, torch.float32, "depth")
+    H, W = flow.shape[-2:]
+    if flow.shape[-3] != 2 or depth.shape[-2:] != (H, W):
+        raise L.MacvoHipError(f"motion_input: flow [.,2,H,W] and depth [.,H,W] must agree (got {tuple(flow.shape)}, {tuple(depth.shape)})")
+    lanes = flow.numel() // (2 * H * W)
+    if depth.numel() != lanes * H * W:
+        raise L.MacvoHipError(f"motion_input: {lanes} flow lanes but {depth.numel() // (H * W)} depth planes")
+    if H < MOTION_IN_SHAPE[1] or W < MOTION_IN_SHAPE[2]:
+        raise L.MacvoHipError(f"motion_input: a {H}x{W} frame does not cover the {MOTION_IN_SHAPE[1]}x{MOTION_IN_SHAPE[2]} PoseNet input")
+    if out is None:
+        out = torch.empty((lanes,) + MOTION_IN_SHAPE, dtype=torch.float32, device=flow.device)
+    else:
+        assert out.shape == (lanes,) + MOTION_IN_SHAPE and out.dtype == torch.float32 and out.is_contiguous()
+    bl_fx = float(baseline) * float(fx)            # the reference's Python double product, rounded once to fp32 by ctypes
+    L.check(lib.mv_motion_input_lanes(lanes, H, W, flow.data_ptr(), 2 * H * W, depth.data_ptr(), H * W, fx, fy, cx, cy, bl_fx,
+                                      out.data_ptr(), _stream()), "mv_motion_input_lanes")
+    return out
+
+
+def pose_exp_compose(prev: torch.Tensor, raw: torch.Tensor, norm: torch.Tensor | None = None,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """``prev @ pp.se3(raw * pose_norm).Exp()`` in fp32 (MotionModel.py:112, StereoVO_Interface.py:194): ``prev [n,7]`` or ``[7]``, raw
+    PoseNet output ``[n,6]`` or ``[6]`` -> ``[n,7]`` (``[7]`` for a single pose)."""
+    lib = L.load()
+    single = prev.dim() == 1
+    prev = _req(prev.reshape(-1, 7), torch.float32, "prev")
+    raw = _req(raw.reshape(-1, 6), torch.float32, "raw")
+    n = prev.shape[0]
+    if raw.shape[0] != n:
+        raise L.MacvoHipError(f"pose_exp_compose: {n} poses but {raw.shape[0]} motions")
+    nrm = pose_norm(prev.device) if norm is None else _req(norm.reshape(6), torch.float32, "norm")
+    if out is None:
+        out = torch.empty((n, 7), dtype=torch.float32, device=prev.device)
+    L.check(lib.mv_pose_exp_compose(n, prev.data_ptr(), raw.data_ptr(), 6, nrm.data_ptr(), out.data_ptr(), _stream()),
+            "mv_pose_exp_compose")
+    return out.reshape(7) if single else out

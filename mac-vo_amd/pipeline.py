@@ -110,6 +110,10 @@ class HotPathConfig:
     # (Modifier_Normalize), innermost first.  cov_config_fields() maps a reference `cov.obs` block onto these two fields.
     cov_model: str = "match"
     cov_modifiers: tuple[str, ...] = ()
+    # motion model (`motion` of the experiment YAML, Module/MotionModel.py): "static" = StaticMotionModel (the prior of frame t is the
+    # pose of frame t-1) | "tartan" = TartanMotionNet (prior = pose of frame t-1 @ Exp(PoseNet motion); HotPath's `pose_net` supplies the
+    # network).  motion_config_fields() maps a reference `motion` block onto this field.
+    motion_model: str = "static"
 
 
 _COV_TYPES = {"MatchCovariance": "match", "GaussianMixtureCovariance": "gmm", "NoCovariance": "none",
@@ -144,6 +148,19 @@ def cov_config_fields(obs) -> dict:
             except (KeyError, AttributeError):
                 pass
     return out
+
+
+_MOTION_TYPES = {"StaticMotionModel": "static", "TartanMotionNet": "tartan", "HIP_TartanMotionNet": "tartan"}
+
+
+def motion_config_fields(block) -> dict:
+    """A reference ``motion`` block (``{type, args}`` as a dict or SimpleNamespace) -> ``{"motion_model": ...}`` for :class:`HotPathConfig`.
+    ``TartanMotionNet`` (every configuration the paper reports: Paper_Reproduce.yaml, Ablation_Study/*) -> "tartan"; its ``weight`` /
+    ``device`` args belong to the PoseNet, which the caller hands to :class:`HotPath` as ``pose_net``."""
+    t = _ns_get(block, "type")
+    if t not in _MOTION_TYPES:
+        raise ValueError(f"motion model {t!r} has no HIP form (one of {sorted(set(_MOTION_TYPES))})")
+    return {"motion_model": _MOTION_TYPES[t]}
 
 
 @dataclass
@@ -187,12 +204,23 @@ class FrameResult:
     n_valid: torch.Tensor | None       # [1] int32 GPU surviving observations
     extras: dict = field(default_factory=dict)
     map_points: "ops.MapPoints | None" = None   # mapping mode: the frame's dense map points (valid after sync_pose())
+    prior: torch.Tensor | None = None  # motion_model "tartan": [7] fp32 GPU — the frame's motion-model prior (the LM start)
+
+
+def _check_motion(cfg: HotPathConfig) -> None:
+    if cfg.motion_model not in ("static", "tartan"):
+        raise ops.L.MacvoHipError(f"motion_model must be 'static' or 'tartan', not {cfg.motion_model!r}")
 
 
 class HotPath:
+    """``pose_net`` (motion_model "tartan"): the PoseNet of TartanMotionNet, ``[lanes, 5, 112, 160] -> [lanes, 6]`` raw network output
+    (before ``pose_norm``), called on the current stream between a frame's frontend and its finish."""
+
     def __init__(self, cam: Camera, cfg: HotPathConfig | None = None, device: str | torch.device = "cuda",
-                 keep_extras: bool = False):
+                 keep_extras: bool = False, pose_net=None):
         self.cam, self.cfg = cam, cfg or HotPathConfig()
+        _check_motion(self.cfg)
+        self.pose_net = pose_net
         self.dev = torch.device(device)
         self.keep_extras = keep_extras
         self.lm = ops.lm_default_params()
@@ -335,22 +363,49 @@ class HotPath:
                                     mask_width=c.map_mask_width, max_depth=c.map_max_depth, max_depth_cov=c.map_max_depth_cov)
             host_count_m = torch.empty((4,), dtype=torch.int32, pin_memory=True)
             host_count_m.copy_(cands_m.count, non_blocking=True)
+        motion_in = None
+        if c.motion_model == "tartan":   # TartanMotionNet.predict's input (MotionModel.py:112): temporal flow + depth of frame t
+            motion_in = ops.motion_input(maps1.flow, maps1.depth, cam.fx, cam.fy, cam.cx, cam.cy, cam.baseline)
         ev = torch.cuda.Event()
         ev.record()
         self.maps_prev_for_next = maps1
         pend = _Pending(maps0, maps1, cands, host_count, ev)
+        pend.motion_in = motion_in
+        if motion_in is not None and self.pose_net is not None:
+            # the PoseNet right behind the frame's frontend (between enqueue and finish, MACVO.py:194): in run() it is queued before the NEXT
+            # frame's frontend, so the frame's finish does not wait for that
+            pend.motion = self.pose_net(motion_in)
+            pend.motion_ev = torch.cuda.Event()
+            pend.motion_ev.record()
         pend.cands_m, pend.host_count_m, pend.image0 = cands_m, host_count_m, self._prev_image
         self._prev_image = x.image
         return pend
 
+    def pose_motion(self, pend: "_Pending") -> torch.Tensor:
+        """The raw PoseNet output ``[1, 6]`` of a pending frame (motion_model "tartan"), on the current stream."""
+        if self.pose_net is None:
+            raise ops.L.MacvoHipError("motion_model='tartan' needs a pose_net ([lanes,5,112,160] -> [lanes,6])")
+        return self.pose_net(pend.motion_in)
+
     @traced("Odom_Runtime")
-    def finish(self, pend: "_Pending", pose_sink: torch.Tensor | None = None) -> FrameResult:
+    def finish(self, pend: "_Pending", pose_sink: torch.Tensor | None = None, motion: torch.Tensor | None = None) -> FrameResult:
         """Host randperm (bit-exact indices) + the pose-dependent half: tracking, back-projection, covariances, filter,
         PGO.  The solve runs on a side stream (the GPU analogue of the reference's optimizer child process,
         Optimization/Interface.py:80-96): the next frame's frontend overlaps it, the next frame's back-projection
-        waits for it."""
+        waits for it.  motion_model "tartan": ``motion`` is the frame's raw PoseNet output (default: ``pose_net`` on the frame's
+        ``motion_in``); the prior ``pose of frame t-1 @ Exp(motion * pose_norm)`` is where LM starts and what a lost-track frame keeps,
+        while the world registration still uses the pose of frame t-1 (MACVO.py:193-194,273-281,303-307)."""
         c, cam = self.cfg, self.cam
         maps0, maps1, cands = pend.maps0, pend.maps1, pend.cands
+        motion_ev = None
+        if c.motion_model == "tartan":
+            if motion is None and pend.motion is not None:
+                motion, motion_ev = pend.motion, pend.motion_ev
+            else:
+                if motion is None:
+                    motion = self.pose_motion(pend)
+                motion_ev = torch.cuda.Event()
+                motion_ev.record()
         pend.event.synchronize()
         cands._n = int(pend.host_count[0])
         back, side = self._back, self._side
@@ -363,11 +418,25 @@ class HotPath:
             n = kp0.shape[0]
             if self._pgo_done is not None:
                 back.wait_event(self._pgo_done)   # self.pose of the previous frame is produced on the PGO stream
+            prev_pose = prior = self.pose
+
+            def compose():   # the prior, behind the PoseNet: only the solve (and a frame without keypoints) needs it
+                back.wait_event(motion_ev)
+                return ops.pose_exp_compose(prev_pose, motion.reshape(6).to(torch.float32))
             if n == 0:
-                return FrameResult(self.pose, None, None, kp0, None)
+                if motion_ev is None:
+                    return FrameResult(self.pose, None, None, kp0, None)
+                prior = compose()
+                # nothing tracked: the frame keeps the motion-model prior (MACVO.py:303-307), and the next prior composes onto it
+                done = torch.cuda.Event()
+                done.record(back)
+                self._pgo_done = done
+                self._pgo_keep = (self._pgo_keep[1] if self._pgo_keep else None, (motion, kp0, cands, pend, prev_pose))
+                self.pose = prior
+                return FrameResult(prior, None, None, kp0, None, prior=prior)
 
             tr = ops.kp_track(kp0, maps1.flow, maps1.flow_cov, maps0, maps1, c.edgewidth, c.match_cov_default)
-            pos0_Tc, pos_Tw, rot = ops.backproject(tr.kp0_uv, tr.vals[0], cam.K4, self.pose, want_rot=True)
+            pos0_Tc, pos_Tw, rot = ops.backproject(tr.kp0_uv, tr.vals[0], cam.K4, prev_pose, want_rot=True)
             if c.cov_model == "match" and not tuple(c.cov_modifiers):
                 cov0, cov0_w, cov1 = ops.match_cov_pair(maps0.depth, tr.kp0_uv, tr.sigma0, maps1.depth, tr.kp1_uv, tr.sigma1,
                                                         *cam.K4, rot=rot, kernel_size=c.cov_kernel_size,
@@ -378,9 +447,11 @@ class HotPath:
                                                       modifiers=c.cov_modifiers, rot=rot, kernel_size=c.cov_kernel_size,
                                                       min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov)
             valid, n_valid = ops.obs_filter(tr.inbound, cov0, cov1, tr.vals, c.filters, c.filter_min_depth, self._max_depth)
+            if motion_ev is not None:
+                prior = compose()
 
             batch = ops.PGOBatch(
-                offsets=self._offs[n], init_pose=self.pose.reshape(1, 7), intrinsics=self._intr, baseline=self._bl,
+                offsets=self._offs[n], init_pose=prior.reshape(1, 7), intrinsics=self._intr, baseline=self._bl,
                 pos_Tw=pos_Tw, pixel2_uv=tr.kp1_uv, cov_Tw=cov0_w, pixel2_d=tr.vals[4], pixel2_disp=tr.vals[5],
                 pixel2_disp_cov=tr.vals[6], pixel2_uv_cov=tr.sigma1, obs2_covTc=cov1, valid=valid)
             ready = torch.cuda.Event()
@@ -401,16 +472,17 @@ class HotPath:
                 pend.cands_m._n = int(pend.host_count_m[0])
                 with torch.cuda.stream(back):
                     muv = pend.cands_m.finish(c.map_num_point)
-                    map_pts = ops.map_points(muv, maps0.depth, maps0.depth_cov, cam.K4, batch.init_pose, image=pend.image0,
+                    map_pts = ops.map_points(muv, maps0.depth, maps0.depth_cov, cam.K4, prev_pose.reshape(1, 7), image=pend.image0,
                                              match_cov_default=c.match_cov_default, kernel_size=c.cov_kernel_size,
                                              min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov, cov_model=c.cov_model,
                                              cov_modifiers=c.cov_modifiers)
                     self._map_done = torch.cuda.Event()
                     self._map_done.record(back)
         self._pgo_done = done
-        self._pgo_keep = (self._pgo_keep[1] if self._pgo_keep else None, (batch, tr, cov0, cov1, maps0, maps1, kp0, pos0_Tc, cands, pend))  # keep 2 frames of cross-stream tensors alive
+        self._pgo_keep = (self._pgo_keep[1] if self._pgo_keep else None, (batch, tr, cov0, cov1, maps0, maps1, kp0, pos0_Tc, cands, pend,
+                                                                           prev_pose, motion))  # keep 2 frames of cross-stream tensors alive
         self.pose = new_pose.reshape(7)
-        res = FrameResult(self.pose, pose64, info, kp0, n_valid)
+        res = FrameResult(self.pose, pose64, info, kp0, n_valid, prior=prior if motion_ev is not None else None)
         res.map_points = map_pts
         if self.keep_extras:
             res.extras = dict(tracked=tr, cov0=cov0, cov0_w=cov0_w, cov1=cov1, valid=valid, pos_Tw=pos_Tw,
@@ -461,6 +533,9 @@ class _Pending:
     cands_m: "ops.KeypointCandidates | None" = None     # mapping mode
     host_count_m: torch.Tensor | None = None
     image0: torch.Tensor | None = None
+    motion_in: torch.Tensor | None = None                # motion_model "tartan": the PoseNet input [1, 5, 112, 160]
+    motion: torch.Tensor | None = None                   # ... the PoseNet's raw output, when HotPath.pose_net ran it behind the enqueue
+    motion_ev: "torch.cuda.Event | None" = None
 
 
 # ====================================================================================== native driver (default)
@@ -535,6 +610,11 @@ class _NativeResult:
         return self._per_lane("POSE", torch.float32, (7,))
 
     @property
+    def prior(self):
+        """motion_model "tartan": fp32 [7], this lane's motion-model prior (the LM start); None for the static model."""
+        return self._per_lane("PRIOR", torch.float32, (7,)) if self._hp.cfg.motion_model == "tartan" else None
+
+    @property
     def kp0_uv(self):
         return self._rows("KP0", torch.int64, (2,))
 
@@ -565,8 +645,10 @@ class NativeHotPath:
     lane order — a lane seeded like a stand-alone run therefore selects exactly the keypoints of that stand-alone run."""
 
     def __init__(self, cam: Camera, cfg: HotPathConfig | None = None, device: str | torch.device = "cuda",
-                 keep_extras: bool = False, lanes: int = 1, generators: "list | None" = None):
+                 keep_extras: bool = False, lanes: int = 1, generators: "list | None" = None, pose_net=None):
         self.cam, self.cfg = cam, cfg or HotPathConfig()
+        _check_motion(self.cfg)
+        self.pose_net = pose_net   # motion_model "tartan": [lanes, 5, 112, 160] -> [lanes, 6], run right behind each tracked frame's enqueue
         if self.cfg.mapping and lanes != 1:
             raise ops.L.MacvoHipError("the dense-mapping tail (mapping=True) runs one sequence per pipe (lanes == 1), as the reference does")
         if self.cfg.use_graphs:
@@ -634,7 +716,8 @@ class NativeHotPath:
             max_depth_cov=c.max_depth_cov, max_depth=max_depth, min_flow_cov_sq=c.min_flow_cov ** 2,
             min_depth_cov=c.min_depth_cov, filter_min_depth=c.filter_min_depth, mapping=int(c.mapping), map_num_point=c.map_num_point,
             map_mask_width=c.map_mask_width, async_backend=0 if c.async_backend is None else (1 if c.async_backend else -1), map_max_depth=c.map_max_depth, map_max_depth_cov=c.map_max_depth_cov, lm=self.lm,
-            cov_model=ops._cov_model(c.cov_model), cov_modifiers=ops.cov_modifier_chain(c.cov_modifiers))
+            cov_model=ops._cov_model(c.cov_model), cov_modifiers=ops.cov_modifier_chain(c.cov_modifiers),
+            motion_model=L.MV_MOTION_TARTAN if c.motion_model == "tartan" else L.MV_MOTION_STATIC)
         nbytes = lib.mv_frame_pipe_arena_bytes(C.byref(pc))
         if nbytes == 0:
             raise L.MacvoHipError("mv_frame_pipe_arena_bytes: invalid configuration")
@@ -775,12 +858,25 @@ class NativeHotPath:
     def enqueue_frontend(self, x: FrameInputs):
         assert self._n_enq >= 1, "call initialize() with the first frame"
         self._enqueue(x, True)
+        if self.cfg.motion_model == "tartan":
+            self._motion()
         if self.cfg.mapping:
             self._images.append(self._prev_image)
             self._prev_image = x.image
         if getattr(self, "_map", None) is not None:
             self._times.append(int(x.time_ns))
         return x
+
+    def _motion(self) -> None:
+        """TartanMotionNet of the frame just enqueued: the PoseNet on its input (MV_FB_MOTION_IN, written behind the frame's epilogue) on the
+        current stream, its raw output attached to the frame's finish (mv_frame_pipe_set_motion) — between enqueue and finish, as run_pair does."""
+        if self.pose_net is None:
+            raise ops.L.MacvoHipError("motion_model='tartan' needs a pose_net ([lanes,5,112,160] -> [lanes,6])")
+        lib, st = self._lib, ops._stream()
+        ops.L.check(lib.mv_frame_pipe_wait_motion_input(self._pipe, st), "mv_frame_pipe_wait_motion_input")
+        x = self._view("MOTION_IN", 0, torch.float32, (self.lanes,) + ops.MOTION_IN_SHAPE)
+        raw = self.pose_net(x).reshape(self.lanes, 6).to(torch.float32).contiguous()
+        ops.L.check(lib.mv_frame_pipe_set_motion(self._pipe, raw.data_ptr(), st), "mv_frame_pipe_set_motion")
 
     def enqueue_volume(self, x: FrameInputs) -> None:
         """Issue only the cost-volume GEMM of the frame the NEXT :meth:`enqueue_frontend` call will complete (same ``x``).

@@ -30,7 +30,7 @@ import os
 import torch
 
 from . import ops
-from .interfaces import (GraphInput, GraphOutput, ICovariance2to3, IFrontend, IKeypointSelector, IMatcher, IOptimizer,
+from .interfaces import (GraphInput, GraphOutput, ICovariance2to3, IFrontend, IKeypointSelector, IMatcher, IMotionModel, IOptimizer,
                          IStereoDepth, _is_device)
 
 
@@ -883,3 +883,81 @@ def FunctionCorrelation(tenFirst, tenSecond):
     if torch.is_grad_enabled() and (tenFirst.requires_grad or tenSecond.requires_grad):
         raise NotImplementedError("macvo_amd FunctionCorrelation is forward-only; wrap the call in torch.no_grad()")
     return ops.local_corr81(tenFirst.float(), tenSecond.float())
+
+
+class HIP_TartanMotionNet(IMotionModel):
+    """``TartanMotionNet`` (Module/MotionModel.py:90-123): the pose of the incoming frame = previous pose @ Exp(PoseNet motion).  The
+    PoseNet (TartanVO's ``flowPoseNet``) stays PyTorch-ROCm; everything around it runs in HIP — the intrinsic layer, the three
+    crop + bilinear passes, the depth transform and the channel concatenation in ONE launch (``ops.motion_input``), the
+    ``pose_norm`` scaling, se3 Exp and the SE3 compose in another (``ops.pose_exp_compose``).  Same YAML ``args`` (weight, device).
+    Inside a MAC-VO checkout the network is the reference's in-tree ``TartanStereoVOMotion`` model; ``weight: ""`` keeps its random
+    initialisation.  ``pose_net`` (class attribute or constructor argument) injects a ``[n,5,112,160] -> [n,6]`` callable instead."""
+
+    pose_net = None     # injectable: tests and stand-alone runs without the MAC-VO checkout
+
+    def __init__(self, config: SimpleNamespace, pose_net=None):
+        super().__init__(config)
+        net = pose_net if pose_net is not None else type(self).pose_net
+        if net is None:
+            net = _build_tartan_posenet(self.config)
+        self.net = net
+        self.prev_pose: torch.Tensor | None = None
+
+    @torch.inference_mode()
+    def predict(self, frame, flow: torch.Tensor | None, depth: torch.Tensor | None):
+        if self.prev_pose is None:     # MACVO.initialize (:160): identity, and it becomes the previous pose
+            self.prev_pose = torch.tensor([0, 0, 0, 0, 0, 0, 1.0], dtype=torch.float32, device=self.config.device)
+            return _as_se3(self.prev_pose.clone())
+        assert flow is not None and depth is not None, "Motion model requires flow and depth to predict motion"
+        meta = frame.stereo
+        dev = torch.device(self.config.device)
+        x = ops.motion_input(flow.to(dev, torch.float32), depth.to(dev, torch.float32), float(meta.fx), float(meta.fy), float(meta.cx),
+                             float(meta.cy), float(meta.frame_baseline))
+        raw = self.net(x)
+        prev = _raw_pose(self.prev_pose).to(dev, torch.float32).reshape(7)
+        self.prev_pose = ops.pose_exp_compose(prev, raw.reshape(6).to(torch.float32))
+        return _as_se3(self.prev_pose)
+
+    def update(self, pose) -> None:
+        self.prev_pose = _raw_pose(pose).to(self.config.device, torch.float32).reshape(7)
+
+    @classmethod
+    def is_valid_config(cls, config: SimpleNamespace | None) -> None:
+        cls._enforce_config_spec(config, {"weight": lambda s: isinstance(s, str), "device": _is_device})
+
+
+def _raw_pose(p) -> torch.Tensor:
+    return p.tensor() if hasattr(p, "tensor") and callable(p.tensor) else torch.as_tensor(p)
+
+
+def _as_se3(pose: torch.Tensor):
+    """A PyPose SE3 LieTensor where PyPose is importable (inside the reference), the plain [7] tensor otherwise."""
+    try:
+        import pypose as pp  # type: ignore
+
+        return pp.SE3(pose)
+    except ImportError:
+        return pose
+
+
+def _build_tartan_posenet(config: SimpleNamespace):
+    """The reference's ``TartanStereoVOMotion`` network (StereoVO_Interface.py:21-51: StereoVONet with stereoNormFactor 0.02,
+    poseDepthNormFactor 0.25), with its weights unless ``weight`` is empty; returns its ``flowPoseNet`` as a callable."""
+    try:
+        from Module.Network.TartanVOStereo.StereoVO import StereoVONet  # type: ignore
+    except Exception as e:  # noqa: BLE001
+        raise ops.L.MacvoHipError("HIP_TartanMotionNet needs the MAC-VO checkout on sys.path (Module.Network.TartanVOStereo) "
+                                  "or an injected pose_net") from e
+    model = StereoVONet(flowNormFactor=1.0, stereoNormFactor=0.02, poseDepthNormFactor=0.25)
+    if config.weight:
+        from Module.Network.TartanVOStereo.StereoVO_Interface import TartanStereoVONetInterface  # type: ignore
+
+        holder = SimpleNamespace(model=model)
+        TartanStereoVONetInterface.loadWeight(holder, config.weight)
+        model = holder.model
+    model = model.to(config.device).eval()
+
+    @torch.inference_mode()
+    def pose_net(x):
+        return model.flowPoseNet(x, scale_disp=1.0)
+    return pose_net
