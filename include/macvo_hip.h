@@ -228,7 +228,12 @@ int mv_convex_upsample_m(const float* flow, const void* mask, int mask_dtype, fl
  * The CPU `torch.randperm` (:331,:404,:98) stays on the host so indices are bit-exact; use
  * mv_kp_gather afterwards.
  */
-enum { MV_KP_NODEPTH = 0, MV_KP_FULL = 1, MV_KP_MAPPING = 2 };
+enum { MV_KP_NODEPTH = 0, MV_KP_FULL = 1, MV_KP_MAPPING = 2,
+       /* selectors that look at no map (mv_kp_random_lanes / mv_kp_grid, and as a frame pipe's selector_mode): */
+       MV_KP_RANDOM = 3,      /* RandomSelector (KeypointSelector.py:103-118) */
+       MV_KP_GRID = 4,        /* GridSelector (:216-247) */
+       MV_KP_EXPLICIT = 5     /* frame pipe only: every frame's keypoints come from the caller (mv_frame_pipe_finish_keypoints[_dev]) */
+};
 
 typedef struct {
     int32_t H, W;
@@ -713,7 +718,8 @@ typedef struct {
                                   layout packed on the device (mv_volume_pack, beside the previous frame's GEMM) +
                                   mv_corr_volume_packed, shapes it does not cover run the exact kernel | 3 | 2: fp32 HWC features through the round-1 plane split, multiplied
                                   as MV_BF16X3 / MV_BF16X2 */
-    int32_t selector_mode;     /* MV_KP_NODEPTH | MV_KP_FULL */
+    int32_t selector_mode;     /* MV_KP_NODEPTH | MV_KP_FULL | MV_KP_RANDOM | MV_KP_GRID | MV_KP_EXPLICIT (the last three enqueue no selector kernels, use
+                                  kp_mask_width only, and size the per-keypoint tables by mv_frame_pipe_table_rows) */
     int32_t kp_kernel_size, kp_mask_width;
     int32_t num_point;         /* keypoints per frame (200) */
     int32_t edgewidth;         /* strict border of the tracked keypoints (32) */
@@ -757,7 +763,8 @@ typedef struct {
 
 /* buffers reported by mv_frame_pipe_buffer (element counts, not bytes; MV_FB_VOLUME's element is the volume CELL: fp32, or fp16 — 2 bytes —
  * when the pipe was created with volume_split = MV_VOL_ENC16); each has a leading [lanes] dimension, per-keypoint
- * tables are [lanes, num_point, .] (a lane's live rows = its n_sel), MV_FB_VALS is [11, lanes, num_point] */
+ * tables are [lanes, cap, .] with cap = mv_frame_pipe_table_rows(config) (= num_point except for MV_KP_GRID; a lane's live rows = its n_sel),
+ * MV_FB_VALS is [11, lanes, cap] */
 enum {
     MV_FB_VOLUME = 0, MV_FB_TOKENS, MV_FB_DISPARITY, MV_FB_DISPARITY_COV, MV_FB_DEPTH, MV_FB_DEPTH_COV, MV_FB_MATCH_FLOW,
     MV_FB_MATCH_COV, MV_FB_CAND, MV_FB_COUNT, MV_FB_STATS,                       /* frontend side: age counts enqueued frames */
@@ -847,6 +854,47 @@ int mv_frame_pipe_device_draw(const mvFramePipe* p);
 int mv_frame_pipe_volume_tiled(const mvFramePipe* p);
 int mv_frame_pipe_host_threads(const mvFramePipe* p);   /* 1: the caller issues everything; 2: + the backend launch thread (default where the process has >= 3 cores) */
 int mv_frame_pipe_finish_device(mvFramePipe* p, float* pose_sink);
+/* ---- RandomSelector, GridSelector and caller-supplied keypoints (ABI 8) -------------------------------------------------------------------------------
+ * RandomSelector.select_point is `h = torch.randint(mask, H - mask, (k, 1)); w = torch.randint(mask, W - mask, (k, 1)); cat([w, h], 1)`.  On torch's CPU
+ * generator (the generator the permutations above reproduce) that is one MT19937 word per element, `word % (high - low) + low`: a call advances the generator
+ * by exactly 2 k words — the k rows' v, then their u — and a following torch.randperm continues in the same stream.  Duplicate rows are possible and kept.
+ *   mv_kp_random_lanes     one workgroup per lane draws from the lane's device-resident generator (mv_mt19937_seed representation, `state` [lanes,
+ *                          mv_randperm_state_words()], advanced in place) -> out_uv int64 [lanes, num_point, 2] (u, v); num_point <= mv_kp_random_max_point()
+ *   mv_kp_random_emulated  host-only (no GPU): the same phase functions (csrc/kp_draw_dev.h) run with `threads` emulated threads; `calls` successive calls
+ *                          of one generator seeded with `seed`, out [calls, num_point, 2]
+ *   mv_kp_random_heads     host-only twin on the host's MT19937 (what mv_frame_pipe_finish_seeded draws for a lane of a MV_KP_RANDOM pipe); same layout
+ * All three need H > 2 * mask_width and W > 2 * mask_width.
+ * GridSelector is closed-form; it may return MORE rows than num_point (640 x 480, mask 32, 200 -> 11 x 21 = 231).  mv_kp_grid_count: the row count, 0 for the
+ * shapes where the reference raises (a grid step of 0) or the masked image is empty; mv_kp_grid writes out_uv int64 [count, 2]. */
+int mv_kp_random_max_point(void);
+int mv_kp_random_lanes(uint32_t* state, int lanes, int num_point, int H, int W, int mask_width, int64_t* out_uv, mvStream_t stream);
+int mv_kp_random_emulated(uint64_t seed, int calls, int num_point, int H, int W, int mask_width, int threads, int64_t* out);
+/* mv_kp_random_emulated followed by ONE emulated torch.randperm(perm_n)[:perm_k] of the same generator (out_perm [perm_k], min(perm_n, perm_k) entries) */
+int mv_kp_random_then_randperm_emulated(uint64_t seed, int calls, int num_point, int H, int W, int mask_width, int threads, int64_t* out, int64_t perm_n,
+                                        int perm_k, int64_t* out_perm);
+int mv_kp_random_heads(uint64_t seed, int calls, int num_point, int H, int W, int mask_width, int64_t* out);
+int mv_kp_grid_count(int H, int W, int mask_width, int num_point);
+int mv_kp_grid(int H, int W, int mask_width, int num_point, int64_t* out_uv, mvStream_t stream);
+/* Frame pipe.  Rows of capacity per lane of every per-keypoint table (0: invalid configuration): max(num_point, grid count) for MV_KP_GRID, num_point otherwise.
+ * A configuration is rejected when H <= 2 * kp_mask_width or W <= 2 * kp_mask_width (new modes), when the grid has a step of 0, when the capacity exceeds
+ * MV_KP_TABLE_MAX (the observation filter and the solve walk a lane's rows with one 256-thread workgroup: "a few thousand" is what they are built and tested
+ * for), when MV_KP_RANDOM asks for more than mv_kp_random_max_point() rows (the 1024-word draw buffer of the front launch), and — new modes with cov_model
+ * MATCH / GMM — when kp_mask_width < cov_kernel_size / 2: the covariance patch of a keypoint closer to the border than that leaves the image, where the
+ * reference wraps or raises and the kernel clamps.
+ * With the three new modes a frame enqueues no selector kernel, no candidate list and no count copy; mv_frame_pipe_wait_candidates reports the row count.
+ *   MV_KP_RANDOM  mv_frame_pipe_seed_lanes + mv_frame_pipe_finish_device (drawn inside the front launch) or mv_frame_pipe_finish_seeded (host draw): same bits
+ *   MV_KP_GRID    either of the two (nothing is drawn)
+ * mv_frame_pipe_finish_keypoints: the frame's keypoints as int64 (u, v) rows, kp_uv_host [lanes, cap, 2] with n_sel[l] <= cap live rows per lane.  Valid for
+ * EVERY selector_mode (on a CovAware pipe it bypasses the candidate list; the generators of mv_frame_pipe_seed_lanes do not move).  Every row must lie inside
+ * the image and — cov_model MATCH / GMM — at least cov_kernel_size / 2 from its border: checked here, MV_ERR_INVALID_ARG otherwise.
+ * mv_frame_pipe_finish_keypoints_dev: the same from device memory (kp_uv_dev as above, n_sel_dev int32 [lanes], clamped to [0, cap]), read on the pipe's
+ * streams behind everything enqueued on `stream` so far; never waits for the host.  PRECONDITION (not checked): rows as above.  A row outside the image is
+ * marked out of bounds and a patch that leaves the image is clamped — nothing is read outside the maps — but such a frame no longer follows the reference.
+ * Needs the two-launch backend (the default) and no dense-mapping tail.  The caller may reuse both arrays once `stream` has passed mv_frame_pipe_sync(p, stream, 2). */
+#define MV_KP_TABLE_MAX 4096
+int mv_frame_pipe_table_rows(const mvFramePipeConfig* cfg);
+int mv_frame_pipe_finish_keypoints(mvFramePipe* p, const int64_t* kp_uv_host, const int32_t* n_sel, float* pose_sink);
+int mv_frame_pipe_finish_keypoints_dev(mvFramePipe* p, const int64_t* kp_uv_dev, const int32_t* n_sel_dev, mvStream_t stream, float* pose_sink);
 int mv_frame_pipe_finished_counts(mvFramePipe* p, int age, int32_t* n_cand, int32_t* n_sel);
 /* host-side flow control of a device-driven stream: blocks until the front launch of the finish `lag` finishes back (0 = the newest; lag <= 6) has run */
 int mv_frame_pipe_wait_finished(mvFramePipe* p, int lag);

@@ -17,11 +17,13 @@ MV_F32, MV_F16, MV_BF16, MV_BF16X3, MV_BF16X2, MV_PACK_BF16X3, MV_PACK_F16X2 = 0
 MV_VOL_ENC16 = 16
 MV_LAYOUT_CHW, MV_LAYOUT_HWC = 0, 1
 MV_KP_NODEPTH, MV_KP_FULL, MV_KP_MAPPING = 0, 1, 2
+MV_KP_RANDOM, MV_KP_GRID, MV_KP_EXPLICIT = 3, 4, 5
+MV_KP_TABLE_MAX = 4096
 MV_GRAPH_ICP, MV_GRAPH_REPROJ, MV_GRAPH_DISP = 0, 1, 2
 MV_COV_MATCH, MV_COV_GMM, MV_COV_NONE = 0, 1, 2
 MV_COVMOD_DIAG, MV_COVMOD_NORMALIZE = 1, 2
 MV_MOTION_STATIC, MV_MOTION_TARTAN = 0, 1
-ABI_VERSION = 7
+ABI_VERSION = 8
 MV_MAX_LANES = 64        # include/macvo_hip.h
 
 
@@ -213,6 +215,16 @@ SIGNATURES = {
     "mv_mt19937_seed": (C.c_int, [C.c_uint64, _P]),
     "mv_randperm_head_lanes": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P]),
     "mv_randperm_heads_emulated": (C.c_int, [C.c_uint64, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "mv_kp_random_max_point": (C.c_int, []),
+    "mv_kp_random_lanes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mv_kp_random_emulated": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mv_kp_random_then_randperm_emulated": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.c_int, _P]),
+    "mv_kp_random_heads": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mv_kp_grid_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mv_kp_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mv_frame_pipe_table_rows": (C.c_int, [_P]),
+    "mv_frame_pipe_finish_keypoints": (C.c_int, [_P, _P, _P, _P]),
+    "mv_frame_pipe_finish_keypoints_dev": (C.c_int, [_P, _P, _P, _P, _P]),
     "mv_frame_pipe_timeline": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "mv_frame_pipe_timeline_backend": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "mv_frame_pipe_buffer": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]),

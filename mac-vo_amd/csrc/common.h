@@ -120,6 +120,14 @@ int mv_backend_front_cov_draw_lanes(int cov_model, int32_t cov_modifiers, const 
                                     float match_cov_default, const mvMatchCovParams* cov_params, int64_t* out_perm, int32_t* out_live,
                                     int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
                                     float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream);
+// ... with keypoint rows from no candidate list: RandomSelector drawn in the launch, GridSelector, or an explicit (u, v) table (frontend_ops.hip)
+int mv_backend_front_cov_kp_lanes(int cov_model, int32_t cov_modifiers, int kp_mode, const int64_t* kp_uv, const int32_t* n_live, const int32_t* n_live_dev,
+                                  int n_live_stride, const uint32_t* state_in, uint32_t* state_out, int num_point, int mask_width, int lanes, int cap,
+                                  const float* match_flow, const float* match_cov, const float* depth0, const float* disp0, const float* sdisp0,
+                                  const float* sdd0, const float* depth1, const float* disp1, const float* sdisp1, const float* sdd1, int edge,
+                                  float match_cov_default, const mvMatchCovParams* cov_params, int32_t* out_live, int64_t* out_kp0_uv, float* out_kp0,
+                                  float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0, float* out_sigma1, float* out_pos_Tc,
+                                  double* out_cov0, double* out_cov1, mvStream_t stream);
 
 // ---- wave-level reductions (64 lanes, butterfly so every lane ends with the result) ----
 __device__ __forceinline__ float wave_sum(float v) {

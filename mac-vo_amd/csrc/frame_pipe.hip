@@ -28,6 +28,7 @@
 // cross-stream hazards are closed with events (see `enqueue` / `finish`).
 #include "common.h"
 #include "motion_dev.h"
+#include "kp_draw_dev.h"
 #include <atomic>
 #include <chrono>
 #include <stdio.h>
@@ -67,6 +68,23 @@ namespace {
 constexpr int MAX_PENDING = MV_MAX_PENDING, N_MAPS = MAX_PENDING + 2, N_CAND = MAX_PENDING + 1, N_PERM = 4, N_INEV = 8, MAX_VOL = 4, MAX_LK = 2;
 constexpr int N_MOT = 8;   // motion_model: ring of per-finish motion slots (raw PoseNet output + composed prior of finish g -> slot g % N_MOT)
 constexpr int N_BEV = 8;   // ring of per-finish backend events (finish g -> slot g % N_BEV): the device-driven frame waits for the exact finish whose reads free a slot
+
+// selector modes that look at no map: no selector kernels, no candidate list, no count copy
+inline bool kp_new_mode(int m) { return m == MV_KP_RANDOM || m == MV_KP_GRID || m == MV_KP_EXPLICIT; }
+// rows a frame of such a pipe tracks (RANDOM / EXPLICIT: num_point = the capacity; GRID: the grid's own count, which may exceed num_point)
+inline int frame_rows(const mvFramePipeConfig& c) {
+    return c.selector_mode == MV_KP_GRID ? mvkp::grid_of(c.H, c.W, c.kp_mask_width, c.num_point, nullptr) : c.num_point;
+}
+// THE capacity rule: rows per lane of every per-keypoint table (arena, offsets, views, map_append)
+inline int table_rows(const mvFramePipeConfig& c) {
+    const int g = frame_rows(c);
+    return g > c.num_point ? g : c.num_point;
+}
+inline int cap_of(const mvFramePipeConfig& c) {   // (a pipe without keypoints still carves one row)
+    const int r = table_rows(c);
+    return r > 0 ? r : 1;
+}
+enum { KPJ_PERM = 0, KPJ_HOST = 1, KPJ_DEV = 2, KPJ_RANDOM = 3, KPJ_GRID = 4 };   // FinishJob::kp — where a finish takes its keypoint rows from
 
 struct Maps {
     float *disparity, *disparity_cov, *depth, *depth_cov, *match_flow, *match_cov;
@@ -112,6 +130,10 @@ struct FinishJob {
     int32_t n_sel[MV_MAX_LANES];
     int64_t n_cand[MV_MAX_LANES];   // seeded: candidate count per lane (the permutation is drawn by whoever issues the job)
     bool seeded;
+    int kp = KPJ_PERM;              // != 0: (u, v) rows instead of a permutation over the candidate list — HOST: the caller's / drawn rows (in `perm` / the row
+                                    // argument, [lanes, cap, 2]); DEV: kp_dev / nsel_dev behind e_kpin; RANDOM: drawn inside the front launch; GRID: computed there
+    const int64_t* kp_dev = nullptr;
+    const int32_t* nsel_dev = nullptr;
     bool device = false;            // device-driven frame: the permutation is drawn inside the front launch, n_sel is an upper bound (num_point)
     std::vector<int64_t> perm;      // explicit permutations [lanes, cap] (asynchronous issue: a copy of the caller's array)
     float* pose_sink;
@@ -197,6 +219,7 @@ struct mvFramePipe {
     bool deferred_valid;
     hipEvent_t e_rest[N_INEV];   // inputs of the decoder side (coords, flow, ...) when the GEMM was issued ahead of them
     hipEvent_t e_in[N_INEV], e_vol_done[MAX_VOL], e_vol_free[MAX_VOL], e_cand[N_CAND], e_backend[N_BEV], e_pgo, e_perm[N_PERM];
+    hipEvent_t e_kpin[N_BEV]; // finish g (slot g % N_BEV): the caller's stream when mv_frame_pipe_finish_keypoints_dev was called
     hipEvent_t e_release;     // the consumer's reads of result views enqueued so far (mv_frame_pipe_release)
     bool release_valid;
     hipEvent_t e_posed[2];    // backend slot k: world-frame tables written (side stream, in front of the solve)
@@ -232,7 +255,7 @@ struct mvFramePipe {
     // native keypoint permutations (mv_frame_pipe_seed_lanes): one MT19937 per lane, the engine behind torch's CPU generator
     std::vector<std::mt19937> rng;
     std::vector<int32_t> perm_scratch;   // identity array of the partial Fisher-Yates, reused
-    std::vector<int64_t> perm_host;      // [lanes, cap]
+    std::vector<int64_t> perm_host;      // [lanes, cap] permutations, or [lanes, cap, 2] drawn RandomSelector rows
     std::vector<int32_t> nsel_host;
     // Device-driven frame (round 6, mv_frame_pipe_seed_lanes with MV_PIPE_DEVICE_DRAW != 0): the same generators live in DEVICE memory and the permutation head is
     // drawn inside the backend's front launch (randperm_dev.h) from the count the selector left in device memory — no D2H count, no host wait, no host draw, no
@@ -341,7 +364,7 @@ static size_t carve(mvFramePipe* p, char* base) {
     const mvFramePipeConfig& c = p->c;
     Carver a{base};
     const size_t L = p->lanes;
-    const size_t plane = p->plane, n8 = p->n8, B = c.pairs, N = c.num_point > 0 ? c.num_point : 1;
+    const size_t plane = p->plane, n8 = p->n8, B = c.pairs, N = (size_t)cap_of(c);
     for (int k = 0; k < p->n_volbuf; ++k) p->vol[k] = a.take<float>(B * n8 * n8);
     for (int k = 0; k < 2 * (L <= 2 ? MAX_LK : 1); ++k) p->tok[k] = a.take<float>(B * p->KK * n8);
     for (int k = 0; k < 2; ++k)
@@ -434,8 +457,16 @@ static int check_config(const mvFramePipeConfig* c) {
     MV_CHECK_ARG(c->C > 0 && c->C % 16 == 0 && c->iters >= 0);
     MV_CHECK_ARG(c->pairs >= 2 && c->pairs % 2 == 0 && c->pairs / 2 <= MV_MAX_LANES);   // lane l = pairs 2l (stereo), 2l + 1 (temporal)
     MV_CHECK_ARG(c->radius >= 1 && c->radius <= 4);
-    MV_CHECK_ARG(c->selector_mode == MV_KP_NODEPTH || c->selector_mode == MV_KP_FULL);
+    MV_CHECK_ARG(c->selector_mode == MV_KP_NODEPTH || c->selector_mode == MV_KP_FULL || kp_new_mode(c->selector_mode));
     MV_CHECK_ARG(c->num_point >= 0 && c->edgewidth >= 0 && c->min_num_point >= 0);
+    if (kp_new_mode(c->selector_mode)) {
+        MV_CHECK_ARG(c->kp_mask_width >= 0 && c->H > 2 * c->kp_mask_width && c->W > 2 * c->kp_mask_width);
+        MV_CHECK_ARG(c->selector_mode != MV_KP_GRID || frame_rows(*c) > 0);   // (0: a grid step of 0, where the reference raises)
+        MV_CHECK_ARG(table_rows(*c) <= MV_KP_TABLE_MAX);
+        if (c->selector_mode == MV_KP_RANDOM && c->num_point > mvkp::MAX_POINT) return MV_ERR_UNSUPPORTED;   // (the front launch's 1024-word draw buffer)
+        // the 31 x 31 covariance patch of a keypoint nearer to the border than its half width leaves the image: the reference wraps or raises, the kernel clamps
+        MV_CHECK_ARG(c->cov_model == MV_COV_NONE || c->kp_mask_width >= c->cov_kernel_size / 2);
+    }
     MV_CHECK_ARG(c->graph_type >= MV_GRAPH_ICP && c->graph_type <= MV_GRAPH_DISP);
     MV_CHECK_ARG(c->mapping == 0 || (c->mapping == 1 && c->pairs == 2 && c->map_num_point > 0 && c->map_mask_width >= 0));
     MV_CHECK_ARG(c->volume_split == 0 || c->volume_split == 2 || c->volume_split == 3 || c->volume_split == MV_PACK_BF16X3 ||
@@ -497,6 +528,7 @@ extern "C" void mv_frame_pipe_destroy(mvFramePipe* p) {
     for (int k = 0; k < N_CAND; ++k) ev(p->e_cand[k]);
     for (int k = 0; k < 2; ++k) { ev(p->e_posed[k]); ev(p->e_solved[k]); }
     for (auto e : p->e_backend) ev(e);
+    for (auto e : p->e_kpin) ev(e);
     for (auto e : p->e_motion_in) ev(e);
     for (auto e : p->e_motion_read) ev(e);
     for (auto e : p->e_motion_set) ev(e);
@@ -560,6 +592,7 @@ static int create_impl(mvFramePipe* p) {
         MV_HIP(hipHostMalloc((void**)&p->h_count[k], (size_t)p->lanes * 4 * sizeof(int32_t), hipHostMallocDefault));
     }
     for (auto& e : p->e_backend) MV_HIP(mk(&e));
+    for (auto& e : p->e_kpin) MV_HIP(mk(&e));
     if (c.motion_model == MV_MOTION_TARTAN) {
         for (auto& e : p->e_motion_in) MV_HIP(mk(&e));
         for (auto& e : p->e_motion_read) MV_HIP(mk(&e));
@@ -587,10 +620,10 @@ static int create_impl(mvFramePipe* p) {
     MV_HIP(mk(&p->e_packed[1]));
     MV_HIP(mk(&p->e_map));
     MV_HIP(mk(&p->e_release));
-    const size_t N = c.num_point > 0 ? c.num_point : 1;
-    for (int k = 0; k < N_PERM; ++k) {
+    const size_t N = (size_t)cap_of(c);
+    for (int k = 0; k < N_PERM; ++k) {   // (a slot holds a finish's permutations [lanes, cap] or its keypoint rows [lanes, cap, 2])
         MV_HIP(mk(&p->e_perm[k]));
-        MV_HIP(hipHostMalloc((void**)&p->h_perm[k], (size_t)p->lanes * N * sizeof(int64_t), hipHostMallocDefault));
+        MV_HIP(hipHostMalloc((void**)&p->h_perm[k], (size_t)p->lanes * N * 2 * sizeof(int64_t), hipHostMallocDefault));
     }
     // constants: selector workspace zeroed once (mv_kp_select leaves it zeroed), identity pose, PGO scalars, offsets table
     MV_HIP(hipMemsetAsync(p->kp_ws, 0, p->kp_ws_bytes, p->s_main));
@@ -893,7 +926,7 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
     // behind e_cand) and shares the selector workspace / upsampling buffers with it
     // (alt_indep: NODEPTH selector without upsampling reads nothing of the previous frame and has its own workspace — the segments may overlap and
     // the BACKEND waits for the previous frame's segment instead, finish_issue)
-    const bool indep = p->alt_indep && !up && c.selector_mode == MV_KP_NODEPTH;
+    const bool indep = p->alt_indep && !up && (c.selector_mode == MV_KP_NODEPTH || kp_new_mode(c.selector_mode));
     if (p->alt && !indep && d.f > 0) {
         MV_TRY(ensure_chain_events(p, d.f - 1, -1));
         MV_TRY(wait_if_pending(s, p->e_seg[(d.f - 1) % N_INEV]));
@@ -917,7 +950,10 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
     if (with_selector) {
         mvKpSelectParams sp{c.H, c.W, c.selector_mode, c.kp_kernel_size, c.kp_mask_width, c.max_depth, c.max_depth_cov,
                             c.max_match_cov};
-        if (c.selector_mode == MV_KP_NODEPTH && fuse_epi && !up) {
+        const bool sel_kernels = !kp_new_mode(c.selector_mode);   // (Random / Grid / explicit keypoints: the segment ends with the epilogue)
+        if (!sel_kernels) {
+            // (nothing: the maps are written, the keypoints come with the finish)
+        } else if (c.selector_mode == MV_KP_NODEPTH && fuse_epi && !up) {
             // epilogue + selector's first kernel in one launch (one launch and one pass over the maps less on the chain that
             // bounds a single-sequence stream)
             MV_TRY(mv_frontend_epilogue_select_lanes(in->flow, in->logcov, 1, c.bl_fx, c.bl_fx_sq, mp.disparity, mp.disparity_cov,
@@ -933,7 +969,7 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
             MV_TRY(mv_kp_select_lanes(mp.match_cov, m0.depth, m0.depth_cov, mp.depth, mp.depth_cov, nullptr, nullptr, &sp,
                                       p->kp_ws, p->kp_ws_bytes, p->cand[k], p->count[k], p->stats[k], p->lanes, s));
         }
-        if (!p->dev_draw)   // (the device-driven frame reads the count where it is)
+        if (!p->dev_draw && sel_kernels)   // (the device-driven frame reads the count where it is)
             MV_HIP(hipMemcpyAsync(p->h_count[k], p->count[k], (size_t)p->lanes * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (c.mapping) {
             // MappingPointSelector works on the PREVIOUS frame's depth maps (KeypointSelector.py:87-100; MACVO.py:315): its count
@@ -1095,6 +1131,11 @@ extern "C" int mv_frame_pipe_wait_candidates(mvFramePipe* p, int32_t* n_cand) {
     MV_TRY(selector_of_front_issued(p));
     const Pending& pd = p->pending.front();
     MV_TRY(ensure_chain_events(p, pd.f, pd.cand));
+    if (kp_new_mode(p->c.selector_mode)) {   // no candidate list: the frame's row count is known (the mapping selector's count still travels behind e_cand)
+        if (p->c.mapping) MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));
+        for (int l = 0; l < p->lanes; ++l) n_cand[l] = frame_rows(p->c);
+        return MV_OK;
+    }
     MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));
     if (p->dev_draw)   // (the device-driven pipe has no per-frame count copy)
         MV_HIP(hipMemcpy(p->h_count[pd.cand], p->count[pd.cand], (size_t)p->lanes * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1116,15 +1157,16 @@ extern "C" int mv_frame_pipe_seed_lanes(mvFramePipe* p, const uint64_t* seeds) {
     MV_TRY(flush_jobs(p));   // the launch thread's draw_perms reads rng / perm_host
     p->rng.clear();
     for (int l = 0; l < p->lanes; ++l) p->rng.emplace_back((uint32_t)(seeds[l] & 0xffffffffull));
-    const int cap = p->c.num_point > 0 ? p->c.num_point : 1;
-    p->perm_host.assign((size_t)p->lanes * cap, 0);
+    const int cap = cap_of(p->c);
+    p->perm_host.assign((size_t)p->lanes * cap * (p->c.selector_mode == MV_KP_RANDOM ? 2 : 1), 0);
     p->nsel_host.assign((size_t)p->lanes, 0);
     {
         // ... and the same generators in device memory: the device-driven frame (default wherever it applies; MV_PIPE_DEVICE_DRAW=0: the host draw above).
         // Needs the two-launch backend, a head the device draw covers, and no dense-mapping tail (its second permutation is drawn by the Python side).
         const char* e = getenv("MV_PIPE_DEVICE_DRAW");
         const bool want = e ? atoi(e) != 0 : true;
-        p->dev_draw = want && p->fuse_backend && !p->c.mapping && p->c.num_point >= 1 && p->c.num_point <= mv_randperm_max_head() && p->pending.empty();
+        p->dev_draw = want && p->fuse_backend && !p->c.mapping && p->c.num_point >= 1 && p->c.num_point <= mv_randperm_max_head() && p->pending.empty() &&
+                      p->c.selector_mode != MV_KP_GRID && p->c.selector_mode != MV_KP_EXPLICIT;   // (nothing to draw)
         if (p->dev_draw && p->async_backend && !p->async_explicit && affinity_cores() < 3) {
             // One host thread on small hosts.  The launch thread existed to overlap the host draw + the backend launches with the caller's next enqueue while the caller
             // waited for candidate counts; a device-driven frame has no wait and no draw, and one thread issues it in ~105-140 us — about the frame period.  With the lean
@@ -1181,7 +1223,7 @@ static int finish_host(mvFramePipe* p, const int32_t* n_sel, float* pose_sink, F
     const int L = p->lanes;
     int n_max = 0;
     for (int l = 0; l < L; ++l) {
-        MV_CHECK_ARG(n_sel[l] >= 0 && n_sel[l] <= c.num_point);
+        MV_CHECK_ARG(n_sel[l] >= 0 && n_sel[l] <= table_rows(c));
         n_max = n_sel[l] > n_max ? n_sel[l] : n_max;
     }
     MV_CHECK_ARG(c.motion_model != MV_MOTION_TARTAN || p->motion_g[p->n_fin % N_MOT] == p->n_fin);   // mv_frame_pipe_set_motion for this frame first
@@ -1216,7 +1258,7 @@ static int finish_host(mvFramePipe* p, const int32_t* n_sel, float* pose_sink, F
 // not touch anything but the job, the Backend slot and the launch thread's own events / flags).
 static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_host) {
     const mvFramePipeConfig& c = p->c;
-    const int L = p->lanes, cap = c.num_point > 0 ? c.num_point : 1;
+    const int L = p->lanes, cap = cap_of(c);
     const int n_max = j.n_max;
     const Pending& pd = j.pd;
     const long g = j.g;
@@ -1270,11 +1312,14 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     if (!j.device && p->dev_draw)   // a host-permuted finish in a device-driven pipe: the generators move on to the buffer the NEXT finish reads, unchanged
         MV_HIP(hipMemcpyAsync(p->rp_state[(g + 1) & 1], p->rp_state[g & 1], (size_t)L * (size_t)mv_randperm_state_words() * sizeof(uint32_t),
                               hipMemcpyDeviceToDevice, s));
-    if (!j.device) {
+    const bool host_rows = !j.device && (j.kp == KPJ_PERM || j.kp == KPJ_HOST);   // a permutation or (u, v) rows from the host
+    const size_t rw = j.kp == KPJ_HOST ? 2 : 1;                                     // int64 words per row
+    if (host_rows) {
         if (p->perm_valid[ps]) MV_HIP(hipEventSynchronize(p->e_perm[ps]));   // long done; keeps the slot reuse provably safe
         for (int l = 0; l < L; ++l)
-            memcpy(p->h_perm[ps] + (size_t)l * cap, perm_host + (size_t)l * cap, (size_t)n_sel[l] * sizeof(int64_t));
+            memcpy(p->h_perm[ps] + (size_t)l * cap * rw, perm_host + (size_t)l * cap * rw, (size_t)n_sel[l] * rw * sizeof(int64_t));
     }
+    if (j.kp == KPJ_DEV) MV_HIP(hipStreamWaitEvent(s, p->e_kpin[g % N_BEV], 0));   // the caller's stream as of mv_frame_pipe_finish_keypoints_dev
     if (!on_dec) MV_TRY(wait_if_pending(s, p->e_cand[pd.cand]));   // fired: the host has just read this frame's count (device-driven: a pending barrier)
     else if (g > 0 && p->backend_valid[(g - 1) % N_BEV]) MV_TRY(wait_if_pending(s, p->e_backend[(g - 1) % N_BEV]));
     // alt layout: the previous frame's maps (gathers below) were written by a segment on the other decoder-side stream, which e_cand does not cover.
@@ -1287,10 +1332,10 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     p->last_backend_frame = pd.f;
     const int ti = pd.ti;
     if (ti >= 0) MV_HIP(hipEventRecord(p->tv4[ti], s));
-    const bool perm_in_args = L == 1 && n_max <= 256;   // one lane: the permutation rides in the kernel arguments (no pinned staging copy, no H2D node)
-    if (!perm_in_args && !j.device) {
-        const size_t perm_bytes = ((size_t)(L - 1) * cap + n_sel[L - 1]) * sizeof(int64_t);
-        MV_HIP(hipMemcpyAsync(b.perm, p->h_perm[ps], perm_bytes, hipMemcpyHostToDevice, s));
+    const bool perm_in_args = j.kp == KPJ_PERM && L == 1 && n_max <= 256;   // one lane: the permutation rides in the kernel arguments (no pinned staging copy, no H2D node)
+    if (!perm_in_args && host_rows) {   // (keypoint rows go straight into the frame's kp0 table, which the front launch then reads in place)
+        const size_t perm_bytes = ((size_t)(L - 1) * cap + n_sel[L - 1]) * rw * sizeof(int64_t);
+        MV_HIP(hipMemcpyAsync(j.kp == KPJ_HOST ? b.kp0 : b.perm, p->h_perm[ps], perm_bytes, hipMemcpyHostToDevice, s));
         MV_HIP(hipEventRecord(p->e_perm[ps], s));
         p->perm_valid[ps] = true;
     }
@@ -1302,7 +1347,20 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     // in-order stream.
     const bool fused = p->fuse_backend != 0;
     mvMatchCovParams cp{c.H, c.W, c.cov_kernel_size, 1, c.fx, c.fy, c.cx, c.cy, c.min_flow_cov_sq, c.min_depth_cov};
-    if (j.device) {
+    if (j.kp != KPJ_PERM) {
+        // keypoint rows from no candidate list: the caller's (host rows copied into kp0 above / device rows read where they are), RandomSelector drawn inside
+        // the launch from the lane's device-resident generator (two state buffers, as the permutation draw below), GridSelector computed from the row index
+        const int mode = j.kp == KPJ_RANDOM ? MV_KP_RANDOM : j.kp == KPJ_GRID ? MV_KP_GRID : MV_KP_EXPLICIT;
+        const bool dv = j.kp == KPJ_DEV;
+        MV_TRY(mv_backend_front_cov_kp_lanes(c.cov_model, c.cov_modifiers, mode, dv ? j.kp_dev : b.kp0, dv ? nullptr : n_sel, dv ? j.nsel_dev : nullptr, 1,
+                                             p->rp_state[g & 1], p->rp_state[(g + 1) & 1], c.num_point, c.kp_mask_width, L, cap, m1.match_flow, m1.match_cov,
+                                             m0.depth, m0.disparity, m0.disparity_cov, m0.depth_cov, m1.depth, m1.disparity, m1.disparity_cov, m1.depth_cov,
+                                             c.edgewidth, c.match_cov_default, &cp, dv ? b.live_dev : nullptr, b.kp0, b.kp0f, b.kp1, b.inbound, b.vals, b.sigma0,
+                                             b.sigma1, b.pos_Tc, b.cov0, b.cov1, s));
+        if (c.mapping)
+            MV_TRY(mv_obs_filter_lanes(b.inbound, b.cov0, b.cov1, b.vals, c.filters, c.filter_min_depth, c.max_depth, L, n_sel, cap,
+                                       b.valid, b.n_valid, s));
+    } else if (j.device) {
         // device-driven frame: the front launch draws the permutation itself (count and generator in device memory) and publishes the live-row count
         MV_TRY(mv_backend_front_cov_draw_lanes(c.cov_model, c.cov_modifiers, p->cand[pd.cand], (size_t)p->plane, p->count[pd.cand], 4, p->rp_state[g & 1],
                                            p->rp_state[(g + 1) & 1], c.num_point, L, cap, m1.match_flow, m1.match_cov, m0.depth, m0.disparity, m0.disparity_cov, m0.depth_cov, m1.depth, m1.disparity,
@@ -1348,14 +1406,15 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     if (ti >= 0) MV_HIP(hipEventRecord(p->tv6[ti], ss));
     const size_t N = (size_t)cap;
     const size_t LN = (size_t)L * N;   // value table is [11, lanes, cap]: each of its rows is one concatenated per-point column
-    if (j.device && motion) {
+    const bool live_on_dev = (j.device && j.kp == KPJ_PERM) || j.kp == KPJ_DEV;   // the live-row count exists in device memory only
+    if (live_on_dev && motion) {
         MV_TRY(mv_pgo_solve_posed_motion_dev(L, p->offs, b.live_dev, 2, cap, c.graph_type, pose, prior, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w,
                                              b.rot, b.kp1, b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, c.filters, c.filter_min_depth,
                                              c.max_depth, b.inbound, b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm, b.pose64, b.info,
                                              p->pose[j.pose_to], j.pose_sink, ss));
         MV_HIP(hipEventRecord(p->e_solved[k], ss));
         MV_HIP(hipEventRecord(p->e_pgo, ss));
-    } else if (j.device) {
+    } else if (live_on_dev) {
         MV_TRY(mv_pgo_solve_posed_dev(L, p->offs, b.live_dev, 2, cap, c.graph_type, pose, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w, b.rot, b.kp1,
                                       b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, c.filters, c.filter_min_depth, c.max_depth, b.inbound,
                                       b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm, b.pose64, b.info, p->pose[j.pose_to], j.pose_sink, ss));
@@ -1396,8 +1455,14 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
 }
 
 // permutations of a seeded job: torch.randperm of each lane's generator (see above)
+void mv_kp_random_draw_host(std::mt19937& eng, int k, int H, int W, int mask, int64_t* out_uv);   // (kp_draw.hip)
 static const int64_t* draw_perms(mvFramePipe* p, const FinishJob& j) {
-    const int cap = p->c.num_point > 0 ? p->c.num_point : 1;
+    const int cap = cap_of(p->c);
+    if (j.kp == KPJ_HOST) {   // a seeded RandomSelector frame: 2 * num_point words per lane, v rows first (same bits as the draw inside the front launch)
+        for (int l = 0; l < p->lanes; ++l)
+            mv_kp_random_draw_host(p->rng[(size_t)l], j.n_sel[l], p->c.H, p->c.W, p->c.kp_mask_width, p->perm_host.data() + 2 * (size_t)l * cap);
+        return p->perm_host.data();
+    }
     for (int l = 0; l < p->lanes; ++l)
         randperm_head(p->rng[(size_t)l], j.n_cand[l], p->c.num_point, p->perm_scratch, p->perm_host.data() + (size_t)l * cap);
     return p->perm_host.data();
@@ -1461,8 +1526,8 @@ static int submit_or_issue(mvFramePipe* p, FinishJob& j, const int64_t* perm_hos
         MV_TRY(finish_issue(p, j, j.seeded ? draw_perms(p, j) : perm_host));
         return j.has_sel ? issue_selector_segment(p, j.sel) : MV_OK;
     }
-    if (!j.seeded && !j.device && j.n_max > 0) {
-        const size_t cap = p->c.num_point > 0 ? p->c.num_point : 1;
+    if (!j.seeded && !j.device && (j.kp == KPJ_PERM || j.kp == KPJ_HOST) && j.n_max > 0) {
+        const size_t cap = (size_t)cap_of(p->c) * (j.kp == KPJ_HOST ? 2 : 1);
         j.perm.assign(perm_host, perm_host + (size_t)p->lanes * cap);
     }
     int rc;
@@ -1477,10 +1542,38 @@ static int submit_or_issue(mvFramePipe* p, FinishJob& j, const int64_t* perm_hos
     return rc;
 }
 
+// A frame of a RandomSelector / GridSelector pipe: every lane tracks frame_rows() rows, nothing to wait for.  kp = KPJ_HOST: drawn on the host by whoever issues
+// the job (seeded), KPJ_RANDOM: drawn inside the front launch (device-driven), KPJ_GRID: computed there.
+static int finish_rows(mvFramePipe* p, int kp, float* pose_sink, int32_t* n_cand_out, int32_t* n_sel_out) {
+    MV_TRY(selector_of_front_issued(p));
+    const Pending& pd = p->pending.front();
+    if (kp != KPJ_RANDOM || p->c.mapping) {   // (the device-driven frame's front launch follows its segment in stream order or by a pending barrier)
+        MV_TRY(ensure_chain_events(p, pd.f, pd.cand));
+        if (pd.f > 0) MV_TRY(ensure_chain_events(p, pd.f - 1, -1));
+    }
+    if (p->c.mapping) MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));   // mv_frame_pipe_wait_tracked reads the mapping selector's count behind it
+    FinishJob j{};
+    j.kp = kp;
+    j.seeded = kp == KPJ_HOST;
+    j.device = kp == KPJ_RANDOM;
+    j.t_count = j.t_submit = now_us();
+    int32_t nsel[MV_MAX_LANES];
+    for (int l = 0; l < p->lanes; ++l) {
+        nsel[l] = frame_rows(p->c);
+        if (n_cand_out) n_cand_out[l] = nsel[l];
+        if (n_sel_out) n_sel_out[l] = nsel[l];
+    }
+    MV_TRY(finish_host(p, nsel, pose_sink, j));
+    return submit_or_issue(p, j, nullptr);
+}
+
 // wait_candidates + permutations (per-lane generators of mv_frame_pipe_seed_lanes) + finish in one host call
 extern "C" int mv_frame_pipe_finish_seeded(mvFramePipe* p, float* pose_sink, int32_t* n_cand_out, int32_t* n_sel_out) {
-    MV_CHECK_ARG(p && !p->pending.empty() && (int)p->rng.size() == p->lanes);
+    MV_CHECK_ARG(p && !p->pending.empty());
+    if (p->c.selector_mode == MV_KP_GRID) return finish_rows(p, KPJ_GRID, pose_sink, n_cand_out, n_sel_out);
+    MV_CHECK_ARG((int)p->rng.size() == p->lanes && p->c.selector_mode != MV_KP_EXPLICIT);
     MV_CHECK_ARG(!p->dev_draw);   // (its generators live on the device: mv_frame_pipe_finish_device)
+    if (p->c.selector_mode == MV_KP_RANDOM) return finish_rows(p, KPJ_HOST, pose_sink, n_cand_out, n_sel_out);
     MV_TRY(selector_of_front_issued(p));
     const Pending& pd = p->pending.front();
     const double t_w0 = p->host_stats ? now_us() : 0.0;
@@ -1505,7 +1598,10 @@ extern "C" int mv_frame_pipe_finish_seeded(mvFramePipe* p, float* pose_sink, int
 // The device-driven finish (round 6): nothing to wait for and nothing to draw — the frame's backend + solve are queued behind its selector segment by event, the
 // permutation head is drawn inside the front launch.  The host learns the counts only if it asks (mv_frame_pipe_finished_counts).
 extern "C" int mv_frame_pipe_finish_device(mvFramePipe* p, float* pose_sink) {
-    MV_CHECK_ARG(p && !p->pending.empty() && p->dev_draw);
+    MV_CHECK_ARG(p && !p->pending.empty());
+    if (p->c.selector_mode == MV_KP_GRID) return finish_rows(p, KPJ_GRID, pose_sink, nullptr, nullptr);
+    MV_CHECK_ARG(p->dev_draw);
+    if (p->c.selector_mode == MV_KP_RANDOM) return finish_rows(p, KPJ_RANDOM, pose_sink, nullptr, nullptr);
     MV_TRY(selector_of_front_issued(p));
     FinishJob j{};
     j.seeded = false;
@@ -1524,6 +1620,13 @@ extern "C" int mv_frame_pipe_finish_device(mvFramePipe* p, float* pose_sink) {
 extern "C" int mv_frame_pipe_finished_counts(mvFramePipe* p, int age, int32_t* n_cand, int32_t* n_sel) {
     MV_CHECK_ARG(p && p->dev_draw && age >= 0 && age <= 1 && p->n_fin - 1 - age >= 0);
     MV_TRY(flush_jobs(p));
+    if (kp_new_mode(p->c.selector_mode)) {   // (no candidate list: the row count is the configuration's)
+        for (int l = 0; l < p->lanes; ++l) {
+            if (n_sel) n_sel[l] = p->be[(p->n_fin - 1 - age) & 1].n_sel[l];
+            if (n_cand) n_cand[l] = frame_rows(p->c);
+        }
+        return MV_OK;
+    }
     const long g = p->n_fin - 1 - age;
     MV_HIP(hipEventSynchronize(p->e_backend[g % N_BEV]));
     std::vector<int32_t> h(2 * (size_t)p->lanes);
@@ -1561,7 +1664,7 @@ extern "C" int mv_randperm_heads(uint64_t seed, const int64_t* n, int calls, int
 }
 
 extern "C" int mv_frame_pipe_finish(mvFramePipe* p, const int64_t* perm_host, const int32_t* n_sel, float* pose_sink) {
-    MV_CHECK_ARG(p && n_sel && !p->pending.empty());
+    MV_CHECK_ARG(p && n_sel && !p->pending.empty() && !kp_new_mode(p->c.selector_mode));   // (a permutation needs a candidate list)
     for (int l = 0; l < p->lanes; ++l)
         MV_CHECK_ARG(n_sel[l] >= 0 && n_sel[l] <= p->c.num_point && (n_sel[l] == 0 || perm_host));
     MV_TRY(selector_of_front_issued(p));
@@ -1571,6 +1674,53 @@ extern "C" int mv_frame_pipe_finish(mvFramePipe* p, const int64_t* perm_host, co
     j.seeded = false;
     MV_TRY(finish_host(p, n_sel, pose_sink, j));
     return submit_or_issue(p, j, perm_host);
+}
+
+// Caller-supplied keypoints: any selector's (u, v) rows instead of a permutation over the driver's candidate list — valid for every selector_mode.
+extern "C" int mv_frame_pipe_table_rows(const mvFramePipeConfig* cfg) { return check_config(cfg) == MV_OK ? table_rows(*cfg) : 0; }
+
+static int finish_keypoints_common(mvFramePipe* p) {
+    MV_TRY(selector_of_front_issued(p));
+    const Pending& pd = p->pending.front();
+    MV_TRY(ensure_chain_events(p, pd.f, pd.cand));   // (lean chain: a finish whose front launch waits for the segment by event needs the markers)
+    if (pd.f > 0) MV_TRY(ensure_chain_events(p, pd.f - 1, -1));
+    if (p->c.mapping) MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));
+    return MV_OK;
+}
+
+extern "C" int mv_frame_pipe_finish_keypoints(mvFramePipe* p, const int64_t* kp_uv_host, const int32_t* n_sel, float* pose_sink) {
+    MV_CHECK_ARG(p && n_sel && !p->pending.empty());
+    const mvFramePipeConfig& c = p->c;
+    const int cap = cap_of(c);
+    const int64_t hw = c.cov_model == MV_COV_NONE ? 0 : c.cov_kernel_size / 2;   // the covariance patch must stay inside the image
+    for (int l = 0; l < p->lanes; ++l) {
+        MV_CHECK_ARG(n_sel[l] >= 0 && n_sel[l] <= table_rows(c) && (n_sel[l] == 0 || kp_uv_host));
+        for (int i = 0; i < n_sel[l]; ++i) {
+            const int64_t u = kp_uv_host[2 * ((size_t)l * cap + i)], v = kp_uv_host[2 * ((size_t)l * cap + i) + 1];
+            MV_CHECK_ARG(u >= hw && u < c.W - hw && v >= hw && v < c.H - hw);
+        }
+    }
+    MV_TRY(finish_keypoints_common(p));
+    FinishJob j{};
+    j.seeded = false;
+    j.kp = KPJ_HOST;
+    MV_TRY(finish_host(p, n_sel, pose_sink, j));
+    return submit_or_issue(p, j, kp_uv_host);
+}
+
+extern "C" int mv_frame_pipe_finish_keypoints_dev(mvFramePipe* p, const int64_t* kp_uv_dev, const int32_t* n_sel_dev, mvStream_t stream, float* pose_sink) {
+    MV_CHECK_ARG(p && kp_uv_dev && n_sel_dev && !p->pending.empty() && p->fuse_backend && !p->c.mapping && table_rows(p->c) >= 1);
+    MV_TRY(finish_keypoints_common(p));
+    FinishJob j{};
+    j.seeded = false;
+    j.kp = KPJ_DEV;
+    j.kp_dev = kp_uv_dev;
+    j.nsel_dev = n_sel_dev;
+    MV_HIP(hipEventRecord(p->e_kpin[p->n_fin % N_BEV], (hipStream_t)stream));   // recorded before the job is queued
+    int32_t nsel[MV_MAX_LANES];
+    for (int l = 0; l < p->lanes; ++l) nsel[l] = table_rows(p->c);   // upper bound: rows beyond the live ones are masked by `valid`
+    MV_TRY(finish_host(p, nsel, pose_sink, j));
+    return submit_or_issue(p, j, nullptr);
 }
 
 // Register the newest FINISHED frame in a device-resident map (call right after mv_frame_pipe_finish; lanes == 1): the
@@ -1584,7 +1734,7 @@ extern "C" int mv_frame_pipe_map_append(mvFramePipe* p, const mvMapStores* store
     const mvFramePipeConfig& c = p->c;
     const long g = p->n_fin - 1;
     const Backend& b = p->be[g & 1];
-    const int cap = c.num_point > 0 ? c.num_point : 1;
+    const int cap = cap_of(c);
     mvMapFrame f{};
     f.n_rows = b.n_sel[0];
     f.table_stride = cap;
@@ -1801,7 +1951,7 @@ extern "C" int mv_frame_pipe_buffer(mvFramePipe* p, int which, int age, void** p
     auto front = [&](int depth) { return f >= 0 && age < depth; };
     auto back = [&]() { return g >= 0 && age < 2; };
     const Backend* b = back() ? &p->be[g & 1] : nullptr;
-    const size_t N = L * (size_t)(c.num_point > 0 ? c.num_point : 1);   // capacity rows (a lane's live rows: its n_sel)
+    const size_t N = L * (size_t)cap_of(c);   // capacity rows (a lane's live rows: its n_sel)
     switch (which) {
         case MV_FB_VOLUME:
             // age limit: with a GEMM issued ahead (n_vol > n_enq) the buffer of frame f - 1 is being rewritten

@@ -9,6 +9,7 @@
 //   Utility/Point.py:5-13, and the ten retrieve_pixels gathers of Module/Frontend/Frontend.py:103-118).
 #include "common.h"
 #include "randperm_dev.h"
+#include "kp_draw_dev.h"
 #include "match_cov_dev.h"
 #include "pose_apply_dev.h"
 #include "obs_filter_dev.h"
@@ -320,12 +321,16 @@ struct DrawLds {
 };
 // MODEL / MODS: the frame driver's covariance model (mv_obs_cov; <MV_COV_MATCH, false> = MatchCovariance as before).  GMM reads the dense
 // depth-variance maps the tracking already takes (a.sdd0 / a.sdd1).
+// PM >= 3 — keypoint rows that do not come from a candidate list (`cand` unused): 3 EXPLICIT, an int64 [lanes, cap, 2] (u, v) table passed as `perm` (it may BE
+// out_uv: the row is then not written back), live rows from cnt or — da.count given — from device memory, published to da.out_live; 4 RANDOM, every
+// workgroup draws the lane's 2 k words (kp_draw_dev.h) and workgroup (0, 0, lane) stores the advanced generator into the other state buffer, as PM = 2 does;
+// 5 GRID, computed from the row index.  Their scalars ride in pa.idx: [0] mask_width (4) | cols, sh, sw, mask (5).  Everything behind the row is PM 0-2's.
 template <int PM, int MODEL = MV_COV_MATCH, bool MODS = false>   // PM: where the permutation comes from: 0 device memory, 1 the kernel arguments, 2 drawn here
 __global__ __launch_bounds__(256) void backend_front_kernel(const int32_t* __restrict__ cand, size_t cand_lane_stride, const int64_t* __restrict__ perm,
                                                             PermArg pa, int cap, mvLaneCounts cnt, int64_t* out_uv, TrackArgs a, float fx, float fy,
                                                             float cx, float cy, float* pos_Tc, const float* depth_map0, const float* depth_map1,
                                                             double* out_cov0, double* out_cov1, mvMatchCovParams cp, DrawArgs da) {
-    __shared__ __attribute__((aligned(16))) char draw_raw[PM == 2 ? sizeof(DrawLds) : 16];
+    __shared__ __attribute__((aligned(16))) char draw_raw[PM == 2 ? sizeof(DrawLds) : PM == 4 ? sizeof(mvkp::Scratch) : 16];
     DrawLds& D = *reinterpret_cast<DrawLds*>(draw_raw);
     const int lane = threadIdx.x & 63;
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -341,22 +346,49 @@ __global__ __launch_bounds__(256) void backend_front_kernel(const int32_t* __res
             for (int i = threadIdx.x; i < N; i += 256) da.out_perm[(size_t)pl * cap + i] = D.out[i];
             if (threadIdx.x == 0) { da.out_live[2 * pl] = N; da.out_live[2 * pl + 1] = (int32_t)n_cand; }
         }
+    } else if constexpr (PM == 3) {
+        if (da.count) {
+            const int c = da.count[(size_t)pl * da.count_stride];
+            N = c < 0 ? 0 : (c > cap ? cap : c);
+        } else {
+            N = cnt.n[pl];
+        }
+        if (da.out_live && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { da.out_live[2 * pl] = N; da.out_live[2 * pl + 1] = N; }
+    } else if constexpr (PM == 4) {
+        N = cnt.n[pl];
+        const bool adv = blockIdx.x == 0 && blockIdx.y == 0;
+        mv_kp_random_wg(da.state_in + (size_t)pl * mvrp::MT_STRIDE, adv ? da.state_out + (size_t)pl * mvrp::MT_STRIDE : nullptr, da.k,
+                        *reinterpret_cast<mvkp::Scratch*>(draw_raw));
     } else {
         N = cnt.n[pl];
     }
     if (n < N) {       // (wave-uniform)
-        const int32_t* cand_l = cand + (size_t)pl * cand_lane_stride;
-        const long pi = PM == 2 ? (long)D.out[n] : PM == 1 ? (long)pa.idx[n] : (long)perm[(size_t)pl * cap + n];
-        const int lin = cand_l[pi];
-        const int u0 = lin % a.W, v0 = lin / a.W;
+        int u0, v0;
+        if constexpr (PM <= 2) {
+            const int32_t* cand_l = cand + (size_t)pl * cand_lane_stride;
+            const long pi = PM == 2 ? (long)D.out[n] : PM == 1 ? (long)pa.idx[n] : (long)perm[(size_t)pl * cap + n];
+            const int lin = cand_l[pi];
+            u0 = lin % a.W;
+            v0 = lin / a.W;
+        } else if constexpr (PM == 3) {
+            const int64_t* kp = perm + 2 * ((size_t)pl * cap + n);
+            u0 = (int)kp[0];
+            v0 = (int)kp[1];
+        } else if constexpr (PM == 4) {
+            mvkp::row_of(reinterpret_cast<mvkp::Scratch*>(draw_raw)->w, da.k, n, a.H, a.W, pa.idx[0], u0, v0);
+        } else {
+            mvkp::grid_row(mvkp::Grid{pa.idx[0], 0, pa.idx[1], pa.idx[2], pa.idx[3]}, n, u0, v0);
+        }
         TrackArgs al = a;
         track_lane_offsets(al, pl, cap);
         const size_t ln = (size_t)pl * cap;
         float u, v, suu, svv, suv;
         if (set == 0) {
             if (lane == 0) {     // kp_front_kernel's body; sigma1 is the set-1 wave's row
-                out_uv[2 * (ln + n) + 0] = u0;
-                out_uv[2 * (ln + n) + 1] = v0;
+                if (PM != 3 || out_uv != perm) {
+                    out_uv[2 * (ln + n) + 0] = u0;
+                    out_uv[2 * (ln + n) + 1] = v0;
+                }
                 kp_track_one(n, u0, v0, al.match_flow, al.match_cov, al.depth0, al.disp0, al.sdisp0, al.sdd0, al.depth1, al.disp1, al.sdisp1, al.sdd1,
                              al.H, al.W, al.edge, al.match_cov_default, al.out_kp0, al.out_kp1, al.out_inbound, al.out_vals, (size_t)gridDim.z * cap,
                              nullptr, nullptr);
@@ -586,6 +618,73 @@ int mv_backend_front_cov_draw_lanes(int cov_model, int32_t cov_modifiers, const 
     const DrawArgs da{count_dev, count_stride, state_in, state_out, num_point, 0, out_perm, out_live};
     launch_backend_front<2>(cov_model, cov_modifiers, grid, (hipStream_t)stream, da, cand, cand_lane_stride, (const int64_t*)nullptr, pa, cap, mvLaneCounts{},
                             out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
+    return mv_launch_status();
+}
+
+// The front launch with keypoint rows that come from no candidate list (backend_front_kernel<3 | 4 | 5>).  kp_mode:
+//   MV_KP_EXPLICIT  kp_uv int64 [lanes, cap, 2] in device memory (may be out_kp0_uv itself); live rows n_live[l] (host) or, n_live == NULL,
+//                   n_live_dev[l * n_live_stride] clamped to [0, cap].  Rows are used as given: coordinates outside the image read pixel 0 and are
+//                   marked out of bounds, a covariance patch that leaves the image is clamped — callers keep keypoints cov_kernel_size / 2 inside.
+//   MV_KP_RANDOM    num_point rows per lane drawn from state_in, the advanced generators stored to state_out (!= state_in)
+//   MV_KP_GRID      the mv_kp_grid_count(H, W, mask_width, num_point) rows of GridSelector
+// out_live ([lanes, 2] or NULL): the live-row count as the *_dev solves read it.
+int mv_backend_front_cov_kp_lanes(int cov_model, int32_t cov_modifiers, int kp_mode, const int64_t* kp_uv, const int32_t* n_live, const int32_t* n_live_dev,
+                                  int n_live_stride, const uint32_t* state_in, uint32_t* state_out, int num_point, int mask_width, int lanes, int cap,
+                                  const float* match_flow, const float* match_cov, const float* depth0, const float* disp0, const float* sdisp0,
+                                  const float* sdd0, const float* depth1, const float* disp1, const float* sdisp1, const float* sdd1, int edge,
+                                  float match_cov_default, const mvMatchCovParams* cov_params, int32_t* out_live, int64_t* out_kp0_uv, float* out_kp0,
+                                  float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0, float* out_sigma1, float* out_pos_Tc,
+                                  double* out_cov0, double* out_cov1, mvStream_t stream) {
+    MV_CHECK_ARG(cov_params && edge >= 0 && lanes >= 1 && lanes <= MV_MAX_LANES && cap >= 1 && num_point >= 0 && mask_width >= 0);
+    MV_CHECK_ARG(cov_model >= MV_COV_MATCH && cov_model <= MV_COV_NONE && mv_cov_modifiers_ok(cov_modifiers));
+    MV_CHECK_ARG(cov_model != MV_COV_GMM || (sdd0 && sdd1));
+    const mvMatchCovParams cp = *cov_params;
+    MV_CHECK_ARG(cp.H > 0 && cp.W > 0 && cp.kernel_size >= 1 && (cp.kernel_size & 1) && cp.use_patch_var);
+    if (cp.kernel_size > mvcov::MAX_K) return MV_ERR_UNSUPPORTED;
+    MV_CHECK_ARG(match_flow && depth0 && depth1 && out_kp0_uv && out_kp1 && out_inbound && out_vals && out_sigma0 && out_sigma1 && out_pos_Tc && out_cov0 &&
+                 out_cov1);
+    const TrackArgs ta{match_flow, match_cov, depth0, disp0, sdisp0, sdd0, depth1, disp1, sdisp1, sdd1, cp.H, cp.W, edge, match_cov_default,
+                       out_kp0, out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1};
+    mvLaneCounts c{};
+    PermArg pa;
+    pa.idx[0] = 0;
+    int n_max = 0;
+    DrawArgs da{};
+    da.out_live = out_live;
+    if (kp_mode == MV_KP_EXPLICIT) {
+        MV_CHECK_ARG(kp_uv && (n_live || (n_live_dev && n_live_stride >= 1)));
+        if (n_live) {
+            const int rc = check_lanes(lanes, n_live, cap, c, n_max);
+            if (rc != MV_OK) return rc;
+        } else {
+            n_max = cap;
+            da.count = n_live_dev;
+            da.count_stride = n_live_stride;
+        }
+        if (n_max == 0) return MV_OK;
+        launch_backend_front<3>(cov_model, cov_modifiers, dim3(mv_ceil_div(n_max, 4), 2, lanes), (hipStream_t)stream, da, (const int32_t*)nullptr, (size_t)0, kp_uv,
+                                pa, cap, c, out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
+    } else if (kp_mode == MV_KP_RANDOM) {
+        MV_CHECK_ARG(state_in && state_out && state_in != state_out && num_point >= 1 && num_point <= cap && cp.H > 2 * mask_width && cp.W > 2 * mask_width);
+        if (num_point > mvkp::MAX_POINT) return MV_ERR_UNSUPPORTED;
+        for (int l = 0; l < lanes; ++l) c.n[l] = num_point;
+        pa.idx[0] = mask_width;
+        da.state_in = state_in;
+        da.state_out = state_out;
+        da.k = num_point;
+        launch_backend_front<4>(cov_model, cov_modifiers, dim3(mv_ceil_div(num_point, 4), 2, lanes), (hipStream_t)stream, da, (const int32_t*)nullptr, (size_t)0,
+                                (const int64_t*)nullptr, pa, cap, c, out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
+    } else if (kp_mode == MV_KP_GRID) {
+        mvkp::Grid g;
+        const int n = mvkp::grid_of(cp.H, cp.W, mask_width, num_point, &g);
+        MV_CHECK_ARG(n >= 1 && n <= cap);
+        for (int l = 0; l < lanes; ++l) c.n[l] = n;
+        pa.idx[0] = g.cols; pa.idx[1] = g.sh; pa.idx[2] = g.sw; pa.idx[3] = g.mask;
+        launch_backend_front<5>(cov_model, cov_modifiers, dim3(mv_ceil_div(n, 4), 2, lanes), (hipStream_t)stream, da, (const int32_t*)nullptr, (size_t)0,
+                                (const int64_t*)nullptr, pa, cap, c, out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
+    } else {
+        return MV_ERR_INVALID_ARG;
+    }
     return mv_launch_status();
 }
 

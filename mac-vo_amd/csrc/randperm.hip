@@ -9,6 +9,8 @@
 #include "randperm_dev.h"
 #include <vector>
 
+int mv_randperm_heads_emulated_state(uint32_t* state, const int64_t* n, int calls, int k, int threads, int64_t* out);
+
 namespace {
 
 __global__ __launch_bounds__(1024) void randperm_head_kernel(uint32_t* __restrict__ state, const int32_t* __restrict__ n_dev, int n_stride, int k, int cap,
@@ -42,11 +44,16 @@ extern "C" int mv_randperm_head_lanes(uint32_t* state, const int32_t* n_dev, int
 }
 
 extern "C" int mv_randperm_heads_emulated(uint64_t seed, const int64_t* n, int calls, int k, int threads, int64_t* out) {
+    std::vector<uint32_t> state(mvrp::MT_STRIDE);
+    mvrp::mt_seed((uint32_t)(seed & 0xffffffffull), state.data());
+    return mv_randperm_heads_emulated_state(state.data(), n, calls, k, threads, out);
+}
+
+// ... continuing from (and advancing) a generator in its MT_STRIDE-word representation: what follows other draws of the same generator (kp_draw.hip)
+int mv_randperm_heads_emulated_state(uint32_t* state, const int64_t* n, int calls, int k, int threads, int64_t* out) {
     using namespace mvrp;
-    MV_CHECK_ARG(n && out && calls >= 0 && k >= 0 && threads >= 1 && threads <= 4096);
+    MV_CHECK_ARG(state && n && out && calls >= 0 && k >= 0 && threads >= 1 && threads <= 4096);
     if (k > MAX_HEAD) return MV_ERR_UNSUPPORTED;
-    std::vector<uint32_t> state(MT_STRIDE);
-    mt_seed((uint32_t)(seed & 0xffffffffull), state.data());
     std::vector<int32_t> head(NBUCKET);
     Scratch* s = new Scratch;
     const int nt = threads;

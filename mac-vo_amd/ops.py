@@ -417,13 +417,13 @@ class KeypointCandidates:
         lin = self.cand[: self.n].long()
         return torch.stack([lin // self.W, lin % self.W], dim=1)
 
-    def finish(self, numPoint: int, staging: torch.Tensor | None = None) -> torch.Tensor:
+    def finish(self, numPoint: int, staging: torch.Tensor | None = None, generator: "torch.Generator | None" = None) -> torch.Tensor:
         """``selected[torch.randperm(n)[:numPoint]][..., 2:].roll(1, 1)`` (KeypointSelector.py:331-332,404-405).
         The permutation comes from the global CPU generator exactly as in the reference.  ``staging``: optional pinned
         int64 buffer (>= numPoint) so the H2D copy of the permutation is truly asynchronous."""
         lib = L.load()
         n = self.n
-        perm = torch.randperm(n)[:numPoint]
+        perm = (torch.randperm(n) if generator is None else torch.randperm(n, generator=generator))[:numPoint]
         n_sel = perm.numel()
         out = torch.empty((n_sel, 2), dtype=torch.int64, device=self.cand.device)
         if n_sel:
@@ -434,6 +434,57 @@ class KeypointCandidates:
             L.check(lib.mv_kp_gather(self.cand.data_ptr(), perm_d.data_ptr(), n_sel, self.W, out.data_ptr(), _stream()),
                     "mv_kp_gather")
         return out
+
+
+# ------------------------------------------------------------------------------------------- RandomSelector / GridSelector
+def mt19937_state(seeds, device) -> torch.Tensor:
+    """Device-resident generators ``[len(seeds), mv_randperm_state_words()]`` (int32 bit patterns of the uint32 words), each with the bits of
+    ``torch.Generator().manual_seed(seed)``: what ``kp_random`` and the device-drawn permutation heads advance."""
+    import ctypes as C
+
+    import numpy as np
+
+    lib = L.load()
+    W = lib.mv_randperm_state_words()
+    st = np.zeros((len(seeds), W), dtype=np.uint32)
+    for l, sd in enumerate(seeds):
+        L.check(lib.mv_mt19937_seed(C.c_uint64(int(sd) & 0xFFFFFFFFFFFFFFFF), st[l].ctypes.data), "mv_mt19937_seed")
+    return torch.from_numpy(st.view(np.int32)).to(device)
+
+
+def _kp_shape_check(num_point: int, H: int, W: int, mask_width: int) -> None:
+    if num_point < 0 or mask_width < 0 or H <= 2 * mask_width or W <= 2 * mask_width:
+        raise ValueError(f"keypoint selector: need num_point >= 0 and an image larger than twice mask_width (H={H}, W={W}, mask_width={mask_width})")
+
+
+def kp_random(state: torch.Tensor, num_point: int, H: int, W: int, mask_width: int) -> torch.Tensor:
+    """``RandomSelector.select_point`` (KeypointSelector.py:103-118) of every lane's device-resident generator: int64 ``[lanes, num_point, 2]`` (u, v),
+    bit for bit ``torch.randint`` of CPU generators seeded alike (first the rows' v, then their u).  ``state`` (``mt19937_state``) is advanced in place
+    by ``2 * num_point`` draws."""
+    _kp_shape_check(num_point, H, W, mask_width)
+    lib = L.load()
+    if state.dim() != 2 or state.shape[1] != lib.mv_randperm_state_words() or state.dtype != torch.int32 or not state.is_contiguous():
+        raise ValueError("kp_random: state must be the contiguous int32 [lanes, state_words] tensor of mt19937_state")
+    if num_point > lib.mv_kp_random_max_point():
+        raise ValueError(f"kp_random: num_point {num_point} > {lib.mv_kp_random_max_point()} (the draw's word buffer)")
+    out = torch.empty((state.shape[0], num_point, 2), dtype=torch.int64, device=state.device)
+    L.check(lib.mv_kp_random_lanes(state.data_ptr(), state.shape[0], num_point, H, W, mask_width, out.data_ptr(), _stream()), "mv_kp_random_lanes")
+    return out
+
+
+def kp_grid_count(H: int, W: int, mask_width: int, num_point: int) -> int:
+    """Rows ``GridSelector.select_point`` returns (KeypointSelector.py:216-247) — possibly MORE than ``num_point``; 0 where the reference raises."""
+    return int(L.load().mv_kp_grid_count(H, W, mask_width, num_point))
+
+
+def kp_grid(H: int, W: int, mask_width: int, num_point: int, device) -> torch.Tensor:
+    """``GridSelector.select_point``: int64 ``[kp_grid_count(...), 2]`` (u, v)."""
+    n = kp_grid_count(H, W, mask_width, num_point)
+    if n <= 0:
+        raise ValueError(f"kp_grid: empty grid or a grid step of 0 (H={H}, W={W}, mask_width={mask_width}, num_point={num_point}); the reference raises here")
+    out = torch.empty((n, 2), dtype=torch.int64, device=device)
+    L.check(L.load().mv_kp_grid(H, W, mask_width, num_point, out.data_ptr(), _stream()), "mv_kp_grid")
+    return out
 
 
 _ws_cache: dict = {}

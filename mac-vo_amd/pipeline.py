@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import os
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import torch
 
@@ -73,7 +73,10 @@ class HotPathConfig:
     num_point: int = 200
     edgewidth: int = 32
     match_cov_default: float = 0.25
-    selector: str = "nodepth"            # CovAwareSelector_NoDepth | "full" = CovAwareSelector
+    # CovAwareSelector_NoDepth | "full" = CovAwareSelector | "random" = RandomSelector | "grid" = GridSelector (both use kp_mask_width only) |
+    # "explicit" = every frame's keypoints come from the caller (FrameInputs.keypoints / step(..., keypoints=)).  selector_config_fields() maps a
+    # reference `keypoint` block onto this field and the selector's arguments.
+    selector: str = "nodepth"
     kp_kernel_size: int = 7
     kp_mask_width: int = 32
     max_match_cov: float = 100.0
@@ -163,6 +166,83 @@ def motion_config_fields(block) -> dict:
     return {"motion_model": _MOTION_TYPES[t]}
 
 
+_SELECTOR_TYPES = {"CovAwareSelector_NoDepth": "nodepth", "CovAwareSelector": "full", "RandomSelector": "random", "GridSelector": "grid",
+                   "HIP_CovAwareSelector_NoDepth": "nodepth", "HIP_CovAwareSelector": "full", "HIP_RandomSelector": "random", "HIP_GridSelector": "grid"}
+SELECTORS = ("nodepth", "full", "random", "grid", "explicit")
+MAPLESS_SELECTORS = ("random", "grid", "explicit")     # look at no map: no selector kernels, no candidate list
+
+
+def selector_config_fields(block) -> dict:
+    """A reference ``keypoint`` block (``{type, args}`` as a dict or SimpleNamespace) -> ``{"selector", "kp_mask_width", ...}`` for
+    :class:`HotPathConfig`: ``mask_width`` for every selector, and ``kernel_size`` / ``max_depth`` / ``max_depth_cov`` / ``max_match_cov`` for the
+    CovAware ones.  ``GradientSelector``, ``SparseGradienSelector`` and ``SelectorCompose`` have no HIP form: run them from torch and hand their
+    pixels to the pipe as explicit keypoints (``selector="explicit"``)."""
+    t = _ns_get(block, "type")
+    if t not in _SELECTOR_TYPES:
+        raise ValueError(f"keypoint selector {t!r} has no HIP form (one of {sorted(set(_SELECTOR_TYPES))}); "
+                         "its pixels can be fed through selector='explicit'")
+    out = {"selector": _SELECTOR_TYPES[t]}
+    args = _ns_get(block, "args")
+    names = [("mask_width", "kp_mask_width")]
+    if out["selector"] in ("nodepth", "full"):
+        names += [("kernel_size", "kp_kernel_size"), ("max_depth", "max_depth"), ("max_depth_cov", "max_depth_cov"), ("max_match_cov", "max_match_cov")]
+    for k, f in names:
+        try:
+            out[f] = _ns_get(args, k)
+        except (KeyError, AttributeError, TypeError):
+            pass
+    return out
+
+
+def check_selector(cfg: "HotPathConfig", cam: "Camera") -> None:
+    """Configuration-time checks of the selector block (the frame driver's check_config applies the same rules)."""
+    if cfg.selector not in SELECTORS:
+        raise ValueError(f"selector must be one of {SELECTORS}, not {cfg.selector!r}")
+    if cfg.selector not in MAPLESS_SELECTORS:
+        return
+    m = cfg.kp_mask_width
+    if m < 0 or cam.H <= 2 * m or cam.W <= 2 * m:
+        raise ValueError(f"selector {cfg.selector!r}: kp_mask_width {m} leaves no pixel of a {cam.W} x {cam.H} image")
+    if cfg.selector == "grid" and ops.kp_grid_count(cam.H, cam.W, m, cfg.num_point) <= 0:
+        raise ValueError(f"selector 'grid': a grid step of 0 at {cam.W} x {cam.H}, mask_width {m}, num_point {cfg.num_point} (the reference raises here)")
+    if cfg.selector == "random" and cfg.num_point > ops.L.load().mv_kp_random_max_point():
+        raise ValueError(f"selector 'random': num_point {cfg.num_point} > {ops.L.load().mv_kp_random_max_point()} (the draw's word buffer)")
+    if table_rows(cfg, cam) > ops.L.MV_KP_TABLE_MAX:
+        raise ValueError(f"selector {cfg.selector!r}: {table_rows(cfg, cam)} keypoint rows > MV_KP_TABLE_MAX = {ops.L.MV_KP_TABLE_MAX}")
+    if cfg.cov_model in ("match", "gmm") and m < cfg.cov_kernel_size // 2:
+        raise ValueError(
+            f"selector {cfg.selector!r} with cov_model {cfg.cov_model!r}: kp_mask_width {m} < cov_kernel_size // 2 = {cfg.cov_kernel_size // 2}.  The "
+            f"{cfg.cov_kernel_size} x {cfg.cov_kernel_size} covariance patch of a keypoint that close to the border leaves the image; the reference then "
+            "wraps negative indices or raises while the kernel clamps, so such keypoints must not get in (raise kp_mask_width, or use cov_model='none')")
+
+
+def table_rows(cfg: "HotPathConfig", cam: "Camera") -> int:
+    """Rows of capacity per lane of the per-keypoint tables: ``max(num_point, grid count)`` for "grid" (GridSelector may return more rows than
+    ``num_point``: 231 at 640 x 480 / 32 / 200), ``num_point`` otherwise."""
+    if cfg.selector == "grid":
+        return max(cfg.num_point, ops.kp_grid_count(cam.H, cam.W, cfg.kp_mask_width, cfg.num_point))
+    return cfg.num_point
+
+
+def check_keypoints(kp: torch.Tensor, cfg: "HotPathConfig", cam: "Camera") -> None:
+    """Explicit keypoints (host tensors only): inside the image and, for the patch-based covariance models, ``cov_kernel_size // 2`` from its border."""
+    if kp.numel() == 0:
+        return
+    hw = cfg.cov_kernel_size // 2 if cfg.cov_model in ("match", "gmm") else 0
+    u, v = kp[..., 0], kp[..., 1]
+    if int(u.min()) < hw or int(u.max()) >= cam.W - hw or int(v.min()) < hw or int(v.max()) >= cam.H - hw:
+        raise ValueError(f"explicit keypoints must lie at least {hw} pixels inside the {cam.W} x {cam.H} image (cov_model {cfg.cov_model!r}: the covariance "
+                         "patch must not leave the image)")
+
+
+def _randint_rows(num_point: int, H: int, W: int, mask: int, g) -> torch.Tensor:
+    """RandomSelector.select_point (KeypointSelector.py:103-118) on the CPU generator ``g`` (None: torch's global one): first the rows' v, then their u."""
+    kw = {} if g is None else {"generator": g}
+    h = torch.randint(mask, H - mask, (num_point, 1), **kw)
+    w = torch.randint(mask, W - mask, (num_point, 1), **kw)
+    return torch.cat([w, h], dim=1)
+
+
 @dataclass
 class FrameInputs:
     """What the learned layers hand to the hot path for one ``estimate_pair`` (all GPU-resident).
@@ -190,6 +270,11 @@ class FrameInputs:
     image: torch.Tensor | None = None
     # frame timestamp (StereoData.frame_ns) — recorded in the device-resident map when one is attached
     time_ns: int = 0
+    # caller-supplied keypoints of this frame: int64 (u, v) rows [n, 2] ([lanes, n, 2] for a batched step), on the host (checked) or on the device
+    # (used as given: the caller keeps them cov_kernel_size // 2 inside the image).  Required by selector "explicit"; on any other selector they
+    # replace the frame's own selection.  keypoint_counts: live rows per lane (default: all n).
+    keypoints: torch.Tensor | None = None
+    keypoint_counts: "list | None" = None
     # promise that every tensor above lives at a fixed address for the lifetime of the HotPath (e.g. the static output
     # buffers of a graph-captured network, as in the reference's CUDAGraph frontend): allows hipGraph replay
     static: bool = False
@@ -217,10 +302,12 @@ class HotPath:
     (before ``pose_norm``), called on the current stream between a frame's frontend and its finish."""
 
     def __init__(self, cam: Camera, cfg: HotPathConfig | None = None, device: str | torch.device = "cuda",
-                 keep_extras: bool = False, pose_net=None):
+                 keep_extras: bool = False, pose_net=None, generator: "torch.Generator | None" = None):
         self.cam, self.cfg = cam, cfg or HotPathConfig()
         _check_motion(self.cfg)
+        check_selector(self.cfg, cam)
         self.pose_net = pose_net
+        self.generator = generator   # CPU generator of the selector's draws (None: torch's global one, which is what the reference consumes)
         self.dev = torch.device(device)
         self.keep_extras = keep_extras
         self.lm = ops.lm_default_params()
@@ -249,7 +336,7 @@ class HotPath:
         self._tok = None
         self.last_tokens = None
         # offsets table: row n = [0, n] (one problem of n points) — avoids an H2D copy per frame
-        m = self.cfg.num_point + 1
+        m = table_rows(self.cfg, cam) + 1
         self._offs = torch.stack([torch.zeros(m, dtype=torch.int32), torch.arange(m, dtype=torch.int32)], 1).to(self.dev)
 
     # ------------------------------------------------------------------ frontend part of the hot path
@@ -350,7 +437,9 @@ class HotPath:
         c, cam = self.cfg, self.cam
         maps0 = self.maps_prev_for_next
         maps1, cands, host_count = self.frontend(x, with_selector=True)
-        if cands is None:   # CovAwareSelector needs the previous frame's depth maps: eager, after the frontend
+        if c.selector in MAPLESS_SELECTORS or x.keypoints is not None:
+            pass            # no candidate list: the keypoints are drawn / computed / taken from the caller in finish
+        elif cands is None:   # CovAwareSelector needs the previous frame's depth maps: eager, after the frontend
             cands = ops.kp_select("full", cam.H, cam.W, flow_cov=maps1.flow_cov, depth0=maps0.depth,
                                   depth0_cov=maps0.depth_cov, depth1=maps1.depth, depth1_cov=maps1.depth_cov,
                                   kernel_size=c.kp_kernel_size, mask_width=c.kp_mask_width, max_depth=self._max_depth,
@@ -378,6 +467,7 @@ class HotPath:
             pend.motion_ev = torch.cuda.Event()
             pend.motion_ev.record()
         pend.cands_m, pend.host_count_m, pend.image0 = cands_m, host_count_m, self._prev_image
+        pend.keypoints, pend.keypoint_counts = x.keypoints, x.keypoint_counts
         self._prev_image = x.image
         return pend
 
@@ -406,15 +496,33 @@ class HotPath:
                     motion = self.pose_motion(pend)
                 motion_ev = torch.cuda.Event()
                 motion_ev.record()
-        pend.event.synchronize()
-        cands._n = int(pend.host_count[0])
+        mapless = c.selector in MAPLESS_SELECTORS or pend.keypoints is not None
+        if not mapless:
+            pend.event.synchronize()
+            cands._n = int(pend.host_count[0])
         back, side = self._back, self._side
         # The backend runs on its own stream: it must not queue behind the NEXT frame's decoder-side work that
         # enqueue_frontend already put on the main stream (that work waits for the next volume GEMM).
         back.wait_event(pend.event)
         with torch.cuda.stream(back):
             self._perm_slot = (self._perm_slot + 1) % len(self._perm_pinned)
-            kp0 = cands.finish(c.num_point, staging=self._perm_pinned[self._perm_slot])  # CPU randperm, as the reference
+            if pend.keypoints is not None:
+                kp0 = pend.keypoints.reshape(-1, 2)
+                if pend.keypoint_counts is not None:
+                    kp0 = kp0[: int(pend.keypoint_counts[0])]
+                if kp0.shape[0] > table_rows(c, cam):
+                    raise ValueError(f"{kp0.shape[0]} explicit keypoints > the table capacity {table_rows(c, cam)}")
+                if not kp0.is_cuda:
+                    check_keypoints(kp0, c, cam)
+                kp0 = kp0.to(self.dev, torch.int64).contiguous()
+            elif c.selector == "explicit":
+                raise ValueError("selector 'explicit': the frame carries no keypoints (FrameInputs.keypoints / step(..., keypoints=))")
+            elif c.selector == "random":   # torch.randint on the CPU generator, exactly as the reference (KeypointSelector.py:103-118)
+                kp0 = _randint_rows(c.num_point, cam.H, cam.W, c.kp_mask_width, self.generator).to(self.dev)
+            elif c.selector == "grid":
+                kp0 = ops.kp_grid(cam.H, cam.W, c.kp_mask_width, c.num_point, self.dev)
+            else:
+                kp0 = cands.finish(c.num_point, staging=self._perm_pinned[self._perm_slot], generator=self.generator)  # CPU randperm, as the reference
             n = kp0.shape[0]
             if self._pgo_done is not None:
                 back.wait_event(self._pgo_done)   # self.pose of the previous frame is produced on the PGO stream
@@ -471,7 +579,7 @@ class HotPath:
             if int(n_valid.item()) >= c.min_num_point:
                 pend.cands_m._n = int(pend.host_count_m[0])
                 with torch.cuda.stream(back):
-                    muv = pend.cands_m.finish(c.map_num_point)
+                    muv = pend.cands_m.finish(c.map_num_point, generator=self.generator)
                     map_pts = ops.map_points(muv, maps0.depth, maps0.depth_cov, cam.K4, prev_pose.reshape(1, 7), image=pend.image0,
                                              match_cov_default=c.match_cov_default, kernel_size=c.cov_kernel_size,
                                              min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov, cov_model=c.cov_model,
@@ -489,9 +597,12 @@ class HotPath:
                               maps1=maps1, cands=cands)
         return res
 
-    def step(self, x: FrameInputs) -> FrameResult:
-        """One ``run_pair`` start to finish (no cross-frame overlap); results are valid on the current stream."""
+    def step(self, x: FrameInputs, keypoints: torch.Tensor | None = None) -> FrameResult:
+        """One ``run_pair`` start to finish (no cross-frame overlap); results are valid on the current stream.  ``keypoints``: this frame's
+        keypoints (see :class:`FrameInputs`), instead of ``x.keypoints``."""
         assert self.maps_prev_for_next is not None, "call initialize() with the first frame"
+        if keypoints is not None:
+            x = replace(x, keypoints=keypoints, keypoint_counts=None)
         res = self.finish(self.enqueue_frontend(x))
         self.sync_pose()
         return res
@@ -536,6 +647,8 @@ class _Pending:
     motion_in: torch.Tensor | None = None                # motion_model "tartan": the PoseNet input [1, 5, 112, 160]
     motion: torch.Tensor | None = None                   # ... the PoseNet's raw output, when HotPath.pose_net ran it behind the enqueue
     motion_ev: "torch.cuda.Event | None" = None
+    keypoints: torch.Tensor | None = None                # caller-supplied keypoints of the frame (FrameInputs.keypoints)
+    keypoint_counts: "list | None" = None
 
 
 # ====================================================================================== native driver (default)
@@ -551,8 +664,16 @@ def stack_lanes(inputs: "list[FrameInputs]") -> FrameInputs:
     assert len(inputs) == 1 or all(x.image is None for x in inputs), "stack_lanes: per-lane images are not carried"
     cat = lambda name, dim=0: (None if getattr(inputs[0], name) is None  # noqa: E731
                                else torch.cat([getattr(x, name) for x in inputs], dim=dim).contiguous())
+    kps = None
+    if any(x.keypoints is not None for x in inputs):   # per-lane [n_l, 2] rows -> [lanes, max n, 2] + counts
+        assert all(x.keypoints is not None for x in inputs), "stack_lanes: keypoints for every lane or for none"
+        rows = [x.keypoints.reshape(-1, 2) if x.keypoint_counts is None else x.keypoints.reshape(-1, 2)[: int(x.keypoint_counts[0])] for x in inputs]
+        kps = rows[0].new_zeros((len(rows), max(r.shape[0] for r in rows), 2))
+        for l, r in enumerate(rows):
+            kps[l, : r.shape[0]] = r
     return FrameInputs(fmap1=cat("fmap1"), fmap2=cat("fmap2"), coords=cat("coords", 1), flow=cat("flow"), logcov=cat("logcov"),
                        flow8=cat("flow8"), cov8=cat("cov8"), up_mask=cat("up_mask"), cov_mask=cat("cov_mask"),
+                       keypoints=kps, keypoint_counts=None if kps is None else [r.shape[0] for r in rows],
                        image=inputs[0].image if len(inputs) == 1 else None, time_ns=inputs[0].time_ns,
                        static=all(x.static for x in inputs))
 
@@ -648,6 +769,7 @@ class NativeHotPath:
                  keep_extras: bool = False, lanes: int = 1, generators: "list | None" = None, pose_net=None):
         self.cam, self.cfg = cam, cfg or HotPathConfig()
         _check_motion(self.cfg)
+        check_selector(self.cfg, cam)
         self.pose_net = pose_net   # motion_model "tartan": [lanes, 5, 112, 160] -> [lanes, 6], run right behind each tracked frame's enqueue
         if self.cfg.mapping and lanes != 1:
             raise ops.L.MacvoHipError("the dense-mapping tail (mapping=True) runs one sequence per pipe (lanes == 1), as the reference does")
@@ -669,7 +791,14 @@ class NativeHotPath:
             raise ops.L.MacvoHipError("mapping=True draws its second permutation on the Python side: use torch generators")
         self._prev_image = None          # mapping: LEFT image of the previously enqueued frame (map-point colours, MACVO.py:326-328)
         self._images: list = []
-        self._cap = max(self.cfg.num_point, 1)
+        self._cap = max(table_rows(self.cfg, cam), 1)      # the driver's capacity rule (mv_frame_pipe_table_rows)
+        self._frame_rows = (ops.kp_grid_count(cam.H, cam.W, self.cfg.kp_mask_width, self.cfg.num_point) if self.cfg.selector == "grid"
+                            else self.cfg.num_point)
+        # "grid": nothing in a frame waits for the host either (the rows are computed inside the front launch) — run() drives it like a device-driven frame
+        self._hostless = self.cfg.selector == "grid" and not self.cfg.mapping
+        self._kp = torch.zeros((self.lanes, self._cap, 2), dtype=torch.int64)   # host staging of keypoint rows
+        self._kps: list = []             # keypoints of the enqueued, unfinished frames (FrameInputs.keypoints; None: the pipe's own selector)
+        self._kp_keep: list = []         # device keypoints / counts of the newest finishes (read asynchronously by the pipe)
         self._volume_ahead = os.environ.get("MV_PIPE_VOLUME_AHEAD", "1") != "0"   # A/B knobs of run()
         # frames in flight: never more than the slot rotation the library was built with (MV_MAX_PENDING, 3 in the stock build)
         # The default follows the stream layout the driver picks (mv_frame_pipe_default_depth): 3 for the round-5 layout of one- and two-lane pipes (even /
@@ -708,7 +837,8 @@ class NativeHotPath:
         pc = L.mvFramePipeConfig(
             H=cam.H, W=cam.W, C=chans, pairs=pairs, iters=x.coords.shape[0], radius=c.radius, feat_dtype=dt,
             layout=L.MV_LAYOUT_HWC if hwc else L.MV_LAYOUT_CHW, volume_split={"exact": 0, "split3": 3, "split2": 2, "bf16x3": L.MV_PACK_BF16X3, "f16x2": L.MV_PACK_F16X2}[c.volume_precision] if dt == L.MV_F32 else (L.MV_VOL_ENC16 if (c.volume_store == "encoder" and dt == L.MV_F16 and c.radius == 4) else 0),   # 16-bit features: one kernel family
-            selector_mode=L.MV_KP_NODEPTH if c.selector == "nodepth" else L.MV_KP_FULL,
+            selector_mode={"nodepth": L.MV_KP_NODEPTH, "full": L.MV_KP_FULL, "random": L.MV_KP_RANDOM, "grid": L.MV_KP_GRID,
+                           "explicit": L.MV_KP_EXPLICIT}[c.selector],
             kp_kernel_size=c.kp_kernel_size, kp_mask_width=c.kp_mask_width, num_point=c.num_point, edgewidth=c.edgewidth,
             min_num_point=c.min_num_point, graph_type=ops._GRAPH[c.graph_type], filters=c.filters,
             cov_kernel_size=c.cov_kernel_size, fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy, baseline=cam.baseline,
@@ -858,6 +988,7 @@ class NativeHotPath:
     def enqueue_frontend(self, x: FrameInputs):
         assert self._n_enq >= 1, "call initialize() with the first frame"
         self._enqueue(x, True)
+        self._kps.append((x.keypoints, x.keypoint_counts))
         if self.cfg.motion_model == "tartan":
             self._motion()
         if self.cfg.mapping:
@@ -892,6 +1023,23 @@ class NativeHotPath:
         """Host half of a frame: wait for the candidate counts, draw the permutations (CPU generators, lane order), enqueue
         the pose-dependent kernels.  Returns a :class:`_NativeResult` (a list of them, one per lane, for lanes > 1)."""
         L, lib = ops.L, self._lib
+        sink = None if pose_sink is None else pose_sink.data_ptr()
+        kp, kp_counts = self._kps[0] if self._kps else (None, None)     # (taken off the list by _finished: a finish that raises leaves the frame pending)
+        sel = self.cfg.selector
+        if kp is not None or sel == "explicit":
+            return self._finish_keypoints(kp, kp_counts, sink)
+        if sel == "grid":   # nothing to draw and nothing to wait for: the front launch computes the rows
+            L.check(lib.mv_frame_pipe_release(self._pipe, ops._stream()), "mv_frame_pipe_release")
+            L.check(lib.mv_frame_pipe_finish_device(self._pipe, sink), "mv_frame_pipe_finish_device")
+            for l in range(self.lanes):
+                self._nsel[l] = self._ncand[l] = self._frame_rows
+            return self._finished(host_counts=True)
+        if sel == "random" and not self._native_seeds:
+            # torch generators: torch.randint per lane, in lane order, exactly as the reference (KeypointSelector.py:103-118) -> explicit rows
+            c, cam = self.cfg, self.cam
+            for l in range(self.lanes):
+                self._kp[l, : c.num_point] = _randint_rows(c.num_point, cam.H, cam.W, c.kp_mask_width, self.generators[l])
+            return self._finish_keypoints(self._kp, [c.num_point] * self.lanes, sink, checked=True)
         if self.device_driven:
             L.check(lib.mv_frame_pipe_release(self._pipe, ops._stream()), "mv_frame_pipe_release")
             L.check(lib.mv_frame_pipe_finish_device(self._pipe, None if pose_sink is None else pose_sink.data_ptr()), "mv_frame_pipe_finish_device")
@@ -926,6 +1074,40 @@ class NativeHotPath:
                 "mv_frame_pipe_finish")
         return self._finished()
 
+    def _finish_keypoints(self, kp, counts, sink, checked: bool = False):
+        """Finish the oldest pending frame with caller-supplied (or host-drawn) keypoint rows: mv_frame_pipe_finish_keypoints for host tensors,
+        mv_frame_pipe_finish_keypoints_dev — which never waits for the host — for device tensors."""
+        L, lib, C = ops.L, self._lib, ops.C
+        if kp is None:
+            raise ValueError("selector 'explicit': the frame carries no keypoints (FrameInputs.keypoints / step(..., keypoints=))")
+        kp = kp.reshape(self.lanes, -1, 2)
+        n = kp.shape[1]
+        counts = [n] * self.lanes if counts is None else [int(k) for k in counts]
+        if len(counts) != self.lanes or any(k < 0 or k > n for k in counts) or max(counts) > self._cap:
+            raise ValueError(f"keypoints: {counts} live rows of {n} given, table capacity {self._cap}")
+        for l in range(self.lanes):
+            self._nsel[l] = self._ncand[l] = counts[l]
+        L.check(lib.mv_frame_pipe_release(self._pipe, ops._stream()), "mv_frame_pipe_release")
+        if kp.is_cuda:
+            if self.cfg.mapping:
+                raise L.MacvoHipError("device keypoints do not combine with mapping=True (the mapping decision needs the host anyway): pass a host tensor")
+            tab = torch.zeros((self.lanes, self._cap, 2), dtype=torch.int64, device=self.dev)
+            tab[:, :n] = kp.to(torch.int64)
+            cnt = torch.tensor(counts, dtype=torch.int32).to(self.dev, non_blocking=True)
+            self._kp_keep = self._kp_keep[-6:] + [(tab, cnt)]     # alive until the pipe has read them (two more finishes at most)
+            L.check(lib.mv_frame_pipe_finish_keypoints_dev(self._pipe, tab.data_ptr(), cnt.data_ptr(), ops._stream(), sink),
+                    "mv_frame_pipe_finish_keypoints_dev")
+        else:
+            if kp is not self._kp:
+                live = [kp[l, : counts[l]] for l in range(self.lanes)]
+                if not checked:
+                    for r in live:
+                        check_keypoints(r, self.cfg, self.cam)
+                for l, r in enumerate(live):
+                    self._kp[l, : counts[l]] = r
+            L.check(lib.mv_frame_pipe_finish_keypoints(self._pipe, self._kp.data_ptr(), self._nsel, sink), "mv_frame_pipe_finish_keypoints")
+        return self._finished(host_counts=True)
+
     def _map_tail(self, mp):
         """Dense-mapping tail of the frame just finished (Odometry/MACVO.py:303-337): the reference maps only when tracking
         succeeded — so the frame's observation count has to reach the host first (one blocking wait per frame: mapping mode gives
@@ -955,12 +1137,15 @@ class NativeHotPath:
         return ops.MapPoints(v("MAP_UV", f32, (2,)), v("MAP_D", f32, ()), v("MAP_SDD", f32, ()), v("MAP_TC", f32, (3,)), v("MAP_TW", f32, (3,)),
                              v("MAP_COV", torch.float64, (3, 3)), None if img is None else v("MAP_COLOR", torch.uint8, (3,)))
 
-    def _finished(self):
-        """Bookkeeping behind a finish call: map registration, result views."""
+    def _finished(self, host_counts: bool = False):
+        """Bookkeeping behind a finish call: map registration, result views.  host_counts: the frame's row counts are known on the host
+        (self._nsel / self._ncand) although the pipe is device-driven."""
         L, lib = ops.L, self._lib
         self._n_fin += 1
+        if self._kps:
+            self._kps.pop(0)
         mp = getattr(self, "_map", None)
-        dd = self.device_driven
+        dd = self.device_driven and not host_counts
         if mp is not None:
             n_rows = self._cap if dd else int(self._nsel[0])   # (device-driven: an upper bound; the append compacts by the `valid` mask)
             if mp.n_frames + 1 >= mp.cap["frames"] or mp.rows_upper + n_rows >= mp.cap["match"]:
@@ -1007,8 +1192,11 @@ class NativeHotPath:
             self._counts_cache[fin] = got
         return got[0][lane], got[1][lane]
 
-    def step(self, x: FrameInputs):
-        """One ``run_pair`` start to finish (no cross-frame overlap); results are valid on the current stream."""
+    def step(self, x: FrameInputs, keypoints: torch.Tensor | None = None):
+        """One ``run_pair`` start to finish (no cross-frame overlap); results are valid on the current stream.  ``keypoints``: this frame's
+        keypoints (see :class:`FrameInputs`), instead of ``x.keypoints``."""
+        if keypoints is not None:
+            x = replace(x, keypoints=keypoints, keypoint_counts=None)
         self.enqueue_frontend(x)
         res = self.finish()
         self.sync_all()
@@ -1078,7 +1266,7 @@ class NativeHotPath:
         depth = self._depth if depth is None else depth
         it = iter(frames)
         nxt = next(it, None)
-        if self._pipe is not None and self.device_driven:
+        if self._pipe is not None and (self.device_driven or self._hostless):
             # Device-driven frames: nothing in a frame waits for the host, so a frame is enqueued and finished in one go (the next frame's GEMM in between, as
             # in the host-driven order); how far the host runs ahead of the GPU is bounded by the HIP queues, the slot rotation is guarded by events.
             i = 0

@@ -6,6 +6,7 @@ replace, every hot arithmetic step in the HIP kernels (``include/macvo_hip.h``).
     CovAwareSelector_NoDepth                  HIP_CovAwareSelector_NoDepth
     CovAwareSelector                          HIP_CovAwareSelector
     MappingPointSelector                      HIP_MappingPointSelector
+    RandomSelector / GridSelector             HIP_RandomSelector / HIP_GridSelector
     MatchCovariance                           HIP_MatchCovariance
     GaussianMixtureCovariance / NoCovariance  HIP_GaussianMixtureCovariance / HIP_NoCovariance
     Modifier_Diagonalize / Modifier_Normalize HIP_Modifier_Diagonalize / HIP_Modifier_Normalize  (fused into the kernel over a HIP model)
@@ -116,6 +117,61 @@ class HIP_MappingPointSelector(IKeypointSelector):
             "max_depth": lambda v: isinstance(v, float),
             "max_depth_cov": lambda v: isinstance(v, float),
             "mask_width": lambda v: isinstance(v, int),
+        })
+
+
+class HIP_RandomSelector(IKeypointSelector):
+    """``RandomSelector`` (Module/KeypointSelector.py:103-118): ``numPoint`` uniformly random pixels at least ``mask_width`` from the border;
+    duplicates are possible and kept.  Without a ``seed`` the rows are drawn with ``torch.randint`` from torch's global CPU generator — bit-exact
+    with the reference class under ``device: cpu``, in the same word stream as the other selectors' ``torch.randperm`` — and placed on ``device``.
+    An optional ``seed: <int>`` switches to a device-resident generator with the bits of ``torch.Generator().manual_seed(seed)`` and the HIP
+    draw (``ops.kp_random``): no host draw, no host-to-device copy.  (The reference draws from the CUDA generator when ``device`` is a GPU;
+    the CPU generator is the one this project reproduces.)"""
+
+    def __init__(self, config: SimpleNamespace):
+        super().__init__(config)
+        self._state = None
+
+    def select_point(self, frame, numPoint: int, depth0_est, depth1_est, match_est) -> torch.Tensor:
+        dev = torch.device(self.config.device)
+        m = self.config.mask_width
+        seed = getattr(self.config, "seed", None)
+        if seed is None:
+            h = torch.randint(m, frame.height - m, (numPoint, 1))
+            w = torch.randint(m, frame.width - m, (numPoint, 1))
+            return torch.cat([w, h], dim=1).to(dev)
+        if self._state is None:
+            self._state = ops.mt19937_state([seed], dev)
+        return ops.kp_random(self._state, numPoint, frame.height, frame.width, m)[0]
+
+    @classmethod
+    def is_valid_config(cls, config: SimpleNamespace | None) -> None:
+        assert config is not None
+        spec = {
+            "mask_width": lambda m: isinstance(m, int) and m >= 0,
+            "device": _is_device,
+        }
+        seed = getattr(config, "seed", None)
+        if seed is not None:   # (the exact-key-set rule: the optional key is part of the specification only where it is given)
+            spec["seed"] = lambda s: isinstance(s, int) and not isinstance(s, bool) and s >= 0
+        cls._enforce_config_spec(config, spec)
+        if seed is not None and config.device == "cpu":
+            raise ValueError("HIP_RandomSelector: a seeded (device-resident) generator needs a GPU device")
+
+
+class HIP_GridSelector(IKeypointSelector):
+    """``GridSelector`` (Module/KeypointSelector.py:216-247) in one HIP launch.  As in the reference the row count follows from the image size,
+    ``mask_width`` and ``numPoint`` and may exceed ``numPoint`` (``ops.kp_grid_count``); it raises where the reference raises (a grid step of 0)."""
+
+    def select_point(self, frame, numPoint: int, depth0_est, depth1_est, match_est) -> torch.Tensor:
+        return ops.kp_grid(frame.height, frame.width, self.config.mask_width, numPoint, torch.device(self.config.device))
+
+    @classmethod
+    def is_valid_config(cls, config: SimpleNamespace | None) -> None:
+        assert config is not None
+        cls._enforce_config_spec(config, {
+            "mask_width": lambda m: isinstance(m, int) and m >= 0,
+            "device": lambda d: _is_device(d) and d != "cpu",
         })
 
 
