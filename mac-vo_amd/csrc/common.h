@@ -105,29 +105,8 @@ static inline bool mv_cov_modifiers_ok(int32_t m) {
     return true;
 }
 
-// The fused backend front (frontend_ops.hip) with the frame driver's covariance model: mv_backend_front_lanes /
-// mv_backend_front_draw_lanes + (cov_model, cov_modifiers) of mv_obs_cov; depth_cov0 / depth_cov1 (sdd0 / sdd1) must be given for MV_COV_GMM.
-int mv_backend_front_cov_lanes(int cov_model, int32_t cov_modifiers, const int32_t* cand, size_t cand_lane_stride, const int64_t* perm_dev,
-                               const int64_t* perm_host, int lanes, const int32_t* n_live, int cap, const float* match_flow, const float* match_cov,
-                               const float* depth0, const float* disp0, const float* sdisp0, const float* sdd0, const float* depth1, const float* disp1,
-                               const float* sdisp1, const float* sdd1, int edge, float match_cov_default, const mvMatchCovParams* cov_params,
-                               int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
-                               float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream);
-int mv_backend_front_cov_draw_lanes(int cov_model, int32_t cov_modifiers, const int32_t* cand, size_t cand_lane_stride, const int32_t* count_dev,
-                                    int count_stride, const uint32_t* state_in, uint32_t* state_out, int num_point, int lanes, int cap,
-                                    const float* match_flow, const float* match_cov, const float* depth0, const float* disp0, const float* sdisp0,
-                                    const float* sdd0, const float* depth1, const float* disp1, const float* sdisp1, const float* sdd1, int edge,
-                                    float match_cov_default, const mvMatchCovParams* cov_params, int64_t* out_perm, int32_t* out_live,
-                                    int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
-                                    float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream);
-// ... with keypoint rows from no candidate list: RandomSelector drawn in the launch, GridSelector, or an explicit (u, v) table (frontend_ops.hip)
-int mv_backend_front_cov_kp_lanes(int cov_model, int32_t cov_modifiers, int kp_mode, const int64_t* kp_uv, const int32_t* n_live, const int32_t* n_live_dev,
-                                  int n_live_stride, const uint32_t* state_in, uint32_t* state_out, int num_point, int mask_width, int lanes, int cap,
-                                  const float* match_flow, const float* match_cov, const float* depth0, const float* disp0, const float* sdisp0,
-                                  const float* sdd0, const float* depth1, const float* disp1, const float* sdisp1, const float* sdd1, int edge,
-                                  float match_cov_default, const mvMatchCovParams* cov_params, int32_t* out_live, int64_t* out_kp0_uv, float* out_kp0,
-                                  float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0, float* out_sigma1, float* out_pos_Tc,
-                                  double* out_cov0, double* out_cov1, mvStream_t stream);
+// host-side descriptors of the two backend launches (front launch, posed solve) and the internal functions that take them
+#include "backend_desc.h"
 
 // ---- wave-level reductions (64 lanes, butterfly so every lane ends with the result) ----
 __device__ __forceinline__ float wave_sum(float v) {

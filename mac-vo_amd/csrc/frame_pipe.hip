@@ -89,6 +89,7 @@ enum { KPJ_PERM = 0, KPJ_HOST = 1, KPJ_DEV = 2, KPJ_RANDOM = 3, KPJ_GRID = 4 }; 
 struct Maps {
     float *disparity, *disparity_cov, *depth, *depth_cov, *match_flow, *match_cov;
     uint8_t* bad_mask;
+    mvDepthMaps dm;   // depth, disparity, disparity_cov, depth_cov as the front launch reads them (describe_backend)
 };
 
 struct Backend {   // every table is [lanes, cap = num_point, ...]; rows beyond a lane's n_sel are dead (valid = 0)
@@ -99,6 +100,9 @@ struct Backend {   // every table is [lanes, cap = num_point, ...]; rows beyond 
     int32_t* n_valid;
     int32_t* live_dev;   // [lanes, 2] device-driven frame: selected keypoints = live rows, candidate count (written by the front launch's draw)
     int32_t n_sel[MV_MAX_LANES];
+    // the slot's tables as the two backend launches take them, laid out once (describe_backend) and read-only afterwards
+    mvFrontTables front;
+    mvPosedSolve solve;   // ... with everything of the solve that does not change per finish (finish_issue fills in the poses and the live rows)
 };
 
 struct Pending {
@@ -189,6 +193,7 @@ struct mvFramePipe {
     int32_t* count[N_CAND];
     float* stats[N_CAND];
     Backend be[2];
+    mvCovConfig cov;   // the covariance model of every front launch (describe_backend)
     float* pose[3];   // [lanes, 7]
     float *intr, *bl;   // [lanes, 4], [lanes]
     int32_t* offs;    // [lanes + 1]: lane l owns rows [l * cap, (l + 1) * cap) of the backend tables
@@ -451,6 +456,25 @@ static size_t carve(mvFramePipe* p, char* base) {
     return (a.off + 255) & ~(size_t)255;
 }
 
+// What the two backend launches of every finish take and what never changes after `create`: the covariance configuration, each Maps slot's planes and each
+// Backend slot's tables.  THE place where a slot's table pointers are spelled out; finish_issue names a slot.
+static void describe_backend(mvFramePipe* p) {
+    const mvFramePipeConfig& c = p->c;
+    p->cov = mvCovConfig{c.cov_model, c.cov_modifiers, {c.H, c.W, c.cov_kernel_size, 1, c.fx, c.fy, c.cx, c.cy, c.min_flow_cov_sq, c.min_depth_cov},
+                         c.edgewidth, c.match_cov_default};
+    for (Maps& m : p->maps) m.dm = mvDepthMaps{m.depth, m.disparity, m.disparity_cov, m.depth_cov};
+    const int cap = cap_of(c);
+    const size_t LN = (size_t)p->lanes * cap;   // value table is [11, lanes, cap]: each of its rows is one concatenated per-point column
+    for (Backend& b : p->be) {
+        b.front = mvFrontTables{b.kp0, b.kp0f, b.kp1, b.inbound, b.vals, b.sigma0, b.sigma1, b.pos_Tc, b.cov0, b.cov1};
+        // (the observation filters: prologue of the solve's launch; mapping mode needs the count on the host first and keeps the launch)
+        b.solve = mvPosedSolve{p->lanes, p->offs, cap, c.graph_type, nullptr, nullptr, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w, b.rot,
+                               b.kp1, b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, nullptr, nullptr, 0,
+                               c.mapping ? -1 : c.filters, c.filter_min_depth, c.max_depth, b.inbound, b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm,
+                               b.pose64, b.info, nullptr, nullptr};
+    }
+}
+
 static int check_config(const mvFramePipeConfig* c) {
     MV_CHECK_ARG(c);
     MV_CHECK_ARG(c->H > 0 && c->W > 0 && c->H % 8 == 0 && c->W % 8 == 0);
@@ -706,6 +730,7 @@ extern "C" int mv_frame_pipe_create(const mvFramePipeConfig* cfg, void* arena, s
         delete p;
         return MV_ERR_WORKSPACE;
     }
+    describe_backend(p);
     p->newest_maps = -1;
     for (auto& r : p->cand_recorded) r = true;
     {
@@ -1254,8 +1279,36 @@ static int finish_host(mvFramePipe* p, const int32_t* n_sel, float* pose_sink, F
     return MV_OK;
 }
 
+// Where a finish's front launch takes its keypoint rows from (ps: the job's pinned permutation slot)
+static mvKpSource kp_source_of(const mvFramePipe* p, const FinishJob& j, const Backend& b, int ps, bool perm_in_args) {
+    mvKpSource src{};
+    src.num_point = p->c.num_point; src.mask_width = p->c.kp_mask_width;
+    src.state_in = p->rp_state[j.g & 1]; src.state_out = p->rp_state[(j.g + 1) & 1];   // (DRAW / RANDOM: finish g reads one state buffer and writes the other)
+    if (j.kp == KPJ_PERM) {
+        src.kind = j.device ? MV_KPSRC_DRAW : MV_KPSRC_PERM;
+        src.cand = p->cand[j.pd.cand]; src.cand_lane_stride = (size_t)p->plane;
+        if (j.device) {   // device-driven frame: the front launch draws the permutation itself (count and generator in device memory) and publishes the live-row count
+            src.n_live_dev = p->count[j.pd.cand]; src.n_live_stride = 4;
+            src.out_perm = b.perm; src.out_live = b.live_dev;
+        } else {
+            src.perm_dev = b.perm; src.perm_host = perm_in_args ? p->h_perm[ps] : nullptr;
+            src.n_live = j.n_sel;
+        }
+    } else if (j.kp == KPJ_RANDOM || j.kp == KPJ_GRID) {
+        // RandomSelector drawn inside the launch from the lane's device-resident generator, GridSelector computed from the row index
+        src.kind = j.kp == KPJ_RANDOM ? MV_KPSRC_RANDOM : MV_KPSRC_GRID;
+    } else if (j.kp == KPJ_DEV) {   // the caller's rows, read where they are; the live-row count stays on the device
+        src.kind = MV_KPSRC_ROWS;
+        src.rows = j.kp_dev; src.n_live_dev = j.nsel_dev; src.n_live_stride = 1; src.out_live = b.live_dev;
+    } else {                        // ... or host rows, copied into kp0, which the front launch then reads in place
+        src.kind = MV_KPSRC_ROWS;
+        src.rows = b.kp0; src.n_live = j.n_sel;
+    }
+    return src;
+}
+
 // Device part: every launch of the frame's backend + solve.  Runs on the caller's thread, or on the launch thread (then it must
-// not touch anything but the job, the Backend slot and the launch thread's own events / flags).
+// not touch anything but the job, the Backend slot and the launch thread's own events / flags; what describe_backend laid out is read-only).
 static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_host) {
     const mvFramePipeConfig& c = p->c;
     const int L = p->lanes, cap = cap_of(c);
@@ -1270,9 +1323,11 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     // previous finish, which also orders the generator's state buffers and covers the previous frame's segment
     const bool on_dec = j.device && p->front_on_decoder && p->alt && !p->sel_on_back;
     hipStream_t s = on_dec ? p->s_lk[j.pd.f % p->n_lk] : p->s_back;
-    if (n_max == 0 && p->dev_draw)
-        MV_HIP(hipMemcpyAsync(p->rp_state[(g + 1) & 1], p->rp_state[g & 1], (size_t)L * (size_t)mv_randperm_state_words() * sizeof(uint32_t),
-                              hipMemcpyDeviceToDevice, s));
+    // a finish that draws nothing on the device, in a device-driven pipe: the generators move on to the buffer the NEXT finish reads, unchanged
+    const auto pass_generators = [&] {
+        return hipMemcpyAsync(p->rp_state[(g + 1) & 1], p->rp_state[g & 1], (size_t)L * (size_t)mv_randperm_state_words() * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
+    };
+    if (n_max == 0 && p->dev_draw) MV_HIP(pass_generators());
     const bool motion = c.motion_model == MV_MOTION_TARTAN;
     float* const prior = motion ? p->prior[g % N_MOT] : nullptr;
     if (motion) {   // prior = previous pose @ Exp(raw * pose_norm), on the solve's stream behind the previous solve and the caller's set_motion
@@ -1300,7 +1355,8 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
         p->nvalid_valid[k] = false;   // (mv_frame_pipe_wait_tracked then reports 0 observations: no mapping either)
         return MV_OK;
     }
-    const Maps &m0 = p->maps[pd.maps_prev], &m1 = p->maps[pd.maps];
+    const mvFrontMaps fm{p->maps[pd.maps].match_flow, p->maps[pd.maps].match_cov, p->maps[pd.maps_prev].dm, p->maps[pd.maps].dm};
+    const mvFrontTables& t = b.front;
 
     // Slot reuse.  This backend slot's tables were last read by the solve of frame g - 2 (side stream) and by whoever looked at
     // that frame's result views: the former has its event, the latter the event of mv_frame_pipe_release (a consumer that
@@ -1309,9 +1365,7 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     if (p->release_valid) MV_TRY(wait_if_pending(s, p->e_release));
     // permutations [lanes, cap] -> pinned slot -> device (ONE copy; rows beyond a lane's n_sel are never read)
     const int ps = (int)(g % N_PERM);
-    if (!j.device && p->dev_draw)   // a host-permuted finish in a device-driven pipe: the generators move on to the buffer the NEXT finish reads, unchanged
-        MV_HIP(hipMemcpyAsync(p->rp_state[(g + 1) & 1], p->rp_state[g & 1], (size_t)L * (size_t)mv_randperm_state_words() * sizeof(uint32_t),
-                              hipMemcpyDeviceToDevice, s));
+    if (!j.device && p->dev_draw) MV_HIP(pass_generators());   // (a host-permuted finish)
     const bool host_rows = !j.device && (j.kp == KPJ_PERM || j.kp == KPJ_HOST);   // a permutation or (u, v) rows from the host
     const size_t rw = j.kp == KPJ_HOST ? 2 : 1;                                     // int64 words per row
     if (host_rows) {
@@ -1346,47 +1400,24 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     // the SOLVE's stream right behind the previous solve, so the critical chain is solve -> mv_pose_apply_lanes -> solve on one
     // in-order stream.
     const bool fused = p->fuse_backend != 0;
-    mvMatchCovParams cp{c.H, c.W, c.cov_kernel_size, 1, c.fx, c.fy, c.cx, c.cy, c.min_flow_cov_sq, c.min_depth_cov};
-    if (j.kp != KPJ_PERM) {
-        // keypoint rows from no candidate list: the caller's (host rows copied into kp0 above / device rows read where they are), RandomSelector drawn inside
-        // the launch from the lane's device-resident generator (two state buffers, as the permutation draw below), GridSelector computed from the row index
-        const int mode = j.kp == KPJ_RANDOM ? MV_KP_RANDOM : j.kp == KPJ_GRID ? MV_KP_GRID : MV_KP_EXPLICIT;
-        const bool dv = j.kp == KPJ_DEV;
-        MV_TRY(mv_backend_front_cov_kp_lanes(c.cov_model, c.cov_modifiers, mode, dv ? j.kp_dev : b.kp0, dv ? nullptr : n_sel, dv ? j.nsel_dev : nullptr, 1,
-                                             p->rp_state[g & 1], p->rp_state[(g + 1) & 1], c.num_point, c.kp_mask_width, L, cap, m1.match_flow, m1.match_cov,
-                                             m0.depth, m0.disparity, m0.disparity_cov, m0.depth_cov, m1.depth, m1.disparity, m1.disparity_cov, m1.depth_cov,
-                                             c.edgewidth, c.match_cov_default, &cp, dv ? b.live_dev : nullptr, b.kp0, b.kp0f, b.kp1, b.inbound, b.vals, b.sigma0,
-                                             b.sigma1, b.pos_Tc, b.cov0, b.cov1, s));
-        if (c.mapping)
-            MV_TRY(mv_obs_filter_lanes(b.inbound, b.cov0, b.cov1, b.vals, c.filters, c.filter_min_depth, c.max_depth, L, n_sel, cap,
-                                       b.valid, b.n_valid, s));
-    } else if (j.device) {
-        // device-driven frame: the front launch draws the permutation itself (count and generator in device memory) and publishes the live-row count
-        MV_TRY(mv_backend_front_cov_draw_lanes(c.cov_model, c.cov_modifiers, p->cand[pd.cand], (size_t)p->plane, p->count[pd.cand], 4, p->rp_state[g & 1],
-                                           p->rp_state[(g + 1) & 1], c.num_point, L, cap, m1.match_flow, m1.match_cov, m0.depth, m0.disparity, m0.disparity_cov, m0.depth_cov, m1.depth, m1.disparity,
-                                           m1.disparity_cov, m1.depth_cov, c.edgewidth, c.match_cov_default, &cp, b.perm, b.live_dev, b.kp0, b.kp0f, b.kp1,
-                                           b.inbound, b.vals, b.sigma0, b.sigma1, b.pos_Tc, b.cov0, b.cov1, s));
-    } else if (fused) {
-        // gather + track + back-projection + both covariance models + observation filters = ONE launch
-        MV_TRY(mv_backend_front_cov_lanes(c.cov_model, c.cov_modifiers, p->cand[pd.cand], (size_t)p->plane, b.perm, perm_in_args ? p->h_perm[ps] : nullptr, L, n_sel, cap,
-                                      m1.match_flow, m1.match_cov, m0.depth, m0.disparity, m0.disparity_cov, m0.depth_cov, m1.depth, m1.disparity,
-                                      m1.disparity_cov, m1.depth_cov, c.edgewidth, c.match_cov_default, &cp, b.kp0, b.kp0f, b.kp1, b.inbound, b.vals,
-                                      b.sigma0, b.sigma1, b.pos_Tc, b.cov0, b.cov1, s));
+    const mvKpSource src = kp_source_of(p, j, b, ps, perm_in_args);
+    const auto obs_filter = [&] {
+        return mv_obs_filter_lanes(t.inbound, t.cov0, t.cov1, t.vals, c.filters, c.filter_min_depth, c.max_depth, L, n_sel, cap, b.valid, b.n_valid, s);
+    };
+    if (fused || src.kind != MV_KPSRC_PERM) {
+        // gather + track + back-projection + both covariance models = ONE launch
+        MV_TRY(mv_backend_front(src, L, cap, fm, p->cov, t, s));
         // (the observation filters: prologue of the solve's launch below; mapping mode needs the count on the host first and keeps the launch)
-        if (c.mapping)
-            MV_TRY(mv_obs_filter_lanes(b.inbound, b.cov0, b.cov1, b.vals, c.filters, c.filter_min_depth, c.max_depth, L, n_sel, cap,
-                                       b.valid, b.n_valid, s));
+        if (c.mapping && src.kind != MV_KPSRC_DRAW) MV_TRY(obs_filter());
     } else {   // MV_PIPE_FUSE_BACKEND=0: the five-launch form (the reference point of the bitwise test)
-        MV_TRY(mv_kp_front_lanes(p->cand[pd.cand], (size_t)p->plane, b.perm, perm_in_args ? p->h_perm[ps] : nullptr, L, n_sel, cap,
-                                 m1.match_flow, m1.match_cov, m0.depth, m0.disparity, m0.disparity_cov, m0.depth_cov, m1.depth,
-                                 m1.disparity, m1.disparity_cov, m1.depth_cov, c.H, c.W, c.edgewidth, c.match_cov_default, c.fx, c.fy,
-                                 c.cx, c.cy, b.kp0, b.kp0f, b.kp1, b.inbound, b.vals, b.sigma0, b.sigma1, b.pos_Tc, s));
+        MV_TRY(mv_kp_front_lanes(src.cand, src.cand_lane_stride, src.perm_dev, src.perm_host, L, n_sel, cap, fm.match_flow, fm.match_cov, fm.f0.depth,
+                                 fm.f0.disp, fm.f0.sdisp, fm.f0.sdd, fm.f1.depth, fm.f1.disp, fm.f1.sdisp, fm.f1.sdd, c.H, c.W, c.edgewidth,
+                                 c.match_cov_default, c.fx, c.fy, c.cx, c.cy, t.kp0_uv, t.kp0, t.kp1, t.inbound, t.vals, t.sigma0, t.sigma1, t.pos_Tc, s));
     }
-    if (!fused) {
-        MV_TRY(mv_obs_cov_pair_lanes(c.cov_model, c.cov_modifiers, m0.depth, m0.depth_cov, b.kp0f, b.sigma0, nullptr, b.cov0, nullptr, m1.depth,
-                                     m1.depth_cov, b.kp1, b.sigma1, b.cov1, &cp, L, n_sel, cap, s));
-        MV_TRY(mv_obs_filter_lanes(b.inbound, b.cov0, b.cov1, b.vals, c.filters, c.filter_min_depth, c.max_depth, L, n_sel, cap,
-                                   b.valid, b.n_valid, s));
+    if (!fused) {   // (behind a fused front launch — keypoint rows — the covariances are computed again: same bits)
+        MV_TRY(mv_obs_cov_pair_lanes(c.cov_model, c.cov_modifiers, fm.f0.depth, fm.f0.sdd, t.kp0, t.sigma0, nullptr, t.cov0, nullptr, fm.f1.depth,
+                                     fm.f1.sdd, t.kp1, t.sigma1, t.cov1, &p->cov.cp, L, n_sel, cap, s));
+        MV_TRY(obs_filter());
     }
     if (c.mapping) {   // the mapping decision of this frame (MACVO.py:303-307) needs the observation count on the host
         MV_HIP(hipMemcpyAsync(p->h_nvalid[k], b.n_valid, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1402,52 +1433,30 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     // the next frame's priors (StaticMotionModel)
     hipStream_t ss = p->s_side;
     if (ss != s) MV_HIP(hipStreamWaitEvent(ss, p->e_backend[g % N_BEV], 0));   // (alt layout: backend + solve share one in-order stream)
-    const float* pose = p->pose[j.pose_from];
     if (ti >= 0) MV_HIP(hipEventRecord(p->tv6[ti], ss));
-    const size_t N = (size_t)cap;
-    const size_t LN = (size_t)L * N;   // value table is [11, lanes, cap]: each of its rows is one concatenated per-point column
-    const bool live_on_dev = (j.device && j.kp == KPJ_PERM) || j.kp == KPJ_DEV;   // the live-row count exists in device memory only
-    if (live_on_dev && motion) {
-        MV_TRY(mv_pgo_solve_posed_motion_dev(L, p->offs, b.live_dev, 2, cap, c.graph_type, pose, prior, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w,
-                                             b.rot, b.kp1, b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, c.filters, c.filter_min_depth,
-                                             c.max_depth, b.inbound, b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm, b.pose64, b.info,
-                                             p->pose[j.pose_to], j.pose_sink, ss));
-        MV_HIP(hipEventRecord(p->e_solved[k], ss));
-        MV_HIP(hipEventRecord(p->e_pgo, ss));
-    } else if (live_on_dev) {
-        MV_TRY(mv_pgo_solve_posed_dev(L, p->offs, b.live_dev, 2, cap, c.graph_type, pose, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w, b.rot, b.kp1,
-                                      b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, c.filters, c.filter_min_depth, c.max_depth, b.inbound,
-                                      b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm, b.pose64, b.info, p->pose[j.pose_to], j.pose_sink, ss));
-        MV_HIP(hipEventRecord(p->e_solved[k], ss));
-        MV_HIP(hipEventRecord(p->e_pgo, ss));
-    } else if (p->fuse_backend && motion) {
-        MV_TRY(mv_pgo_solve_posed_motion(L, p->offs, n_sel, cap, c.graph_type, pose, prior, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w, b.rot,
-                                         b.kp1, b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, c.mapping ? -1 : c.filters,
-                                         c.filter_min_depth, c.max_depth, b.inbound, b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm, b.pose64,
-                                         b.info, p->pose[j.pose_to], j.pose_sink, ss));
-        MV_HIP(hipEventRecord(p->e_solved[k], ss));
-        MV_HIP(hipEventRecord(p->e_pgo, ss));
-    } else if (p->fuse_backend) {
+    mvPosedSolve sv = b.solve;
+    sv.init_pose = p->pose[j.pose_from];
+    sv.out_pose_f32 = p->pose[j.pose_to];
+    if (fused) {
         // ... and the pose-dependent half = ONE launch: the rotation into the world frame is the solve kernel's prologue, the caller's pose
         // sink its second output (the 28-byte device-to-device copy was a DMA node on the critical stream).  No e_posed: the world-frame
         // tables are consumed behind e_solved (mv_frame_pipe_map_append).
-        MV_TRY(mv_pgo_solve_posed(L, p->offs, n_sel, cap, c.graph_type, pose, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w, b.rot, b.kp1,
-                                  b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, c.mapping ? -1 : c.filters, c.filter_min_depth,
-                                  c.max_depth, b.inbound, b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm, b.pose64, b.info,
-                                  p->pose[j.pose_to], j.pose_sink, ss));
-        MV_HIP(hipEventRecord(p->e_solved[k], ss));
-        MV_HIP(hipEventRecord(p->e_pgo, ss));
+        sv.start_pose = prior;   // (motion model: LM starts from the prior)
+        sv.pose_sink = j.pose_sink;
+        sv.n_live = src.out_live ? nullptr : n_sel;
+        sv.n_live_dev = src.out_live; sv.n_live_stride = 2;   // (given: the live-row count exists in device memory only, where the front launch published it)
+        MV_TRY(mv_posed_solve(sv, ss));
     } else {
-        MV_TRY(mv_pose_apply_lanes(pose, b.pos_Tc, b.cov0, L, n_sel, cap, b.pos_Tw, b.rot, b.cov0w, ss));
+        MV_TRY(mv_pose_apply_lanes(sv.init_pose, sv.pos_Tc, sv.cov_Tc, L, n_sel, cap, sv.pos_Tw, sv.out_rot, sv.cov_Tw, ss));
         MV_HIP(hipEventRecord(p->e_posed[k], ss));
-        MV_TRY(mv_pgo_solve(L, p->offs, c.graph_type, motion ? prior : pose, p->intr, p->bl, b.pos_Tw, b.cov0w, b.kp1, b.vals + 4 * LN,
-                            b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, b.valid, c.min_num_point, &c.lm, b.pose64, b.info,
-                            p->pose[j.pose_to], ss));
+        MV_TRY(mv_pgo_solve(L, sv.offsets, sv.graph_type, motion ? prior : sv.init_pose, sv.intrinsics, sv.baseline, sv.pos_Tw, sv.cov_Tw, sv.pixel2_uv,
+                            sv.pixel2_d, sv.pixel2_disp, sv.pixel2_disp_cov, sv.pixel2_uv_cov, sv.obs2_covTc, sv.valid, sv.min_points, sv.params,
+                            sv.out_pose, sv.out_info, sv.out_pose_f32, ss));
         if (j.pose_sink)
             MV_HIP(hipMemcpyAsync(j.pose_sink, p->pose[j.pose_to], (size_t)L * 7 * sizeof(float), hipMemcpyDeviceToDevice, ss));
-        MV_HIP(hipEventRecord(p->e_pgo, ss));
-        MV_HIP(hipEventRecord(p->e_solved[k], ss));
     }
+    MV_HIP(hipEventRecord(p->e_solved[k], ss));   // (two adjacent records on one in-order stream, nothing between them: both fire behind the solve, in either order)
+    MV_HIP(hipEventRecord(p->e_pgo, ss));
     if (ti >= 0) MV_HIP(hipEventRecord(p->tv7[ti], ss));
     p->pgo_valid = true;
     p->solved_valid[k] = true;
@@ -1542,29 +1551,44 @@ static int submit_or_issue(mvFramePipe* p, FinishJob& j, const int64_t* perm_hos
     return rc;
 }
 
-// A frame of a RandomSelector / GridSelector pipe: every lane tracks frame_rows() rows, nothing to wait for.  kp = KPJ_HOST: drawn on the host by whoever issues
-// the job (seeded), KPJ_RANDOM: drawn inside the front launch (device-driven), KPJ_GRID: computed there.
-static int finish_rows(mvFramePipe* p, int kp, float* pose_sink, int32_t* n_cand_out, int32_t* n_sel_out) {
+// What every finish does before it takes the frame off the pending list: the frame's selector segment is issued; `markers`: the chain events of this and
+// the previous frame exist (lean chain: a finish whose front launch waits for the segment by event needs them); `map_count`: mapping mode —
+// mv_frame_pipe_wait_tracked reads the mapping selector's count behind the frame's e_cand
+static int finish_prologue(mvFramePipe* p, bool markers, bool map_count) {
     MV_TRY(selector_of_front_issued(p));
     const Pending& pd = p->pending.front();
-    if (kp != KPJ_RANDOM || p->c.mapping) {   // (the device-driven frame's front launch follows its segment in stream order or by a pending barrier)
+    if (markers) {
         MV_TRY(ensure_chain_events(p, pd.f, pd.cand));
         if (pd.f > 0) MV_TRY(ensure_chain_events(p, pd.f - 1, -1));
     }
-    if (p->c.mapping) MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));   // mv_frame_pipe_wait_tracked reads the mapping selector's count behind it
+    if (map_count && p->c.mapping) MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));
+    return MV_OK;
+}
+static FinishJob new_job(const mvFramePipe* p, int kp, bool seeded, bool device) {
     FinishJob j{};
-    j.kp = kp;
-    j.seeded = kp == KPJ_HOST;
-    j.device = kp == KPJ_RANDOM;
-    j.t_count = j.t_submit = now_us();
+    j.kp = kp; j.seeded = seeded; j.device = device;
+    j.t_count = j.t_submit = p->host_stats ? now_us() : 0.0;
+    return j;
+}
+// ... and last, for a frame whose every lane tracks `rows` rows (an upper bound where the live count exists on the device only: rows beyond are masked by `valid`)
+static int finish_uniform(mvFramePipe* p, FinishJob& j, int rows, float* pose_sink) {
     int32_t nsel[MV_MAX_LANES];
-    for (int l = 0; l < p->lanes; ++l) {
-        nsel[l] = frame_rows(p->c);
-        if (n_cand_out) n_cand_out[l] = nsel[l];
-        if (n_sel_out) n_sel_out[l] = nsel[l];
-    }
+    for (int l = 0; l < p->lanes; ++l) nsel[l] = rows;
     MV_TRY(finish_host(p, nsel, pose_sink, j));
     return submit_or_issue(p, j, nullptr);
+}
+
+// A frame of a RandomSelector / GridSelector pipe: every lane tracks frame_rows() rows, nothing to wait for.  kp = KPJ_HOST: drawn on the host by whoever issues
+// the job (seeded), KPJ_RANDOM: drawn inside the front launch (device-driven), KPJ_GRID: computed there.
+static int finish_rows(mvFramePipe* p, int kp, float* pose_sink, int32_t* n_cand_out, int32_t* n_sel_out) {
+    // (the device-driven frame's front launch follows its segment in stream order or by a pending barrier: no markers)
+    MV_TRY(finish_prologue(p, kp != KPJ_RANDOM || p->c.mapping, true));
+    FinishJob j = new_job(p, kp, kp == KPJ_HOST, kp == KPJ_RANDOM);
+    for (int l = 0; l < p->lanes; ++l) {
+        if (n_cand_out) n_cand_out[l] = frame_rows(p->c);
+        if (n_sel_out) n_sel_out[l] = frame_rows(p->c);
+    }
+    return finish_uniform(p, j, frame_rows(p->c), pose_sink);
 }
 
 // wait_candidates + permutations (per-lane generators of mv_frame_pipe_seed_lanes) + finish in one host call
@@ -1574,13 +1598,11 @@ extern "C" int mv_frame_pipe_finish_seeded(mvFramePipe* p, float* pose_sink, int
     MV_CHECK_ARG((int)p->rng.size() == p->lanes && p->c.selector_mode != MV_KP_EXPLICIT);
     MV_CHECK_ARG(!p->dev_draw);   // (its generators live on the device: mv_frame_pipe_finish_device)
     if (p->c.selector_mode == MV_KP_RANDOM) return finish_rows(p, KPJ_HOST, pose_sink, n_cand_out, n_sel_out);
-    MV_TRY(selector_of_front_issued(p));
+    MV_TRY(finish_prologue(p, false, false));
     const Pending& pd = p->pending.front();
     const double t_w0 = p->host_stats ? now_us() : 0.0;
     MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));
-    FinishJob j{};
-    j.seeded = true;
-    j.t_count = now_us();
+    FinishJob j = new_job(p, KPJ_PERM, true, false);
     if (p->host_stats) p->st_wait += j.t_count - t_w0;
     int32_t nsel[MV_MAX_LANES];
     for (int l = 0; l < p->lanes; ++l) {
@@ -1602,15 +1624,9 @@ extern "C" int mv_frame_pipe_finish_device(mvFramePipe* p, float* pose_sink) {
     if (p->c.selector_mode == MV_KP_GRID) return finish_rows(p, KPJ_GRID, pose_sink, nullptr, nullptr);
     MV_CHECK_ARG(p->dev_draw);
     if (p->c.selector_mode == MV_KP_RANDOM) return finish_rows(p, KPJ_RANDOM, pose_sink, nullptr, nullptr);
-    MV_TRY(selector_of_front_issued(p));
-    FinishJob j{};
-    j.seeded = false;
-    j.device = true;
-    j.t_count = j.t_submit = p->host_stats ? now_us() : 0.0;
-    int32_t nsel[MV_MAX_LANES];
-    for (int l = 0; l < p->lanes; ++l) nsel[l] = p->c.num_point;   // upper bound: rows beyond the live ones are masked by `valid`
-    MV_TRY(finish_host(p, nsel, pose_sink, j));
-    const int rc = submit_or_issue(p, j, nullptr);
+    MV_TRY(finish_prologue(p, false, false));
+    FinishJob j = new_job(p, KPJ_PERM, false, true);
+    const int rc = finish_uniform(p, j, p->c.num_point, pose_sink);
     if (p->host_stats) { p->st_fin += now_us() - j.t_count; p->st_calls += 1; }
     return rc;
 }
@@ -1667,26 +1683,14 @@ extern "C" int mv_frame_pipe_finish(mvFramePipe* p, const int64_t* perm_host, co
     MV_CHECK_ARG(p && n_sel && !p->pending.empty() && !kp_new_mode(p->c.selector_mode));   // (a permutation needs a candidate list)
     for (int l = 0; l < p->lanes; ++l)
         MV_CHECK_ARG(n_sel[l] >= 0 && n_sel[l] <= p->c.num_point && (n_sel[l] == 0 || perm_host));
-    MV_TRY(selector_of_front_issued(p));
-    MV_TRY(ensure_chain_events(p, p->pending.front().f, p->pending.front().cand));       // (lean chain: a host-permuted finish waits for the markers)
-    if (p->pending.front().f > 0) MV_TRY(ensure_chain_events(p, p->pending.front().f - 1, -1));
-    FinishJob j{};
-    j.seeded = false;
+    MV_TRY(finish_prologue(p, true, false));       // (lean chain: a host-permuted finish waits for the markers)
+    FinishJob j = new_job(p, KPJ_PERM, false, false);
     MV_TRY(finish_host(p, n_sel, pose_sink, j));
     return submit_or_issue(p, j, perm_host);
 }
 
 // Caller-supplied keypoints: any selector's (u, v) rows instead of a permutation over the driver's candidate list — valid for every selector_mode.
 extern "C" int mv_frame_pipe_table_rows(const mvFramePipeConfig* cfg) { return check_config(cfg) == MV_OK ? table_rows(*cfg) : 0; }
-
-static int finish_keypoints_common(mvFramePipe* p) {
-    MV_TRY(selector_of_front_issued(p));
-    const Pending& pd = p->pending.front();
-    MV_TRY(ensure_chain_events(p, pd.f, pd.cand));   // (lean chain: a finish whose front launch waits for the segment by event needs the markers)
-    if (pd.f > 0) MV_TRY(ensure_chain_events(p, pd.f - 1, -1));
-    if (p->c.mapping) MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));
-    return MV_OK;
-}
 
 extern "C" int mv_frame_pipe_finish_keypoints(mvFramePipe* p, const int64_t* kp_uv_host, const int32_t* n_sel, float* pose_sink) {
     MV_CHECK_ARG(p && n_sel && !p->pending.empty());
@@ -1700,27 +1704,20 @@ extern "C" int mv_frame_pipe_finish_keypoints(mvFramePipe* p, const int64_t* kp_
             MV_CHECK_ARG(u >= hw && u < c.W - hw && v >= hw && v < c.H - hw);
         }
     }
-    MV_TRY(finish_keypoints_common(p));
-    FinishJob j{};
-    j.seeded = false;
-    j.kp = KPJ_HOST;
+    MV_TRY(finish_prologue(p, true, true));
+    FinishJob j = new_job(p, KPJ_HOST, false, false);
     MV_TRY(finish_host(p, n_sel, pose_sink, j));
     return submit_or_issue(p, j, kp_uv_host);
 }
 
 extern "C" int mv_frame_pipe_finish_keypoints_dev(mvFramePipe* p, const int64_t* kp_uv_dev, const int32_t* n_sel_dev, mvStream_t stream, float* pose_sink) {
     MV_CHECK_ARG(p && kp_uv_dev && n_sel_dev && !p->pending.empty() && p->fuse_backend && !p->c.mapping && table_rows(p->c) >= 1);
-    MV_TRY(finish_keypoints_common(p));
-    FinishJob j{};
-    j.seeded = false;
-    j.kp = KPJ_DEV;
+    MV_TRY(finish_prologue(p, true, true));
+    FinishJob j = new_job(p, KPJ_DEV, false, false);
     j.kp_dev = kp_uv_dev;
     j.nsel_dev = n_sel_dev;
     MV_HIP(hipEventRecord(p->e_kpin[p->n_fin % N_BEV], (hipStream_t)stream));   // recorded before the job is queued
-    int32_t nsel[MV_MAX_LANES];
-    for (int l = 0; l < p->lanes; ++l) nsel[l] = table_rows(p->c);   // upper bound: rows beyond the live ones are masked by `valid`
-    MV_TRY(finish_host(p, nsel, pose_sink, j));
-    return submit_or_issue(p, j, nullptr);
+    return finish_uniform(p, j, table_rows(p->c), pose_sink);
 }
 
 // Register the newest FINISHED frame in a device-resident map (call right after mv_frame_pipe_finish; lanes == 1): the

@@ -440,6 +440,19 @@ void launch_backend_front(int model, int32_t mods, dim3 grid, hipStream_t st, Dr
         hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_NONE, true>), grid, dim3(256), 0, st, args..., da);
 }
 
+// ... with PM chosen at run time (PM 1 first, as ever: the order of instantiation is the kernels' order in the code object)
+template <typename... Args>
+void launch_backend_front_pm(int pm, Args... args) {
+    switch (pm) {
+        case 1: return launch_backend_front<1>(args...);
+        case 0: return launch_backend_front<0>(args...);
+        case 2: return launch_backend_front<2>(args...);
+        case 3: return launch_backend_front<3>(args...);
+        case 4: return launch_backend_front<4>(args...);
+        case 5: return launch_backend_front<5>(args...);
+    }
+}
+
 }  // namespace
 
 static inline int check_lanes(int lanes, const int32_t* n_live, int cap, mvLaneCounts& c, int& n_max) {
@@ -529,59 +542,114 @@ extern "C" int mv_kp_front_lanes(const int32_t* cand, size_t cand_lane_stride, c
     return mv_launch_status();
 }
 
+// The front launch: ONE backend_front_kernel<PM, model, modifiers?>; the keypoint source (backend_desc.h) selects PM, the live rows and the grid.
+// sdd of both frames must be given for MV_COV_GMM.
+int mv_backend_front(const mvKpSource& src, int lanes, int cap, const mvFrontMaps& m, const mvCovConfig& cv, const mvFrontTables& t, mvStream_t stream) {
+    const mvMatchCovParams& cp = cv.cp;
+    const int kind = src.kind, num_point = src.num_point;
+    MV_CHECK_ARG(kind >= MV_KPSRC_PERM && kind <= MV_KPSRC_GRID && cv.edge >= 0);
+    if (kind != MV_KPSRC_PERM) MV_CHECK_ARG(lanes >= 1 && lanes <= MV_MAX_LANES && cap >= 1 && num_point >= 0);
+    if (kind == MV_KPSRC_DRAW) MV_CHECK_ARG(num_point <= cap && src.n_live_stride >= 1);
+    if (kind >= MV_KPSRC_ROWS) MV_CHECK_ARG(src.mask_width >= 0);
+    MV_CHECK_ARG(cv.model >= MV_COV_MATCH && cv.model <= MV_COV_NONE && mv_cov_modifiers_ok(cv.modifiers));
+    MV_CHECK_ARG(cv.model != MV_COV_GMM || (m.f0.sdd && m.f1.sdd));
+    MV_CHECK_ARG(cp.H > 0 && cp.W > 0 && cp.kernel_size >= 1 && (cp.kernel_size & 1) && cp.use_patch_var);
+    if (cp.kernel_size > mvcov::MAX_K || (kind == MV_KPSRC_DRAW && num_point > mvrp::MAX_HEAD)) return MV_ERR_UNSUPPORTED;
+    mvLaneCounts c{};
+    int n_max = 0;   // rows per lane the grid covers
+    if (kind == MV_KPSRC_PERM) {
+        const int rc = check_lanes(lanes, src.n_live, cap, c, n_max);
+        if (rc != MV_OK) return rc;
+        if (n_max == 0) return MV_OK;
+    }
+    MV_CHECK_ARG(m.match_flow && m.f0.depth && m.f1.depth && t.kp0_uv && t.kp1 && t.inbound && t.vals && t.sigma0 && t.sigma1 && t.pos_Tc && t.cov0 &&
+                 t.cov1);
+    const TrackArgs ta{m.match_flow, m.match_cov, m.f0.depth, m.f0.disp, m.f0.sdisp, m.f0.sdd, m.f1.depth, m.f1.disp, m.f1.sdisp, m.f1.sdd, cp.H, cp.W,
+                       cv.edge, cv.match_cov_default, t.kp0, t.kp1, t.inbound, t.vals, t.sigma0, t.sigma1};
+    const int32_t* cand = nullptr;   // PM <= 2
+    size_t cand_stride = 0;
+    const int64_t* rows = nullptr;   // the kernel's `perm`: the permutation (PM 0) or the (u, v) table (PM 3)
+    PermArg pa;
+    pa.idx[0] = 0;
+    DrawArgs da{};
+    int pm;
+    if (kind == MV_KPSRC_PERM) {
+        MV_CHECK_ARG(src.cand && (src.perm_dev || src.perm_host));
+        cand = src.cand;
+        cand_stride = src.cand_lane_stride;
+        if (src.perm_host && lanes == 1 && n_max <= 256) {     // the permutation rides in the kernel arguments
+            for (int i = 0; i < n_max; ++i) {
+                MV_CHECK_ARG(src.perm_host[i] >= 0 && src.perm_host[i] <= 0x7fffffffLL);
+                pa.idx[i] = (int32_t)src.perm_host[i];
+            }
+            pm = 1;
+        } else {
+            MV_CHECK_ARG(src.perm_dev);
+            rows = src.perm_dev;
+            pm = 0;
+        }
+    } else if (kind == MV_KPSRC_DRAW) {
+        MV_CHECK_ARG(src.cand && src.n_live_dev && src.state_in && src.state_out && src.state_in != src.state_out && src.out_perm && src.out_live);
+        cand = src.cand;
+        cand_stride = src.cand_lane_stride;
+        n_max = num_point > 0 ? num_point : 1;   // (num_point == 0: workgroup (0, 0, l) still advances the generator)
+        da = DrawArgs{src.n_live_dev, src.n_live_stride, src.state_in, src.state_out, num_point, 0, src.out_perm, src.out_live};
+        pm = 2;
+    } else if (kind == MV_KPSRC_ROWS) {
+        MV_CHECK_ARG(src.rows && (src.n_live || (src.n_live_dev && src.n_live_stride >= 1)));
+        da.out_live = src.out_live;
+        if (src.n_live) {
+            const int rc = check_lanes(lanes, src.n_live, cap, c, n_max);
+            if (rc != MV_OK) return rc;
+        } else {
+            n_max = cap;
+            da.count = src.n_live_dev;
+            da.count_stride = src.n_live_stride;
+        }
+        if (n_max == 0) return MV_OK;
+        rows = src.rows;
+        pm = 3;
+    } else if (kind == MV_KPSRC_RANDOM) {
+        MV_CHECK_ARG(src.state_in && src.state_out && src.state_in != src.state_out && num_point >= 1 && num_point <= cap && cp.H > 2 * src.mask_width &&
+                     cp.W > 2 * src.mask_width);
+        if (num_point > mvkp::MAX_POINT) return MV_ERR_UNSUPPORTED;
+        n_max = num_point;
+        pa.idx[0] = src.mask_width;
+        da.state_in = src.state_in;
+        da.state_out = src.state_out;
+        da.k = num_point;
+        pm = 4;
+    } else {
+        mvkp::Grid g;
+        n_max = mvkp::grid_of(cp.H, cp.W, src.mask_width, num_point, &g);
+        MV_CHECK_ARG(n_max >= 1 && n_max <= cap);
+        pa.idx[0] = g.cols; pa.idx[1] = g.sh; pa.idx[2] = g.sw; pa.idx[3] = g.mask;
+        pm = 5;
+    }
+    if (pm >= 4)
+        for (int l = 0; l < lanes; ++l) c.n[l] = n_max;
+    const dim3 grid(mv_ceil_div(n_max, 4), 2, lanes);
+    launch_backend_front_pm(pm, cv.model, cv.modifiers, grid, (hipStream_t)stream, da, cand, cand_stride, rows, pa, cap, c, t.kp0_uv, ta, cp.fx, cp.fy, cp.cx,
+                            cp.cy, t.pos_Tc, m.f0.depth, m.f1.depth, t.cov0, t.cov1, cp);
+    return mv_launch_status();
+}
+
 extern "C" int mv_backend_front_lanes(const int32_t* cand, size_t cand_lane_stride, const int64_t* perm_dev, const int64_t* perm_host, int lanes,
                                       const int32_t* n_live, int cap, const float* match_flow, const float* match_cov, const float* depth0,
                                       const float* disp0, const float* sdisp0, const float* sdd0, const float* depth1, const float* disp1,
                                       const float* sdisp1, const float* sdd1, int edge, float match_cov_default, const mvMatchCovParams* cov_params,
                                       int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
                                       float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream) {
-    return mv_backend_front_cov_lanes(MV_COV_MATCH, 0, cand, cand_lane_stride, perm_dev, perm_host, lanes, n_live, cap, match_flow, match_cov, depth0,
-                                      disp0, sdisp0, sdd0, depth1, disp1, sdisp1, sdd1, edge, match_cov_default, cov_params, out_kp0_uv, out_kp0,
-                                      out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1, out_pos_Tc, out_cov0, out_cov1, stream);
+    MV_CHECK_ARG(cov_params);
+    mvKpSource src{};
+    src.kind = MV_KPSRC_PERM;
+    src.cand = cand; src.cand_lane_stride = cand_lane_stride; src.perm_dev = perm_dev; src.perm_host = perm_host; src.n_live = n_live;
+    return mv_backend_front(src, lanes, cap, {match_flow, match_cov, {depth0, disp0, sdisp0, sdd0}, {depth1, disp1, sdisp1, sdd1}},
+                            {MV_COV_MATCH, 0, *cov_params, edge, match_cov_default},
+                            {out_kp0_uv, out_kp0, out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1, out_pos_Tc, out_cov0, out_cov1}, stream);
 }
 
-int mv_backend_front_cov_lanes(int cov_model, int32_t cov_modifiers, const int32_t* cand, size_t cand_lane_stride, const int64_t* perm_dev,
-                               const int64_t* perm_host, int lanes, const int32_t* n_live, int cap, const float* match_flow, const float* match_cov,
-                               const float* depth0, const float* disp0, const float* sdisp0, const float* sdd0, const float* depth1, const float* disp1,
-                               const float* sdisp1, const float* sdd1, int edge, float match_cov_default, const mvMatchCovParams* cov_params,
-                               int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
-                               float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream) {
-    MV_CHECK_ARG(cov_params && edge >= 0);
-    MV_CHECK_ARG(cov_model >= MV_COV_MATCH && cov_model <= MV_COV_NONE && mv_cov_modifiers_ok(cov_modifiers));
-    MV_CHECK_ARG(cov_model != MV_COV_GMM || (sdd0 && sdd1));
-    const mvMatchCovParams cp = *cov_params;
-    MV_CHECK_ARG(cp.H > 0 && cp.W > 0 && cp.kernel_size >= 1 && (cp.kernel_size & 1) && cp.use_patch_var);
-    if (cp.kernel_size > mvcov::MAX_K) return MV_ERR_UNSUPPORTED;
-    mvLaneCounts c{};
-    int n_max = 0;
-    const int rc = check_lanes(lanes, n_live, cap, c, n_max);
-    if (rc != MV_OK) return rc;
-    if (n_max == 0) return MV_OK;
-    MV_CHECK_ARG(cand && (perm_dev || perm_host) && match_flow && depth0 && depth1 && out_kp0_uv && out_kp1 && out_inbound && out_vals &&
-                 out_sigma0 && out_sigma1 && out_pos_Tc && out_cov0 && out_cov1);
-    const TrackArgs ta{match_flow, match_cov, depth0, disp0, sdisp0, sdd0, depth1, disp1, sdisp1, sdd1, cp.H, cp.W, edge, match_cov_default,
-                       out_kp0, out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1};
-    const dim3 grid(mv_ceil_div(n_max, 4), 2, lanes);
-    if (perm_host && lanes == 1 && n_max <= 256) {     // the permutation rides in the kernel arguments
-        PermArg pa;
-        for (int i = 0; i < n_max; ++i) {
-            MV_CHECK_ARG(perm_host[i] >= 0 && perm_host[i] <= 0x7fffffffLL);
-            pa.idx[i] = (int32_t)perm_host[i];
-        }
-        launch_backend_front<1>(cov_model, cov_modifiers, grid, (hipStream_t)stream, DrawArgs{}, cand, cand_lane_stride, (const int64_t*)nullptr, pa, cap, c,
-                                out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
-    } else {
-        MV_CHECK_ARG(perm_dev);
-        PermArg pa;
-        pa.idx[0] = 0;
-        launch_backend_front<0>(cov_model, cov_modifiers, grid, (hipStream_t)stream, DrawArgs{}, cand, cand_lane_stride, perm_dev, pa, cap, c, out_kp0_uv, ta,
-                                cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
-    }
-    return mv_launch_status();
-}
-
-// mv_backend_front_lanes of the device-driven frame (round 6): the permutation is drawn inside the launch (backend_front_kernel<2>), the number of live rows
-// never reaches the host — the grid covers `num_point` rows per lane and the waves beyond min(count, num_point) retire at once.
+// mv_backend_front_lanes of the device-driven frame (round 6): MV_KPSRC_DRAW
 extern "C" int mv_backend_front_draw_lanes(const int32_t* cand, size_t cand_lane_stride, const int32_t* count_dev, int count_stride, const uint32_t* state_in,
                                            uint32_t* state_out, int num_point, int lanes, int cap, const float* match_flow, const float* match_cov,
                                            const float* depth0, const float* disp0, const float* sdisp0, const float* sdd0, const float* depth1,
@@ -589,103 +657,14 @@ extern "C" int mv_backend_front_draw_lanes(const int32_t* cand, size_t cand_lane
                                            const mvMatchCovParams* cov_params, int64_t* out_perm, int32_t* out_live, int64_t* out_kp0_uv, float* out_kp0,
                                            float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0, float* out_sigma1, float* out_pos_Tc,
                                            double* out_cov0, double* out_cov1, mvStream_t stream) {
-    return mv_backend_front_cov_draw_lanes(MV_COV_MATCH, 0, cand, cand_lane_stride, count_dev, count_stride, state_in, state_out, num_point, lanes, cap,
-                                           match_flow, match_cov, depth0, disp0, sdisp0, sdd0, depth1, disp1, sdisp1, sdd1, edge, match_cov_default,
-                                           cov_params, out_perm, out_live, out_kp0_uv, out_kp0, out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1,
-                                           out_pos_Tc, out_cov0, out_cov1, stream);
-}
-
-int mv_backend_front_cov_draw_lanes(int cov_model, int32_t cov_modifiers, const int32_t* cand, size_t cand_lane_stride, const int32_t* count_dev,
-                                    int count_stride, const uint32_t* state_in, uint32_t* state_out, int num_point, int lanes, int cap,
-                                    const float* match_flow, const float* match_cov, const float* depth0, const float* disp0, const float* sdisp0,
-                                    const float* sdd0, const float* depth1, const float* disp1, const float* sdisp1, const float* sdd1, int edge,
-                                    float match_cov_default, const mvMatchCovParams* cov_params, int64_t* out_perm, int32_t* out_live,
-                                    int64_t* out_kp0_uv, float* out_kp0, float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0,
-                                    float* out_sigma1, float* out_pos_Tc, double* out_cov0, double* out_cov1, mvStream_t stream) {
-    MV_CHECK_ARG(cov_params && edge >= 0 && lanes >= 1 && lanes <= MV_MAX_LANES && cap >= 1 && num_point >= 0 && num_point <= cap && count_stride >= 1);
-    MV_CHECK_ARG(cov_model >= MV_COV_MATCH && cov_model <= MV_COV_NONE && mv_cov_modifiers_ok(cov_modifiers));
-    MV_CHECK_ARG(cov_model != MV_COV_GMM || (sdd0 && sdd1));
-    const mvMatchCovParams cp = *cov_params;
-    MV_CHECK_ARG(cp.H > 0 && cp.W > 0 && cp.kernel_size >= 1 && (cp.kernel_size & 1) && cp.use_patch_var);
-    if (cp.kernel_size > mvcov::MAX_K || num_point > mvrp::MAX_HEAD) return MV_ERR_UNSUPPORTED;
-    MV_CHECK_ARG(cand && count_dev && state_in && state_out && state_in != state_out && out_perm && out_live && match_flow && depth0 && depth1 &&
-                 out_kp0_uv && out_kp1 && out_inbound && out_vals && out_sigma0 && out_sigma1 && out_pos_Tc && out_cov0 && out_cov1);
-    const TrackArgs ta{match_flow, match_cov, depth0, disp0, sdisp0, sdd0, depth1, disp1, sdisp1, sdd1, cp.H, cp.W, edge, match_cov_default,
-                       out_kp0, out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1};
-    const dim3 grid(mv_ceil_div(num_point > 0 ? num_point : 1, 4), 2, lanes);   // (num_point == 0: workgroup (0, 0, l) still advances the generator)
-    PermArg pa;
-    pa.idx[0] = 0;
-    const DrawArgs da{count_dev, count_stride, state_in, state_out, num_point, 0, out_perm, out_live};
-    launch_backend_front<2>(cov_model, cov_modifiers, grid, (hipStream_t)stream, da, cand, cand_lane_stride, (const int64_t*)nullptr, pa, cap, mvLaneCounts{},
-                            out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
-    return mv_launch_status();
-}
-
-// The front launch with keypoint rows that come from no candidate list (backend_front_kernel<3 | 4 | 5>).  kp_mode:
-//   MV_KP_EXPLICIT  kp_uv int64 [lanes, cap, 2] in device memory (may be out_kp0_uv itself); live rows n_live[l] (host) or, n_live == NULL,
-//                   n_live_dev[l * n_live_stride] clamped to [0, cap].  Rows are used as given: coordinates outside the image read pixel 0 and are
-//                   marked out of bounds, a covariance patch that leaves the image is clamped — callers keep keypoints cov_kernel_size / 2 inside.
-//   MV_KP_RANDOM    num_point rows per lane drawn from state_in, the advanced generators stored to state_out (!= state_in)
-//   MV_KP_GRID      the mv_kp_grid_count(H, W, mask_width, num_point) rows of GridSelector
-// out_live ([lanes, 2] or NULL): the live-row count as the *_dev solves read it.
-int mv_backend_front_cov_kp_lanes(int cov_model, int32_t cov_modifiers, int kp_mode, const int64_t* kp_uv, const int32_t* n_live, const int32_t* n_live_dev,
-                                  int n_live_stride, const uint32_t* state_in, uint32_t* state_out, int num_point, int mask_width, int lanes, int cap,
-                                  const float* match_flow, const float* match_cov, const float* depth0, const float* disp0, const float* sdisp0,
-                                  const float* sdd0, const float* depth1, const float* disp1, const float* sdisp1, const float* sdd1, int edge,
-                                  float match_cov_default, const mvMatchCovParams* cov_params, int32_t* out_live, int64_t* out_kp0_uv, float* out_kp0,
-                                  float* out_kp1, uint8_t* out_inbound, float* out_vals, float* out_sigma0, float* out_sigma1, float* out_pos_Tc,
-                                  double* out_cov0, double* out_cov1, mvStream_t stream) {
-    MV_CHECK_ARG(cov_params && edge >= 0 && lanes >= 1 && lanes <= MV_MAX_LANES && cap >= 1 && num_point >= 0 && mask_width >= 0);
-    MV_CHECK_ARG(cov_model >= MV_COV_MATCH && cov_model <= MV_COV_NONE && mv_cov_modifiers_ok(cov_modifiers));
-    MV_CHECK_ARG(cov_model != MV_COV_GMM || (sdd0 && sdd1));
-    const mvMatchCovParams cp = *cov_params;
-    MV_CHECK_ARG(cp.H > 0 && cp.W > 0 && cp.kernel_size >= 1 && (cp.kernel_size & 1) && cp.use_patch_var);
-    if (cp.kernel_size > mvcov::MAX_K) return MV_ERR_UNSUPPORTED;
-    MV_CHECK_ARG(match_flow && depth0 && depth1 && out_kp0_uv && out_kp1 && out_inbound && out_vals && out_sigma0 && out_sigma1 && out_pos_Tc && out_cov0 &&
-                 out_cov1);
-    const TrackArgs ta{match_flow, match_cov, depth0, disp0, sdisp0, sdd0, depth1, disp1, sdisp1, sdd1, cp.H, cp.W, edge, match_cov_default,
-                       out_kp0, out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1};
-    mvLaneCounts c{};
-    PermArg pa;
-    pa.idx[0] = 0;
-    int n_max = 0;
-    DrawArgs da{};
-    da.out_live = out_live;
-    if (kp_mode == MV_KP_EXPLICIT) {
-        MV_CHECK_ARG(kp_uv && (n_live || (n_live_dev && n_live_stride >= 1)));
-        if (n_live) {
-            const int rc = check_lanes(lanes, n_live, cap, c, n_max);
-            if (rc != MV_OK) return rc;
-        } else {
-            n_max = cap;
-            da.count = n_live_dev;
-            da.count_stride = n_live_stride;
-        }
-        if (n_max == 0) return MV_OK;
-        launch_backend_front<3>(cov_model, cov_modifiers, dim3(mv_ceil_div(n_max, 4), 2, lanes), (hipStream_t)stream, da, (const int32_t*)nullptr, (size_t)0, kp_uv,
-                                pa, cap, c, out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
-    } else if (kp_mode == MV_KP_RANDOM) {
-        MV_CHECK_ARG(state_in && state_out && state_in != state_out && num_point >= 1 && num_point <= cap && cp.H > 2 * mask_width && cp.W > 2 * mask_width);
-        if (num_point > mvkp::MAX_POINT) return MV_ERR_UNSUPPORTED;
-        for (int l = 0; l < lanes; ++l) c.n[l] = num_point;
-        pa.idx[0] = mask_width;
-        da.state_in = state_in;
-        da.state_out = state_out;
-        da.k = num_point;
-        launch_backend_front<4>(cov_model, cov_modifiers, dim3(mv_ceil_div(num_point, 4), 2, lanes), (hipStream_t)stream, da, (const int32_t*)nullptr, (size_t)0,
-                                (const int64_t*)nullptr, pa, cap, c, out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
-    } else if (kp_mode == MV_KP_GRID) {
-        mvkp::Grid g;
-        const int n = mvkp::grid_of(cp.H, cp.W, mask_width, num_point, &g);
-        MV_CHECK_ARG(n >= 1 && n <= cap);
-        for (int l = 0; l < lanes; ++l) c.n[l] = n;
-        pa.idx[0] = g.cols; pa.idx[1] = g.sh; pa.idx[2] = g.sw; pa.idx[3] = g.mask;
-        launch_backend_front<5>(cov_model, cov_modifiers, dim3(mv_ceil_div(n, 4), 2, lanes), (hipStream_t)stream, da, (const int32_t*)nullptr, (size_t)0,
-                                (const int64_t*)nullptr, pa, cap, c, out_kp0_uv, ta, cp.fx, cp.fy, cp.cx, cp.cy, out_pos_Tc, depth0, depth1, out_cov0, out_cov1, cp);
-    } else {
-        return MV_ERR_INVALID_ARG;
-    }
-    return mv_launch_status();
+    MV_CHECK_ARG(cov_params);
+    mvKpSource src{};
+    src.kind = MV_KPSRC_DRAW;
+    src.cand = cand; src.cand_lane_stride = cand_lane_stride; src.n_live_dev = count_dev; src.n_live_stride = count_stride;
+    src.state_in = state_in; src.state_out = state_out; src.num_point = num_point; src.out_perm = out_perm; src.out_live = out_live;
+    return mv_backend_front(src, lanes, cap, {match_flow, match_cov, {depth0, disp0, sdisp0, sdd0}, {depth1, disp1, sdisp1, sdd1}},
+                            {MV_COV_MATCH, 0, *cov_params, edge, match_cov_default},
+                            {out_kp0_uv, out_kp0, out_kp1, out_inbound, out_vals, out_sigma0, out_sigma1, out_pos_Tc, out_cov0, out_cov1}, stream);
 }
 
 extern "C" int mv_kp_track(const int64_t* kp0_uv, int N, const float* match_flow, const float* match_cov,

@@ -589,64 +589,43 @@ extern "C" void mv_lm_default_params(mvLMParams* p) {
     p->reject = 16; p->max_steps = 10; p->patience = 2; p->stop_on_reject = 1;
 }
 
-struct PoseApplyArgs {   // mv_pgo_solve_posed's extra arguments (all null for the plain solve)
-    const float* pos_Tc;
-    const double* cov_Tc;
-    double* out_rot;
-    float* pose_sink;
-    const int32_t* n_live;
-    int filter_flags = -1;
-    const int32_t* live_dev = nullptr;
-    int live_stride = 0;
-    float filter_min_depth = 0.f, filter_max_depth = 0.f;
-    int cap = 0;
-    const uint8_t* inbound = nullptr;
-    const float* vals = nullptr;
-    uint8_t* valid_out = nullptr;
-    int32_t* count_out = nullptr;
-    const float* start_pose = nullptr;   // mv_pgo_solve_posed_motion(_dev): the LM start (init_pose then only rotates the rows)
-};
-
-static int pgo_solve_impl(int nprob, const int32_t* offsets, int graph_type, const float* init_pose,
-                          const float* intrinsics, const float* baseline, const float* pos_Tw, const double* cov_Tw,
-                          const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp,
-                          const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
-                          const uint8_t* valid, int min_points, const mvLMParams* params, double* out_pose,
-                          double* out_info, float* out_pose_f32, const PoseApplyArgs& pa, mvStream_t stream) {
+// One pgo_solve_kernel launch.  d.pos_Tc given (mv_posed_solve): the pose-dependent remainder of the backend is the launch's prologue.
+static int pgo_solve_impl(const mvPosedSolve& d, mvStream_t stream) {
+    const int nprob = d.nprob;
+    const mvLMParams* params = d.params;
     MV_CHECK_ARG(nprob >= 0 && params);
     if (nprob == 0) return MV_OK;
-    MV_CHECK_ARG(offsets && init_pose && intrinsics && baseline && pos_Tw && pixel2_uv && out_pose && out_info);
+    MV_CHECK_ARG(d.offsets && d.init_pose && d.intrinsics && d.baseline && d.pos_Tw && d.pixel2_uv && d.out_pose && d.out_info);
     MV_CHECK_ARG(params->max_steps >= 1 && params->reject >= 0 && params->stop_on_reject >= 0 && params->radius > 0 && params->huber_delta > 0);
-    PgoArgs a{offsets, init_pose, intrinsics, baseline, pos_Tw, cov_Tw, pixel2_uv, pixel2_d, pixel2_disp,
-              pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, out_pose, out_info, out_pose_f32, 1};
-    a.pose_sink = pa.pose_sink;
-    MV_CHECK_ARG(!pa.start_pose || (pa.pos_Tc && nprob < 512));   // (the motion kernel is the 4-wave form)
-    if (pa.pos_Tc) {
-        MV_CHECK_ARG(nprob <= MV_MAX_LANES && (pa.n_live || pa.live_dev));
-        a.live_dev = pa.live_dev;
-        a.live_stride = pa.live_stride;
-        a.apply_pos_Tc = pa.pos_Tc;
-        a.apply_cov_Tc = pa.cov_Tc;
-        a.apply_pos_Tw = const_cast<float*>(pos_Tw);        // the solve's own input tables are the outputs of the fold
-        a.apply_cov_Tw = pa.cov_Tc ? const_cast<double*>(cov_Tw) : nullptr;
-        a.apply_rot = pa.out_rot;
-        for (int l = 0; l < nprob && pa.n_live; ++l) {
-            MV_CHECK_ARG(pa.n_live[l] >= 0);
-            a.apply_live[l] = pa.n_live[l];
+    PgoArgs a{d.offsets, d.init_pose, d.intrinsics, d.baseline, d.pos_Tw, d.cov_Tw, d.pixel2_uv, d.pixel2_d, d.pixel2_disp,
+              d.pixel2_disp_cov, d.pixel2_uv_cov, d.obs2_covTc, d.valid, d.min_points, d.out_pose, d.out_info, d.out_pose_f32, 1};
+    a.pose_sink = d.pose_sink;
+    MV_CHECK_ARG(!d.start_pose || (d.pos_Tc && nprob < 512));   // (the motion kernel is the 4-wave form)
+    if (d.pos_Tc) {
+        MV_CHECK_ARG(nprob <= MV_MAX_LANES && (d.n_live || d.n_live_dev));
+        a.live_dev = d.n_live_dev;
+        a.live_stride = d.n_live_dev ? d.n_live_stride : 0;
+        a.apply_pos_Tc = d.pos_Tc;
+        a.apply_cov_Tc = d.cov_Tc;
+        a.apply_pos_Tw = d.pos_Tw;        // the solve's own input tables are the outputs of the fold
+        a.apply_cov_Tw = d.cov_Tc ? d.cov_Tw : nullptr;
+        a.apply_rot = d.out_rot;
+        for (int l = 0; l < nprob && d.n_live; ++l) {
+            MV_CHECK_ARG(d.n_live[l] >= 0);
+            a.apply_live[l] = d.n_live[l];
         }
-        if (pa.filter_flags >= 0) {
-            MV_CHECK_ARG(pa.valid_out && pa.count_out && pa.cap >= 0 && (!(pa.filter_flags & 1) || (pa.cov_Tc && obs2_covTc)) &&
-                         (!(pa.filter_flags & 6) || pa.vals));
-            a.filter_flags = pa.filter_flags;
-            a.filter_min_depth = pa.filter_min_depth;
-            a.filter_max_depth = pa.filter_max_depth;
-            a.filter_cap = pa.cap;
-            a.filter_inbound = pa.inbound;
-            a.filter_vals = pa.vals;
-            a.valid_out = pa.valid_out;
-            a.count_out = pa.count_out;
-            a.valid = pa.valid_out;      // what the solve reads
-            for (int l = 0; l < nprob && pa.n_live; ++l) MV_CHECK_ARG(pa.n_live[l] <= pa.cap);
+        if (d.filter_flags >= 0) {   // the observation filters write `valid`, which the solve then reads
+            MV_CHECK_ARG(d.valid && d.count_out && d.cap >= 0 && (!(d.filter_flags & 1) || (d.cov_Tc && d.obs2_covTc)) &&
+                         (!(d.filter_flags & 6) || d.vals));
+            a.filter_flags = d.filter_flags;
+            a.filter_min_depth = d.filter_min_depth;
+            a.filter_max_depth = d.filter_max_depth;
+            a.filter_cap = d.cap;
+            a.filter_inbound = d.inbound;
+            a.filter_vals = d.vals;
+            a.valid_out = d.valid;
+            a.count_out = d.count_out;
+            for (int l = 0; l < nprob && d.n_live; ++l) MV_CHECK_ARG(d.n_live[l] <= d.cap);
         }
     }
     {
@@ -660,20 +639,20 @@ static int pgo_solve_impl(int nprob, const int32_t* offsets, int graph_type, con
     const bool wide = nprob < 512;
     dim3 grid(nprob), block(wide ? 256 : 64);
 #define MV_PGO(G)                                                                             \
-    if (pa.start_pose) hipLaunchKernelGGL((pgo_solve_kernel<G, 4 + PGO_MOTION>), grid, block, 0, s, PgoMotionArgs{a, pa.start_pose}, *params); \
+    if (d.start_pose) hipLaunchKernelGGL((pgo_solve_kernel<G, 4 + PGO_MOTION>), grid, block, 0, s, PgoMotionArgs{a, d.start_pose}, *params); \
     else if (wide) hipLaunchKernelGGL((pgo_solve_kernel<G, 4>), grid, block, 0, s, a, *params);    \
     else hipLaunchKernelGGL((pgo_solve_kernel<G, 1>), grid, block, 0, s, a, *params)
-    switch (graph_type) {
+    switch (d.graph_type) {
         case MV_GRAPH_ICP:
-            MV_CHECK_ARG(cov_Tw && obs2_covTc && pixel2_d);
+            MV_CHECK_ARG(d.cov_Tw && d.obs2_covTc && d.pixel2_d);
             MV_PGO(MV_GRAPH_ICP);
             break;
         case MV_GRAPH_REPROJ:
-            MV_CHECK_ARG(pixel2_uv_cov);
+            MV_CHECK_ARG(d.pixel2_uv_cov);
             MV_PGO(MV_GRAPH_REPROJ);
             break;
         case MV_GRAPH_DISP:
-            MV_CHECK_ARG(pixel2_uv_cov && pixel2_disp && pixel2_disp_cov);
+            MV_CHECK_ARG(d.pixel2_uv_cov && d.pixel2_disp && d.pixel2_disp_cov);
             MV_PGO(MV_GRAPH_DISP);
             break;
         default:
@@ -689,40 +668,38 @@ extern "C" int mv_pgo_solve(int nprob, const int32_t* offsets, int graph_type, c
                             const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
                             const uint8_t* valid, int min_points, const mvLMParams* params, double* out_pose,
                             double* out_info, float* out_pose_f32, mvStream_t stream) {
-    return pgo_solve_impl(nprob, offsets, graph_type, init_pose, intrinsics, baseline, pos_Tw, cov_Tw, pixel2_uv, pixel2_d, pixel2_disp,
-                          pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, params, out_pose, out_info, out_pose_f32,
-                          PoseApplyArgs{nullptr, nullptr, nullptr, nullptr, nullptr}, stream);
+    mvPosedSolve d{};
+    d.nprob = nprob; d.offsets = offsets; d.graph_type = graph_type; d.init_pose = init_pose; d.intrinsics = intrinsics; d.baseline = baseline;
+    d.pos_Tw = const_cast<float*>(pos_Tw); d.cov_Tw = const_cast<double*>(cov_Tw);   // (read only without pos_Tc)
+    d.pixel2_uv = pixel2_uv; d.pixel2_d = pixel2_d; d.pixel2_disp = pixel2_disp; d.pixel2_disp_cov = pixel2_disp_cov; d.pixel2_uv_cov = pixel2_uv_cov;
+    d.obs2_covTc = obs2_covTc; d.filter_flags = -1; d.valid = const_cast<uint8_t*>(valid); d.min_points = min_points; d.params = params;
+    d.out_pose = out_pose; d.out_info = out_info; d.out_pose_f32 = out_pose_f32;
+    return pgo_solve_impl(d, stream);
 }
 
-static int solve_posed(int nprob, const int32_t* offsets, const int32_t* n_live, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
-                       const float* init_pose, const float* start_pose, const float* intrinsics, const float* baseline, const float* pos_Tc,
-                       const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
-                       const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
-                       int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
-                       uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
-                       float* out_pose_f32, float* pose_sink, mvStream_t stream);
+// The posed solve: filters + rotation into the world frame with init_pose (the previous pose) + LM solve.  Live rows of problem l: n_live[l] (host) or —
+// the device-driven frame (round 6), the host never learns the count — n_live_dev[l * n_live_stride] <= cap, written earlier on the stream by the front
+// launch.  start_pose given = the motion-model form (TartanMotionNet, MACVO.py:193-194,273-281,303-307): LM starts from it (the prior) and a problem below
+// min_points returns it; that is pgo_solve_kernel<G, 4 + PGO_MOTION>, every other call keeps its instantiation.
+int mv_posed_solve(const mvPosedSolve& d, mvStream_t stream) {
+    MV_CHECK_ARG(d.pos_Tc && d.pos_Tw && (d.n_live || (d.n_live_dev && d.n_live_stride >= 1)) && (!d.cov_Tc || d.cov_Tw));
+    MV_CHECK_ARG(d.nprob < 512);   // (the 256-thread solve variant: the filter body is written for it)
+    return pgo_solve_impl(d, stream);
+}
 
-extern "C" int mv_pgo_solve_posed(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type, const float* init_pose,
-                                  const float* intrinsics, const float* baseline, const float* pos_Tc, const double* cov_Tc,
+extern "C" int mv_pgo_solve_posed(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type,
+                                  const float* init_pose, const float* intrinsics, const float* baseline, const float* pos_Tc, const double* cov_Tc,
                                   float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
-                                  const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov,
-                                  const double* obs2_covTc, int filter_flags, float filter_min_depth, float filter_max_depth,
-                                  const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out, int min_points,
-                                  const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32, float* pose_sink,
-                                  mvStream_t stream) {
-    MV_CHECK_ARG(pos_Tc && pos_Tw && n_live && (!cov_Tc || cov_Tw));
-    MV_CHECK_ARG(nprob < 512);   // (the 256-thread solve variant: the filter body is written for it)
-    PoseApplyArgs pa{pos_Tc, cov_Tc, out_rot, pose_sink, n_live};
-    if (filter_flags >= 0) {
-        pa.filter_flags = filter_flags; pa.filter_min_depth = filter_min_depth; pa.filter_max_depth = filter_max_depth; pa.cap = cap;
-        pa.inbound = inbound; pa.vals = vals; pa.valid_out = valid; pa.count_out = count_out;
-    }
-    return pgo_solve_impl(nprob, offsets, graph_type, init_pose, intrinsics, baseline, pos_Tw, cov_Tw, pixel2_uv, pixel2_d, pixel2_disp,
-                          pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, params, out_pose, out_info, out_pose_f32, pa, stream);
+                                  const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
+                                  int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
+                                  uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
+                                  float* out_pose_f32, float* pose_sink, mvStream_t stream) {
+    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, nullptr, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
+                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, n_live, nullptr, 0,
+                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
+                           out_pose, out_info, out_pose_f32, pose_sink}, stream);
 }
 
-// mv_pgo_solve_posed of the device-driven frame (round 6): the live-row count of problem l is read from device memory (n_live_dev[l * n_live_stride] <= cap,
-// written by mv_backend_front_draw_lanes earlier on the stream) — the host never learns it.
 extern "C" int mv_pgo_solve_posed_dev(int nprob, const int32_t* offsets, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
                                       const float* init_pose, const float* intrinsics, const float* baseline, const float* pos_Tc, const double* cov_Tc,
                                       float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
@@ -730,68 +707,36 @@ extern "C" int mv_pgo_solve_posed_dev(int nprob, const int32_t* offsets, const i
                                       int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
                                       uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
                                       float* out_pose_f32, float* pose_sink, mvStream_t stream) {
-    MV_CHECK_ARG(pos_Tc && pos_Tw && n_live_dev && n_live_stride >= 1 && (!cov_Tc || cov_Tw));
-    MV_CHECK_ARG(nprob < 512);
-    PoseApplyArgs pa{pos_Tc, cov_Tc, out_rot, pose_sink, nullptr};
-    pa.live_dev = n_live_dev;
-    pa.live_stride = n_live_stride;
-    if (filter_flags >= 0) {
-        pa.filter_flags = filter_flags; pa.filter_min_depth = filter_min_depth; pa.filter_max_depth = filter_max_depth; pa.cap = cap;
-        pa.inbound = inbound; pa.vals = vals; pa.valid_out = valid; pa.count_out = count_out;
-    }
-    return pgo_solve_impl(nprob, offsets, graph_type, init_pose, intrinsics, baseline, pos_Tw, cov_Tw, pixel2_uv, pixel2_d, pixel2_disp,
-                          pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, params, out_pose, out_info, out_pose_f32, pa, stream);
+    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, nullptr, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
+                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, nullptr, n_live_dev, n_live_stride,
+                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
+                           out_pose, out_info, out_pose_f32, pose_sink}, stream);
 }
 
-// The motion-model forms (TartanMotionNet, MACVO.py:193-194,273-281,303-307): the rows are rotated into the world frame with init_pose (the previous
-// pose), LM starts from start_pose (the prior), a problem below min_points returns start_pose.  pgo_solve_kernel<G, 4, true>; the entry points above
-// keep their instantiations.
-static int solve_posed(int nprob, const int32_t* offsets, const int32_t* n_live, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
-                       const float* init_pose, const float* start_pose, const float* intrinsics, const float* baseline, const float* pos_Tc,
-                       const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
-                       const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
-                       int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
-                       uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
-                       float* out_pose_f32, float* pose_sink, mvStream_t stream) {
-    MV_CHECK_ARG(pos_Tc && pos_Tw && start_pose && (n_live || (n_live_dev && n_live_stride >= 1)) && (!cov_Tc || cov_Tw));
-    MV_CHECK_ARG(nprob < 512);
-    PoseApplyArgs pa{pos_Tc, cov_Tc, out_rot, pose_sink, n_live};
-    pa.live_dev = n_live_dev;
-    pa.live_stride = n_live_dev ? n_live_stride : 0;
-    pa.start_pose = start_pose;
-    if (filter_flags >= 0) {
-        pa.filter_flags = filter_flags; pa.filter_min_depth = filter_min_depth; pa.filter_max_depth = filter_max_depth; pa.cap = cap;
-        pa.inbound = inbound; pa.vals = vals; pa.valid_out = valid; pa.count_out = count_out;
-    }
-    return pgo_solve_impl(nprob, offsets, graph_type, init_pose, intrinsics, baseline, pos_Tw, cov_Tw, pixel2_uv, pixel2_d, pixel2_disp,
-                          pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, params, out_pose, out_info, out_pose_f32, pa, stream);
-}
-
-extern "C" int mv_pgo_solve_posed_motion(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type, const float* init_pose,
-                                         const float* start_pose, const float* intrinsics, const float* baseline, const float* pos_Tc, const double* cov_Tc,
+extern "C" int mv_pgo_solve_posed_motion(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type,
+                                         const float* init_pose, const float* start_pose, const float* intrinsics, const float* baseline, const float* pos_Tc, const double* cov_Tc,
                                          float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
-                                         const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov,
-                                         const double* obs2_covTc, int filter_flags, float filter_min_depth, float filter_max_depth,
-                                         const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out, int min_points,
-                                         const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32, float* pose_sink,
-                                         mvStream_t stream) {
-    MV_CHECK_ARG(n_live);
-    return solve_posed(nprob, offsets, n_live, nullptr, 0, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw,
-                       out_rot, pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, filter_flags, filter_min_depth,
-                       filter_max_depth, inbound, vals, valid, count_out, min_points, params, out_pose, out_info, out_pose_f32, pose_sink, stream);
+                                         const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
+                                         int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
+                                         uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
+                                         float* out_pose_f32, float* pose_sink, mvStream_t stream) {
+    MV_CHECK_ARG(n_live && start_pose);
+    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
+                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, n_live, nullptr, 0,
+                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
+                           out_pose, out_info, out_pose_f32, pose_sink}, stream);
 }
 
 extern "C" int mv_pgo_solve_posed_motion_dev(int nprob, const int32_t* offsets, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
-                                             const float* init_pose, const float* start_pose, const float* intrinsics, const float* baseline,
-                                             const float* pos_Tc, const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot,
-                                             const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp, const float* pixel2_disp_cov,
-                                             const float* pixel2_uv_cov, const double* obs2_covTc, int filter_flags, float filter_min_depth,
-                                             float filter_max_depth, const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out,
-                                             int min_points, const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32,
-                                             float* pose_sink, mvStream_t stream) {
-    MV_CHECK_ARG(n_live_dev);
-    return solve_posed(nprob, offsets, nullptr, n_live_dev, n_live_stride, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc,
-                       pos_Tw, cov_Tw, out_rot, pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, filter_flags,
-                       filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params, out_pose, out_info, out_pose_f32,
-                       pose_sink, stream);
+                                             const float* init_pose, const float* start_pose, const float* intrinsics, const float* baseline, const float* pos_Tc, const double* cov_Tc,
+                                             float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
+                                             const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
+                                             int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
+                                             uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
+                                             float* out_pose_f32, float* pose_sink, mvStream_t stream) {
+    MV_CHECK_ARG(n_live_dev && start_pose);
+    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
+                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, nullptr, n_live_dev, n_live_stride,
+                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
+                           out_pose, out_info, out_pose_f32, pose_sink}, stream);
 }
