@@ -196,6 +196,12 @@ int mv_corr_lookup_tiled_vol16(const void* vol_f16, const float* coords, float* 
  *     disparity = |flow[0,0]|, disparity_cov = cov[0,0], depth = bl_fx * (1/disparity),
  *     depth_cov = bl_fx_sq * ((disparity_cov * (1/d^2)) / d^2), bad_mask = flow[0,0] <= 0 (uint8),
  *     match_flow [2,H,W] = flow[1], match_cov [3,H,W] = (cov[1,0], cov[1,1], 0)
+ *   A frontend without covariances (MV_NOCOV_*; StereoDepth.py:121-128, Matching.py:142-147) says so through the outputs it leaves out:
+ *   disparity_cov == depth_cov == NULL = no depth covariance, logcov[0] is not read; match_flow given and match_cov == NULL = no match
+ *   covariance, logcov[1] is not read; logcov itself may be NULL when no covariance output is asked for.  Depth, disparity, bad_mask and
+ *   match_flow are the same bits in every form.
+ *   (A call that leaves those outputs out while passing logcov — legal before, though nothing in this library made it — now runs the
+ *   partial kernel instead of the full one: the same bits for everything it writes.)
  */
 int mv_frontend_epilogue(const float* flow, const float* logcov, int cov_is_log, int H, int W,
                          float bl_fx, float bl_fx_sq, float* disparity, float* disparity_cov,
@@ -370,6 +376,9 @@ int mv_match_cov_pair(const float* depth_map0, const float* kp_uv0, float* flow_
  * out_stats [N, 2] fp32 = (mean depth, variance) for MATCH / GMM, NaN for NONE. */
 enum { MV_COV_MATCH = 0, MV_COV_GMM = 1, MV_COV_NONE = 2 };
 enum { MV_COVMOD_DIAG = 1, MV_COVMOD_NORMALIZE = 2 };
+/* Covariances a frontend does NOT provide (IFrontend.provide_cov, Frontend.py:137-139): the depth model's (no disparity variance, no depth
+ * variance: FlowFormerDepth) and / or the matcher's (no match covariance: FlowFormerMatcher).  0 = both there, as everywhere before. */
+enum { MV_NOCOV_DEPTH = 1, MV_NOCOV_MATCH = 2 };
 
 int mv_obs_cov(int model, int32_t modifiers, const float* depth_map, const float* depth_cov_map, const float* kp_uv,
                float* flow_cov, const float* depth_cov, const double* rot, const mvMatchCovParams* params /* host */, int N,
@@ -380,6 +389,17 @@ int mv_obs_cov_pair_lanes(int model, int32_t modifiers, const float* depth_map0,
                           float* flow_cov0, const double* rot0, double* out_cov0, double* out_cov_rot0, const float* depth_map1,
                           const float* depth_cov_map1, const float* kp_uv1, float* flow_cov1, double* out_cov1,
                           const mvMatchCovParams* params /* host */, int lanes, const int32_t* n_live, int cap, mvStream_t stream);
+/* mv_obs_cov_pair_lanes of a frame whose matcher gives no covariance (MV_NOCOV_MATCH; MACVO.py:231-232,241-242): set 0 as above; set 1 is the model
+ * called with flow_cov = None (Project2to3.py:128-135,162-172,211-218,254-255) — sigma = (c, c, 0) with c = model_match_cov_default (the covariance
+ * model's OWN match_cov_default), not clamped by min_flow_cov; the depth variance is depth_cov1 [lanes, cap] (the depth-variance map gathered at the
+ * truncated kp1: row 7 of mv_kp_track's value table) where the depth model gives one — MATCH then clamps it by min_depth_cov, GMM keeps its mixture mean
+ * and takes this variance — and the patch statistic when depth_cov1 is NULL (MATCH only: GMM needs the depth model's variance).  The set-1 sigma table
+ * is neither read nor written: it keeps the (-1, -1, -1) placeholders of MACVO.py:263. */
+int mv_obs_cov_pair_nomatch_lanes(int model, int32_t modifiers, const float* depth_map0, const float* depth_cov_map0, const float* kp_uv0,
+                                  float* flow_cov0, const double* rot0, double* out_cov0, double* out_cov_rot0, const float* depth_map1,
+                                  const float* depth_cov_map1, const float* kp_uv1, const float* depth_cov1, float model_match_cov_default,
+                                  double* out_cov1, const mvMatchCovParams* params /* host */, int lanes, const int32_t* n_live, int cap,
+                                  mvStream_t stream);
 
 /* -------------------------------------------------------------------------------------------
  * TartanMotionNet motion prior (Module/MotionModel.py:90-123): everything around the learned PoseNet.
@@ -745,6 +765,13 @@ typedef struct {
                                   PoseNet input is written to MV_FB_MOTION_IN right behind its epilogue, the caller runs the PoseNet and attaches its raw
                                   output with mv_frame_pipe_set_motion before the frame's finish; prior = previous pose @ Exp(raw * pose_norm) is the LM
                                   start, the pose of a frame without tracked keypoints and the frame's prior in mv_frame_pipe_map_append */
+    int32_t frontend_nocov;    /* MV_NOCOV_* mask of the covariances the frontend does not provide; 0 = both there.  With a bit set the matching inputs
+                                  (logcov / cov8 / cov_mask: NULL when both are) are not read, the covariance maps do not exist (mv_frame_pipe_buffer
+                                  reports an error for them), the stored rows carry the reference's -1 placeholders (MACVO.py:253-263) and whatever would
+                                  read a missing covariance is an invalid configuration: MV_NOCOV_DEPTH with MV_KP_FULL, mapping, MV_COV_GMM or
+                                  MV_GRAPH_DISP; MV_NOCOV_MATCH with MV_KP_NODEPTH, MV_KP_FULL, MV_GRAPH_REPROJ or MV_GRAPH_DISP */
+    float cov_match_cov_default;   /* MV_NOCOV_MATCH: the covariance model's own match_cov_default (Project2to3.py:133,216) — the sigma of the second
+                                  observation; match_cov_default above stays the sigma of the first (MACVO.py:228) */
 } mvFramePipeConfig;
 enum { MV_MOTION_STATIC = 0, MV_MOTION_TARTAN = 1 };
 
@@ -754,11 +781,11 @@ typedef struct {
     const void* fmap2;
     const float* coords;    /* [iters, pairs, 2, H/8, W/8]: coords1 entering each decoder iteration (covhead.py:85-92) */
     const float* flow;      /* [pairs, 2, H, W] last upsampled flow        } either these two ...            */
-    const float* logcov;    /* [pairs, 2, H, W] last upsampled log-sigma   }                                  */
+    const float* logcov;    /* [pairs, 2, H, W] last upsampled log-sigma   }  (logcov / cov8 / cov_mask: only the pairs  */
     const float* flow8;     /* [pairs, 2, H/8, W/8]   } ... or the 1/8-resolution fields + convex-upsampling */
-    const float* cov8;      /* [pairs, 2, H/8, W/8]   }     masks of the last iteration (covhead.py:119-135); */
+    const float* cov8;      /* [pairs, 2, H/8, W/8]   }     masks of the last iteration (covhead.py:119-135); (whose covariance the   */
     const float* up_mask;   /* [pairs, 576, H/8, W/8] }     up_mask BEFORE its 0.25 scale, cov_mask after      */
-    const float* cov_mask;  /* [pairs, 576, H/8, W/8] }                                                       */
+    const float* cov_mask;  /* [pairs, 576, H/8, W/8] }   (frontend provides are read; NULL with both MV_NOCOV_* bits set)           */
 } mvFrameInputs;
 
 /* buffers reported by mv_frame_pipe_buffer (element counts, not bytes; MV_FB_VOLUME's element is the volume CELL: fp32, or fp16 — 2 bytes —

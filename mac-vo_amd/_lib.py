@@ -23,6 +23,7 @@ MV_GRAPH_ICP, MV_GRAPH_REPROJ, MV_GRAPH_DISP = 0, 1, 2
 MV_COV_MATCH, MV_COV_GMM, MV_COV_NONE = 0, 1, 2
 MV_COVMOD_DIAG, MV_COVMOD_NORMALIZE = 1, 2
 MV_MOTION_STATIC, MV_MOTION_TARTAN = 0, 1
+MV_NOCOV_DEPTH, MV_NOCOV_MATCH = 1, 2
 ABI_VERSION = 8
 MV_MAX_LANES = 64        # include/macvo_hip.h
 
@@ -61,7 +62,7 @@ class mvFramePipeConfig(C.Structure):
         "cov_kernel_size", "mapping", "map_num_point", "map_mask_width", "async_backend")] + [(n, C.c_float) for n in (
         "fx", "fy", "cx", "cy", "baseline", "bl_fx", "bl_fx_sq", "match_cov_default", "max_match_cov", "max_depth_cov",
         "max_depth", "min_flow_cov_sq", "min_depth_cov", "filter_min_depth", "map_max_depth", "map_max_depth_cov")] + [("lm", mvLMParams)] + [
-        (n, C.c_int32) for n in ("cov_model", "cov_modifiers", "motion_model")]
+        (n, C.c_int32) for n in ("cov_model", "cov_modifiers", "motion_model", "frontend_nocov")] + [("cov_match_cov_default", C.c_float)]
 
 
 class mvMapStores(C.Structure):
@@ -130,6 +131,7 @@ SIGNATURES = {
     "mv_match_cov_pair": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(mvMatchCovParams), C.c_int, _P]),
     "mv_obs_cov": (C.c_int, [C.c_int, C.c_int32, _P, _P, _P, _P, _P, _P, C.POINTER(mvMatchCovParams), C.c_int, _P, _P, _P, _P]),
     "mv_obs_cov_pair_lanes": (C.c_int, [C.c_int, C.c_int32] + [_P] * 12 + [C.POINTER(mvMatchCovParams), C.c_int, _P, C.c_int, _P]),
+    "mv_obs_cov_pair_nomatch_lanes": (C.c_int, [C.c_int, C.c_int32] + [_P] * 11 + [C.c_float, _P, C.POINTER(mvMatchCovParams), C.c_int, _P, C.c_int, _P]),
     "mv_motion_input_lanes": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_longlong, _P, C.c_longlong] + [C.c_float] * 5 + [_P, _P]),
     "mv_pose_exp_compose": (C.c_int, [C.c_int, _P, _P, C.c_longlong, _P, _P, _P]),
     "mv_pgo_solve_posed_motion": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int] + [_P] * 15 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int,

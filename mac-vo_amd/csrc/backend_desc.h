@@ -26,6 +26,8 @@ struct mvCovConfig {   // mv_obs_cov's model + modifier chain, and the tracking 
     mvMatchCovParams cp;
     int edge;
     float match_cov_default;
+    int nocov;                        // MV_NOCOV_*: covariances the frontend does not provide (0 = all there)
+    float model_match_cov_default;    // MV_NOCOV_MATCH: the model's own sigma of a keypoint without match covariance (Project2to3.py:133,216)
 };
 // Where the keypoint rows of a front launch come from (PM of backend_front_kernel); each kind reads only the fields named for it.
 enum mvKpSourceKind {

@@ -59,6 +59,39 @@ __device__ __forceinline__ void mv_epilogue_pixel(const mvEpiArgs& a, int plane,
         a.match_cov[2 * plane + i] = 0.f;
     }
 }
+// mv_epilogue_pixel of a frontend that lacks the depth model's covariance (D = false), the matcher's (M = false) or both (StereoDepth.py:121-128,
+// Matching.py:142-147: `cov` / `disparity_uncertainty` are None).  Only the covariance planes of a pair whose flag is set are read and written; `logcov`
+// may be null when neither is.  Same expressions as above for everything that is written.
+template <bool D, bool M>
+__device__ __forceinline__ void mv_epilogue_pixel_partial(const mvEpiArgs& a, int plane, int i) {
+    const float fx0 = a.flow[i];
+    const float d = fabsf(fx0);
+    if (a.disparity) a.disparity[i] = d;
+    if (a.depth) a.depth[i] = a.bl_fx * (1.f / d);
+    if constexpr (D) {
+        const float lc0 = a.logcov[i];
+        const float dcov = a.cov_is_log ? expf(lc0 * 2.f) : lc0;
+        if (a.disparity_cov) a.disparity_cov[i] = dcov;
+        if (a.depth_cov) {
+            const float d2 = d * d;
+            const float err2 = dcov * (1.f / d2);
+            a.depth_cov[i] = a.bl_fx_sq * (err2 / d2);
+        }
+    }
+    if (a.bad_mask) a.bad_mask[i] = fx0 <= 0.f;
+    if (a.match_flow) {
+        a.match_flow[i] = a.flow[2 * plane + i];
+        a.match_flow[plane + i] = a.flow[3 * plane + i];
+    }
+    if constexpr (M) {
+        if (a.match_cov) {
+            const float l0 = a.logcov[2 * plane + i], l1 = a.logcov[3 * plane + i];
+            a.match_cov[i] = a.cov_is_log ? expf(l0 * 2.f) : l0;
+            a.match_cov[plane + i] = a.cov_is_log ? expf(l1 * 2.f) : l1;
+            a.match_cov[2 * plane + i] = 0.f;
+        }
+    }
+}
 #endif
 
 struct mvLaneCounts {

@@ -379,16 +379,18 @@ static size_t carve(mvFramePipe* p, char* base) {
         for (int o = 0; o < 2; ++o) p->pk[k][o] = p->packed ? (void*)a.take<char>(p->pk_bytes) : nullptr;
     // (carved for every Fast-mode pipe whose shape the tiled form covers — the sizing call knows the configuration, not MV_PIPE_TILED: 2 % of the volume buffers)
     p->tile16 = (c.volume_split == MV_VOL_ENC16 && c.radius == 4 && p->w8 % 4 == 0) ? (void*)a.take<uint16_t>(B * (size_t)mv_tiled_slice_cells(p->h8, p->w8) * c.C) : nullptr;
+    // (covariance planes the frontend does not provide — c.frontend_nocov — are not carved: their pointers stay null all the way into the launches)
+    const bool no_d = (c.frontend_nocov & MV_NOCOV_DEPTH) != 0, no_m = (c.frontend_nocov & MV_NOCOV_MATCH) != 0;
     p->up_flow = a.take<float>(B * 2 * plane);
-    p->up_cov = a.take<float>(B * 2 * plane);
+    p->up_cov = (no_d && no_m) ? nullptr : a.take<float>(B * 2 * plane);
     for (int k = 0; k < N_MAPS; ++k) {   // every map is [lanes, ch, H, W]
         Maps& m = p->maps[k];
         m.disparity = a.take<float>(L * plane);
-        m.disparity_cov = a.take<float>(L * plane);
+        m.disparity_cov = no_d ? nullptr : a.take<float>(L * plane);
         m.depth = a.take<float>(L * plane);
-        m.depth_cov = a.take<float>(L * plane);
+        m.depth_cov = no_d ? nullptr : a.take<float>(L * plane);
         m.match_flow = a.take<float>(L * 2 * plane);
-        m.match_cov = a.take<float>(L * 3 * plane);
+        m.match_cov = no_m ? nullptr : a.take<float>(L * 3 * plane);
         m.bad_mask = a.take<uint8_t>(L * plane);
     }
     p->kp_ws_bytes = L * mv_kp_select_workspace_bytes(c.H, c.W);
@@ -461,7 +463,7 @@ static size_t carve(mvFramePipe* p, char* base) {
 static void describe_backend(mvFramePipe* p) {
     const mvFramePipeConfig& c = p->c;
     p->cov = mvCovConfig{c.cov_model, c.cov_modifiers, {c.H, c.W, c.cov_kernel_size, 1, c.fx, c.fy, c.cx, c.cy, c.min_flow_cov_sq, c.min_depth_cov},
-                         c.edgewidth, c.match_cov_default};
+                         c.edgewidth, c.match_cov_default, c.frontend_nocov, c.cov_match_cov_default};
     for (Maps& m : p->maps) m.dm = mvDepthMaps{m.depth, m.disparity, m.disparity_cov, m.depth_cov};
     const int cap = cap_of(c);
     const size_t LN = (size_t)p->lanes * cap;   // value table is [11, lanes, cap]: each of its rows is one concatenated per-point column
@@ -500,6 +502,16 @@ static int check_config(const mvFramePipeConfig* c) {
     MV_CHECK_ARG(!(c->volume_split == 2 || c->volume_split == 3) || c->layout == MV_LAYOUT_HWC);   // (the packed form takes either layout)
     MV_CHECK_ARG(c->cov_model >= MV_COV_MATCH && c->cov_model <= MV_COV_NONE && mv_cov_modifiers_ok(c->cov_modifiers));
     MV_CHECK_ARG(c->motion_model == MV_MOTION_STATIC || (c->motion_model == MV_MOTION_TARTAN && motion::crop_scale(c->H, c->W) >= 1));
+    // A frontend without covariances (frontend_nocov; 0 = both there).  What reads a missing covariance is refused, not emulated: the reference asserts
+    // on depth.cov in CovAwareSelector / MappingPointSelector / GaussianMixtureCovariance, needs match.cov in both CovAware selectors, and builds the
+    // reproj / disp weights by inverting the -1 placeholders of pixel2_uv_cov / pixel2_disp_cov (Graphs.py:54-55,97-103,133).
+    MV_CHECK_ARG((c->frontend_nocov & ~(MV_NOCOV_DEPTH | MV_NOCOV_MATCH)) == 0);
+    if (c->frontend_nocov & MV_NOCOV_DEPTH)
+        MV_CHECK_ARG(c->selector_mode != MV_KP_FULL && !c->mapping && c->cov_model != MV_COV_GMM && c->graph_type != MV_GRAPH_DISP);
+    if (c->frontend_nocov & MV_NOCOV_MATCH) {
+        MV_CHECK_ARG(c->selector_mode != MV_KP_FULL && c->selector_mode != MV_KP_NODEPTH && c->graph_type == MV_GRAPH_ICP);
+        MV_CHECK_ARG(c->cov_model == MV_COV_NONE || c->cov_match_cov_default > 0.f);
+    }
     return MV_OK;
 }
 
@@ -959,26 +971,37 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
     void* const kp_ws = (indep && (d.f & 1)) ? p->kp_ws2 : p->kp_ws;
     Maps& mp = p->maps[m];
     constexpr bool fuse_epi = true;   // epilogue + the selector's first kernel in one launch (the separate form was an A/B knob of rounds 2-4)
+    const int nocov = c.frontend_nocov;
     if (up) {
         MV_TRY(mv_convex_upsample(in->flow8, in->up_mask, p->up_flow, B, p->h8, p->w8, 0.25f, 0, s));
-        MV_TRY(mv_convex_upsample(in->cov8, in->cov_mask, p->up_cov, B, p->h8, p->w8, 1.0f, 1, s));
+        if (!nocov) {
+            MV_TRY(mv_convex_upsample(in->cov8, in->cov_mask, p->up_cov, B, p->h8, p->w8, 1.0f, 1, s));
+        } else if (nocov != (MV_NOCOV_DEPTH | MV_NOCOV_MATCH)) {
+            // one side only: the covariance field of THAT pair of every lane (pair 2l = lane l's stereo pair, 2l + 1 its temporal pair); the other pair's
+            // planes of cov8 / cov_mask / up_cov are neither read nor written
+            for (int l = 0; l < p->lanes; ++l) {
+                const size_t pr = 2 * (size_t)l + ((nocov & MV_NOCOV_DEPTH) ? 1 : 0);
+                MV_TRY(mv_convex_upsample(in->cov8 + pr * 2 * p->n8, in->cov_mask + pr * 576 * p->n8, p->up_cov + pr * 2 * p->plane, 1, p->h8, p->w8,
+                                          1.0f, 1, s));
+            }
+        }
         MV_TRY(mv_frontend_epilogue_lanes(p->up_flow, p->up_cov, 0, c.H, c.W, c.bl_fx, c.bl_fx_sq, mp.disparity,
                                           mp.disparity_cov, mp.depth, mp.depth_cov, nullptr, mp.match_flow, mp.match_cov,
                                           p->lanes, s));
-    } else if (!(fuse_epi && with_selector && c.selector_mode == MV_KP_NODEPTH)) {
+    } else if (nocov || !(fuse_epi && with_selector && c.selector_mode == MV_KP_NODEPTH)) {   // (no fused epilogue + selector launch without depth covariance)
         MV_TRY(mv_frontend_epilogue_lanes(in->flow, in->logcov, 1, c.H, c.W, c.bl_fx, c.bl_fx_sq, mp.disparity,
                                           mp.disparity_cov, mp.depth, mp.depth_cov, nullptr, mp.match_flow, mp.match_cov,
                                           p->lanes, s));
     }
     const Pending pd{m, d.maps_prev, k, with_selector, ti};
-    if (with_selector && c.motion_model == MV_MOTION_TARTAN && !(c.selector_mode == MV_KP_NODEPTH && fuse_epi && !up)) MV_TRY(issue_motion_input(p, m, s));
+    if (with_selector && c.motion_model == MV_MOTION_TARTAN && !(c.selector_mode == MV_KP_NODEPTH && fuse_epi && !up && !nocov)) MV_TRY(issue_motion_input(p, m, s));
     if (with_selector) {
         mvKpSelectParams sp{c.H, c.W, c.selector_mode, c.kp_kernel_size, c.kp_mask_width, c.max_depth, c.max_depth_cov,
                             c.max_match_cov};
         const bool sel_kernels = !kp_new_mode(c.selector_mode);   // (Random / Grid / explicit keypoints: the segment ends with the epilogue)
         if (!sel_kernels) {
             // (nothing: the maps are written, the keypoints come with the finish)
-        } else if (c.selector_mode == MV_KP_NODEPTH && fuse_epi && !up) {
+        } else if (c.selector_mode == MV_KP_NODEPTH && fuse_epi && !up && !nocov) {
             // epilogue + selector's first kernel in one launch (one launch and one pass over the maps less on the chain that
             // bounds a single-sequence stream)
             MV_TRY(mv_frontend_epilogue_select_lanes(in->flow, in->logcov, 1, c.bl_fx, c.bl_fx_sq, mp.disparity, mp.disparity_cov,
@@ -1042,7 +1065,8 @@ extern "C" int mv_frame_pipe_enqueue(mvFramePipe* p, const mvFrameInputs* in, mv
     const mvFramePipeConfig& c = p->c;
     MV_CHECK_ARG(c.iters == 0 || in->coords);
     const bool up = in->flow8 != nullptr;
-    MV_CHECK_ARG(up ? (in->cov8 && in->up_mask && in->cov_mask) : (in->flow && in->logcov));
+    const bool any_cov = c.frontend_nocov != (MV_NOCOV_DEPTH | MV_NOCOV_MATCH);   // (a frontend without covariances hands over no logcov / cov8 / cov_mask)
+    MV_CHECK_ARG(up ? (in->up_mask && (!any_cov || (in->cov8 && in->cov_mask))) : (in->flow && (!any_cov || in->logcov)));
     const long f = p->n_enq;
     const int k = (int)(f % N_CAND), m = (int)(f % N_MAPS);
     MV_CHECK_ARG(!with_selector || p->newest_maps >= 0);   // a tracked frame needs the previous frame's maps
@@ -1415,8 +1439,13 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
                                  c.match_cov_default, c.fx, c.fy, c.cx, c.cy, t.kp0_uv, t.kp0, t.kp1, t.inbound, t.vals, t.sigma0, t.sigma1, t.pos_Tc, s));
     }
     if (!fused) {   // (behind a fused front launch — keypoint rows — the covariances are computed again: same bits)
-        MV_TRY(mv_obs_cov_pair_lanes(c.cov_model, c.cov_modifiers, fm.f0.depth, fm.f0.sdd, t.kp0, t.sigma0, nullptr, t.cov0, nullptr, fm.f1.depth,
-                                     fm.f1.sdd, t.kp1, t.sigma1, t.cov1, &p->cov.cp, L, n_sel, cap, s));
+        if (c.frontend_nocov & MV_NOCOV_MATCH)   // (set 1: the model's own sigma, the depth variance the tracking gathered at kp1 — value row 7)
+            MV_TRY(mv_obs_cov_pair_nomatch_lanes(c.cov_model, c.cov_modifiers, fm.f0.depth, fm.f0.sdd, t.kp0, t.sigma0, nullptr, t.cov0, nullptr, fm.f1.depth,
+                                                 fm.f1.sdd, t.kp1, fm.f1.sdd ? t.vals + 7 * (size_t)L * cap : nullptr, c.cov_match_cov_default, t.cov1,
+                                                 &p->cov.cp, L, n_sel, cap, s));
+        else
+            MV_TRY(mv_obs_cov_pair_lanes(c.cov_model, c.cov_modifiers, fm.f0.depth, fm.f0.sdd, t.kp0, t.sigma0, nullptr, t.cov0, nullptr, fm.f1.depth,
+                                         fm.f1.sdd, t.kp1, t.sigma1, t.cov1, &p->cov.cp, L, n_sel, cap, s));
         MV_TRY(obs_filter());
     }
     if (c.mapping) {   // the mapping decision of this frame (MACVO.py:303-307) needs the observation count on the host
@@ -1956,11 +1985,11 @@ extern "C" int mv_frame_pipe_buffer(mvFramePipe* p, int which, int age, void** p
             *ptr = p->vol[f % p->n_volbuf]; *count = (size_t)c.pairs * p->n8 * p->n2t; return MV_OK;   // (n2t cells per slice: padded for a tiled fp16 volume with h8 % 4 != 0)
         case MV_FB_TOKENS: if (!front(1) || c.iters == 0) break; *ptr = p->tok[2 * (f % p->n_lk) + ((c.iters - 1) & 1)]; *count = (size_t)c.pairs * p->KK * p->n8; return MV_OK;
         case MV_FB_DISPARITY: if (!front(N_MAPS)) break; *ptr = p->maps[f % N_MAPS].disparity; *count = plane; return MV_OK;
-        case MV_FB_DISPARITY_COV: if (!front(N_MAPS)) break; *ptr = p->maps[f % N_MAPS].disparity_cov; *count = plane; return MV_OK;
+        case MV_FB_DISPARITY_COV: if (!front(N_MAPS) || !p->maps[0].disparity_cov) break; *ptr = p->maps[f % N_MAPS].disparity_cov; *count = plane; return MV_OK;
         case MV_FB_DEPTH: if (!front(N_MAPS)) break; *ptr = p->maps[f % N_MAPS].depth; *count = plane; return MV_OK;
-        case MV_FB_DEPTH_COV: if (!front(N_MAPS)) break; *ptr = p->maps[f % N_MAPS].depth_cov; *count = plane; return MV_OK;
+        case MV_FB_DEPTH_COV: if (!front(N_MAPS) || !p->maps[0].depth_cov) break; *ptr = p->maps[f % N_MAPS].depth_cov; *count = plane; return MV_OK;
         case MV_FB_MATCH_FLOW: if (!front(N_MAPS)) break; *ptr = p->maps[f % N_MAPS].match_flow; *count = 2 * plane; return MV_OK;
-        case MV_FB_MATCH_COV: if (!front(N_MAPS)) break; *ptr = p->maps[f % N_MAPS].match_cov; *count = 3 * plane; return MV_OK;
+        case MV_FB_MATCH_COV: if (!front(N_MAPS) || !p->maps[0].match_cov) break; *ptr = p->maps[f % N_MAPS].match_cov; *count = 3 * plane; return MV_OK;
         case MV_FB_CAND: if (!front(N_CAND)) break; *ptr = p->cand[f % N_CAND]; *count = plane; return MV_OK;
         case MV_FB_COUNT: if (!front(N_CAND)) break; *ptr = p->count[f % N_CAND]; *count = 4 * L; return MV_OK;
         case MV_FB_STATS: if (!front(N_CAND)) break; *ptr = p->stats[f % N_CAND]; *count = 4 * L; return MV_OK;

@@ -38,6 +38,30 @@ __global__ __launch_bounds__(256) void frontend_epilogue_kernel(
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += gridDim.x * blockDim.x) mv_epilogue_pixel(ea, plane, i);
 }
 
+// frontend_epilogue_kernel of a covariance-free (D = M = false) or mixed frontend (mv_epilogue_pixel_partial); the covariance outputs of a missing
+// side are null.  A kernel of its own: the full epilogue above is the code it always was.
+template <bool D, bool M>
+__global__ __launch_bounds__(256) void frontend_epilogue_partial_kernel(const float* __restrict__ flow, const float* __restrict__ logcov, int cov_is_log,
+                                                                        int plane, float bl_fx, float bl_fx_sq, float* __restrict__ disparity,
+                                                                        float* __restrict__ disparity_cov, float* __restrict__ depth,
+                                                                        float* __restrict__ depth_cov, uint8_t* __restrict__ bad_mask,
+                                                                        float* __restrict__ match_flow, float* __restrict__ match_cov) {
+    MV_CHAIN_KERNEL_PRIO();
+    const size_t lo = (size_t)blockIdx.y * plane;
+    flow += 4 * lo;
+    if (D || M) logcov += 4 * lo;
+    if (disparity) disparity += lo;
+    if (D && disparity_cov) disparity_cov += lo;
+    if (depth) depth += lo;
+    if (D && depth_cov) depth_cov += lo;
+    if (bad_mask) bad_mask += lo;
+    if (match_flow) match_flow += 2 * lo;
+    if (M && match_cov) match_cov += 3 * lo;
+    const mvEpiArgs ea{flow, logcov, cov_is_log, bl_fx, bl_fx_sq, disparity, D ? disparity_cov : nullptr, depth, D ? depth_cov : nullptr, match_flow,
+                       M ? match_cov : nullptr, bad_mask};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += gridDim.x * blockDim.x) mv_epilogue_pixel_partial<D, M>(ea, plane, i);
+}
+
 // Lane-batched: blockIdx.y = lane; every per-keypoint table is [lanes, ..., cap] with `cap` rows of capacity per lane of
 // which cnt.n[lane] are live (rows beyond are left untouched); every map is [lanes, ch, H, W].  lanes = 1, cap = N is the
 // plain single-frame call.
@@ -307,6 +331,7 @@ __global__ __launch_bounds__(256) void obs_filter_kernel(const uint8_t* __restri
 struct DrawArgs {
     const int32_t* count;      // [lanes, count_stride]: candidate count of lane l at count[l * count_stride]
     int count_stride;
+    float nomatch_c;           // backend_front_kernel<., ., ., true>: the covariance model's own match_cov_default (any PM; in what was padding)
     const uint32_t* state_in;  // [lanes, mvrp::MT_STRIDE]
     uint32_t* state_out;       // [lanes, mvrp::MT_STRIDE], != state_in
     int k;                     // num_point
@@ -325,7 +350,12 @@ struct DrawLds {
 // out_uv: the row is then not written back), live rows from cnt or — da.count given — from device memory, published to da.out_live; 4 RANDOM, every
 // workgroup draws the lane's 2 k words (kp_draw_dev.h) and workgroup (0, 0, lane) stores the advanced generator into the other state buffer, as PM = 2 does;
 // 5 GRID, computed from the row index.  Their scalars ride in pa.idx: [0] mask_width (4) | cols, sh, sw, mask (5).  Everything behind the row is PM 0-2's.
-template <int PM, int MODEL = MV_COV_MATCH, bool MODS = false>   // PM: where the permutation comes from: 0 device memory, 1 the kernel arguments, 2 drawn here
+// NOMATCH — the matcher gives no covariance (a.match_cov null): the set-1 wave writes the (-1, -1, -1) placeholder row of MACVO.py:263 to the sigma1 table
+// and hands the model (c, c, 0), c = da.nomatch_c, unclamped, with the depth variance read from a.sdd1 at the truncated kp1 (0 for a row out of bounds, as
+// the value table holds it) where the depth model gives one and the patch statistic where it does not (mvcov::match_cov_wave_vals<., ., true>).
+// NOMATCH exists for the row sources only (PM >= 3: ROWS / RANDOM / GRID): a permutation over a candidate list (PM 0-2) needs a CovAware selector, which
+// reads the match covariance itself — those forms are not instantiated and mv_backend_front refuses them.
+template <int PM, int MODEL = MV_COV_MATCH, bool MODS = false, bool NOMATCH = false>   // PM: where the permutation comes from: 0 device memory, 1 the kernel arguments, 2 drawn here
 __global__ __launch_bounds__(256) void backend_front_kernel(const int32_t* __restrict__ cand, size_t cand_lane_stride, const int64_t* __restrict__ perm,
                                                             PermArg pa, int cap, mvLaneCounts cnt, int64_t* out_uv, TrackArgs a, float fx, float fy,
                                                             float cx, float cy, float* pos_Tc, const float* depth_map0, const float* depth_map1,
@@ -407,6 +437,15 @@ __global__ __launch_bounds__(256) void backend_front_kernel(const int32_t* __res
             const int i0 = ok0 ? v0 * al.W + u0 : 0;
             u = (float)u0 + al.match_flow[i0];                                    // kp_track_one's u1, v1 and match sigma, re-derived
             v = (float)v0 + al.match_flow[plane + i0];
+            if constexpr (NOMATCH) {
+                if (lane == 0) { al.out_sigma1[3 * n] = -1.f; al.out_sigma1[3 * n + 1] = -1.f; al.out_sigma1[3 * n + 2] = -1.f; }
+                const bool inb = ok0 && (u < (float)(al.W - al.edge)) && (u > (float)al.edge) && (v < (float)(al.H - al.edge)) && (v > (float)al.edge);
+                const bool have_var = al.sdd1 != nullptr;
+                const float var = have_var && inb ? al.sdd1[(int)v * al.W + (int)u] : 0.f;   // kp_track_one's o[7]
+                const mvcov::CovSet S1{depth_map1, nullptr, nullptr, nullptr, nullptr, out_cov1, nullptr, nullptr};
+                mvcov::match_cov_wave_vals<MODEL, MODS, true>(S1, cp, cap, pl, n, u, v, da.nomatch_c, da.nomatch_c, 0.f, da.cov_mods, a.sdd1, var, have_var);
+                return;
+            }
             suu = al.match_cov ? al.match_cov[i0] : -1.f;
             svv = al.match_cov ? al.match_cov[plane + i0] : -1.f;
             suv = al.match_cov ? al.match_cov[2 * plane + i0] : -1.f;
@@ -423,9 +462,25 @@ __global__ __launch_bounds__(256) void backend_front_kernel(const int32_t* __res
 
 // one backend_front_kernel<PM, model, modifiers?> launch
 template <int PM, typename... Args>
-void launch_backend_front(int model, int32_t mods, dim3 grid, hipStream_t st, DrawArgs da, Args... args) {
+void launch_backend_front(int model, int32_t mods, bool nomatch, float nomatch_c, dim3 grid, hipStream_t st, DrawArgs da, Args... args) {
     const bool m = mods != 0;
     da.cov_mods = mods;
+    if constexpr (PM >= 3) if (nomatch) {   // a matcher without covariance: instantiations of their own, behind the ones that exist (row sources only)
+        da.nomatch_c = nomatch_c;
+        if (model == MV_COV_MATCH && !m)
+            hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_MATCH, false, true>), grid, dim3(256), 0, st, args..., da);
+        else if (model == MV_COV_MATCH)
+            hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_MATCH, true, true>), grid, dim3(256), 0, st, args..., da);
+        else if (model == MV_COV_GMM && !m)
+            hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_GMM, false, true>), grid, dim3(256), 0, st, args..., da);
+        else if (model == MV_COV_GMM)
+            hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_GMM, true, true>), grid, dim3(256), 0, st, args..., da);
+        else if (!m)
+            hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_NONE, false, true>), grid, dim3(256), 0, st, args..., da);
+        else
+            hipLaunchKernelGGL((backend_front_kernel<PM, MV_COV_NONE, true, true>), grid, dim3(256), 0, st, args..., da);
+        return;
+    }
     if (model == MV_COV_MATCH && !m)
         hipLaunchKernelGGL((backend_front_kernel<PM>), grid, dim3(256), 0, st, args..., da);
     else if (model == MV_COV_MATCH)
@@ -470,9 +525,24 @@ extern "C" int mv_frontend_epilogue_lanes(const float* flow, const float* logcov
                                           float bl_fx, float bl_fx_sq, float* disparity, float* disparity_cov,
                                           float* depth, float* depth_cov, uint8_t* bad_mask, float* match_flow,
                                           float* match_cov, int lanes, mvStream_t stream) {
-    MV_CHECK_ARG(flow && logcov && H > 0 && W > 0 && lanes >= 1 && lanes <= MV_MAX_LANES);
+    MV_CHECK_ARG(flow && H > 0 && W > 0 && lanes >= 1 && lanes <= MV_MAX_LANES);
     const int plane = H * W;
     const int blocks = min(mv_ceil_div(plane, 256), 2048);
+    // a frontend without the depth model's covariance (no disparity_cov, no depth_cov), without the matcher's (match_flow but no match_cov) or without
+    // both (logcov null: then no covariance output at all)
+    const bool no_d = !disparity_cov && !depth_cov, no_m = match_flow && !match_cov;
+    MV_CHECK_ARG(logcov || (no_d && !match_cov));
+    if (!logcov || no_d || no_m) {
+        const dim3 grid(blocks, lanes);
+#define MV_EPI_PARTIAL(D, M)                                                                                                                             \
+    hipLaunchKernelGGL((frontend_epilogue_partial_kernel<D, M>), grid, dim3(256), 0, (hipStream_t)stream, flow, logcov, cov_is_log, plane, bl_fx, bl_fx_sq, \
+                       disparity, disparity_cov, depth, depth_cov, bad_mask, match_flow, match_cov)
+        if (!logcov || (no_d && !match_cov)) MV_EPI_PARTIAL(false, false);
+        else if (no_d) MV_EPI_PARTIAL(false, true);
+        else MV_EPI_PARTIAL(true, false);
+#undef MV_EPI_PARTIAL
+        return mv_launch_status();
+    }
     hipLaunchKernelGGL(frontend_epilogue_kernel, dim3(blocks, lanes), dim3(256), 0, (hipStream_t)stream, flow, logcov,
                        cov_is_log, plane, bl_fx, bl_fx_sq, disparity, disparity_cov, depth, depth_cov, bad_mask,
                        match_flow, match_cov);
@@ -553,6 +623,9 @@ int mv_backend_front(const mvKpSource& src, int lanes, int cap, const mvFrontMap
     if (kind >= MV_KPSRC_ROWS) MV_CHECK_ARG(src.mask_width >= 0);
     MV_CHECK_ARG(cv.model >= MV_COV_MATCH && cv.model <= MV_COV_NONE && mv_cov_modifiers_ok(cv.modifiers));
     MV_CHECK_ARG(cv.model != MV_COV_GMM || (m.f0.sdd && m.f1.sdd));
+    const bool nomatch = (cv.nocov & MV_NOCOV_MATCH) != 0;
+    MV_CHECK_ARG(!nomatch || (m.match_cov == nullptr && kind >= MV_KPSRC_ROWS));   // (no candidate list without match covariance: CovAware selectors read it)
+    MV_CHECK_ARG(!(cv.nocov & MV_NOCOV_DEPTH) || (cv.model != MV_COV_GMM && !m.f0.sdd && !m.f1.sdd && !m.f0.sdisp && !m.f1.sdisp));
     MV_CHECK_ARG(cp.H > 0 && cp.W > 0 && cp.kernel_size >= 1 && (cp.kernel_size & 1) && cp.use_patch_var);
     if (cp.kernel_size > mvcov::MAX_K || (kind == MV_KPSRC_DRAW && num_point > mvrp::MAX_HEAD)) return MV_ERR_UNSUPPORTED;
     mvLaneCounts c{};
@@ -593,7 +666,7 @@ int mv_backend_front(const mvKpSource& src, int lanes, int cap, const mvFrontMap
         cand = src.cand;
         cand_stride = src.cand_lane_stride;
         n_max = num_point > 0 ? num_point : 1;   // (num_point == 0: workgroup (0, 0, l) still advances the generator)
-        da = DrawArgs{src.n_live_dev, src.n_live_stride, src.state_in, src.state_out, num_point, 0, src.out_perm, src.out_live};
+        da = DrawArgs{src.n_live_dev, src.n_live_stride, 0.f, src.state_in, src.state_out, num_point, 0, src.out_perm, src.out_live};
         pm = 2;
     } else if (kind == MV_KPSRC_ROWS) {
         MV_CHECK_ARG(src.rows && (src.n_live || (src.n_live_dev && src.n_live_stride >= 1)));
@@ -629,7 +702,7 @@ int mv_backend_front(const mvKpSource& src, int lanes, int cap, const mvFrontMap
     if (pm >= 4)
         for (int l = 0; l < lanes; ++l) c.n[l] = n_max;
     const dim3 grid(mv_ceil_div(n_max, 4), 2, lanes);
-    launch_backend_front_pm(pm, cv.model, cv.modifiers, grid, (hipStream_t)stream, da, cand, cand_stride, rows, pa, cap, c, t.kp0_uv, ta, cp.fx, cp.fy, cp.cx,
+    launch_backend_front_pm(pm, cv.model, cv.modifiers, nomatch, cv.model_match_cov_default, grid, (hipStream_t)stream, da, cand, cand_stride, rows, pa, cap, c, t.kp0_uv, ta, cp.fx, cp.fy, cp.cx,
                             cp.cy, t.pos_Tc, m.f0.depth, m.f1.depth, t.cov0, t.cov1, cp);
     return mv_launch_status();
 }

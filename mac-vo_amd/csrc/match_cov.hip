@@ -42,6 +42,29 @@ __global__ __launch_bounds__(256) void obs_cov_kernel(CovSet s0, CovSet s1, mvMa
     match_cov_wave<MODEL, MODS>(blockIdx.y ? s1 : s0, p, cap, pl, n, mods, blockIdx.y ? depth_cov_map1 : depth_cov_map0);
 }
 
+// the pair launch of a frame whose matcher gives no covariance (mv_obs_cov_pair_nomatch_lanes): set 0 as ever, set 1 = match_cov_wave_nomatch.
+// Instantiations of their own: match_cov_kernel / obs_cov_kernel stay as they are.
+template <int MODEL, bool MODS>
+__global__ __launch_bounds__(256) void obs_cov_nomatch_kernel(CovSet s0, CovSet s1, mvMatchCovParams p, int cap, mvLaneCounts cnt, int32_t mods,
+                                                              const float* depth_cov_map0, const float* depth_cov_map1, float c1) {
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int pl = blockIdx.z;
+    if (n >= cnt.n[pl]) return;
+    if (blockIdx.y == 0)
+        match_cov_wave<MODEL, MODS>(s0, p, cap, pl, n, mods, depth_cov_map0);
+    else
+        match_cov_wave_nomatch<MODEL, MODS>(s1, p, cap, pl, n, c1, mods, depth_cov_map1);
+}
+
+template <int MODEL>
+void launch_nomatch(bool m, dim3 grid, hipStream_t st, const CovSet& s0, const CovSet& s1, const mvMatchCovParams& p, int cap, const mvLaneCounts& c,
+                    int32_t mods, const float* dcm0, const float* dcm1, float c1) {
+    if (m)
+        hipLaunchKernelGGL((obs_cov_nomatch_kernel<MODEL, true>), grid, dim3(256), 0, st, s0, s1, p, cap, c, mods, dcm0, dcm1, c1);
+    else
+        hipLaunchKernelGGL((obs_cov_nomatch_kernel<MODEL, false>), grid, dim3(256), 0, st, s0, s1, p, cap, c, mods, dcm0, dcm1, c1);
+}
+
 int launch_obs_cov(int model, int32_t mods, dim3 grid, hipStream_t st, const CovSet& s0, const CovSet& s1, const mvMatchCovParams& p, int cap,
                    const mvLaneCounts& c, const float* dcm0, const float* dcm1) {
     const bool m = mods != 0;
@@ -158,4 +181,38 @@ extern "C" int mv_obs_cov_pair_lanes(int model, int32_t modifiers, const float* 
     const CovSet s1{depth_map1, kp_uv1, flow_cov1, nullptr, nullptr, out_cov1, nullptr, nullptr};
     return launch_obs_cov(model, modifiers, dim3(mv_ceil_div(n_max, 4), 2, lanes), (hipStream_t)stream, s0, s1, p, cap, c, depth_cov_map0,
                           depth_cov_map1);
+}
+
+extern "C" int mv_obs_cov_pair_nomatch_lanes(int model, int32_t modifiers, const float* depth_map0, const float* depth_cov_map0, const float* kp_uv0,
+                                             float* flow_cov0, const double* rot0, double* out_cov0, double* out_cov_rot0, const float* depth_map1,
+                                             const float* depth_cov_map1, const float* kp_uv1, const float* depth_cov1, float model_match_cov_default,
+                                             double* out_cov1, const mvMatchCovParams* params, int lanes, const int32_t* n_live, int cap,
+                                             mvStream_t stream) {
+    MV_CHECK_ARG(model >= MV_COV_MATCH && model <= MV_COV_NONE && mv_cov_modifiers_ok(modifiers));
+    MV_CHECK_ARG(params && lanes >= 1 && lanes <= MV_MAX_LANES && n_live && cap >= 0);
+    mvLaneCounts c{};
+    int n_max = 0;
+    for (int l = 0; l < lanes; ++l) {
+        MV_CHECK_ARG(n_live[l] >= 0 && n_live[l] <= cap);
+        c.n[l] = n_live[l];
+        n_max = n_live[l] > n_max ? n_live[l] : n_max;
+    }
+    if (n_max == 0) return MV_OK;
+    MV_CHECK_ARG(depth_map0 && kp_uv0 && flow_cov0 && out_cov0 && depth_map1 && kp_uv1 && out_cov1);
+    MV_CHECK_ARG(model != MV_COV_GMM || (depth_cov_map0 && depth_cov_map1 && depth_cov1));   // the mixture model needs the depth model's variance
+    const mvMatchCovParams p = *params;
+    MV_CHECK_ARG(p.H > 0 && p.W > 0 && p.kernel_size >= 1 && (p.kernel_size & 1) && p.use_patch_var);
+    if (p.kernel_size > MAX_K) return MV_ERR_UNSUPPORTED;
+    MV_CHECK_ARG(!out_cov_rot0 || rot0);
+    const CovSet s0{depth_map0, kp_uv0, flow_cov0, nullptr, rot0, out_cov0, out_cov_rot0, nullptr};
+    const CovSet s1{depth_map1, kp_uv1, nullptr, depth_cov1, nullptr, out_cov1, nullptr, nullptr};
+    const dim3 grid(mv_ceil_div(n_max, 4), 2, lanes);
+    const bool m = modifiers != 0;
+    if (model == MV_COV_MATCH)
+        launch_nomatch<MV_COV_MATCH>(m, grid, (hipStream_t)stream, s0, s1, p, cap, c, modifiers, depth_cov_map0, depth_cov_map1, model_match_cov_default);
+    else if (model == MV_COV_GMM)
+        launch_nomatch<MV_COV_GMM>(m, grid, (hipStream_t)stream, s0, s1, p, cap, c, modifiers, depth_cov_map0, depth_cov_map1, model_match_cov_default);
+    else
+        launch_nomatch<MV_COV_NONE>(m, grid, (hipStream_t)stream, s0, s1, p, cap, c, modifiers, depth_cov_map0, depth_cov_map1, model_match_cov_default);
+    return mv_launch_status();
 }

@@ -77,10 +77,15 @@ __device__ __forceinline__ void store_cov(double c[9], int32_t mods, const doubl
 // (u, v) = the keypoint, (suu, svv, suv) = its match covariance as the tables hold them: match_cov_wave reads them from S.kp_uv / S.flow_cov,
 // the fused backend kernel hands over the values it has just computed (another wave may still be writing those tables).
 // MODEL = MV_COV_* and MODS (a modifier chain `mods` is applied) select the model; <MV_COV_MATCH, false> is MatchCovariance as it always was.
-template <int MODEL = MV_COV_MATCH, bool MODS = false>
+// NOMATCH — the keypoint set has no match covariance (a matcher with provide_cov = False: `estimate(..., flow_cov=None)`, Project2to3.py:128-135,
+// 162-172, 211-218, 254-255): (suu, svv, suv) = the model's own (match_cov_default, match_cov_default, 0), NOT clamped by min_flow_cov; the sigma table
+// S.flow_cov is left as the caller filled it (the -1 placeholders of MACVO.py:263); the depth variance is `var_given` (the depth-variance map at the
+// keypoint, as the caller gathered it) when `have_var`, the patch statistic when the depth model gives no variance either.  p.use_patch_var is not read.
+template <int MODEL = MV_COV_MATCH, bool MODS = false, bool NOMATCH = false>
 __device__ __forceinline__ void match_cov_wave_vals(const CovSet& S, const mvMatchCovParams& p, int cap, int pl, int n, float u, float v,
                                                     float suu, float svv, float suv, int32_t mods = 0,
-                                                    const float* depth_cov_map_all = nullptr /* [lanes, H, W] dense depth variance: MV_COV_GMM */) {
+                                                    const float* depth_cov_map_all = nullptr /* [lanes, H, W] dense depth variance: MV_COV_GMM */,
+                                                    float var_given = 0.f, bool have_var = false /* NOMATCH only */) {
     const int lane = threadIdx.x & 63;
     const size_t ln = (size_t)pl * cap;
     const float* __restrict__ depth_map = S.depth_map + (size_t)pl * p.H * p.W;
@@ -93,8 +98,10 @@ __device__ __forceinline__ void match_cov_wave_vals(const CovSet& S, const mvMat
 
     if constexpr (MODEL == MV_COV_NONE) {   // NoCovariance: identity, the caller's flow_cov left as it is (the sigma rows are still written)
         if (lane == 0) {
-            flow_cov[3 * n] = suu;
-            flow_cov[3 * n + 1] = svv;
+            if constexpr (!NOMATCH) {
+                flow_cov[3 * n] = suu;
+                flow_cov[3 * n + 1] = svv;
+            }
             double c[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
             store_cov<MODS>(c, mods, rot, out_cov, out_cov_rot, out_stats, n, __builtin_nanf(""), __builtin_nanf(""));
         }
@@ -103,12 +110,16 @@ __device__ __forceinline__ void match_cov_wave_vals(const CovSet& S, const mvMat
     const float* __restrict__ depth_cov_map = MODEL == MV_COV_GMM ? depth_cov_map_all + (size_t)pl * p.H * p.W : nullptr;
 
     const int iu = (int)u, iv = (int)v;  // .long(): truncation toward zero
-    suu = clamp_min_nanprop(suu, p.min_flow_cov_sq);
-    svv = clamp_min_nanprop(svv, p.min_flow_cov_sq);
-    if (lane == 0) {  // the reference clamps the caller's tensor in place
-        flow_cov[3 * n] = suu;
-        flow_cov[3 * n + 1] = svv;
+    if constexpr (!NOMATCH) {
+        suu = clamp_min_nanprop(suu, p.min_flow_cov_sq);
+        svv = clamp_min_nanprop(svv, p.min_flow_cov_sq);
+        if (lane == 0) {  // the reference clamps the caller's tensor in place
+            flow_cov[3 * n] = suu;
+            flow_cov[3 * n + 1] = svv;
+        }
     }
+    bool patch_var;
+    if constexpr (NOMATCH) patch_var = !have_var; else patch_var = p.use_patch_var;
 
     // Sigma^-1 (torch.pinverse == inverse for a non-singular 2x2) and the 1/(2*pi*sqrt(det)) factor
     const float det = suu * svv - suv * suv;
@@ -161,7 +172,8 @@ __device__ __forceinline__ void match_cov_wave_vals(const CovSet& S, const mvMat
         }
         mu = wave_sum(mu);
         e2 = wave_sum(e2);
-        var = p.use_patch_var ? (e2 - mu * mu) / 2.f : depth_cov[n];   // no min_depth_cov clamp in this model
+        if constexpr (NOMATCH) var = patch_var ? (e2 - mu * mu) / 2.f : var_given;
+        else var = patch_var ? (e2 - mu * mu) / 2.f : depth_cov[n];   // no min_depth_cov clamp in this model
     } else {
 #pragma unroll
         for (int r = 0; r < MAX_TAPS_PER_LANE; ++r) {
@@ -170,7 +182,7 @@ __device__ __forceinline__ void match_cov_wave_vals(const CovSet& S, const mvMat
         }
         mu = wave_sum(mu);
 
-        if (p.use_patch_var) {
+        if (patch_var) {
             var = 0.f;
 #pragma unroll
             for (int r = 0; r < MAX_TAPS_PER_LANE; ++r) {
@@ -179,7 +191,7 @@ __device__ __forceinline__ void match_cov_wave_vals(const CovSet& S, const mvMat
             }
             var = wave_sum(var);
         } else {
-            var = depth_cov[n];
+            if constexpr (NOMATCH) var = var_given; else var = depth_cov[n];
         }
         var = clamp_min_nanprop(var, p.min_depth_cov);
     }
@@ -232,6 +244,18 @@ __device__ __forceinline__ void match_cov_wave(const CovSet& S, const mvMatchCov
     const float* __restrict__ flow_cov = S.flow_cov + 3 * ln;
     match_cov_wave_vals<MODEL, MODS>(S, p, cap, pl, n, kp_uv[2 * n], kp_uv[2 * n + 1], flow_cov[3 * n], flow_cov[3 * n + 1], flow_cov[3 * n + 2],
                                      mods, depth_cov_map);
+}
+
+// match_cov_wave of a keypoint set without match covariance (NOMATCH above): sigma = (c, c, 0), the depth variance from the per-keypoint table
+// S.depth_cov where the set has one (the caller's gather of the depth-variance map at the keypoint), S.flow_cov neither read nor written.
+template <int MODEL, bool MODS>
+__device__ __forceinline__ void match_cov_wave_nomatch(const CovSet& S, const mvMatchCovParams& p, int cap, int pl, int n, float c, int32_t mods,
+                                                       const float* depth_cov_map) {
+    const size_t ln = (size_t)pl * cap;
+    const float* __restrict__ kp_uv = S.kp_uv + 2 * ln;
+    const bool have = S.depth_cov != nullptr;
+    const float var = have ? S.depth_cov[ln + n] : 0.f;
+    match_cov_wave_vals<MODEL, MODS, true>(S, p, cap, pl, n, kp_uv[2 * n], kp_uv[2 * n + 1], c, c, 0.f, mods, depth_cov_map, var, have);
 }
 
 }  // namespace mvcov

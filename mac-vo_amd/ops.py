@@ -274,37 +274,54 @@ def corr_volume_out16(f1: torch.Tensor, f2: torch.Tensor, out: torch.Tensor | No
 # ------------------------------------------------------------------------------------------- A8 / A2
 @dataclass
 class FrontendMaps:
-    """The planes of IStereoDepth.Output / IMatcher.Output, each ``[1, C, H, W]`` float32 on the GPU."""
+    """The planes of IStereoDepth.Output / IMatcher.Output, each ``[1, C, H, W]`` float32 on the GPU.  ``depth_cov`` / ``disparity_cov``
+    are None for a depth model without covariance, ``flow_cov`` for a matcher without (``provide_cov``, Frontend.py:137-139)."""
     depth: torch.Tensor
-    depth_cov: torch.Tensor
+    depth_cov: torch.Tensor | None
     disparity: torch.Tensor
-    disparity_cov: torch.Tensor
+    disparity_cov: torch.Tensor | None
     bad_mask: torch.Tensor | None
     flow: torch.Tensor | None
     flow_cov: torch.Tensor | None
 
 
-def frontend_epilogue(flow: torch.Tensor, cov: torch.Tensor, baseline: float, fx: float, cov_is_log: bool = True,
-                      enforce_positive_disparity: bool = False, want_match: bool = True) -> FrontendMaps:
+def frontend_cov_flags(frontend_cov) -> "tuple[bool, bool]":
+    """``(depth model provides covariance, matcher provides covariance)`` as two bools (``IFrontend.provide_cov``)."""
+    d, m = frontend_cov
+    return bool(d), bool(m)
+
+
+def frontend_epilogue(flow: torch.Tensor, cov: torch.Tensor | None, baseline: float, fx: float, cov_is_log: bool = True,
+                      enforce_positive_disparity: bool = False, want_match: bool = True, provide_cov=(True, True)) -> FrontendMaps:
     """Network output ``flow, logcov [2,2,H,W]`` -> depth / match records (Frontend.py:183-200, flownet.py:44,
     StereoDepth.py:270-282, Matching.py:28-40) in one launch.  ``baseline``/``fx`` are Python floats exactly as
-    ``frame.frame_baseline`` / ``frame.fx`` are in the reference."""
+    ``frame.frame_baseline`` / ``frame.fx`` are in the reference.  ``provide_cov = (depth, match)``: a side without covariance
+    (FlowFormerDepth / FlowFormerMatcher) gets no covariance planes (None in the result) and its sample of ``cov`` is not read;
+    ``cov`` may be None when neither side has one.  The other planes are the same bits in every form."""
     lib = L.load()
+    pd, pm = frontend_cov_flags(provide_cov)
+    pm = pm and want_match
     flow = _req(flow, torch.float32, "flow")
-    cov = _req(cov, torch.float32, "cov")
-    assert flow.shape == cov.shape and flow.shape[1] == 2
+    if cov is None:
+        if pd or pm:
+            raise L.MacvoHipError("frontend_epilogue: cov is None but provide_cov asks for a covariance")
+    else:
+        cov = _req(cov, torch.float32, "cov")
+        assert flow.shape == cov.shape
+    assert flow.shape[1] == 2
     assert flow.shape[0] == 2 or (flow.shape[0] == 1 and not want_match), "sample 0 = stereo pair, sample 1 = temporal pair"
     _, _, H, W = flow.shape
     dev = flow.device
     mk = lambda c: torch.empty((1, c, H, W), dtype=torch.float32, device=dev)  # noqa: E731
-    disparity, disparity_cov, depth, depth_cov = mk(1), mk(1), mk(1), mk(1)
+    disparity, depth = mk(1), mk(1)
+    disparity_cov, depth_cov = (mk(1), mk(1)) if pd else (None, None)
     bad = torch.empty((1, 1, H, W), dtype=torch.bool, device=dev) if enforce_positive_disparity else None
     mflow = mk(2) if want_match else None
-    mcov = mk(3) if want_match else None
+    mcov = mk(3) if pm else None
     bl_fx = float(baseline) * float(fx)            # python double product, rounded once to fp32 by ctypes
-    L.check(lib.mv_frontend_epilogue(flow.data_ptr(), cov.data_ptr(), int(cov_is_log), H, W, bl_fx, bl_fx ** 2,
-                                     disparity.data_ptr(), disparity_cov.data_ptr(), depth.data_ptr(),
-                                     depth_cov.data_ptr(), _ptr(bad), _ptr(mflow), _ptr(mcov), _stream()),
+    L.check(lib.mv_frontend_epilogue(flow.data_ptr(), _ptr(cov) if (pd or pm) else None, int(cov_is_log), H, W, bl_fx, bl_fx ** 2,
+                                     disparity.data_ptr(), _ptr(disparity_cov), depth.data_ptr(),
+                                     _ptr(depth_cov), _ptr(bad), _ptr(mflow), _ptr(mcov), _stream()),
             "mv_frontend_epilogue")
     return FrontendMaps(depth, depth_cov, disparity, disparity_cov, bad, mflow, mcov)
 
@@ -756,19 +773,24 @@ def obs_cov(model: str, depth_map: torch.Tensor, kp_uv: torch.Tensor, flow_cov: 
 
 
 def obs_cov_pair(model: str, depth0: torch.Tensor, kp0_uv: torch.Tensor, sigma0: torch.Tensor, depth1: torch.Tensor,
-                 kp1_uv: torch.Tensor, sigma1: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
+                 kp1_uv: torch.Tensor, sigma1: torch.Tensor | None, fx: float, fy: float, cx: float, cy: float,
                  depth_cov_map0: torch.Tensor | None = None, depth_cov_map1: torch.Tensor | None = None, modifiers=(),
                  rot: torch.Tensor | None = None, kernel_size: int = 31, min_flow_cov: float = 0.25, min_depth_cov: float = 0.05,
-                 n_live: "list[int] | None" = None):
+                 n_live: "list[int] | None" = None, no_match_cov: bool = False, match_cov_default: float = 0.25,
+                 depth_cov1: torch.Tensor | None = None):
     """Both ObsCovModel calls of a frame (MACVO.py:241-242) with the model / modifiers of :func:`obs_cov`, one launch
     (``mv_obs_cov_pair_lanes``).  Lane-batched when the inputs carry a leading lane axis: depth ``[L, H, W]``, keypoint
     tables ``[L, cap, .]`` and ``n_live`` (default: ``cap`` rows per lane); ``rot`` is then ``[L, 3, 3]``.
+    ``no_match_cov`` — the matcher gives no covariance (``mv_obs_cov_pair_nomatch_lanes``): the second call is the model with
+    ``flow_cov=None``, i.e. sigma ``(c, c, 0)`` with ``c = match_cov_default`` (the MODEL's own), unclamped, and the depth variance
+    ``depth_cov1 [.., cap]`` (the depth-variance map gathered at kp1: ``tracked.vals[7]``) where the depth model has one, the patch
+    statistic where it is None; ``sigma1`` is neither read nor written.
     -> (cov0, cov0_world | None, cov1)."""
     lib = L.load()
     m, chain = _cov_model(model), cov_modifier_chain(modifiers)
     d0, d1 = _req(depth0, torch.float32, "depth0"), _req(depth1, torch.float32, "depth1")
     k0, k1 = _req(kp0_uv, torch.float32, "kp0_uv"), _req(kp1_uv, torch.float32, "kp1_uv")
-    for t_, nm in ((sigma0, "sigma0"), (sigma1, "sigma1")):
+    for t_, nm in ((sigma0, "sigma0"),) + (() if no_match_cov else ((sigma1, "sigma1"),)):
         if t_.dtype != torch.float32 or not t_.is_contiguous() or not t_.is_cuda:
             raise L.MacvoHipError(f"obs_cov_pair: {nm} must be a contiguous float32 GPU tensor (clamped in place)")
     if m == L.MV_COV_GMM and (depth_cov_map0 is None or depth_cov_map1 is None):
@@ -788,6 +810,15 @@ def obs_cov_pair(model: str, depth0: torch.Tensor, kp0_uv: torch.Tensor, sigma0:
     c0w = torch.empty(lead + (3, 3), dtype=torch.float64, device=dev) if r is not None else None
     p = L.mvMatchCovParams(H, W, kernel_size, 1, fx, fy, cx, cy, min_flow_cov ** 2, min_depth_cov)
     nl = (C.c_int32 * lanes)(*n_live)
+    if no_match_cov:
+        if m == L.MV_COV_GMM and depth_cov1 is None:
+            raise L.MacvoHipError("obs_cov_pair: the gaussian-mixture model without match covariance needs depth_cov1 (the depth model's variance at kp1)")
+        dc1 = None if depth_cov1 is None else _req(depth_cov1, torch.float32, "depth_cov1")
+        assert dc1 is None or dc1.shape == k1.shape[:-1]
+        L.check(lib.mv_obs_cov_pair_nomatch_lanes(m, chain, d0.data_ptr(), _ptr(dcm0), k0.data_ptr(), sigma0.data_ptr(), _ptr(r), c0.data_ptr(),
+                                                  _ptr(c0w), d1.data_ptr(), _ptr(dcm1), k1.data_ptr(), _ptr(dc1), float(match_cov_default),
+                                                  c1.data_ptr(), C.byref(p), lanes, nl, cap, _stream()), "mv_obs_cov_pair_nomatch_lanes")
+        return c0, c0w, c1
     L.check(lib.mv_obs_cov_pair_lanes(m, chain, d0.data_ptr(), _ptr(dcm0), k0.data_ptr(), sigma0.data_ptr(), _ptr(r), c0.data_ptr(),
                                       _ptr(c0w), d1.data_ptr(), _ptr(dcm1), k1.data_ptr(), sigma1.data_ptr(), c1.data_ptr(), C.byref(p),
                                       lanes, nl, cap, _stream()), "mv_obs_cov_pair_lanes")

@@ -117,6 +117,47 @@ class HotPathConfig:
     # pose of frame t-1) | "tartan" = TartanMotionNet (prior = pose of frame t-1 @ Exp(PoseNet motion); HotPath's `pose_net` supplies the
     # network).  motion_config_fields() maps a reference `motion` block onto this field.
     motion_model: str = "static"
+    # which covariances the frontend provides, (depth model, matcher) = IFrontend.provide_cov (Frontend.py:137-139).  (True, True) = FlowFormerCov;
+    # (False, False) = FrontendCompose(FlowFormerDepth, FlowFormerMatcher), the paper's "no covariance at all" baseline (Ablation_Study/
+    # TartanAirv2_Vanilla.yaml); the mixed composes set one.  A missing side has no covariance input, no covariance map, -1 placeholders in the stored
+    # rows (MACVO.py:253-263); whatever would read it is refused (check_frontend_cov).  frontend_config_fields() maps a `frontend` block onto it.
+    frontend_cov: "tuple[bool, bool]" = (True, True)
+    # the covariance MODEL's own `match_cov_default` (cov.obs args; Project2to3.py:133,216): sigma of the second observation when the matcher gives no
+    # covariance.  Not `match_cov_default` above (Odometry.args), which stays the sigma of the first observation and of map points (MACVO.py:228,322).
+    cov_match_cov_default: float = 0.25
+
+
+def check_frontend_cov(cfg: "HotPathConfig") -> None:
+    """Configuration-time refusals of a frontend without covariances (the frame driver's check_config applies the same rules).  The reference asserts
+    on ``depth.cov`` in CovAwareSelector / MappingPointSelector / GaussianMixtureCovariance, reads ``match.cov`` in both CovAware selectors, and
+    builds the ``reproj`` / ``disp`` weights by inverting the -1 placeholders of ``pixel2_uv_cov`` / ``pixel2_disp_cov`` (Graphs.py:54-55,97-103,133)."""
+    fc = cfg.frontend_cov
+    if not (isinstance(fc, (tuple, list)) and len(fc) == 2):
+        raise ValueError(f"frontend_cov must be (depth provides covariance, matcher provides covariance), not {fc!r}")
+    d, m = bool(fc[0]), bool(fc[1])
+    no_d = "the depth model provides no covariance (frontend_cov[0] is False: no depth / disparity variance)"
+    no_m = "the matcher provides no covariance (frontend_cov[1] is False: no match covariance)"
+    if not d:
+        if cfg.selector == "full":
+            raise ValueError(f"selector 'full' (CovAwareSelector) reads depth.cov, but {no_d}")
+        if cfg.mapping:
+            raise ValueError(f"mapping=True (MappingPointSelector) reads depth.cov, but {no_d}")
+        if cfg.cov_model == "gmm":
+            raise ValueError(f"cov_model 'gmm' (GaussianMixtureCovariance) reads depth.cov, but {no_d}")
+        if cfg.graph_type == "disp":
+            raise ValueError(f"graph_type 'disp' weighs its residual by pixel2_disp_cov, but {no_d}")
+    if not m:
+        if cfg.selector in ("nodepth", "full"):
+            raise ValueError(f"selector {cfg.selector!r} (CovAwareSelector{'_NoDepth' if cfg.selector == 'nodepth' else ''}) reads match.cov, but {no_m}")
+        if cfg.graph_type in ("reproj", "disp"):
+            raise ValueError(f"graph_type {cfg.graph_type!r} weighs its residual by pixel2_uv_cov, but {no_m}")
+        if cfg.cov_model != "none" and not cfg.cov_match_cov_default > 0:
+            raise ValueError(f"cov_match_cov_default must be > 0 (it is the second observation's sigma when {no_m})")
+
+
+def _nocov_mask(cfg: "HotPathConfig") -> int:
+    d, m = ops.frontend_cov_flags(cfg.frontend_cov)
+    return (0 if d else ops.L.MV_NOCOV_DEPTH) | (0 if m else ops.L.MV_NOCOV_MATCH)
 
 
 _COV_TYPES = {"MatchCovariance": "match", "GaussianMixtureCovariance": "gmm", "NoCovariance": "none",
@@ -143,9 +184,10 @@ def cov_config_fields(obs) -> dict:
     out = {"cov_model": _COV_TYPES[t], "cov_modifiers": tuple(reversed(mods))}
     args = _ns_get(obs, "args")
     if args is not None and _COV_TYPES[t] != "none":
-        # (not the model's match_cov_default: it only stands in for an absent flow_cov, which the pipe never passes; the
-        # constant kp0 / map-point sigma is Odometry.args.match_cov_default, MACVO.py:228,322)
-        for k, f in (("kernel_size", "cov_kernel_size"), ("min_flow_cov", "min_flow_cov"), ("min_depth_cov", "min_depth_cov")):
+        # (the model's own match_cov_default stands in for an absent flow_cov — a matcher without covariance, frontend_cov[1] False — and goes to
+        # cov_match_cov_default; the constant kp0 / map-point sigma is Odometry.args.match_cov_default, MACVO.py:228,322)
+        for k, f in (("kernel_size", "cov_kernel_size"), ("min_flow_cov", "min_flow_cov"), ("min_depth_cov", "min_depth_cov"),
+                     ("match_cov_default", "cov_match_cov_default")):
             try:
                 out[f] = _ns_get(args, k)
             except (KeyError, AttributeError):
@@ -192,6 +234,99 @@ def selector_config_fields(block) -> dict:
         except (KeyError, AttributeError, TypeError):
             pass
     return out
+
+
+_DEPTH_TYPES = {"FlowFormerCovDepth": True, "HIP_FlowFormerCovDepth": True, "FlowFormerDepth": False, "HIP_FlowFormerDepth": False}
+_MATCH_TYPES = {"FlowFormerCovMatcher": True, "HIP_FlowFormerCovMatcher": True, "FlowFormerMatcher": False, "HIP_FlowFormerMatcher": False}
+_JOINT_FRONTENDS = ("FlowFormerCovFrontend", "CUDAGraph_FlowFormerCovFrontend", "HIP_FlowFormerCovFrontend", "HIP_CUDAGraph_FlowFormerCovFrontend")
+
+
+def frontend_config_fields(block) -> dict:
+    """A reference ``frontend`` block (``{type, args}`` as a dict or SimpleNamespace) -> ``{"frontend_cov": (depth, match)}`` for
+    :class:`HotPathConfig` = the frontend's ``provide_cov``: the joint FlowFormerCov frontends give both covariances, a ``FrontendCompose`` what its
+    ``depth`` (``FlowFormerCovDepth`` / ``FlowFormerDepth``) and ``match`` (``FlowFormerCovMatcher`` / ``FlowFormerMatcher``) modules give.  The
+    ground-truth and TartanVO modules have no HIP form."""
+    t = _ns_get(block, "type")
+    if t in _JOINT_FRONTENDS:
+        return {"frontend_cov": (True, True)}
+    if t != "FrontendCompose":
+        raise ValueError(f"frontend {t!r} has no HIP form (one of {sorted(_JOINT_FRONTENDS)} or a FrontendCompose of "
+                         f"{sorted(_DEPTH_TYPES)} x {sorted(_MATCH_TYPES)})")
+    args = _ns_get(block, "args")
+    dt, mt = _ns_get(_ns_get(args, "depth"), "type"), _ns_get(_ns_get(args, "match"), "type")
+    if dt not in _DEPTH_TYPES:
+        raise ValueError(f"depth model {dt!r} has no HIP form (one of {sorted(_DEPTH_TYPES)})")
+    if mt not in _MATCH_TYPES:
+        raise ValueError(f"matcher {mt!r} has no HIP form (one of {sorted(_MATCH_TYPES)})")
+    return {"frontend_cov": (_DEPTH_TYPES[dt], _MATCH_TYPES[mt])}
+
+
+_FILTER_TYPES = {"CovarianceSanityFilter": ops.FILTER_COV_SANITY, "SimpleDepthFilter": ops.FILTER_SIMPLE_DEPTH,
+                 "LikelyFrontOfCamFilter": ops.FILTER_FRONT_OF_CAM, "IdentityFilter": 0}
+
+
+def filter_config_fields(block) -> dict:
+    """A reference ``outlier`` block (``{type, args}``; ``FilterCompose`` nests its filters in ``args.filter_args``) -> ``{"filters", and for a
+    SimpleDepthFilter "filter_min_depth" and "max_depth"}``.  The filters are a conjunction, so their order does not matter.  The pipe has ONE
+    ``max_depth`` (the selector's bound and this filter's): :func:`hot_path_config` reconciles the two."""
+    out = {"filters": 0}
+
+    def one(b):
+        t = _ns_get(b, "type")
+        if t == "FilterCompose":
+            for sub in _ns_get(_ns_get(b, "args"), "filter_args"):
+                one(sub)
+            return
+        if t not in _FILTER_TYPES:
+            raise ValueError(f"observation filter {t!r} has no HIP form (one of {sorted(_FILTER_TYPES)} or a FilterCompose of them)")
+        out["filters"] |= _FILTER_TYPES[t]
+        if t == "SimpleDepthFilter":
+            args = _ns_get(b, "args")
+            for k, f in (("min_depth", "filter_min_depth"), ("max_depth", "max_depth")):
+                v = _ns_get(args, k)
+                if f in out and out[f] != v:
+                    raise ValueError(f"two SimpleDepthFilters with different {k} ({out[f]!r}, {v!r}): the pipe has one")
+                out[f] = v
+    one(block)
+    return out
+
+
+def hot_path_config(odometry, **overrides) -> HotPathConfig:
+    """The ``Odometry`` block of a reference experiment YAML (dict or SimpleNamespace, e.g. ``load_config(...)[0].Odometry``) ->
+    :class:`HotPathConfig`: ``cov.obs``, ``keypoint``, ``motion``, ``frontend`` and ``outlier`` through their mappers, ``mappoint`` (the
+    MappingPointSelector's bounds), ``optimizer.args.graph_type`` and ``args.{num_point, edgewidth, match_cov_default, mapping}``.  The optimizer's
+    ``autodiff`` / ``vectorize`` / ``parallel`` / ``device`` are ignored: the solver's analytic Jacobians are the same residual's, and it runs on its own
+    stream.  ``overrides`` win (e.g. ``feature_layout``)."""
+    f: dict = {}
+    args = _ns_get(odometry, "args")
+    for k in ("num_point", "edgewidth", "match_cov_default", "mapping"):
+        f[k] = _ns_get(args, k)
+    f.update(cov_config_fields(_ns_get(_ns_get(odometry, "cov"), "obs")))
+    f.update(motion_config_fields(_ns_get(odometry, "motion")))
+    f.update(frontend_config_fields(_ns_get(odometry, "frontend")))
+    sel = selector_config_fields(_ns_get(odometry, "keypoint"))
+    flt = filter_config_fields(_ns_get(odometry, "outlier"))
+    if "max_depth" in sel and "max_depth" in flt and sel["max_depth"] != flt["max_depth"]:
+        raise ValueError(f"keypoint.args.max_depth = {sel['max_depth']!r} but the SimpleDepthFilter's max_depth = {flt['max_depth']!r}: the pipe has one max_depth")
+    f.update(flt)
+    f.update(sel)
+    try:
+        mp = _ns_get(odometry, "mappoint")
+    except (KeyError, AttributeError):
+        mp = None                                     # (only the block's absence is tolerated: HotPathConfig's defaults are MACVO_Fast's)
+    if mp is not None and _ns_get(mp, "type") in ("MappingPointSelector", "HIP_MappingPointSelector"):
+        for k, name in (("max_depth", "map_max_depth"), ("max_depth_cov", "map_max_depth_cov"), ("mask_width", "map_mask_width")):
+            try:
+                f[name] = _ns_get(_ns_get(mp, "args"), k)
+            except (KeyError, AttributeError, TypeError):
+                raise ValueError(f"mappoint.args lacks {k!r} (MappingPointSelector takes max_depth, max_depth_cov, mask_width)") from None
+    elif mp is not None and f["mapping"]:
+        raise ValueError(f"mapping: true with mappoint {_ns_get(mp, 'type')!r}: only MappingPointSelector has a HIP form")
+    f["graph_type"] = _ns_get(_ns_get(_ns_get(odometry, "optimizer"), "args"), "graph_type")
+    f.update(overrides)
+    cfg = HotPathConfig(**f)
+    check_frontend_cov(cfg)
+    return cfg
 
 
 def check_selector(cfg: "HotPathConfig", cam: "Camera") -> None:
@@ -251,12 +386,18 @@ class FrameInputs:
                     (L_t2 vs R_t2), pair 1 = temporal (L_t1 vs L_t2)  (Frontend.py:219-220)
     coords        : ``[iters, 2, 2, H/8, W/8]`` fp32 — coords1 entering each decoder iteration (covhead.py:85-92)
     flow, logcov  : ``[2, 2, H, W]`` fp32 — last upsampled flow / log-sigma predictions (covhead.py:140)
+
+    With ``HotPathConfig.frontend_cov`` not ``(True, True)`` only the covariance samples of a side that provides one are read (sample 0 = depth
+    model, sample 1 = matcher); ``logcov`` / ``cov8`` / ``cov_mask`` are None when neither does (plain FlowFormer has no covariance head).
     """
     fmap1: torch.Tensor
     fmap2: torch.Tensor
     coords: torch.Tensor
     flow: torch.Tensor | None = None
     logcov: torch.Tensor | None = None
+    # False: `logcov` already holds sigma^2 = exp(2 * log-sigma), which is what the network's `inference` returns (flownet.py:44) — the epilogue then
+    # takes it as it is (mv_frontend_epilogue's cov_is_log = 0).  pipeline.HotPath only; the native driver takes log-sigma.
+    cov_is_log: bool = True
     # alternative to flow/logcov (SURVEY §8(f) rank 1): the last decoder iteration's 1/8-resolution fields and convex
     # upsampling masks (covhead.py:119-135); the hot path then runs mv_convex_upsample (+ fused exp(2*cov)) itself
     flow8: torch.Tensor | None = None        # [2, 2, H/8, W/8]  coords1 - coords0
@@ -306,6 +447,8 @@ class HotPath:
         self.cam, self.cfg = cam, cfg or HotPathConfig()
         _check_motion(self.cfg)
         check_selector(self.cfg, cam)
+        check_frontend_cov(self.cfg)
+        self._fcov = ops.frontend_cov_flags(self.cfg.frontend_cov)
         self.pose_net = pose_net
         self.generator = generator   # CPU generator of the selector's draws (None: torch's global one, which is what the reference consumes)
         self.dev = torch.device(device)
@@ -373,12 +516,24 @@ class HotPath:
         tok = None
         for it in range(x.coords.shape[0]):
             tok = ops.corr_lookup(vol, x.coords[it], c.radius, out=tok)
-        if x.flow8 is not None:
+        fd, fm = self._fcov
+        if x.flow8 is not None and fd and fm:
             flow = ops.convex_upsample(x.flow8, x.up_mask, mask_scale=0.25)
             cov = ops.convex_upsample(x.cov8, x.cov_mask, mask_scale=1.0, exp2_out=True)     # exp(2*cov) fused
             maps = ops.frontend_epilogue(flow, cov, cam.baseline, cam.fx, cov_is_log=False)
+        elif x.flow8 is not None:
+            # a side without covariance: no covariance upsampling for its pair (pair 0 = the depth model's, pair 1 = the matcher's)
+            flow = ops.convex_upsample(x.flow8, x.up_mask, mask_scale=0.25)
+            cov = None
+            if fd or fm:
+                k = 0 if fd else 1
+                cov = torch.empty_like(flow)
+                cov[k: k + 1] = ops.convex_upsample(x.cov8[k: k + 1], x.cov_mask[k: k + 1], mask_scale=1.0, exp2_out=True)
+            maps = ops.frontend_epilogue(flow, cov, cam.baseline, cam.fx, cov_is_log=False, provide_cov=(fd, fm))
+        elif not (fd and fm):
+            maps = ops.frontend_epilogue(x.flow, x.logcov if (fd or fm) else None, cam.baseline, cam.fx, cov_is_log=x.cov_is_log, provide_cov=(fd, fm))
         else:
-            maps = ops.frontend_epilogue(x.flow, x.logcov, cam.baseline, cam.fx, cov_is_log=True)
+            maps = ops.frontend_epilogue(x.flow, x.logcov, cam.baseline, cam.fx, cov_is_log=x.cov_is_log)
         cands = None
         if with_selector:
             cands = ops.kp_select("nodepth", cam.H, cam.W, flow_cov=maps.flow_cov, kernel_size=c.kp_kernel_size,
@@ -545,7 +700,15 @@ class HotPath:
 
             tr = ops.kp_track(kp0, maps1.flow, maps1.flow_cov, maps0, maps1, c.edgewidth, c.match_cov_default)
             pos0_Tc, pos_Tw, rot = ops.backproject(tr.kp0_uv, tr.vals[0], cam.K4, prev_pose, want_rot=True)
-            if c.cov_model == "match" and not tuple(c.cov_modifiers):
+            if not self._fcov[1]:
+                # the matcher gives no covariance: tr.sigma1 holds the -1 placeholders, the second call is the model with flow_cov=None
+                cov0, cov0_w, cov1 = ops.obs_cov_pair(c.cov_model, maps0.depth, tr.kp0_uv, tr.sigma0, maps1.depth, tr.kp1_uv, None,
+                                                      *cam.K4, depth_cov_map0=maps0.depth_cov, depth_cov_map1=maps1.depth_cov,
+                                                      modifiers=c.cov_modifiers, rot=rot, kernel_size=c.cov_kernel_size,
+                                                      min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov, no_match_cov=True,
+                                                      match_cov_default=c.cov_match_cov_default,
+                                                      depth_cov1=tr.vals[7] if self._fcov[0] else None)
+            elif c.cov_model == "match" and not tuple(c.cov_modifiers):
                 cov0, cov0_w, cov1 = ops.match_cov_pair(maps0.depth, tr.kp0_uv, tr.sigma0, maps1.depth, tr.kp1_uv, tr.sigma1,
                                                         *cam.K4, rot=rot, kernel_size=c.cov_kernel_size,
                                                         min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov)
@@ -770,6 +933,7 @@ class NativeHotPath:
         self.cam, self.cfg = cam, cfg or HotPathConfig()
         _check_motion(self.cfg)
         check_selector(self.cfg, cam)
+        check_frontend_cov(self.cfg)
         self.pose_net = pose_net   # motion_model "tartan": [lanes, 5, 112, 160] -> [lanes, 6], run right behind each tracked frame's enqueue
         if self.cfg.mapping and lanes != 1:
             raise ops.L.MacvoHipError("the dense-mapping tail (mapping=True) runs one sequence per pipe (lanes == 1), as the reference does")
@@ -847,7 +1011,8 @@ class NativeHotPath:
             min_depth_cov=c.min_depth_cov, filter_min_depth=c.filter_min_depth, mapping=int(c.mapping), map_num_point=c.map_num_point,
             map_mask_width=c.map_mask_width, async_backend=0 if c.async_backend is None else (1 if c.async_backend else -1), map_max_depth=c.map_max_depth, map_max_depth_cov=c.map_max_depth_cov, lm=self.lm,
             cov_model=ops._cov_model(c.cov_model), cov_modifiers=ops.cov_modifier_chain(c.cov_modifiers),
-            motion_model=L.MV_MOTION_TARTAN if c.motion_model == "tartan" else L.MV_MOTION_STATIC)
+            motion_model=L.MV_MOTION_TARTAN if c.motion_model == "tartan" else L.MV_MOTION_STATIC,
+            frontend_nocov=_nocov_mask(c), cov_match_cov_default=c.cov_match_cov_default)
         nbytes = lib.mv_frame_pipe_arena_bytes(C.byref(pc))
         if nbytes == 0:
             raise L.MacvoHipError("mv_frame_pipe_arena_bytes: invalid configuration")
@@ -938,8 +1103,9 @@ class NativeHotPath:
     def maps(self, age: int = 0, lane: int = 0) -> "ops.FrontendMaps":
         H, W = self.cam.H, self.cam.W
         v = lambda n, c: self._view(n, age, torch.float32, (self.lanes, c, H, W))[lane: lane + 1]  # noqa: E731
-        return ops.FrontendMaps(v("DEPTH", 1), v("DEPTH_COV", 1), v("DISPARITY", 1), v("DISPARITY_COV", 1), None,
-                                v("MATCH_FLOW", 2), v("MATCH_COV", 3))
+        fd, fm = ops.frontend_cov_flags(self.cfg.frontend_cov)    # (a covariance map the frontend does not provide does not exist in the pipe)
+        return ops.FrontendMaps(v("DEPTH", 1), v("DEPTH_COV", 1) if fd else None, v("DISPARITY", 1), v("DISPARITY_COV", 1) if fd else None, None,
+                                v("MATCH_FLOW", 2), v("MATCH_COV", 3) if fm else None)
 
     # ------------------------------------------------------------------ frame API
     def _inputs(self, x: FrameInputs):
@@ -955,6 +1121,8 @@ class NativeHotPath:
         return st
 
     def _enqueue(self, x: FrameInputs, with_selector: bool) -> None:
+        if not x.cov_is_log:
+            raise ops.L.MacvoHipError("FrameInputs.cov_is_log=False (sigma^2 instead of log-sigma) is pipeline.HotPath's; the native driver takes log-sigma")
         if self._pipe is None:
             self._create(x)
         if x.ready is not None:

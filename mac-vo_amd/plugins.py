@@ -14,6 +14,7 @@ replace, every hot arithmetic step in the HIP kernels (``include/macvo_hip.h``).
     FlowFormerCovFrontend                     HIP_FlowFormerCovFrontend  (network stays PyTorch; lookups + epilogue in HIP)
     CUDAGraph_FlowFormerCovFrontend           HIP_CUDAGraph_FlowFormerCovFrontend  (same, inference replayed as a hipGraph)
     FlowFormerCovDepth / FlowFormerCovMatcher HIP_FlowFormerCovDepth / HIP_FlowFormerCovMatcher  (for FrontendCompose configs)
+    FlowFormerDepth / FlowFormerMatcher       HIP_FlowFormerDepth / HIP_FlowFormerMatcher  (the same without covariance: provide_cov = False)
     TartanVOCovMatcher                        HIP_TartanVOCovMatcher  (in-tree RAFTFlowCovNet stays PyTorch; its local correlations in HIP)
     (FlowFormerCov's volume / lookup)         install_flowformer_hooks(model)
 
@@ -644,6 +645,89 @@ class HIP_FlowFormerCovMatcher(IMatcher):
     @classmethod
     def is_valid_config(cls, config: SimpleNamespace | None) -> None:
         cls._enforce_config_spec(config, _FF_COV_SPEC)
+
+
+def _build_flowformer_plain(config: SimpleNamespace, who: str):
+    """The plain FlowFormer exactly as the reference builds it (StereoDepth.py:105-115, Matching.py:126-137) — or ``config.model``
+    (anything with ``inference(imageA, imageB) -> (flow [2,H,W], _)``: the plain network's ``inference`` is unbatched, which is what the
+    reference's ``est_flow[:1]`` / ``flow.unsqueeze(0)`` rely on)."""
+    model = getattr(config, "model", None)
+    if model is None:
+        try:
+            from Module.Network.FlowFormer.configs.submission import get_cfg
+            from Module.Network.FlowFormer.core import build_flowformer
+        except Exception as e:  # noqa: BLE001
+            raise ImportError(f"{who}: the FlowFormer network (Module/Network/FlowFormer, the MAC-VO/S_FlowFormer submodule) is "
+                              "not importable; initialise the submodule or pass a constructed network as config.model") from e
+        model = build_flowformer(get_cfg())
+        model.load_ddp_state_dict(torch.load(config.weight, weights_only=True))
+        model.to(config.device)
+        model.eval()
+    if hasattr(model, "memory_decoder") or hasattr(model, "memory_encoder"):
+        install_flowformer_hooks(model)
+    return model
+
+
+def _unbatched_flow(est_flow: torch.Tensor, who: str) -> torch.Tensor:
+    if est_flow.dim() == 4 and est_flow.shape[0] == 1:
+        est_flow = est_flow[0]
+    if est_flow.dim() != 3 or est_flow.shape[0] != 2:
+        raise ops.L.MacvoHipError(f"{who}: the plain FlowFormer's inference returns an unbatched [2, H, W] flow, got {tuple(est_flow.shape)}")
+    return est_flow.float().contiguous()
+
+
+_FF_PLAIN_SPEC = {
+    "weight": lambda s: isinstance(s, str),
+    "device": lambda s: isinstance(s, str) and ("cuda" in s),              # the HIP hot path has no CPU fallback
+}
+
+
+class HIP_FlowFormerDepth(IStereoDepth):
+    """``FlowFormerDepth`` (Module/Frontend/StereoDepth.py:99-134), the depth model of the covariance-free ``FrontendCompose`` configs
+    (Ablation_Study/TartanAirv2_Vanilla.yaml): ``provide_cov = False``, the record is ``Output(depth, disparity)`` with ``cov`` and
+    ``disparity_uncertainty`` None.  Network in PyTorch (its window lookups through ``mv_corr_lookup``), ``abs`` + ``disparity_to_depth``
+    (:127-128) in one ``mv_frontend_epilogue`` launch that reads no covariance."""
+
+    def __init__(self, config: SimpleNamespace):
+        super().__init__(config)
+        self.model = _build_flowformer_plain(config, "HIP_FlowFormerDepth")
+
+    @property
+    def provide_cov(self) -> bool:
+        return False
+
+    @torch.inference_mode()
+    def estimate(self, frame) -> "IStereoDepth.Output":
+        est_flow, _ = self.model.inference(frame.imageL.to(self.config.device), frame.imageR.to(self.config.device))
+        flow = _unbatched_flow(est_flow, "HIP_FlowFormerDepth").unsqueeze(0)
+        m = ops.frontend_epilogue(flow, None, frame.frame_baseline, frame.fx, want_match=False, provide_cov=(False, False))
+        return IStereoDepth.Output(depth=m.depth, disparity=m.disparity)
+
+    @classmethod
+    def is_valid_config(cls, config: SimpleNamespace | None) -> None:
+        cls._enforce_config_spec(config, _FF_PLAIN_SPEC)
+
+
+class HIP_FlowFormerMatcher(IMatcher):
+    """``FlowFormerMatcher`` (Module/Frontend/Matching.py:120-155): ``provide_cov = False``, the record is ``Output(flow)`` with ``cov`` None —
+    the network's flow with a batch axis, no arithmetic behind the network.  Its window lookups run through ``mv_corr_lookup``."""
+
+    def __init__(self, config: SimpleNamespace):
+        super().__init__(config)
+        self.model = _build_flowformer_plain(config, "HIP_FlowFormerMatcher")
+
+    @property
+    def provide_cov(self) -> bool:
+        return False
+
+    @torch.inference_mode()
+    def forward(self, frame_t1, frame_t2) -> "IMatcher.Output":
+        flow, _ = self.model.inference(frame_t1.imageL.to(self.config.device), frame_t2.imageL.to(self.config.device))
+        return IMatcher.Output(flow=_unbatched_flow(flow, "HIP_FlowFormerMatcher").unsqueeze(0))
+
+    @classmethod
+    def is_valid_config(cls, config: SimpleNamespace | None) -> None:
+        cls._enforce_config_spec(config, _FF_PLAIN_SPEC)
 
 
 class HIP_CUDAGraph_FlowFormerCovFrontend(HIP_FlowFormerCovFrontend):
