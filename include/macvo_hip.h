@@ -513,6 +513,35 @@ int mv_pgo_solve_posed_motion_dev(int nprob, const int32_t* offsets, const int32
                                   float filter_max_depth, const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out,
                                   int min_points, const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32,
                                   float* pose_sink, mvStream_t stream);
+/* The local-frame forms (Local_TwoFrame_PGO: Module/Optimization/TwoFramePGO/Optimizer.py:111-150).  ref_pose [nprob,7] fp32 is T_o2w, the pose stored at map
+ * index frame_idx - 1 when get_graph_data runs (:119-121).  world_to_optim (:131-143) and optim_to_world (:145-150, Utility/Math.py:124-133) in the reference's
+ * precisions and order: T_w2o = Inv(ref_pose) and the LM start T_w2o @ start in fp32; every row read as pos_To = Act(T_w2o, pos_Tw) in fp32 and
+ * cov_To = (R_w2o cov_Tw) R_w2o^T in fp64 with R_w2o the fp32 rotation matrix widened — the pos_Tw / cov_Tw tables keep their world-frame contents (in the
+ * posed forms the world registration with init_pose still runs first and is what is stored); the unchanged LM loop; then
+ * NormalizeQuat(ref_pose @ float(result)) in fp32 -> out_pose_f32 and pose_sink.  out_pose (fp64) keeps the local-frame LM result, out_info is as above.
+ * A problem with fewer than min_points valid rows returns its start pose unchanged, in the world frame (Odometry/MACVO.py:303-307).
+ * mv_pgo_solve_local: mv_pgo_solve + ref_pose.  mv_pgo_solve_posed_local(_dev): mv_pgo_solve_posed(_dev) + start_pose (NULL = init_pose; given = the
+ * motion-model form, Odometry/MACVO.py:193-194) + ref_pose.  The entry points above compile to the same kernels as before. */
+int mv_pgo_solve_local(int nprob, const int32_t* offsets, int graph_type, const float* init_pose, const float* ref_pose,
+                       const float* intrinsics, const float* baseline, const float* pos_Tw, const double* cov_Tw,
+                       const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp, const float* pixel2_disp_cov,
+                       const float* pixel2_uv_cov, const double* obs2_covTc, const uint8_t* valid, int min_points,
+                       const mvLMParams* params /* host */, double* out_pose, double* out_info, float* out_pose_f32, mvStream_t stream);
+int mv_pgo_solve_posed_local(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type, const float* init_pose,
+                             const float* start_pose, const float* ref_pose, const float* intrinsics, const float* baseline, const float* pos_Tc,
+                             const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv, const float* pixel2_d,
+                             const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
+                             int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
+                             uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
+                             float* out_pose_f32, float* pose_sink, mvStream_t stream);
+int mv_pgo_solve_posed_local_dev(int nprob, const int32_t* offsets, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
+                                 const float* init_pose, const float* start_pose, const float* ref_pose, const float* intrinsics,
+                                 const float* baseline, const float* pos_Tc, const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot,
+                                 const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp, const float* pixel2_disp_cov,
+                                 const float* pixel2_uv_cov, const double* obs2_covTc, int filter_flags, float filter_min_depth,
+                                 float filter_max_depth, const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out,
+                                 int min_points, const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32,
+                                 float* pose_sink, mvStream_t stream);
 
 /* -------------------------------------------------------------------------------------------
  * A23  PWC-Net local correlation, forward (the reference's only hand-written CUDA kernel; non-default matcher path).
@@ -604,6 +633,11 @@ int mv_map_append(const mvMapFrame* frame /* host */, const mvMapStores* stores 
  * slots are full. */
 int mv_map_append_points(const mvMapStores* stores /* host */, int n, const float* pos_Tw, const double* cov, const uint8_t* color,
                          mvStream_t stream);
+/* A non-keyframe (UniformKeyframe: Module/KeyframeSelector.py:31-39; Odometry/MACVO.py:177-179 -> push_keyframe(frame1, pose of the previous keyframe,
+ * need_interp=True), :339-348): ONE frame row with need_interp = 1 and pose_dev [7] fp32 (device), no frame2match range, no match rows, no point rows.  Only
+ * counts[0] advances (counts[3], the lost frames, does not).  Refused (counts[4] += 1) when the frame store is full. */
+int mv_map_append_skipped(const mvMapStores* stores /* host */, const float* K_dev, const float* T_BS_dev, const float* pose_dev, float baseline,
+                          int64_t time_ns, mvStream_t stream);
 /* out[i] = T_BS[i] @ pose[i] @ T_BS[i]^-1 in fp32 (Odometry/Interface.py:47-49) */
 int mv_body_poses(const float* pose, const float* T_BS, int T, float* out, mvStream_t stream);
 /* MotionInterpolate.elaborate_map on pose [T,7] in place (fp64 inside); scratch: double[7*(T-1)]; out_count int32[1] or NULL =
@@ -931,6 +965,20 @@ int mv_frame_pipe_wait_finished(mvFramePipe* p, int lag);
 int mv_frame_pipe_map_append(mvFramePipe* p, const mvMapStores* stores /* host */, int frame_idx, int prev_frame,
                              const float* K_dev, const float* T_BS_dev, float baseline, int64_t time_ns,
                              const uint8_t* color_dev /* [n_sel,3] or NULL */);
+/* The frame the pipe's LM solve runs in (Module/Optimization/TwoFramePGO/Optimizer.py:111-150).  MV_SOLVE_LOCAL: every finish solves in the frame of
+ * ref_pose = pose[frame_idx - 1] (mv_pgo_solve_posed_local*) — the previous keyframe's current pose, which is what the rows are registered with, or, when
+ * mv_frame_pipe_skip was called since the previous finish, the pose that keyframe was pushed with (its prior: MV_FB_PRIOR under MV_MOTION_TARTAN).  Call
+ * before the first enqueue; any lane count.  A pipe on which none of the three calls below is made issues exactly the launches it issued before. */
+enum { MV_SOLVE_WORLD = 0, MV_SOLVE_LOCAL = 1 };
+int mv_frame_pipe_set_solve_frame(mvFramePipe* p, int solve_frame);
+/* A non-keyframe passes (Odometry/MACVO.py:177-179): nothing of it is computed.  The pipe notes that the row in front of the next finished frame is a
+ * skipped one, holding the previous keyframe's prior (its optimised pose is not written back before the next run_pair, :187). */
+int mv_frame_pipe_skip(mvFramePipe* p);
+/* ... and its row in the device-resident map (mv_map_append_skipped; lanes = 1): the pose is copied ON THE DEVICE from the previous keyframe's prior slot,
+ * on the stream that carries the pipe's own mv_frame_pipe_map_append (row indices come from the device-side counter), without any host wait.
+ * frame_idx = the map index the row receives (= frames pushed so far). */
+int mv_frame_pipe_map_skip(mvFramePipe* p, const mvMapStores* stores /* host */, int frame_idx, const float* K_dev, const float* T_BS_dev,
+                           float baseline, int64_t time_ns);
 /* Result views and slot reuse: a consumer that reads result views (mv_frame_pipe_buffer) asynchronously on its own stream
  * calls this before it finishes the next frame; the pipe then orders the kernels that recycle those buffers behind
  * everything enqueued on `stream` so far.  (Host-synchronous consumers do not need it.) */

@@ -23,6 +23,7 @@ MV_GRAPH_ICP, MV_GRAPH_REPROJ, MV_GRAPH_DISP = 0, 1, 2
 MV_COV_MATCH, MV_COV_GMM, MV_COV_NONE = 0, 1, 2
 MV_COVMOD_DIAG, MV_COVMOD_NORMALIZE = 1, 2
 MV_MOTION_STATIC, MV_MOTION_TARTAN = 0, 1
+MV_SOLVE_WORLD, MV_SOLVE_LOCAL = 0, 1
 MV_NOCOV_DEPTH, MV_NOCOV_MATCH = 1, 2
 ABI_VERSION = 8
 MV_MAX_LANES = 64        # include/macvo_hip.h
@@ -147,6 +148,12 @@ SIGNATURES = {
                                      C.POINTER(mvLMParams)] + [_P] * 5),
     "mv_pgo_solve_posed_dev": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int] + [_P] * 14 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int,
                                          C.POINTER(mvLMParams)] + [_P] * 5),
+    "mv_pgo_solve_local": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int,
+                                     C.POINTER(mvLMParams), _P, _P, _P, _P]),
+    "mv_pgo_solve_posed_local": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int] + [_P] * 16 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int,
+                                           C.POINTER(mvLMParams)] + [_P] * 5),
+    "mv_pgo_solve_posed_local_dev": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int] + [_P] * 16 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int,
+                                               C.POINTER(mvLMParams)] + [_P] * 5),
     "mv_backend_front_draw_lanes": (C.c_int, [_P, C.c_size_t, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int] + [_P] * 10 +
                                     [C.c_int, C.c_float, C.POINTER(mvMatchCovParams)] + [_P] * 13),
     "mv_backend_front_lanes": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_int, _P, C.c_int] + [_P] * 10 + [C.c_int, C.c_float, C.POINTER(mvMatchCovParams)] +
@@ -192,6 +199,10 @@ SIGNATURES = {
     "mv_frame_pipe_wait_candidates": (C.c_int, [_P, _P]),
     "mv_frame_pipe_finish": (C.c_int, [_P, _P, _P, _P]),
     "mv_map_append_points": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "mv_map_append_skipped": (C.c_int, [C.POINTER(mvMapStores), _P, _P, _P, C.c_float, C.c_int64, _P]),
+    "mv_frame_pipe_set_solve_frame": (C.c_int, [_P, C.c_int]),
+    "mv_frame_pipe_skip": (C.c_int, [_P]),
+    "mv_frame_pipe_map_skip": (C.c_int, [_P, C.POINTER(mvMapStores), C.c_int, _P, _P, C.c_float, C.c_int64]),
     "mv_kp_front_lanes": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_int, _P, C.c_int] + [_P] * 10 + [C.c_int, C.c_int, C.c_int] +
                           [C.c_float] * 5 + [_P] * 8 + [_P]),
     "mv_frame_pipe_wait_tracked": (C.c_int, [_P, _P, _P]),

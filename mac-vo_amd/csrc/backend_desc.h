@@ -83,6 +83,7 @@ struct mvPosedSolve {   // mv_pgo_solve_posed*'s arguments; the plain mv_pgo_sol
     const mvLMParams* params;
     double *out_pose, *out_info;
     float *out_pose_f32, *pose_sink;
+    const float* ref_pose;       // (optional, last: the positional initialisers leave it null) T_o2w [nprob, 7]: solve in its frame (Local_TwoFrame_PGO)
 };
 
 // (hidden: the library exports the C entry points of macvo_hip.h only)

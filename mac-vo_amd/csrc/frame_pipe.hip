@@ -130,6 +130,7 @@ struct FinishJob {
     Pending pd;
     long g;                 // finish index; backend slot k = g & 1
     int pose_from, pose_to; // pose slots: prior of the frame / its optimised pose
+    bool skipped = false;   // mv_frame_pipe_skip since the previous finish: the local solve's frame is the previous keyframe's prior
     int n_max;
     int32_t n_sel[MV_MAX_LANES];
     int64_t n_cand[MV_MAX_LANES];   // seeded: candidate count per lane (the permutation is drawn by whoever issues the job)
@@ -237,6 +238,8 @@ struct mvFramePipe {
     int lookups_on_main;   // default 1; MV_PIPE_LOOKUPS_ON=vol is the measured alternative
     int pose_cur;
     int prior_slot;        // pose slot the newest finished frame started from (its motion-model prior)
+    int solve_frame = MV_SOLVE_WORLD;   // mv_frame_pipe_set_solve_frame
+    bool skipped = false;               // mv_frame_pipe_skip since the newest finish
     hipEvent_t e_map;
     int newest_maps;
     std::deque<Pending> pending;
@@ -1291,6 +1294,8 @@ static int finish_host(mvFramePipe* p, const int32_t* n_sel, float* pose_sink, F
     Backend& b = p->be[j.g & 1];
     for (int l = 0; l < L; ++l) b.n_sel[l] = j.n_sel[l] = n_sel[l];
     p->n_fin = j.g + 1;
+    j.skipped = p->skipped;
+    p->skipped = false;
     p->prior_slot = p->pose_cur;
     j.pose_from = p->pose_cur;
     j.pose_to = (p->pose_cur + 1) % 3;
@@ -1466,6 +1471,13 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     mvPosedSolve sv = b.solve;
     sv.init_pose = p->pose[j.pose_from];
     sv.out_pose_f32 = p->pose[j.pose_to];
+    if (p->solve_frame == MV_SOLVE_LOCAL) {
+        // Local_TwoFrame_PGO: T_o2w = pose[frame_idx - 1] (Optimizer.py:119-121).  Nothing skipped: the previous keyframe's row, whose current pose is the
+        // one the rows are rotated with.  Behind a skipped frame: that frame's row = the pose the previous keyframe was PUSHED with — its prior, i.e. the
+        // slot finish g - 1 started from (two rotations back; solve g + 1 is the next to write it, behind this one on the same stream), or finish g - 1's
+        // composed prior under the motion model.  (Before the first finish the previous keyframe is frame 0: prior == pose.)
+        sv.ref_pose = !j.skipped || g == 0 ? p->pose[j.pose_from] : motion ? p->prior[(g - 1) % N_MOT] : p->pose[(j.pose_from + 2) % 3];
+    }
     if (fused) {
         // ... and the pose-dependent half = ONE launch: the rotation into the world frame is the solve kernel's prologue, the caller's pose
         // sink its second output (the 28-byte device-to-device copy was a DMA node on the critical stream).  No e_posed: the world-frame
@@ -1478,6 +1490,11 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     } else {
         MV_TRY(mv_pose_apply_lanes(sv.init_pose, sv.pos_Tc, sv.cov_Tc, L, n_sel, cap, sv.pos_Tw, sv.out_rot, sv.cov_Tw, ss));
         MV_HIP(hipEventRecord(p->e_posed[k], ss));
+        if (sv.ref_pose)
+            MV_TRY(mv_pgo_solve_local(L, sv.offsets, sv.graph_type, motion ? prior : sv.init_pose, sv.ref_pose, sv.intrinsics, sv.baseline, sv.pos_Tw, sv.cov_Tw,
+                                      sv.pixel2_uv, sv.pixel2_d, sv.pixel2_disp, sv.pixel2_disp_cov, sv.pixel2_uv_cov, sv.obs2_covTc, sv.valid, sv.min_points,
+                                      sv.params, sv.out_pose, sv.out_info, sv.out_pose_f32, ss));
+        else
         MV_TRY(mv_pgo_solve(L, sv.offsets, sv.graph_type, motion ? prior : sv.init_pose, sv.intrinsics, sv.baseline, sv.pos_Tw, sv.cov_Tw, sv.pixel2_uv,
                             sv.pixel2_d, sv.pixel2_disp, sv.pixel2_disp_cov, sv.pixel2_uv_cov, sv.obs2_covTc, sv.valid, sv.min_points, sv.params,
                             sv.out_pose, sv.out_info, sv.out_pose_f32, ss));
@@ -1785,6 +1802,37 @@ extern "C" int mv_frame_pipe_map_append(mvFramePipe* p, const mvMapStores* store
                           p->s_side));
     MV_HIP(hipEventRecord(p->e_pgo, p->s_side));
     p->pgo_valid = true;
+    return MV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ keyframe policy, local solve
+extern "C" int mv_frame_pipe_set_solve_frame(mvFramePipe* p, int solve_frame) {
+    MV_CHECK_ARG(p && (solve_frame == MV_SOLVE_WORLD || solve_frame == MV_SOLVE_LOCAL) && p->n_enq == 0);
+    p->solve_frame = solve_frame;
+    return MV_OK;
+}
+
+extern "C" int mv_frame_pipe_skip(mvFramePipe* p) {
+    MV_CHECK_ARG(p && p->n_enq > 0);   // (between the finishes of the keyframes around it: the next finish consumes the note)
+    p->skipped = true;
+    return MV_OK;
+}
+
+// The skipped frame's row: push_keyframe(frame1, pose row of the previous keyframe, need_interp=True) (MACVO.py:177-179).  That row still holds the prior the
+// keyframe was pushed with, so the pose is copied from the prior slot — on the backend stream, in order with the pipe's own appends.
+extern "C" int mv_frame_pipe_map_skip(mvFramePipe* p, const mvMapStores* stores, int frame_idx, const float* K_dev, const float* T_BS_dev, float baseline,
+                                      int64_t time_ns) {
+    MV_CHECK_ARG(p && stores && K_dev && T_BS_dev && p->lanes == 1 && p->n_enq > 0 && frame_idx >= 1 && frame_idx < stores->cap_frames);
+    MV_TRY(flush_jobs(p));
+    const long g = p->n_fin - 1;   // the previous keyframe's finish (-1: frame 0, pushed at the pose set by mv_frame_pipe_set_pose)
+    const float* prior = g < 0 ? p->pose[p->pose_cur] : p->c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];
+    // The prior slot is written on the side stream in FRONT of finish g's solve (the slot that solve started from, or the prior composed for it).  The event
+    // mv_frame_pipe_map_append made this stream wait for when it registered finish g lies behind that write, so stream order already covers it and the wait
+    // below adds nothing to the stream; it only keeps a caller that registers no keyframes correct.  (Not e_pgo: that is re-recorded behind the append's pose
+    // copy and would put the backend stream behind work it does not depend on.)
+    if (g >= 0) MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[g & 1] : p->e_posed[g & 1], 0));
+    MV_TRY(mv_map_append_skipped(stores, K_dev, T_BS_dev, prior, baseline, time_ns, p->s_back));
+    MV_HIP(hipEventRecord(p->e_map, p->s_back));
     return MV_OK;
 }
 

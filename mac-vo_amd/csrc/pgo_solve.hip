@@ -37,6 +37,7 @@
 #include <type_traits>
 #include "pgo_math.h"
 #include "pose_apply_dev.h"
+#include "pgo_local_dev.h"
 #include "obs_filter_dev.h"
 #include <stdlib.h>
 
@@ -193,12 +194,39 @@ constexpr int PGO_MOTION = 64;
 struct PgoMotionArgs : PgoArgs {
     const float* start_pose;
 };
+// + PGO_LOCAL for the local-frame form (Local_TwoFrame_PGO, Optimizer.py:111-150; mv_pgo_solve_local, mv_pgo_solve_posed_local*): the solve runs in the frame of
+// ref_pose (T_o2w) — LM starts from Inv(ref_pose) @ start, every row is moved by Inv(ref_pose) where it is loaded (pgo_local_dev.h; the pos_Tw / cov_Tw
+// tables keep their world-frame contents), and the fp32 outputs are NormalizeQuat(ref_pose @ result).  start_pose may be null (= init_pose), so one
+// instantiation serves the plain, the posed and the motion-model call.  As with PGO_MOTION the other instantiations keep their names, argument blocks and code.
+constexpr int PGO_LOCAL = 128;
+struct PgoLocalArgs : PgoArgs {
+    const float* start_pose;
+    const float* ref_pose;
+};
+template <int NWM>
+using pgo_args_t = typename std::conditional<(NWM >= PGO_LOCAL), PgoLocalArgs, typename std::conditional<(NWM >= PGO_MOTION), PgoMotionArgs, PgoArgs>::type>::type;
+
+// load_point, and for the local form the row moved into the optimisation frame behind it
+template <int GT, bool LOCAL>
+__device__ __forceinline__ void load_row(const PgoArgs& a, const Geometry& g, const mvLMParams& lm, const LocalFrame* lf, int i, bool in_range, PointData<GT>& d) {
+    load_point<GT>(a, g, lm, i, in_range, d);
+    if constexpr (LOCAL) {
+        if (d.valid) local_point<GT>(*lf, a.pos_Tw + 3 * (size_t)i, d);   // (lf is null in the other forms and never touched there)
+    }
+}
+
+// (opaque per use: hipcc otherwise hoists the loop-invariant LDS reads of the frame out of the LM loop, back into 25 live vector registers)
+template <bool LOCAL>
+__device__ __forceinline__ const LocalFrame* lf_reread(const LocalFrame* lf) {
+    if constexpr (LOCAL) asm volatile("" : "+s"(lf));
+    return lf;
+}
 
 template <int GT, int NWM>
-__global__ __launch_bounds__(64 * (NWM % PGO_MOTION)) void pgo_solve_kernel(typename std::conditional<(NWM >= PGO_MOTION), PgoMotionArgs, PgoArgs>::type a,
-                                                                           mvLMParams lm) {
+__global__ __launch_bounds__(64 * (NWM % PGO_MOTION)) void pgo_solve_kernel(pgo_args_t<NWM> a, mvLMParams lm) {
     constexpr int NW = NWM % PGO_MOTION;
-    constexpr bool MOTION = NWM >= PGO_MOTION;
+    constexpr bool LOCAL = NWM >= PGO_LOCAL;
+    constexpr bool MOTION = !LOCAL && NWM >= PGO_MOTION;
     constexpr int PGO_THREADS = 64 * NW;
     __shared__ double red_tab[NW][NRED];
     __shared__ __attribute__((aligned(16))) double red_fin[NW == 4 ? NRED + 1 : 1];
@@ -248,15 +276,32 @@ __global__ __launch_bounds__(64 * (NWM % PGO_MOTION)) void pgo_solve_kernel(type
     Pose P;
     const float* start = a.init_pose;
     if constexpr (MOTION) start = a.start_pose;
+    const LocalFrame* lf = nullptr;   // (the local form only)
+    if constexpr (LOCAL) {
+        // the frame lives in LDS: with several points per thread every pass of the LM loop re-reads it, and 25 uniform values held in vector registers
+        // through the loop spilled the ICP form
+        __shared__ LocalFrame lf_lds;
+        if (a.start_pose) start = a.start_pose;
+        if (tid == 0) local_frame(a.ref_pose + 7 * prob, lf_lds);
+        __syncthreads();
+        lf = &lf_lds;
+        float T_c2o[7];
+        se3_mul_f32(lf_lds.T_w2o, start + 7 * prob, T_c2o);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) P.t[k] = (double)start[7 * prob + k];
+        for (int k = 0; k < 3; ++k) P.t[k] = (double)T_c2o[k];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) P.q[k] = (double)start[7 * prob + 3 + k];
+        for (int k = 0; k < 4; ++k) P.q[k] = (double)T_c2o[3 + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) P.t[k] = (double)start[7 * prob + k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) P.q[k] = (double)start[7 * prob + 3 + k];
+    }
     pose_finish(P);
 
     PointData<GT> mine;
     mine.valid = false;
-    if (cached) load_point<GT>(a, g, lm, beg + tid, tid < npts, mine);
+    if (cached) load_row<GT, LOCAL>(a, g, lm, lf, beg + tid, tid < npts, mine);
     if (SPEC && cached) {   // (read behind the barriers of the observation count below)
         pt_valid[tid] = mine.valid ? 1 : 0;
 #pragma unroll
@@ -312,7 +357,7 @@ __global__ __launch_bounds__(64 * (NWM % PGO_MOTION)) void pgo_solve_kernel(type
             for (int k = 0; k < NRED; ++k) acc[k] = 0.0;
             for (int i = beg + tid; i < end; i += PGO_THREADS) {
                 PointData<GT> d;
-                load_point<GT>(a, g, lm, i, true, d);
+                load_row<GT, LOCAL>(a, g, lm, lf_reread<LOCAL>(lf), i, true, d);
                 if (d.valid) accumulate_point<GT, true>(g, lm, P, d, acc, lin);
             }
             reduce_many<NRED, NW, false>(acc, red_part, red_fin, red_rows);
@@ -412,7 +457,7 @@ __global__ __launch_bounds__(64 * (NWM % PGO_MOTION)) void pgo_solve_kernel(type
                     double la[1] = {0.0};
                     for (int i = beg + tid; i < end; i += PGO_THREADS) {
                         PointData<GT> d;
-                        load_point<GT>(a, g, lm, i, true, d);
+                        load_row<GT, LOCAL>(a, g, lm, lf_reread<LOCAL>(lf), i, true, d);
                         if (d.valid) la[0] += point_loss<GT>(g, lm, P, d.pw, d.obs);
                     }
                     block_sum<1, NW>(la, red_tab);
@@ -555,6 +600,23 @@ __global__ __launch_bounds__(64 * (NWM % PGO_MOTION)) void pgo_solve_kernel(type
         double* inf = a.out_info + 4 * (size_t)prob;
         inf[0] = loss; inf[1] = (double)steps; inf[2] = (double)reject_count; inf[3] = loss0;
         if (a.spec == 2) inf[3] = (double)(dbg_rounds * 1000 + dbg_trials);
+        if constexpr (LOCAL) {
+            // optim_to_world (Optimizer.py:145-150), then write_graph_data; a lost problem keeps its start pose as it is (MACVO.py:303-307: no solve)
+            float w[7];
+            if (!have_loss) {   // (the LM loop never ran)
+                const float* kept = a.start_pose ? a.start_pose : a.init_pose;
+#pragma unroll
+                for (int k = 0; k < 7; ++k) w[k] = kept[7 * prob + k];
+            } else {
+                local_to_world_f32(a.ref_pose + 7 * prob, P.t, P.q, w);
+            }
+#pragma unroll
+            for (int k = 0; k < 7; ++k) {
+                if (a.out_pose_f32) a.out_pose_f32[7 * (size_t)prob + k] = w[k];
+                if (a.pose_sink) a.pose_sink[7 * (size_t)prob + k] = w[k];
+            }
+            return;
+        }
         if (a.out_pose_f32) {
             float* of = a.out_pose_f32 + 7 * (size_t)prob;  // write_graph_data: pose = motion.float()
             of[0] = (float)P.t[0]; of[1] = (float)P.t[1]; of[2] = (float)P.t[2];
@@ -639,7 +701,9 @@ static int pgo_solve_impl(const mvPosedSolve& d, mvStream_t stream) {
     const bool wide = nprob < 512;
     dim3 grid(nprob), block(wide ? 256 : 64);
 #define MV_PGO(G)                                                                             \
-    if (d.start_pose) hipLaunchKernelGGL((pgo_solve_kernel<G, 4 + PGO_MOTION>), grid, block, 0, s, PgoMotionArgs{a, d.start_pose}, *params); \
+    if (d.ref_pose && wide) hipLaunchKernelGGL((pgo_solve_kernel<G, 4 + PGO_LOCAL>), grid, block, 0, s, PgoLocalArgs{a, d.start_pose, d.ref_pose}, *params); \
+    else if (d.ref_pose) hipLaunchKernelGGL((pgo_solve_kernel<G, 1 + PGO_LOCAL>), grid, block, 0, s, PgoLocalArgs{a, d.start_pose, d.ref_pose}, *params); \
+    else if (d.start_pose) hipLaunchKernelGGL((pgo_solve_kernel<G, 4 + PGO_MOTION>), grid, block, 0, s, PgoMotionArgs{a, d.start_pose}, *params); \
     else if (wide) hipLaunchKernelGGL((pgo_solve_kernel<G, 4>), grid, block, 0, s, a, *params);    \
     else hipLaunchKernelGGL((pgo_solve_kernel<G, 1>), grid, block, 0, s, a, *params)
     switch (d.graph_type) {
@@ -739,4 +803,51 @@ extern "C" int mv_pgo_solve_posed_motion_dev(int nprob, const int32_t* offsets, 
                            pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, nullptr, n_live_dev, n_live_stride,
                            filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
                            out_pose, out_info, out_pose_f32, pose_sink}, stream);
+}
+
+// The local-frame forms (Local_TwoFrame_PGO, Module/Optimization/TwoFramePGO/Optimizer.py:111-150): the same launches with ref_pose [nprob, 7] (T_o2w) —
+// pgo_solve_kernel<G, NW + PGO_LOCAL>; every entry point above keeps its instantiation.
+extern "C" int mv_pgo_solve_local(int nprob, const int32_t* offsets, int graph_type, const float* init_pose, const float* ref_pose,
+                                  const float* intrinsics, const float* baseline, const float* pos_Tw, const double* cov_Tw,
+                                  const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp,
+                                  const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
+                                  const uint8_t* valid, int min_points, const mvLMParams* params, double* out_pose,
+                                  double* out_info, float* out_pose_f32, mvStream_t stream) {
+    MV_CHECK_ARG(ref_pose);
+    mvPosedSolve d{};
+    d.nprob = nprob; d.offsets = offsets; d.graph_type = graph_type; d.init_pose = init_pose; d.intrinsics = intrinsics; d.baseline = baseline;
+    d.pos_Tw = const_cast<float*>(pos_Tw); d.cov_Tw = const_cast<double*>(cov_Tw);   // (read only without pos_Tc)
+    d.pixel2_uv = pixel2_uv; d.pixel2_d = pixel2_d; d.pixel2_disp = pixel2_disp; d.pixel2_disp_cov = pixel2_disp_cov; d.pixel2_uv_cov = pixel2_uv_cov;
+    d.obs2_covTc = obs2_covTc; d.filter_flags = -1; d.valid = const_cast<uint8_t*>(valid); d.min_points = min_points; d.params = params;
+    d.out_pose = out_pose; d.out_info = out_info; d.out_pose_f32 = out_pose_f32; d.ref_pose = ref_pose;
+    return pgo_solve_impl(d, stream);
+}
+
+extern "C" int mv_pgo_solve_posed_local(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type,
+                                        const float* init_pose, const float* start_pose, const float* ref_pose, const float* intrinsics, const float* baseline,
+                                        const float* pos_Tc, const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot, const float* pixel2_uv,
+                                        const float* pixel2_d, const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov,
+                                        const double* obs2_covTc, int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound,
+                                        const float* vals, uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose,
+                                        double* out_info, float* out_pose_f32, float* pose_sink, mvStream_t stream) {
+    MV_CHECK_ARG(n_live && ref_pose);
+    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
+                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, n_live, nullptr, 0,
+                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
+                           out_pose, out_info, out_pose_f32, pose_sink, ref_pose}, stream);
+}
+
+extern "C" int mv_pgo_solve_posed_local_dev(int nprob, const int32_t* offsets, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
+                                            const float* init_pose, const float* start_pose, const float* ref_pose, const float* intrinsics,
+                                            const float* baseline, const float* pos_Tc, const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot,
+                                            const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp, const float* pixel2_disp_cov,
+                                            const float* pixel2_uv_cov, const double* obs2_covTc, int filter_flags, float filter_min_depth,
+                                            float filter_max_depth, const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out,
+                                            int min_points, const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32,
+                                            float* pose_sink, mvStream_t stream) {
+    MV_CHECK_ARG(n_live_dev && ref_pose);
+    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
+                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, nullptr, n_live_dev, n_live_stride,
+                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
+                           out_pose, out_info, out_pose_f32, pose_sink, ref_pose}, stream);
 }

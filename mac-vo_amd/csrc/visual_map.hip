@@ -236,6 +236,35 @@ __global__ __launch_bounds__(256) void map_append_kernel(mvMapFrame fr, mvMapSto
     }
 }
 
+// a non-keyframe (UniformKeyframe: Odometry/MACVO.py:177-179 -> push_keyframe(frame1, pose of the previous keyframe, need_interp=True), :339-348): one frame row
+// flagged for interpolation, no match / point rows, no frame2match range; only the frame count advances (it is not a lost frame)
+__global__ void map_skip_kernel(mvMapStores st, const float* __restrict__ K, const float* __restrict__ T_BS, const float* __restrict__ pose, float baseline,
+                                int64_t time_ns) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int64_t* cnt = st.counts;
+    const int64_t F = cnt[0];
+    if (F >= st.cap_frames) {   // refused like any append when the store is full
+        cnt[4] += 1;
+        return;
+    }
+    const size_t f = (size_t)F;
+    for (int c = 0; c < 9; ++c) st.K[9 * f + c] = K[c];
+    st.baseline[f] = baseline;
+    for (int c = 0; c < 7; ++c) {
+        st.pose[7 * f + c] = pose[c];
+        st.T_BS[7 * f + c] = T_BS[c];
+    }
+    st.time_ns[f] = time_ns;
+    st.need_interp[f] = 1;
+    for (int c = 0; c < 2 * st.max_frame_range; ++c) {
+        st.frame2match_ranges[2 * st.max_frame_range * f + c] = -1;
+        st.frame2map_ranges[2 * st.max_frame_range * f + c] = -1;
+    }
+    st.frame2match_num[f] = 0;
+    st.frame2map_num[f] = 0;
+    cnt[0] = F + 1;
+}
+
 // dense-mapping tail: map_points.push + frame2map.add for the newest frame (Odometry/MACVO.py:329-337)
 __global__ __launch_bounds__(256) void map_append_points_kernel(mvMapStores st, int n, const float* __restrict__ pos, const double* __restrict__ cov,
                                                                  const uint8_t* __restrict__ color) {
@@ -388,6 +417,17 @@ extern "C" int mv_map_append(const mvMapFrame* frame, const mvMapStores* stores,
     MV_CHECK_ARG(s.frame2match_ranges && s.frame2match_num && s.frame2map_ranges && s.frame2map_num && s.match2frame1 &&
                  s.match2frame2 && s.match2point && s.point2match_edges && s.point2match_deg);
     hipLaunchKernelGGL(map_append_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, f, s);
+    return mv_launch_status();
+}
+
+extern "C" int mv_map_append_skipped(const mvMapStores* stores, const float* K_dev, const float* T_BS_dev, const float* pose_dev, float baseline,
+                                     int64_t time_ns, mvStream_t stream) {
+    MV_CHECK_ARG(stores && K_dev && T_BS_dev && pose_dev);
+    const mvMapStores& s = *stores;
+    MV_CHECK_ARG(s.counts && s.cap_frames > 0 && s.max_frame_range >= 1);
+    MV_CHECK_ARG(s.K && s.baseline && s.pose && s.T_BS && s.need_interp && s.time_ns && s.frame2match_ranges && s.frame2match_num &&
+                 s.frame2map_ranges && s.frame2map_num);
+    hipLaunchKernelGGL(map_skip_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, s, K_dev, T_BS_dev, pose_dev, baseline, time_ns);
     return mv_launch_status();
 }
 

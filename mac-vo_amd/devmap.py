@@ -70,6 +70,7 @@ class DeviceVisualMap:
         }
         self.counts = torch.zeros(6, dtype=i64, device=self.dev)      # {frames, matches, points, lost frames, refused appends, map points}: advanced on device
         self.n_frames = 0                                             # exact (one per push)
+        self.last_keyframe = -1                                       # map index of the newest frame that is not a skipped one (MACVO.prev_keyframe[1])
         self.rows_upper = 0                                           # upper bound of matches == points pushed
         self.map_rows_upper = 0                                       # upper bound of map points pushed
         self._stores = None
@@ -139,7 +140,7 @@ class DeviceVisualMap:
         Td = ops._req(T_BS.to(self.dev, f32).reshape(7), f32, "T_BS")
         pr = None if prior_pose is None else ops._req(prior_pose.to(self.dev, f32).reshape(7), f32, "prior_pose")
         q = lambda t, dt, nm: None if t is None else ops._req(t, dt, nm).data_ptr()  # noqa: E731
-        fr = L.mvMapFrame(n_rows=n, table_stride=n if n else 0, prev_frame=self.n_frames - 1, min_num_point=min_num_point,
+        fr = L.mvMapFrame(n_rows=n, table_stride=n if n else 0, prev_frame=self.last_keyframe, min_num_point=min_num_point,
                           valid=q(None if valid is None else valid.view(torch.uint8) if valid.dtype == torch.bool else valid, torch.uint8, "valid"),
                           kp0=q(None if n == 0 else tracked.kp0_uv, f32, "kp0"), kp1=q(None if n == 0 else tracked.kp1_uv, f32, "kp1"),
                           vals=q(None if n == 0 else tracked.vals, f32, "vals"),
@@ -151,8 +152,27 @@ class DeviceVisualMap:
         L.check(self.lib.mv_map_append(C.byref(fr), C.byref(self.stores()), ops._stream()), "mv_map_append")
         self._keep = (Kd, Td, pr)
         idx = self.n_frames
+        self.last_keyframe = idx
         self.n_frames += 1
         self.rows_upper += n
+        return idx
+
+    def push_skipped(self, K, T_BS, baseline: float, time_ns: int, pose) -> int:
+        """Register a non-keyframe (``UniformKeyframe``: Odometry/MACVO.py:177-179,339-348): one frame row with ``need_interp`` set and the given
+        pose — the pose the previous keyframe was pushed with — no frame2match range, no match rows, no point rows; only ``counts[0]`` advances
+        (it is not a lost frame).  Refused like any append when the store is full.  Returns the row's map index."""
+        from . import ops
+
+        self.reserve(0)
+        f32 = torch.float32
+        Kd = ops._req(K.to(self.dev, f32).reshape(3, 3), f32, "K")
+        Td = ops._req(T_BS.to(self.dev, f32).reshape(7), f32, "T_BS")
+        pd = ops._req(pose.to(self.dev, f32).reshape(7), f32, "pose")
+        L.check(self.lib.mv_map_append_skipped(C.byref(self.stores()), Kd.data_ptr(), Td.data_ptr(), pd.data_ptr(), float(baseline), int(time_ns),
+                                               ops._stream()), "mv_map_append_skipped")
+        self._keep = (Kd, Td, pd)
+        idx = self.n_frames
+        self.n_frames += 1
         return idx
 
     def push_map_points(self, pos_Tw: torch.Tensor, cov: torch.Tensor, color: torch.Tensor | None = None) -> None:

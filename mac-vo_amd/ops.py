@@ -854,26 +854,40 @@ _GRAPH = {"icp": L.MV_GRAPH_ICP, "reproj": L.MV_GRAPH_REPROJ, "disp": L.MV_GRAPH
 
 
 def pgo_solve(batch: PGOBatch, graph_type: str = "disp", params: L.mvLMParams | None = None, min_points: int = 0,
-              out_pose_f32: torch.Tensor | None = None):
+              out_pose_f32: torch.Tensor | None = None, ref_pose: torch.Tensor | None = None):
     """Batched two-frame PGO (Optimizer.py:81-102 + PyposeOptimizers.py:160-194) -> (pose [nprob,7] f64, info [nprob,4] f64).
-    ``out_pose_f32`` (optional ``[nprob,7]`` float32 GPU tensor) receives ``motion.float()`` (Optimizer.py:104-108)."""
+    ``out_pose_f32`` (optional ``[nprob,7]`` float32 GPU tensor) receives ``motion.float()`` (Optimizer.py:104-108).
+    ``ref_pose`` (``[nprob,7]`` float32, T_o2w): the ``Local_TwoFrame_PGO`` form (Optimizer.py:111-150) — the solve runs in that pose's frame, the
+    returned fp64 pose is the local-frame LM result and ``out_pose_f32`` the world pose ``NormalizeQuat(ref_pose @ result)``."""
     lib = L.load()
     p = params or lm_default_params()
     nprob = batch.init_pose.shape[0]
     dev = batch.init_pose.device
-    f32 = lambda t, n: None if t is None else _req(t, torch.float32, n)  # noqa: E731
-    f64 = lambda t, n: None if t is None else _req(t, torch.float64, n)  # noqa: E731
+    keep = []   # (contiguous copies stay alive until the launch is enqueued)
+
+    def f32(t, n, dt=torch.float32):
+        if t is not None:
+            keep.append(_req(t, dt, n))
+            return keep[-1]
+
+    f64 = lambda t, n: f32(t, n, torch.float64)  # noqa: E731
     out_pose = torch.empty((nprob, 7), dtype=torch.float64, device=dev)
     out_info = torch.empty((nprob, 4), dtype=torch.float64, device=dev)
-    L.check(lib.mv_pgo_solve(nprob, _req(batch.offsets, torch.int32, "offsets").data_ptr(), _GRAPH[graph_type],
-                             f32(batch.init_pose, "init_pose").data_ptr(), f32(batch.intrinsics, "intrinsics").data_ptr(),
-                             f32(batch.baseline, "baseline").data_ptr(), f32(batch.pos_Tw, "pos_Tw").data_ptr(),
-                             _ptr(f64(batch.cov_Tw, "cov_Tw")), f32(batch.pixel2_uv, "pixel2_uv").data_ptr(),
-                             _ptr(f32(batch.pixel2_d, "pixel2_d")), _ptr(f32(batch.pixel2_disp, "pixel2_disp")),
-                             _ptr(f32(batch.pixel2_disp_cov, "pixel2_disp_cov")),
-                             _ptr(f32(batch.pixel2_uv_cov, "pixel2_uv_cov")), _ptr(f64(batch.obs2_covTc, "obs2_covTc")),
-                             _ptr(_u8(batch.valid)), int(min_points), C.byref(p), out_pose.data_ptr(),
-                             out_info.data_ptr(), _ptr(out_pose_f32), _stream()), "mv_pgo_solve")
+    head = [nprob, _req(batch.offsets, torch.int32, "offsets").data_ptr(), _GRAPH[graph_type], f32(batch.init_pose, "init_pose").data_ptr()]
+    tail = [f32(batch.intrinsics, "intrinsics").data_ptr(),
+            f32(batch.baseline, "baseline").data_ptr(), f32(batch.pos_Tw, "pos_Tw").data_ptr(),
+            _ptr(f64(batch.cov_Tw, "cov_Tw")), f32(batch.pixel2_uv, "pixel2_uv").data_ptr(),
+            _ptr(f32(batch.pixel2_d, "pixel2_d")), _ptr(f32(batch.pixel2_disp, "pixel2_disp")),
+            _ptr(f32(batch.pixel2_disp_cov, "pixel2_disp_cov")),
+            _ptr(f32(batch.pixel2_uv_cov, "pixel2_uv_cov")), _ptr(f64(batch.obs2_covTc, "obs2_covTc")),
+            _ptr(f32(_u8(batch.valid), "valid", torch.uint8)), int(min_points), C.byref(p), out_pose.data_ptr(),
+            out_info.data_ptr(), _ptr(out_pose_f32), _stream()]
+    if ref_pose is None:
+        L.check(lib.mv_pgo_solve(*head, *tail), "mv_pgo_solve")
+    else:
+        ref = f32(ref_pose, "ref_pose")
+        assert ref.shape == (nprob, 7), ref.shape
+        L.check(lib.mv_pgo_solve_local(*head, ref.data_ptr(), *tail), "mv_pgo_solve_local")
     return out_pose, out_info
 
 

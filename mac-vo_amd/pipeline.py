@@ -125,6 +125,49 @@ class HotPathConfig:
     # the covariance MODEL's own `match_cov_default` (cov.obs args; Project2to3.py:133,216): sigma of the second observation when the matcher gives no
     # covariance.  Not `match_cov_default` above (Odometry.args), which stays the sigma of the first observation and of map points (MACVO.py:228,322).
     cov_match_cov_default: float = 0.25
+    # frame the LM solve runs in (`optimizer.type` of the experiment YAML): "world" = TwoFrame_PGO | "local" = Local_TwoFrame_PGO, the frame of the pose
+    # stored at map index frame_idx - 1 (Optimizer.py:111-150).  optimizer_config_fields() maps an `optimizer` block onto this field and graph_type.
+    solve_frame: str = "world"
+    # keyframe policy (`keyframe` of the experiment YAML, Module/KeyframeSelector.py): 1 = AllKeyframe, k = UniformKeyframe(keyframe_freq=k) — frame i
+    # of a run() is a keyframe when i % k == 0, the others are registered with need_interp and filled in by MotionInterpolate (MACVO.py:177-179).
+    keyframe_freq: int = 1
+
+
+SOLVE_FRAMES = ("world", "local")
+_OPTIMIZER_TYPES = {"TwoFrame_PGO": "world", "HIP_TwoFrame_PGO": "world", "Local_TwoFrame_PGO": "local", "HIP_Local_TwoFrame_PGO": "local"}
+
+
+def optimizer_config_fields(block) -> dict:
+    """A reference ``optimizer`` block (``{type, args}`` as a dict or SimpleNamespace) -> ``{"solve_frame", "graph_type"}`` for
+    :class:`HotPathConfig`.  ``autodiff`` / ``vectorize`` / ``parallel`` / ``device`` are ignored (see :func:`hot_path_config`)."""
+    t = _ns_get(block, "type")
+    if t not in _OPTIMIZER_TYPES:
+        raise ValueError(f"optimizer {t!r} has no HIP form (one of {sorted(_OPTIMIZER_TYPES)})")
+    g = _ns_get(_ns_get(block, "args"), "graph_type")
+    if g not in ("icp", "reproj", "disp"):
+        raise ValueError(f"optimizer {t!r}: graph_type {g!r} is not one of icp, reproj, disp")
+    return {"solve_frame": _OPTIMIZER_TYPES[t], "graph_type": g}
+
+
+def keyframe_config_fields(block) -> dict:
+    """A reference ``keyframe`` block (``{type, args}``) -> ``{"keyframe_freq"}`` for :class:`HotPathConfig`: ``AllKeyframe`` -> 1,
+    ``UniformKeyframe`` -> its ``keyframe_freq``."""
+    t = _ns_get(block, "type")
+    if t == "AllKeyframe":
+        return {"keyframe_freq": 1}
+    if t != "UniformKeyframe":
+        raise ValueError(f"keyframe selector {t!r} has no HIP form (AllKeyframe or UniformKeyframe)")
+    k = _ns_get(_ns_get(block, "args"), "keyframe_freq")
+    if not (isinstance(k, int) and not isinstance(k, bool) and k >= 1):
+        raise ValueError(f"UniformKeyframe: keyframe_freq must be an integer >= 1, not {k!r}")
+    return {"keyframe_freq": k}
+
+
+def check_keyframes(cfg: "HotPathConfig") -> None:
+    if cfg.solve_frame not in SOLVE_FRAMES:
+        raise ValueError(f"solve_frame must be one of {SOLVE_FRAMES}, not {cfg.solve_frame!r}")
+    if not (isinstance(cfg.keyframe_freq, int) and cfg.keyframe_freq >= 1):
+        raise ValueError(f"keyframe_freq must be an integer >= 1, not {cfg.keyframe_freq!r}")
 
 
 def check_frontend_cov(cfg: "HotPathConfig") -> None:
@@ -293,8 +336,8 @@ def filter_config_fields(block) -> dict:
 
 def hot_path_config(odometry, **overrides) -> HotPathConfig:
     """The ``Odometry`` block of a reference experiment YAML (dict or SimpleNamespace, e.g. ``load_config(...)[0].Odometry``) ->
-    :class:`HotPathConfig`: ``cov.obs``, ``keypoint``, ``motion``, ``frontend`` and ``outlier`` through their mappers, ``mappoint`` (the
-    MappingPointSelector's bounds), ``optimizer.args.graph_type`` and ``args.{num_point, edgewidth, match_cov_default, mapping}``.  The optimizer's
+    :class:`HotPathConfig`: ``cov.obs``, ``keypoint``, ``motion``, ``frontend``, ``outlier``, ``optimizer`` and ``keyframe`` (where the block
+    exists) through their mappers, ``mappoint`` (the MappingPointSelector's bounds) and ``args.{num_point, edgewidth, match_cov_default, mapping}``.  The optimizer's
     ``autodiff`` / ``vectorize`` / ``parallel`` / ``device`` are ignored: the solver's analytic Jacobians are the same residual's, and it runs on its own
     stream.  ``overrides`` win (e.g. ``feature_layout``)."""
     f: dict = {}
@@ -322,10 +365,17 @@ def hot_path_config(odometry, **overrides) -> HotPathConfig:
                 raise ValueError(f"mappoint.args lacks {k!r} (MappingPointSelector takes max_depth, max_depth_cov, mask_width)") from None
     elif mp is not None and f["mapping"]:
         raise ValueError(f"mapping: true with mappoint {_ns_get(mp, 'type')!r}: only MappingPointSelector has a HIP form")
-    f["graph_type"] = _ns_get(_ns_get(_ns_get(odometry, "optimizer"), "args"), "graph_type")
+    f.update(optimizer_config_fields(_ns_get(odometry, "optimizer")))
+    try:
+        kf = _ns_get(odometry, "keyframe")
+    except (KeyError, AttributeError):
+        kf = None
+    if kf is not None:
+        f.update(keyframe_config_fields(kf))
     f.update(overrides)
     cfg = HotPathConfig(**f)
     check_frontend_cov(cfg)
+    check_keyframes(cfg)
     return cfg
 
 
@@ -448,7 +498,14 @@ class HotPath:
         _check_motion(self.cfg)
         check_selector(self.cfg, cam)
         check_frontend_cov(self.cfg)
+        check_keyframes(self.cfg)
         self._fcov = ops.frontend_cov_flags(self.cfg.frontend_cov)
+        self._prev_prior = None                   # the pose the previous keyframe was pushed with (= what a skipped frame's row holds)
+        self._prev_prior_ev = None
+        self._skipped = False                     # a frame has been skipped since the previous keyframe
+        self._n_key_enq = self._n_key_fin = 0
+        self._skip_queue: list = []               # (keyframes that must have finished first, time_ns)
+        self._map = None
         self.pose_net = pose_net
         self.generator = generator   # CPU generator of the selector's draws (None: torch's global one, which is what the reference consumes)
         self.dev = torch.device(device)
@@ -582,6 +639,52 @@ class HotPath:
         self._prev_image = x.image
         if init_pose is not None:
             self.pose = init_pose.to(self.dev, torch.float32).reshape(7).clone()
+        self._prev_prior, self._prev_prior_ev, self._skipped = self.pose, None, False
+        self._frame_index = 0
+
+    def attach_map(self, devmap, K: torch.Tensor, T_BS: torch.Tensor | None = None) -> None:
+        """The map :meth:`skip` registers non-keyframes in (only the driver knows the pose a skipped row carries).  Keyframes are registered by the
+        caller from their :class:`FrameResult` (``DeviceVisualMap.push_frame`` / ``set_pose``), as before."""
+        self._map = devmap
+        self._map_K = K.to(self.dev, torch.float32).reshape(3, 3).contiguous()
+        self._map_TBS = (torch.tensor([0, 0, 0, 0, 0, 0, 1.0]) if T_BS is None else T_BS).to(self.dev, torch.float32).reshape(7).contiguous()
+
+    def skip(self, time_ns: int = 0) -> None:
+        """A non-keyframe (MACVO.py:177-179): nothing of it is computed.  It is registered in the attached map (if any) with ``need_interp`` and the
+        pose the previous keyframe was PUSHED with — that keyframe's optimised pose is not written back before the next ``run_pair`` — and the next
+        local solve takes that pose as its reference frame: ``pose[frame_idx - 1]`` is this row (Optimizer.py:119-121).  Called while keyframes
+        are still pending (``run``), it takes effect once they have finished."""
+        if self._n_key_fin < self._n_key_enq:
+            self._skip_queue.append((self._n_key_enq, int(time_ns)))
+            return
+        self._skip_now(time_ns)
+
+    def _skip_now(self, time_ns: int) -> None:
+        self._skipped = True
+        if self._map is not None:
+            if self._prev_prior_ev is not None:
+                torch.cuda.current_stream().wait_event(self._prev_prior_ev)
+            self._map.push_skipped(self._map_K, self._map_TBS, self.cam.baseline, int(time_ns), self._prev_prior)
+
+    def _keyframes_of(self, frames):
+        """The keyframes of ``frames`` (UniformKeyframe.isKeyframe: frame index % keyframe_freq == 0, the frame of ``initialize`` being index 0);
+        the frames in between are skipped as they are passed."""
+        k = self.cfg.keyframe_freq
+        for x in frames:
+            self._frame_index += 1
+            if self._frame_index % k == 0:
+                yield x
+            else:
+                self.skip(x.time_ns)
+
+    def _keyframe_done(self, prior: torch.Tensor, ev) -> None:
+        self._prev_prior, self._prev_prior_ev, self._skipped = prior, ev, False
+        self._n_key_fin += 1
+
+    def _flush_skips(self) -> None:
+        """Deferred skips whose keyframes have finished — run() calls it once the consumer has taken that keyframe's result (and registered its row)."""
+        while self._skip_queue and self._skip_queue[0][0] <= self._n_key_fin:
+            self._skip_now(self._skip_queue.pop(0)[1])
 
     # ------------------------------------------------------------------ one run_pair, in two halves
     @traced("Frontend.estimate")
@@ -624,6 +727,7 @@ class HotPath:
         pend.cands_m, pend.host_count_m, pend.image0 = cands_m, host_count_m, self._prev_image
         pend.keypoints, pend.keypoint_counts = x.keypoints, x.keypoint_counts
         self._prev_image = x.image
+        self._n_key_enq += 1
         return pend
 
     def pose_motion(self, pend: "_Pending") -> torch.Tensor:
@@ -641,6 +745,7 @@ class HotPath:
         ``motion_in``); the prior ``pose of frame t-1 @ Exp(motion * pose_norm)`` is where LM starts and what a lost-track frame keeps,
         while the world registration still uses the pose of frame t-1 (MACVO.py:193-194,273-281,303-307)."""
         c, cam = self.cfg, self.cam
+        self._flush_skips()
         maps0, maps1, cands = pend.maps0, pend.maps1, pend.cands
         motion_ev = None
         if c.motion_model == "tartan":
@@ -688,6 +793,7 @@ class HotPath:
                 return ops.pose_exp_compose(prev_pose, motion.reshape(6).to(torch.float32))
             if n == 0:
                 if motion_ev is None:
+                    self._keyframe_done(self.pose, self._pgo_done)
                     return FrameResult(self.pose, None, None, kp0, None)
                 prior = compose()
                 # nothing tracked: the frame keeps the motion-model prior (MACVO.py:303-307), and the next prior composes onto it
@@ -696,6 +802,7 @@ class HotPath:
                 self._pgo_done = done
                 self._pgo_keep = (self._pgo_keep[1] if self._pgo_keep else None, (motion, kp0, cands, pend, prev_pose))
                 self.pose = prior
+                self._keyframe_done(prior, done)
                 return FrameResult(prior, None, None, kp0, None, prior=prior)
 
             tr = ops.kp_track(kp0, maps1.flow, maps1.flow_cov, maps0, maps1, c.edgewidth, c.match_cov_default)
@@ -730,7 +837,10 @@ class HotPath:
         side.wait_event(ready)
         with torch.cuda.stream(side):
             new_pose = torch.empty((1, 7), dtype=torch.float32, device=self.dev)
-            pose64, info = ops.pgo_solve(batch, c.graph_type, self.lm, min_points=c.min_num_point, out_pose_f32=new_pose)
+            # the local solve's frame is pose[frame_idx - 1] (Optimizer.py:119-121): the previous keyframe's row — its current pose, the one the
+            # rows were registered with — or, behind a skipped frame, that frame's row, which holds the previous keyframe's prior
+            ref_pose = None if c.solve_frame != "local" else (self._prev_prior if self._skipped else prev_pose).reshape(1, 7)
+            pose64, info = ops.pgo_solve(batch, c.graph_type, self.lm, min_points=c.min_num_point, out_pose_f32=new_pose, ref_pose=ref_pose)
             if pose_sink is not None:
                 pose_sink.copy_(new_pose.reshape(7), non_blocking=True)
             done = torch.cuda.Event()
@@ -753,6 +863,7 @@ class HotPath:
         self._pgo_keep = (self._pgo_keep[1] if self._pgo_keep else None, (batch, tr, cov0, cov1, maps0, maps1, kp0, pos0_Tc, cands, pend,
                                                                            prev_pose, motion))  # keep 2 frames of cross-stream tensors alive
         self.pose = new_pose.reshape(7)
+        self._keyframe_done(prior, ready)
         res = FrameResult(self.pose, pose64, info, kp0, n_valid, prior=prior if motion_ev is not None else None)
         res.map_points = map_pts
         if self.keep_extras:
@@ -779,8 +890,10 @@ class HotPath:
 
     def run(self, frames, pose_sink: torch.Tensor | None = None):
         """Software-pipelined stream: frame t+1's frontend is enqueued before frame t's host-side randperm, so the GPU
-        never idles on the selector's host round trip.  Yields a FrameResult per frame (same results as ``step``)."""
-        it = iter(frames)
+        never idles on the selector's host round trip.  Yields a FrameResult per KEYFRAME (same results as ``step``).  ``keyframe_freq`` k > 1:
+        frame i of ``frames`` (the frame after ``initialize``'s has index 1) is a keyframe when ``i % k == 0``; the others are not enqueued — only
+        their ``time_ns`` is read (:meth:`skip`)."""
+        it = self._keyframes_of(frames)
         try:
             nxt = self.enqueue_frontend(next(it))
         except StopIteration:
@@ -793,6 +906,7 @@ class HotPath:
             except StopIteration:
                 nxt = None
             yield self.finish(cur, None if pose_sink is None else pose_sink[i])
+            self._flush_skips()
             i += 1
         self.sync_pose()
 
@@ -934,6 +1048,9 @@ class NativeHotPath:
         _check_motion(self.cfg)
         check_selector(self.cfg, cam)
         check_frontend_cov(self.cfg)
+        check_keyframes(self.cfg)
+        self._skip_queue: list = []      # (finishes that must have happened first, time_ns)
+        self._frame_index = 0
         self.pose_net = pose_net   # motion_model "tartan": [lanes, 5, 112, 160] -> [lanes, 6], run right behind each tracked frame's enqueue
         if self.cfg.mapping and lanes != 1:
             raise ops.L.MacvoHipError("the dense-mapping tail (mapping=True) runs one sequence per pipe (lanes == 1), as the reference does")
@@ -1021,6 +1138,8 @@ class NativeHotPath:
         pipe = C.c_void_p()
         L.check(lib.mv_frame_pipe_create(C.byref(pc), self._base, nbytes, C.byref(pipe)), "mv_frame_pipe_create")
         self._pipe, self._lib, self._pc = pipe, lib, pc
+        if c.solve_frame == "local":      # (a pipe on which this is never called issues exactly the world-frame launches)
+            L.check(lib.mv_frame_pipe_set_solve_frame(pipe, L.MV_SOLVE_LOCAL), "mv_frame_pipe_set_solve_frame")
         self.device_driven = False
         if self._native_seeds:
             seeds = (C.c_uint64 * self.lanes)(*[int(g) & 0xFFFFFFFFFFFFFFFF for g in self.generators])
@@ -1146,11 +1265,49 @@ class NativeHotPath:
     def initialize(self, x: FrameInputs, init_pose: torch.Tensor | None = None) -> None:
         """Frame 0: ``MACVO.initialize`` (:158-171) — depth only, pose = prior."""
         self._init_pose = init_pose
+        self._frame_index = 0
+        self._skip_queue.clear()
         self._enqueue(x, False)
         self._prev_image = x.image
         if getattr(self, "_map", None) is not None:   # MACVO.initialize pushes the first frame at the prior (:162-169)
             self._map.push_frame(K=self._map_K, T_BS=self._map_TBS, baseline=self.cam.baseline, time_ns=x.time_ns, prior_pose=init_pose)
             torch.cuda.current_stream().synchronize()   # later frames are appended on the pipe's streams: order them after this one
+
+    def skip(self, time_ns: int = 0) -> None:
+        """A non-keyframe (MACVO.py:177-179), see :meth:`HotPath.skip`: the pipe notes that the next solve's reference frame is the previous keyframe's
+        prior (mv_frame_pipe_skip), and with an attached map the row is appended on the pipe's own stream with that prior copied on the device
+        (mv_frame_pipe_map_skip) — no host wait.  Called while tracked frames are still pending (``run``), it takes effect once they have finished."""
+        assert self._n_enq >= 1, "call initialize() with the first frame"
+        if self._has_pending():
+            self._skip_queue.append((self._n_enq - 1, int(time_ns)))
+            return
+        self._skip_now(time_ns)
+
+    def _skip_now(self, time_ns: int) -> None:
+        L, lib = ops.L, self._lib
+        L.check(lib.mv_frame_pipe_skip(self._pipe), "mv_frame_pipe_skip")
+        mp = getattr(self, "_map", None)
+        if mp is not None:
+            if mp.n_frames + 1 >= mp.cap["frames"]:
+                self.synchronize()
+                mp.reserve(0)
+                torch.cuda.synchronize()
+            L.check(lib.mv_frame_pipe_map_skip(self._pipe, ops.C.byref(mp.stores()), mp.n_frames, self._map_K.data_ptr(), self._map_TBS.data_ptr(),
+                                               float(self.cam.baseline), int(time_ns)), "mv_frame_pipe_map_skip")
+            mp.n_frames += 1
+
+    def _keyframes_of(self, frames):
+        """:meth:`HotPath._keyframes_of`: the keyframes of ``frames``; the frames in between are skipped as they are passed."""
+        k = self.cfg.keyframe_freq
+        if k == 1:
+            yield from frames
+            return
+        for x in frames:
+            self._frame_index += 1
+            if self._frame_index % k == 0:
+                yield x
+            else:
+                self.skip(x.time_ns)
 
     @traced("Frontend.estimate")
     def enqueue_frontend(self, x: FrameInputs):
@@ -1320,9 +1477,10 @@ class NativeHotPath:
                 self.synchronize()                          # growth re-allocates the stores: rare (capacity doubles), so simply drain
                 mp.reserve(n_rows)
                 torch.cuda.synchronize()
-            L.check(lib.mv_frame_pipe_map_append(self._pipe, ops.C.byref(mp.stores()), mp.n_frames, mp.n_frames - 1,
+            L.check(lib.mv_frame_pipe_map_append(self._pipe, ops.C.byref(mp.stores()), mp.n_frames, mp.last_keyframe,
                                                  self._map_K.data_ptr(), self._map_TBS.data_ptr(), float(self.cam.baseline),
                                                  self._times.pop(0), None), "mv_frame_pipe_map_append")
+            mp.last_keyframe = mp.n_frames
             mp.n_frames += 1
             mp.rows_upper += n_rows
         map_pts = self._map_tail(mp) if self.cfg.mapping else None
@@ -1333,6 +1491,8 @@ class NativeHotPath:
             if self.keep_extras and not dd:
                 res.extras   # noqa: B018  (host-driven frames: build the views now, as before)
             out.append(res)
+        while self._skip_queue and self._skip_queue[0][0] <= self._n_fin:
+            self._skip_now(self._skip_queue.pop(0)[1])
         return out[0] if self.lanes == 1 else out
 
     def _extras_of(self, res: "_NativeResult") -> dict:
@@ -1432,7 +1592,7 @@ class NativeHotPath:
         the host has to run that far ahead for the GEMM stream to stay busy.  ``pose_sink``: ``[steps, 7]``
         (``[steps, lanes, 7]`` for lanes > 1) device tensor receiving each step's poses."""
         depth = self._depth if depth is None else depth
-        it = iter(frames)
+        it = iter(frames) if self.cfg.keyframe_freq == 1 else self._keyframes_of(frames)
         nxt = next(it, None)
         if self._pipe is not None and (self.device_driven or self._hostless):
             # Device-driven frames: nothing in a frame waits for the host, so a frame is enqueued and finished in one go (the next frame's GEMM in between, as

@@ -11,6 +11,7 @@ replace, every hot arithmetic step in the HIP kernels (``include/macvo_hip.h``).
     GaussianMixtureCovariance / NoCovariance  HIP_GaussianMixtureCovariance / HIP_NoCovariance
     Modifier_Diagonalize / Modifier_Normalize HIP_Modifier_Diagonalize / HIP_Modifier_Normalize  (fused into the kernel over a HIP model)
     TwoFrame_PGO                              HIP_TwoFrame_PGO
+    Local_TwoFrame_PGO                        HIP_Local_TwoFrame_PGO
     FlowFormerCovFrontend                     HIP_FlowFormerCovFrontend  (network stays PyTorch; lookups + epilogue in HIP)
     CUDAGraph_FlowFormerCovFrontend           HIP_CUDAGraph_FlowFormerCovFrontend  (same, inference replayed as a hipGraph)
     FlowFormerCovDepth / FlowFormerCovMatcher HIP_FlowFormerCovDepth / HIP_FlowFormerCovMatcher  (for FrontendCompose configs)
@@ -433,10 +434,20 @@ class HIP_TwoFrame_PGO(IOptimizer[GraphInput, dict, GraphOutput]):
             pixel2_disp=up(_bundle(obs, "pixel2_disp"), torch.float32).reshape(-1),
             pixel2_disp_cov=up(_bundle(obs, "pixel2_disp_cov"), torch.float32).reshape(-1),
             pixel2_uv_cov=up(_bundle(obs, "pixel2_uv_cov"), torch.float32), obs2_covTc=up(_bundle(obs, "obs2_covTc"), torch.float64))
-        pose, info = ops.pgo_solve(batch, context["graph_type"], context["lm"])
-        host = torch.empty((1, 7), dtype=torch.float64, pin_memory=True)
-        host.copy_(pose, non_blocking=True)
-        return host, info, batch
+        ref = getattr(g, "ref_pose", None)      # HIP_Local_TwoFrame_PGO.get_graph_data
+        if ref is None:
+            pose, info = ops.pgo_solve(batch, context["graph_type"], context["lm"])
+            host = torch.empty((1, 7), dtype=torch.float64, pin_memory=True)
+            host.copy_(pose, non_blocking=True)
+            return host, info, batch
+        # the local form: row 0 = the LM result in the optimisation frame (what the reference's _optimize returns), row 1 = the kernel's fp32 world pose
+        world = torch.empty((1, 7), dtype=torch.float32, device=dev)
+        pose, info = ops.pgo_solve(batch, context["graph_type"], context["lm"], out_pose_f32=world,
+                                   ref_pose=torch.as_tensor(ref).reshape(1, 7).to(dev, torch.float32, non_blocking=True))
+        host = torch.empty((2, 7), dtype=torch.float64, pin_memory=True)
+        host[0:1].copy_(pose, non_blocking=True)
+        host[1:2].copy_(world, non_blocking=True)     # (fp32 -> fp64 is exact)
+        return host, info, (batch, world)
 
     @staticmethod
     def _optimize(context: dict, graph_data: GraphInput):
@@ -482,6 +493,69 @@ class HIP_TwoFrame_PGO(IOptimizer[GraphInput, dict, GraphOutput]):
 
     def terminate(self) -> None:
         self._pending = None
+
+
+def _so3_act(q, p):           # PyPose SO3_Act on torch tensors (the reference's own CPU arithmetic: Optimizer.py:145-150 runs there too)
+    uv = torch.linalg.cross(q[..., :3], p)
+    uv = uv + uv
+    return p + q[..., 3:] * uv + torch.linalg.cross(q[..., :3], uv)
+
+
+def _optim_to_world(T_o2w: torch.Tensor, T_c2o: torch.Tensor) -> torch.Tensor:
+    """``NormalizeQuat(T_o2w @ T_c2o.to(T_o2w))`` (Optimizer.py:145-150, Utility/Math.py:124-133) on plain ``[7]`` tensors."""
+    a, b = T_o2w.reshape(7), T_c2o.reshape(7).to(T_o2w.dtype)
+    av, aw, bv, bw = a[3:6], a[6:], b[3:6], b[6:]
+    q = torch.cat([aw * bv + bw * av + torch.linalg.cross(av, bv), aw * bw - (av * bv).sum(-1, keepdim=True)])
+    return torch.cat([a[:3] + _so3_act(a[3:], b[:3]), q / q.norm(dim=-1, keepdim=True)])
+
+
+class HIP_Local_TwoFrame_PGO(HIP_TwoFrame_PGO):
+    """``Local_TwoFrame_PGO`` (Module/Optimization/TwoFramePGO/Optimizer.py:111-150): the same solve in the frame of the pose stored at map index
+    ``frame_idx - 1`` — numerically stabler in scenes 1000+ m across.  Same args as ``TwoFrame_PGO``, parallel and sequential modes.
+
+    ``get_graph_data`` reads ``pose[frame_idx - 1]`` when it is called and hands the WORLD-frame tables on: ``world_to_optim`` (:131-143) is applied
+    inside the kernel where a row is loaded, and ``optim_to_world`` (:145-150) at its end (``mv_pgo_solve_local``).  ``write_graph_data`` re-reads that
+    index, as the reference does; should the row have changed in between (it does not in ``MACVO.run_pair``'s call order) the local-frame result is
+    re-expressed with the row's new pose on the host."""
+
+    def get_graph_data(self, global_map, frame_idx, observations=None, edges=None) -> GraphInput:
+        g = super().get_graph_data(global_map, frame_idx, observations, edges)
+        self.T_o2w_idx = frame_idx - 1
+        g.ref_pose = torch.as_tensor(global_map.frames.data["pose"][frame_idx - 1]).detach().reshape(1, 7).to("cpu", torch.float32).clone()
+        return g
+
+    @staticmethod
+    def _optimize(context: dict, graph_data: GraphInput):
+        host, _, _keep = HIP_TwoFrame_PGO._launch(context, graph_data)
+        torch.cuda.current_stream().synchronize()
+        return context, HIP_Local_TwoFrame_PGO._output(host, graph_data)
+
+    @staticmethod
+    def _output(host: torch.Tensor, g: GraphInput) -> GraphOutput:
+        out = GraphOutput(motion=host[0:1].clone(), frame_idx=g.frame_idx, from_idx=g.from_idx)    # T_c2o, fp64
+        out.world_f32, out.ref_pose = host[1].to(torch.float32), g.ref_pose
+        return out
+
+    def get_result(self):
+        if self._pending is not None:
+            host, done, g, _keep, _ = self._pending
+            done.synchronize()
+            self.optimize_res = self._output(host, g)
+            self._pending = None
+            self.has_opt_job = False
+        return self.optimize_res
+
+    get_optimal = get_result
+
+    def write_graph_data(self, result, global_map) -> None:
+        if result is None:
+            return
+        T_o2w = torch.as_tensor(global_map.frames.data["pose"][self.T_o2w_idx]).detach().reshape(7).to("cpu", torch.float32)
+        if torch.equal(T_o2w, result.ref_pose.reshape(7)):
+            pose = result.world_f32
+        else:
+            pose = _optim_to_world(T_o2w, result.motion[0])
+        global_map.frames.data["pose"][result.frame_idx] = pose.reshape(1, 7)                           # Optimizer.py:104-108
 
 
 # ----------------------------------------------------------------------------------------------- IFrontend

@@ -104,6 +104,14 @@ CHECKS = [
     (r"^backend_front_kernel<", lambda r: r["private_segment_fixed_size"] == 0 and regs(r) <= 128, "backend front: fits beside a GEMM wave"),
     (r"^pgo_solve_kernel<\d, 4>", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0,
      "LM solve (4-wave form): one point per thread in registers, no spills (430-504 registers + 77 KB of LDS: it needs a CU without a GEMM workgroup)"),
+    (r"^pgo_solve_kernel<\d, 68>", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0,
+     "LM solve, motion-model form: the 4-wave form's budget"),
+    (r"^pgo_solve_kernel<[12], 132>", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0,
+     "LM solve, local-frame forms (REPROJ / DISP): no spills, the frame lives in LDS"),
+    (r"^pgo_solve_kernel<\d, 129>", lambda r: r["private_segment_fixed_size"] == 0,
+     "LM solve, local-frame one-wave forms: no scratch (as the world one-wave forms, up to 2 registers parked in AGPRs)"),
+    (r"^pgo_solve_kernel<0, 132>", lambda r: r["private_segment_fixed_size"] <= 16 and r["vgpr_spill_count"] <= 2 and r["group_segment_fixed_size"] <= 77552,
+     "LM solve, local-frame ICP form: at the 512-register limit, at most the 2 registers spilled outside the LM loop (DESIGN section 7)"),
     (r"^kp_nms_kernel<|^kp_finish_kernel<(1024, 16, 5|512, 16, 10)", lambda r: r["private_segment_fixed_size"] == 0,
      "selector at 640 x 480: no scratch (the 24-rows-per-thread finishing variant for larger images spills 61-74 registers)"),
 ]
