@@ -93,8 +93,9 @@ int mv_split_bf16x3(const float* x, void* planes, size_t n, mvStream_t stream);
  *   mv_patch_embed_pack   OIHW fp32 weights + biases of the three Conv2d layers -> fragment-ordered 16-bit (+ fp32 biases), once per model
  *   mv_cost_patch_embed   cost_maps [S, H2, W2] fp32 -> token_layout ? [S, (H2/8)*(W2/8), 64] : [S, 64, H2/8, W2/8] fp32; operand_type must be
  *                         the one `packed` was built with
- *   mv_cost_patch_embed_supported   the slice sizes the LDS plan covers: 60 x 80 (640x480 frames) and 64 x 80 (the padded slice PatchEmbed.forward hands
- *                                   to `proj`; 640x512 frames); others: MV_ERR_UNSUPPORTED */
+ *   mv_cost_patch_embed_supported   the slice sizes the kernels are instantiated for, each as the raw 1/8 slice and as the padded one PatchEmbed.forward
+ *                                   hands to `proj`: 60 / 64 x 80 (640x480, 640x512 frames), 80 x 80 (640x640), 90 / 96 x 160 (1280x720), 47 x 98 /
+ *                                   48 x 104 (KITTI, 376x784 frames) and 60 x 94 / 64 x 96 (EuRoC, 480x752); others: MV_ERR_UNSUPPORTED */
 size_t mv_patch_embed_packed_bytes(void);
 int mv_patch_embed_pack(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, void* packed,
                         int operand_type, mvStream_t stream);
@@ -116,8 +117,10 @@ int mv_cost_patch_embed_t(const void* cost_maps, int in_dtype, const void* packe
  * mv_volume_pack       both feature maps ([B,C,N] for MV_LAYOUT_CHW, [B,N,C] for MV_LAYOUT_HWC, fp32) -> packed operands
  *                      [B][ceil(N/32)+1 row blocks][C/16 k-steps][pieces][64 lanes][8 x 16 bit], one launch;
  *                      mv_volume_pack_bytes(B, C, N, mode) bytes each (0 = unsupported mode / shape).
- * mv_corr_volume_packed  out[b,i,j] fp32 [B,N1,N2] from two packed operands (C == 256, N2 % 64 == 0, N1*N2 < 2^30:
+ * mv_corr_volume_packed  out[b,i,j] fp32 [B,N1,N2] from two packed operands (C == 256, N1 >= 32, any N2 >= 64, N1*N2 < 2^30:
  *                      mv_corr_volume_packed_supported; MV_ERR_UNSUPPORTED otherwise — callers then use mv_corr_volume(MV_F32)).
+ *                      N2 % 64 != 0 (KITTI: 47 x 98 maps, EuRoC: 60 x 94): the last 64-column sub-tile of a row is partial — its
+ *                      operand rows past N2 are the pack's copies of row N2 - 1, its stores are lane-masked.
  * Two entry points because the pack needs nothing but the feature maps: the frame driver issues it on another stream one
  * frame ahead of the GEMM. */
 size_t mv_volume_pack_bytes(int B, int C, int N, int mode);
@@ -154,7 +157,8 @@ int mv_corr_lookup(const float* vol, const float* coords, float* out, int B, int
 /* Fast mode (Config/Experiment/MACVO/MACVO_Fast.yaml:73-74: enc_dtype fp16): with 16-bit feature maps the reference's `einsum` returns the
  * volume in that 16-bit type and Module/Network/FlowFormerCov/flownet.py:27 merely widens it.  mv_corr_volume_out16 is that einsum with its ONE
  * rounding (fp32 accumulators -> round-to-nearest-even -> in_dtype) in the GEMM's epilogue and 2-byte cells: out [B, N1, N2] of in_dtype, half the
- * bytes of the output-bound kernel.  HWC feature maps, C = 128 / 256, N2 % 64 == 0 (mv_corr_volume_out16_supported; MV_ERR_UNSUPPORTED otherwise:
+ * bytes of the output-bound kernel.  HWC feature maps, C = 128 / 256, an EVEN N2 >= 64 (a lane stores a column pair; N2 % 64 != 0: partial last
+ * sub-tile, operand rows clamped to N2 - 1, lane-masked stores) and B * N1 * N2 >= 2^22 (mv_corr_volume_out16_supported; MV_ERR_UNSUPPORTED otherwise:
  * use mv_corr_volume + a cast).  mv_corr_lookup_vol16 is mv_corr_lookup on such an fp16 volume (cells widened on load = `cost_maps.float()`,
  * everything behind the load identical to the fp32 form); radius 4. */
 int mv_corr_volume_out16_supported(int B, int C, int N1, int N2, int in_dtype, int layout);

@@ -1018,7 +1018,11 @@ __device__ long long* g_hs_stamps = nullptr;
 #else
 #define HS_STAMP(i) ((void)0)
 #endif
-template <bool IS_BF16, int KS, bool OUT16 = false>
+// RAG (OUT16 only): N2 is an even number, no multiple of 64 — a lane's dword holds a column pair; the last sub-tile of a row of items is partial.  This kernel reads
+// f2 itself, so the B rows of that sub-tile are CLAMPED to row N2 - 1 the way the tile kernels clamp theirs (no load leaves the operand), and the lanes whose
+// column lies past N2 are switched off in its stores (vol_asm.h).  Order and number of a wave's memory operations are those of the aligned form, which aligned
+// shapes keep running (RAG = false).  fp32 cells have no ragged form: the tile kernel measured faster there (mv_corr_volume).
+template <bool IS_BF16, int KS, bool OUT16 = false, bool RAG = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void corr_volume_h_stream(
     const uint16_t* __restrict__ f1, const uint16_t* __restrict__ f2, float* __restrict__ out, int N1, int N2, int B, int R) {
     constexpr int C = KS * 16, CH = KS * 2;      // channels; 16-byte chunks per row
@@ -1038,7 +1042,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int kh = lane >> 5, li = lane & 31;
-    const int nb = (N1 + 127) >> 7, nc = N2 >> 6;
+    const int nb = (N1 + 127) >> 7, nc = RAG ? (N2 + 63) >> 6 : N2 >> 6;
     // Item order: pair, then one of R column REGIONS (sub-tiles [g * nc / R, (g + 1) * nc / R)), then band, then sub-tile inside the
     // region.  The list is cut into 8 equal runs, one per XCD (workgroup id % 8 = XCD under round-robin dispatch), and each
     // XCD's run into equal runs for its gridDim / 8 workgroups: what an XCD reads at any time is ONE region's B rows (host picks
@@ -1079,6 +1083,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     ld_c0 = reg_c0(ld_g);
     ld_cend = reg_c0(ld_g + 1);
     const uint16_t* ld_ptr = f2 + ((size_t)ld_b * N2 + (size_t)ld_c * 64) * C;   // f2 row 0 of the (pair, sub-tile) of item ld_it
+    int ld_lim = RAG ? N2 - 1 - ld_c * 64 : 0;            // RAG: last row of f2 this sub-tile may read (>= 63: a full sub-tile)
     unsigned lane_src[NP];                       // element offset of this lane's source chunk inside the sub-tile, per instruction
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
@@ -1087,7 +1092,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     auto issue_piece = [&](int slot, int p) __attribute__((always_inline)) {   // piece p (constant after unrolling) of item ld_it -> ring slot
 #ifndef MV_HS_PROBE_NODMA                        // (probe builds: timing only)
-        glds16(ld_ptr + lane_src[p], lds0 + (unsigned)(slot * SLOT + (p * 4 + wave) * 64) * 16u);
+        unsigned src = lane_src[p];
+        if (RAG) {
+            // rows past N2 - 1 fetch row N2 - 1 — same chunk: the swizzle keys on the DESTINATION row.  The offset is rebuilt per piece from two lane
+            // constants instead of clamping lane_src[p] (four VALU operations either way): at C = 256 the aligned form already holds 252 of its 256
+            // registers and has no room for NP more offsets.
+            const unsigned lane_d = lane / CH, lane_pd = ((lane % CH) ^ (OUT16 ? lane_d >> 1 : lane_d)) << 3;   // row inside a piece; swizzled chunk (in elements) of a piece at row 0
+            const int base = (p * 4 + wave) * RPI, key = (OUT16 ? base >> 1 : base) & 15;   // (base % RPI == 0 and lane_d < RPI: | and ^ of the two coincide)
+            int lim = __builtin_amdgcn_readfirstlane(ld_lim);
+            asm volatile("" : "+s"(lim));        // computed HERE: hipcc otherwise derives all NP offsets where ld_lim changes and keeps them across the item
+            src = (unsigned)min(base + (int)lane_d, lim) * (unsigned)C + (lane_pd ^ (unsigned)(key << 3));
+        }
+        glds16(ld_ptr + src, lds0 + (unsigned)(slot * SLOT + (p * 4 + wave) * 64) * 16u);
 #endif
     };
     auto advance_b = [&]() __attribute__((always_inline)) {          // behind the last piece of an item
@@ -1106,6 +1122,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 ld_c = ld_c0;
             }
             ld_ptr = f2 + ((size_t)ld_b * N2 + (size_t)ld_c * 64) * C;
+            if (RAG) ld_lim = N2 - 1 - ld_c * 64;
         }
     };
     auto issue_b = [&](int slot) __attribute__((always_inline)) {   // prologue form: the NP pieces as one block
@@ -1123,6 +1140,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // Rows past N1 (last band) hold copies of row N1 - 1 (the A rows are clamped the same way): they are stored ON TOP of row
     // N1 - 1 with identical values instead of being branched around.
     unsigned roff[16];
+    static_assert(!RAG || OUT16, "the ragged form exists for 2-byte cells only");
+    int cur_c = 0;                               // RAG: sub-tile of the item being multiplied, and the lane mask of the item being stored (wave-uniform):
+    unsigned smk[1] = {~0u};                     // lanes l, l + 32 on while the column pair (2 l, 2 l + 1) lies inside N2
     auto pack16 = [&](float lo, float hi) __attribute__((always_inline)) -> unsigned {
         if (IS_BF16) return (unsigned)__builtin_bit_cast(uint16_t, (__bf16)lo) | ((unsigned)__builtin_bit_cast(uint16_t, (__bf16)hi) << 16);
         return (unsigned)__builtin_bit_cast(uint16_t, (_Float16)lo) | ((unsigned)__builtin_bit_cast(uint16_t, (_Float16)hi) << 16);
@@ -1135,7 +1155,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #ifdef MV_HS_PROBE_NOSTORE                       // (probe builds: timing only)
             asm volatile("" ::"v"(d), "v"(roff[r]), "s"(Ob));
 #else
-            asm volatile("global_store_dword %0, %1, %2" MV_VOL_STORE_ASM_MOD ::"v"(roff[r]), "v"(d), "s"(Ob) : "memory");
+            if (RAG) {
+                asm volatile(MV_VOL_STORE_MASKED_ASM("") ::"v"(roff[r]), "v"(d), "s"(Ob), "s"(smk[0]) : "memory");
+            } else
+                asm volatile("global_store_dword %0, %1, %2" MV_VOL_STORE_ASM_MOD ::"v"(roff[r]), "v"(d), "s"(Ob) : "memory");
 #endif
         } else {
             asm volatile("global_store_dword %0, %1, %2" MV_VOL_STORE_ASM_MOD ::"v"(roff[r]), "v"(p0[r]), "s"(Ob) : "memory");
@@ -1214,6 +1237,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         ++n_st;
 #endif
+        if (RAG) {                               // this item's accumulators are the next ones to be stored
+            smk[0] = vol_col_mask((N2 - cur_c * 64) >> 1);
+            ++cur_c;
+        }
         ++it;
         slot ^= 1;
         O += OADV;
@@ -1258,6 +1285,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int r = 0; r < 16; ++r)             // (OUT16: the lane's dword holds columns 2 li, 2 li + 1)
             roff[r] = ((unsigned)min(band * 128 + wave * 32 + 4 * kh + (r & 3) + 8 * (r >> 2), N1 - 1) * (unsigned)N2 + (OUT16 ? 2 * li : li)) * (unsigned)OSZ;
+        cur_c = c0i;
         step(No{}, x0, x1, x0, x1);
         while (it + 2 <= seg_end) {
             step(Yes{}, y0, y1, x0, x1);
@@ -1459,7 +1487,7 @@ void mv_note_volume_kernel(const char* name) { g_last_vol_kernel = name; }   // 
 
 // the streaming kernels number their (pair, 128-row band, 64-column sub-tile) items with an int
 static bool stream_items_fit(int B, int N1, int N2) {
-    return (size_t)B * (size_t)((N1 + 127) / 128) * (size_t)(N2 / 64) < ((size_t)1 << 31);
+    return (size_t)B * (size_t)((N1 + 127) / 128) * (size_t)((N2 + 63) / 64) < ((size_t)1 << 31);
 }
 
 #ifdef MV_HS_STAMPS
@@ -1469,8 +1497,10 @@ extern "C" int mv_hs_probe_stamps(long long* dev_buf) {   // (probe builds only)
 #endif
 
 // the 16-bit streaming kernel's domain and launch (shared by mv_corr_volume and mv_corr_volume_out16)
-static bool h_stream_supported(int B, int C, int N1, int N2) {
-    return (C == 256 || C == 128) && (N2 % 64) == 0 && ((size_t)N1 * N2 * B) >= ((size_t)1 << 22) &&
+// (N2 % 64 != 0: the ragged instantiations, which exist for 2-byte cells — an EVEN N2: a lane writes the column pair (2 l, 2 l + 1) as one dword; fp32 cells at a
+// ragged N2 stay with the tile kernel)
+static bool h_stream_supported(int B, int C, int N1, int N2, bool out16) {
+    return (C == 256 || C == 128) && N2 >= 64 && (out16 ? (N2 % 2) == 0 : (N2 % 64) == 0) && ((size_t)N1 * N2 * B) >= ((size_t)1 << 22) &&
            ((size_t)N1 * N2) < ((size_t)1 << 30) &&   // (32-bit byte offsets inside a pair's block of the output)
            stream_items_fit(B, N1, N2);               // (the item index T = B * bands * sub-tiles is an int)
 }
@@ -1496,6 +1526,7 @@ static int launch_h_stream(const uint16_t* a, const uint16_t* b, void* outp, boo
 #define MV_HS_ATTR(...) (void)hipFuncSetAttribute((const void*)corr_volume_h_stream<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
         MV_HS_ATTR(true, 16); MV_HS_ATTR(false, 16); MV_HS_ATTR(true, 8); MV_HS_ATTR(false, 8);
         MV_HS_ATTR(true, 16, true); MV_HS_ATTR(false, 16, true); MV_HS_ATTR(true, 8, true); MV_HS_ATTR(false, 8, true);
+        MV_HS_ATTR(true, 16, true, true); MV_HS_ATTR(false, 16, true, true); MV_HS_ATTR(true, 8, true, true); MV_HS_ATTR(false, 8, true, true);
 #undef MV_HS_ATTR
         attr_dev[dev].store(true, std::memory_order_release);
     }
@@ -1504,12 +1535,16 @@ static int launch_h_stream(const uint16_t* a, const uint16_t* b, void* outp, boo
     // 1 region (2.4 MB) 47.5 us, 2 regions 41.2, 3: 43.6; 1280x720 4 regions (1.8 MB) 324 us, 6 regions 345)
     static int regs_env = -1;  // MV_H_STREAM_REGIONS: A/B knob
     if (regs_env < 0) { const char* e = getenv("MV_H_STREAM_REGIONS"); regs_env = e ? atoi(e) : 0; }
-    const int nc = N2 / 64;
+    const int nc = (N2 + 63) / 64;               // (the last sub-tile is partial when N2 % 64 != 0: the RAG instantiations)
     int R = regs_env > 0 ? regs_env : (int)(((size_t)nc * 64 * C * 2 + (2u << 20) - 1) / (2u << 20));
     R = std::max(1, std::min(R, nc));
     MV_VOL_KERNEL(out16 ? "corr_volume_h_stream<out16>" : "corr_volume_h_stream");
 #define MV_HS_GO(...) hipLaunchKernelGGL((corr_volume_h_stream<__VA_ARGS__>), g, blk, lds, s, a, b, out, N1, N2, B, R)
-    if (out16) {
+    if (N2 % 64) {                               // ragged: 2-byte cells only (h_stream_supported)
+        if (!out16) return MV_ERR_UNSUPPORTED;
+        if (C == 256) { if (bf) MV_HS_GO(true, 16, true, true); else MV_HS_GO(false, 16, true, true); }
+        else { if (bf) MV_HS_GO(true, 8, true, true); else MV_HS_GO(false, 8, true, true); }
+    } else if (out16) {
         if (C == 256) { if (bf) MV_HS_GO(true, 16, true); else MV_HS_GO(false, 16, true); }
         else { if (bf) MV_HS_GO(true, 8, true); else MV_HS_GO(false, 8, true); }
     } else {
@@ -1623,7 +1658,9 @@ extern "C" int mv_corr_volume(const void* f1, const void* f2, float* out, int B,
             if (C % 32) return MV_ERR_UNSUPPORTED;
             static int hstream = -1;   // MV_H_STREAM=0: the tile form below (A/B knob)
             if (hstream < 0) { const char* e = getenv("MV_H_STREAM"); hstream = (e && atoi(e) == 0) ? 0 : 1; }
-            if (hstream && h_stream_supported(B, C, N1, N2)) return launch_h_stream(a, b, out, false, bf, B, C, N1, N2, s);
+            // (fp32 cells at a ragged N2 stay with the tile kernel below: measured at N = 4606 / 5640, B = 2, it is the faster of the two there — 81 / 88 us against
+            // 106 / 99 us for the streaming form —, while for 2-byte cells the ragged streaming form wins, 66 / 100 us against 106 / 141 us for tile kernel + cast)
+            if (hstream && h_stream_supported(B, C, N1, N2, false)) return launch_h_stream(a, b, out, false, bf, B, C, N1, N2, s);
             MV_VOL_KERNEL("corr_volume_h_hwc");
             static int hbk = -1;
             if (hbk < 0) { const char* e = getenv("MV_H_BK"); hbk = e ? atoi(e) : 32; }
@@ -1649,10 +1686,10 @@ extern "C" int mv_corr_volume(const void* f1, const void* f2, float* out, int B,
 }
 
 // A5, Fast mode: the volume in the ENCODER's 16-bit type (what `einsum` returns for fp16 / bf16 feature maps; flownet.py:27 widens it afterwards).
-// One rounding in the GEMM's epilogue, 2-byte cells: [B, N1, N2] of in_dtype.  HWC feature maps, C = 128 / 256, N2 % 64 == 0 (the streaming
-// kernel's domain): MV_ERR_UNSUPPORTED otherwise — callers then use mv_corr_volume + a cast.  Read it with mv_corr_lookup_vol16 (fp16).
+// One rounding in the GEMM's epilogue, 2-byte cells: [B, N1, N2] of in_dtype.  HWC feature maps, C = 128 / 256, an even N2 >= 64 (the streaming
+// kernel's domain for 2-byte cells; an odd N2 is not supported: a lane stores a column pair): MV_ERR_UNSUPPORTED otherwise — callers then use mv_corr_volume + a cast.  Read it with mv_corr_lookup_vol16 (fp16).
 extern "C" int mv_corr_volume_out16_supported(int B, int C, int N1, int N2, int in_dtype, int layout) {
-    return (in_dtype == MV_F16 || in_dtype == MV_BF16) && layout == MV_LAYOUT_HWC && B > 0 && N1 > 0 && N2 > 0 && h_stream_supported(B, C, N1, N2);
+    return (in_dtype == MV_F16 || in_dtype == MV_BF16) && layout == MV_LAYOUT_HWC && B > 0 && N1 > 0 && N2 > 0 && h_stream_supported(B, C, N1, N2, true);
 }
 extern "C" int mv_corr_volume_out16(const void* f1, const void* f2, void* out, int B, int C, int N1, int N2, int in_dtype, int layout,
                                     mvStream_t stream) {

@@ -235,7 +235,10 @@ __constant__ long long* g_split_stamps = nullptr;   // [workgroup][wave][64 item
 #define STAMP(i) ((void)0)
 #endif
 
-template <int NP, bool F16, int KS, int NWV>
+// RAG: N2 is no multiple of 64 — the last sub-tile of a row of items is partial.  Its B rows past N2 are the pack's copies of row N2 - 1 (no
+// load leaves the packed operand) and the lanes whose column lies past N2 are switched off in its stores (vol_asm.h); everything else, the
+// order and number of this wave's memory operations included, is the aligned form.  Aligned shapes run the RAG = false instantiations.
+template <int NP, bool F16, int KS, int NWV, bool RAG = false>
 __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV / 4, NWV / 4))) void corr_volume_split_stream(
     const uint16_t* __restrict__ pk1, const uint16_t* __restrict__ pk2, float* __restrict__ out, int N1, int N2, int B, int R) {
     using Cf = SplitCfg<NP, F16, KS, NWV>;
@@ -249,7 +252,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV / 
     const int wr = NWV == 8 ? wave >> 1 : wave;
     const int jb0 = NWV == 8 ? wave & 1 : 0;
     const int kh = lane >> 5, li = lane & 31;
-    const int nb = (N1 + 127) >> 7, nc = N2 >> 6;
+    const int nb = (N1 + 127) >> 7, nc = RAG ? (N2 + 63) >> 6 : N2 >> 6;
     const int nrb1 = ((N1 + 31) >> 5) + 1, nrb2 = ((N2 + 31) >> 5) + 1;   // row blocks per pair incl. the replica block
     const int per = nb * nc, T = B * per;                                  // T < 2^31 (host-checked)
     int it, it_end;
@@ -372,6 +375,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV / 
     };
 
     float* O = nullptr;                          // wave-uniform: column 0 of the CURRENT item's output block (row 0 of the pair)
+    unsigned smk[2] = {~0u, ~0u};             // RAG: lane masks of the two column blocks of the item whose accumulators are being stored (wave-uniform)
     unsigned roff[16];                           // per-lane byte offsets of the 16 accumulator rows (C/D layout), fixed for a band segment
 #ifdef MV_SPLIT_PROBE_STORE4
     unsigned toff[4];                            // (probe) lane l -> row 8 g + l / 8, 16-byte column chunk l % 8
@@ -403,9 +407,15 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV / 
                 asm volatile("" ::"v"(v));
             }
 #else
-            if (j == 0) asm volatile("global_store_dword %0, %1, %2" MV_VOL_STORE_ASM_MOD ::"v"(roff[r]), "v"(v), "s"(Ob) : "memory");
+            if (RAG) {
+                if (j == 0) asm volatile(MV_VOL_STORE_MASKED_ASM("") ::"v"(roff[r]), "v"(v), "s"(Ob), "s"(smk[0]) : "memory");
+                else asm volatile(MV_VOL_STORE_MASKED_ASM(" offset:128") ::"v"(roff[r]), "v"(v), "s"(Ob), "s"(smk[1]) : "memory");
+            } else if (j == 0) asm volatile("global_store_dword %0, %1, %2" MV_VOL_STORE_ASM_MOD ::"v"(roff[r]), "v"(v), "s"(Ob) : "memory");
             else asm volatile("global_store_dword %0, %1, %2 offset:128" MV_VOL_STORE_ASM_MOD ::"v"(roff[r]), "v"(v), "s"(Ob) : "memory");
 #endif
+        } else if (RAG) {
+            if (j == 0) asm volatile(MV_VOL_STORE_MASKED_ASM("") ::"v"(roff[r]), "a"(pj[r]), "s"(Ob), "s"(smk[0]) : "memory");
+            else asm volatile(MV_VOL_STORE_MASKED_ASM(" offset:128") ::"v"(roff[r]), "a"(pj[r]), "s"(Ob), "s"(smk[1]) : "memory");
         } else {
             if (j == 0) asm volatile("global_store_dword %0, %1, %2" MV_VOL_STORE_ASM_MOD ::"v"(roff[r]), "a"(pj[r]), "s"(Ob) : "memory");
             else asm volatile("global_store_dword %0, %1, %2 offset:128" MV_VOL_STORE_ASM_MOD ::"v"(roff[r]), "a"(pj[r]), "s"(Ob) : "memory");
@@ -562,6 +572,11 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV / 
     auto item = [&](auto W0, auto W1, auto PREV, auto FK, f32x16& c0, f32x16& c1, const f32x16& p0, const f32x16& p1, int (&ec)[2], int (&ep)[2]) __attribute__((always_inline)) {
         half(H0{}, W0, PREV, FK, c0, c1, p0, p1, ec, ep);
         half(H1{}, W1, PREV, FK, c0, c1, p0, p1, ec, ep);
+        if (RAG) {                               // this item's accumulators are the next ones to be stored (all its own stores of the item before are out)
+            const int rem = N2 - cur_c * 64 - jb0 * 32;
+            smk[0] = vol_col_mask(rem);
+            smk[1] = vol_col_mask(rem - 32);
+        }
         ++cur_c;
 #ifdef MV_SPLIT_PROBE
         if (DBG(16) && lane == 0 && n_stamped < 64) {
@@ -740,9 +755,9 @@ extern "C" int mv_volume_pack_tiled(const float* f1, const float* f2, void* pack
 // shapes the streaming GEMM covers (the caller falls back to the exact fp32 kernel otherwise — never less accurate)
 extern "C" int mv_corr_volume_packed_supported(int B, int C, int N1, int N2, int mode) {
     // (cu_count() >= 8: the persistent grid is a multiple of 8 workgroups, one run per XCD — part of "supported" so that callers fall back BEFORE they pack)
-    return cu_count() >= 8 && pieces_of(mode) != 0 && C == 256 && B > 0 && B <= 65535 && N1 >= 32 && N2 >= 64 && (N2 % 64) == 0 &&
+    return cu_count() >= 8 && pieces_of(mode) != 0 && C == 256 && B > 0 && B <= 65535 && N1 >= 32 && N2 >= 64 &&
            ((size_t)N1 * N2) < ((size_t)1 << 30) &&                                               // 32-bit byte offsets inside a pair's block
-           (size_t)B * (size_t)((N1 + 127) / 128) * (size_t)(N2 / 64) < ((size_t)1 << 31);        // int item index
+           (size_t)B * (size_t)((N1 + 127) / 128) * (size_t)((N2 + 63) / 64) < ((size_t)1 << 31);   // int item index
 }
 
 extern "C" int mv_corr_volume_packed(const void* packed1, const void* packed2, float* out, int B, int C, int N1, int N2, int mode,
@@ -767,6 +782,8 @@ extern "C" int mv_corr_volume_packed_shared(const void* packed1, const void* pac
     if (!attr_done[dev].load(std::memory_order_acquire)) {
         (void)hipFuncSetAttribute((const void*)corr_volume_split_stream<3, false, 16, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)corr_volume_split_stream<2, true, 16, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)corr_volume_split_stream<3, false, 16, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)corr_volume_split_stream<2, true, 16, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done[dev].store(true, std::memory_order_release);
     }
     if (cu_count() < 8) return MV_ERR_UNSUPPORTED;   // the persistent grid is a multiple of 8 workgroups (one run per XCD): callers fall back to the exact kernel
@@ -777,7 +794,8 @@ extern "C" int mv_corr_volume_packed_shared(const void* packed1, const void* pac
     // band segments (each segment change reloads 192 KB of A fragments per workgroup, ~3 us) against L2 hits on the B sub-tiles
     static int regs_env = -1;   // MV_SPLIT_REGIONS: A/B knob
     if (regs_env < 0) { const char* e = getenv("MV_SPLIT_REGIONS"); regs_env = e ? atoi(e) : 0; }
-    const int nc = N2 / 64;
+    const int nc = (N2 + 63) / 64;               // (the last sub-tile is partial when N2 % 64 != 0: the RAG instantiations)
+    const bool rag = (N2 % 64) != 0;
     int R = regs_env > 0 ? regs_env : (int)(((size_t)nc * 64 * C * 2 * np + (4u << 20) - 1) / (4u << 20));
     R = std::max(1, std::min(R, nc));
 #ifdef MV_SPLIT_PROBE
@@ -804,13 +822,21 @@ extern "C" int mv_corr_volume_packed_shared(const void* packed1, const void* pac
     if (mode == MV_PACK_BF16X3) {
         using K = SplitCfg<3, false, 16, 4>;
         mv_note_volume_kernel("corr_volume_split_stream<bf16x3>");
-        hipLaunchKernelGGL((corr_volume_split_stream<3, false, 16, 4>), g, dim3(256), lds_bytes(K::NSLOT * K::SLOT_BYTES), (hipStream_t)stream,
-                           (const uint16_t*)packed1, (const uint16_t*)packed2, out, N1, N2, B, R);
+        if (rag)
+            hipLaunchKernelGGL((corr_volume_split_stream<3, false, 16, 4, true>), g, dim3(256), lds_bytes(K::NSLOT * K::SLOT_BYTES), (hipStream_t)stream,
+                               (const uint16_t*)packed1, (const uint16_t*)packed2, out, N1, N2, B, R);
+        else
+            hipLaunchKernelGGL((corr_volume_split_stream<3, false, 16, 4>), g, dim3(256), lds_bytes(K::NSLOT * K::SLOT_BYTES), (hipStream_t)stream,
+                               (const uint16_t*)packed1, (const uint16_t*)packed2, out, N1, N2, B, R);
     } else {
         using K = SplitCfg<2, true, 16, 4>;
         mv_note_volume_kernel("corr_volume_split_stream<f16x2>");
-        hipLaunchKernelGGL((corr_volume_split_stream<2, true, 16, 4>), g, dim3(256), lds_bytes(K::NSLOT * K::SLOT_BYTES), (hipStream_t)stream,
-                           (const uint16_t*)packed1, (const uint16_t*)packed2, out, N1, N2, B, R);
+        if (rag)
+            hipLaunchKernelGGL((corr_volume_split_stream<2, true, 16, 4, true>), g, dim3(256), lds_bytes(K::NSLOT * K::SLOT_BYTES), (hipStream_t)stream,
+                               (const uint16_t*)packed1, (const uint16_t*)packed2, out, N1, N2, B, R);
+        else
+            hipLaunchKernelGGL((corr_volume_split_stream<2, true, 16, 4>), g, dim3(256), lds_bytes(K::NSLOT * K::SLOT_BYTES), (hipStream_t)stream,
+                               (const uint16_t*)packed1, (const uint16_t*)packed2, out, N1, N2, B, R);
     }
     return mv_launch_status();
 }

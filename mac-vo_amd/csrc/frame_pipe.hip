@@ -377,6 +377,8 @@ static size_t carve(mvFramePipe* p, char* base) {
     for (int k = 0; k < 2 * (L <= 2 ? MAX_LK : 1); ++k) p->tok[k] = a.take<float>(B * p->KK * n8);
     for (int k = 0; k < 2; ++k)
         p->planes[k] = (c.volume_split == 2 || c.volume_split == 3) ? (void*)a.take<uint16_t>(3 * B * n8 * c.C) : nullptr;
+    // (ceil(n8 / 32) + 1 row blocks per pair: the rounded-up last block and the replica block the GEMM's ragged last sub-tile reads — n8 % 64 != 0, 376 x 784 and
+    // 480 x 752 frames — are inside; the volume itself keeps its pitch of n8 cells)
     p->pk_bytes = p->packed ? mv_volume_pack_bytes((int)B, c.C, (int)n8, c.volume_split) : 0;
     for (int k = 0; k < 2; ++k)
         for (int o = 0; o < 2; ++o) p->pk[k][o] = p->packed ? (void*)a.take<char>(p->pk_bytes) : nullptr;

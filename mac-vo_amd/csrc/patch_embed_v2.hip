@@ -12,7 +12,10 @@
 //
 //   every layer's LDS buffer is a WINDOW of the zero-padded map (window row = map row - r0); only the rows of the window that exist in the map are
 //   computed, the others are zeroed, so the halo rows between strips are recomputed (90 x 160, R3 = 4: conv2 x 1.33, conv1 x 1.5: + 17 % of the FLOPs) and a
-//   slice that fits (80 x 80, 60 x 80: one strip) pays nothing.  No state is carried between strips: (slice, strip) items are spread over the persistent
+//   slice that fits (80 x 80, 60 x 80: one strip) pays nothing.  The KITTI and EuRoC slices (47 x 98 / 48 x 104: 6 x 13 tokens, R3 = 6, 127 KB of LDS;
+//   60 x 94 / 64 x 96: 8 x 12 tokens, R3 = 8, 131 KB) are one strip each too: halo cost 0.  Their raw forms have rows of 98 / 94 cells, which start on
+//   8-byte (fp32) / 4-byte (16-bit) boundaries only: the staging loads are cell PAIRS there (PG::NARROW); the columns W2 .. WP - 1 are never written and stay
+//   the zeros F.pad would put there, as the rows H2 .. HP - 1 do.  No state is carried between strips: (slice, strip) items are spread over the persistent
 //   workgroups like slices were.
 //
 // Implicit GEMMs as in patch_embed.hip (v_mfma_f32_16x16x32, K = taps x input channels, cin innermost, maps stored [8-channel chunk][column parity][row]
@@ -25,6 +28,7 @@
 #include "patch_embed_dev.h"
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 using namespace pe;
 
@@ -60,7 +64,9 @@ struct PG {
     static constexpr int pad_xh(int lo, int r) { int x = lo; while (x % 8 != r) ++x; return x; }
     // a 16-lane read group walks up to two consumer rows of L pixels (L = Wc for the conv1 map, W3 for the conv2 map), 2 x pitch cells apart: the groups tile
     // the 16 slots of a bank row when 2 x pitch = L (mod 16): L = 20 -> pitch = 2 (mod 8), 10 -> 5, 40 -> 4 (model: 1.00x for all three geometries)
-    static_assert(Wc % 2 == 0 && W3 % 2 == 0, "even consumer rows");
+    // (an odd token row — W3 = 13: 104 padded columns — has no such pitch: 2 x pitch = 12 (mod 16) makes the second row of a group start one slot early; the model
+    // gives conv3's fragment reads 2.0x their ideal cycles there.  Its formula is kept, the addresses are right for any pitch)
+    static_assert(Wc % 2 == 0, "even consumer rows of the conv1 map");
     static constexpr int O1_XH = pad_xh(O1_COLS / 2, (Wc % 16) / 2);
     static constexpr int O2_XH = pad_xh(O2_COLS / 2, (W3 % 16) / 2);
     static constexpr unsigned plane_pad(unsigned b) { return b + ((128u + 256u - b % 256u) % 256u); }   // -> = 128 (mod 256): the four 16-lane groups of a
@@ -80,7 +86,10 @@ struct PG {
     static constexpr unsigned RED_BYTES = 2u * NT3 * 2 * 64 * 16;
     static_assert(RED_BYTES <= IN0_BYTES + O1_BYTES, "K-half exchange area");
     static constexpr int EPL32 = 4, EPL16 = 8;
-    static_assert(W2 % 8 == 0, "16-byte staging loads of 16-bit cells");
+    // staging loads: 16 bytes where every row of the slice starts on a 16-byte boundary for both cell sizes (W2 % 8 == 0); otherwise (98- and 94-cell rows: 8-byte
+    // aligned as fp32, 4-byte aligned as 16-bit cells) NARROW loads of one cell PAIR — more load instructions for the same registers
+    static constexpr bool NARROW = W2 % 8 != 0;
+    static_assert(W2 % 2 == 0, "cell pairs: 8-byte (fp32) / 4-byte (16-bit) staging loads");
 };
 
 // One (slice, strip) item.  All row quantities are uniform (SGPRs).
@@ -120,7 +129,7 @@ __global__ __launch_bounds__(256) void cost_patch_embed_strip_kernel(const void*
     char* const o1 = smem_pe2 + P::OFF_O1;
     char* const o2 = smem_pe2 + P::OFF_O2;
     const char* const vol = reinterpret_cast<const char*>(vol_);
-    constexpr int EPL = IN16 ? P::EPL16 : P::EPL32;                           // cells per 16-byte load
+    constexpr int EPL = P::NARROW ? 2 : IN16 ? P::EPL16 : P::EPL32;           // cells per staging load (16 bytes; NARROW: a cell pair)
     constexpr int RQ = W2 / EPL;                                              // loads per input row
     constexpr int NPRE = cdiv(P::ROWSIN * RQ, 256);
     constexpr int ESZ = IN16 ? 2 : 4;
@@ -165,7 +174,9 @@ __global__ __launch_bounds__(256) void cost_patch_embed_strip_kernel(const void*
     __syncthreads();
 
     // staging: this thread's 16-byte pieces of the NEXT item's input window travel in registers while the current one is convolved
-    i32x4 pre[NPRE];
+    // (NARROW: a pair of fp32 cells travels as ONE 64-bit scalar, a pair of 16-bit cells as one dword)
+    using PreT = std::conditional_t<!P::NARROW, i32x4, std::conditional_t<IN16, unsigned, unsigned long long>>;
+    PreT pre[NPRE];
     auto fetch = [&](int item) {
         const bool live = item < S * P::NS;
         const Strip sn = make_strip<P>(live ? item : 0);
@@ -174,6 +185,9 @@ __global__ __launch_bounds__(256) void cost_patch_embed_strip_kernel(const void*
             const int q = t + 256 * i;
             const int row = q / RQ, y = sn.r0_in + row;
             const bool ok = live && row < sn.nin && y >= 0 && y < H2;
+            if constexpr (P::NARROW)
+                pre[i] = ok ? __builtin_nontemporal_load(reinterpret_cast<const PreT*>(vol + ((size_t)sn.slice * (H2 * W2) + (size_t)y * W2) * ESZ) + (q - row * RQ)) : PreT(0);
+            else
             pre[i] = ok ? __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(vol + ((size_t)sn.slice * (H2 * W2) + (size_t)y * W2) * ESZ) + (q - row * RQ))
                         : i32x4{0, 0, 0, 0};
         }
@@ -209,7 +223,10 @@ __global__ __launch_bounds__(256) void cost_patch_embed_strip_kernel(const void*
             const int row = q / RQ, x = EPL * (q - row * RQ);
             if (row < st.nin) {
                 unsigned* d = reinterpret_cast<unsigned*>(in0 + (row * P::IN_PITCH + x + 2) * 2);
-                if constexpr (IN16) {
+                if constexpr (P::NARROW) {
+                    if constexpr (IN16) d[0] = (unsigned)pre[i];
+                    else d[0] = cvt_pack<F16>(__builtin_bit_cast(float, (unsigned)pre[i]), __builtin_bit_cast(float, (unsigned)(pre[i] >> 32)));
+                } else if constexpr (IN16) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) d[e] = (unsigned)pre[i][e];
                 } else {
@@ -472,9 +489,15 @@ int mv_cost_patch_embed_strip(const void* cost_maps, int in16, const void* packe
     if (H2 == 96 && W2 == 160) return dispatch_strip<96, 160, 4>(cost_maps, in16, packed, out, out16, S, token_layout, f16, st);    // the padded slice PatchEmbed.forward hands over
     if (H2 == 60 && W2 == 80) return dispatch_strip<60, 80, 8>(cost_maps, in16, packed, out, out16, S, token_layout, f16, st);      // (A/B against patch_embed.hip: MV_PE_STRIP=1)
     if (H2 == 64 && W2 == 80) return dispatch_strip<64, 80, 8>(cost_maps, in16, packed, out, out16, S, token_layout, f16, st);
+    // KITTI (376 x 784 frames: 47 x 98 maps) and EuRoC (480 x 752: 60 x 94) as PatchEmbed.forward hands their slices to `proj`, padded to multiples of 8; one strip each
+    if (H2 == 47 && W2 == 98) return dispatch_strip<47, 98, 6>(cost_maps, in16, packed, out, out16, S, token_layout, f16, st);      // the raw slices: cell-pair staging
+    if (H2 == 60 && W2 == 94) return dispatch_strip<60, 94, 8>(cost_maps, in16, packed, out, out16, S, token_layout, f16, st);
+    if (H2 == 48 && W2 == 104) return dispatch_strip<48, 104, 6>(cost_maps, in16, packed, out, out16, S, token_layout, f16, st);    // 6 x 13 = 78 tokens
+    if (H2 == 64 && W2 == 96) return dispatch_strip<64, 96, 8>(cost_maps, in16, packed, out, out16, S, token_layout, f16, st);      // 8 x 12 = 96 tokens
     return MV_ERR_UNSUPPORTED;
 }
 
 int mv_cost_patch_embed_strip_supported(int H2, int W2) {
-    return (H2 == 80 && W2 == 80) || ((H2 == 90 || H2 == 96) && W2 == 160) || ((H2 == 60 || H2 == 64) && W2 == 80);
+    return (H2 == 80 && W2 == 80) || ((H2 == 90 || H2 == 96) && W2 == 160) || ((H2 == 60 || H2 == 64) && W2 == 80) ||
+           (H2 == 47 && W2 == 98) || (H2 == 48 && W2 == 104) || (H2 == 60 && W2 == 94) || (H2 == 64 && W2 == 96);
 }

@@ -40,6 +40,17 @@ __device__ __forceinline__ void glds16_next(unsigned voff, const void* sbase) {
     asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" ::"v"(voff), "s"(sbase), "n"(OFF) : "memory");
 }
 
+// ---- the ragged column edge of the streaming kernels (N2 % 64 != 0) ----
+// A store of theirs writes one volume row x 32 (or 64) columns, one column (pair) per lane.  In the last, partial sub-tile of a row the
+// lanes whose column lies past N2 are switched off for that ONE instruction: EXEC is set to the (wave-uniform) mask and back to all-ones
+// inside the statement (these kernels never diverge: every branch of theirs is wave-uniform and all 256 threads stay to the end).  The
+// store is issued whatever the mask — with every lane off too — so it counts in vmcnt like any other and the hand-counted waits hold
+// unchanged.  Operands: %0 lane offset, %1 data, %2 scalar base, %3 the 32-bit mask, applied to lanes l and l + 32 alike.
+#define MV_VOL_STORE_MASKED_ASM(IMM) \
+    "s_mov_b32 exec_lo, %3\n\ts_mov_b32 exec_hi, %3\n\tglobal_store_dword %0, %1, %2" IMM MV_VOL_STORE_ASM_MOD "\n\ts_mov_b64 exec, -1"
+// lanes (l, l + 32) on for l < rem: the mask of a 32-column block with `rem` columns left (all on for rem >= 32, none for rem <= 0)
+__device__ __forceinline__ unsigned vol_col_mask(int rem) { return rem >= 32 ? 0xffffffffu : rem <= 0 ? 0u : (1u << rem) - 1u; }
+
 // LDS-DMA: 64 lanes x 16 B from per-lane global addresses to LDS bytes [lds_dst, lds_dst + 1024) in lane order.  M0 carries the
 // destination and is compiler-reserved: saved, written and restored inside the one statement.  Invisible to hipcc's s_waitcnt
 // bookkeeping (counted by hand, see the kernel).

@@ -70,7 +70,7 @@ def corr_volume(f1: torch.Tensor, f2: torch.Tensor, layout: str = "chw", out: to
     precision (fp32 inputs only; None = ``default_volume_precision()``, 16-bit inputs ignore it): "exact" = fp32 MFMA (bitwise fmaf chain); "f16x2" = rows scaled by a power of two into fp16's
     range, two fp16 pieces, three products (error <= ~2^-21 sum |a||b|: inside the parity bar, the fastest form); "bf16x3" = operands packed into three bf16 pieces
     (``volume_pack``) + the streaming six-product kernel on the 16-bit matrix pipe, fp32-class accuracy (same parity bar as
-    "exact", not bitwise), either layout, shapes the kernel does not cover fall back to "exact"; "split3" / "split2" = the
+    "exact", not bitwise), either layout, shapes the kernel does not cover (C != 256, N1 < 32, N2 < 64 — any larger N2, multiple of 64 or not) fall back to "exact"; "split3" / "split2" = the
     round-1/2 tile kernels over pre-split planes (6 / 3 products; "split2": relative error ~2^-16, finer than TF32, the class
     the reference's fast frontend allows itself) — both layout "hwc" only.
     Returns ``cost_maps [B*H1*W1, 1, H2, W2]`` float32 (layout "hwc" with 3-D inputs: ``[B*N1, 1, 1, N2]``).
@@ -163,7 +163,7 @@ def volume_pack(f1: torch.Tensor, f2: torch.Tensor, layout: str = "chw", out: "t
 def corr_volume_packed(pk1: torch.Tensor, pk2: torch.Tensor, B: int, C_: int, N1: int, N2: int, out: torch.Tensor | None = None,
                        mode: str = "bf16x3", free_cus: int = 0) -> torch.Tensor:
     """The cost volume ``[B*N1, 1, 1, N2]`` fp32 from two packed operands (``mv_corr_volume_packed``: six bf16 / three fp16 piece
-    products, fp32 accumulate).  ``free_cus``: compute units left without a persistent workgroup (``mv_corr_volume_packed_shared``;
+    products, fp32 accumulate; C = 256, N1 >= 32, any N2 >= 64).  ``free_cus``: compute units left without a persistent workgroup (``mv_corr_volume_packed_shared``;
     same bits)."""
     lib = L.load()
     if out is None:
@@ -245,7 +245,7 @@ def corr_volume_out16(f1: torch.Tensor, f2: torch.Tensor, out: torch.Tensor | No
                       scratch: torch.Tensor | None = None) -> torch.Tensor | None:
     """Fast mode (enc_dtype fp16 / bf16, MACVO_Fast.yaml:73-74): the volume in the encoder's 16-bit type — what ``einsum`` returns there and
     flownet.py:27 widens — rounded ONCE in the GEMM's epilogue.  ``f1, f2 [B, H, W, C]`` (HWC) fp16 / bf16 -> ``[B*H1*W1, 1, H2, W2]`` of that
-    dtype; ``None`` for shapes outside the streaming kernel's domain (callers then cast ``corr_volume``'s fp32 result).
+    dtype; ``None`` for shapes outside the streaming kernel's domain — C not 128 / 256, N2 < 64 or odd, B * N1 * N2 < 2^22 — (callers then cast ``corr_volume``'s fp32 result).
     ``tiled``: every slice in 4 x 4-cell tiles (``fmap_tile_rows16`` on ``f2`` first, into ``scratch`` if given) for
     ``corr_lookup(..., tiled=True)``."""
     lib = L.load()

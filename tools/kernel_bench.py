@@ -140,6 +140,61 @@ def main():
                 print(f"  unfused torch conv2d chain (bf16, channels_last, MIOpen): {e0.elapsed_time(e1) * 1e3 / 3:8.1f} us")
             except Exception as e:  # noqa: BLE001
                 print("  unfused torch conv2d chain failed:", repr(e)[:200])
+        elif w == "dataset_ab":
+            # KITTI / EuRoC frames (--H 376 --W 784: 47 x 98 maps, N = 4606; --H 480 --W 752: 60 x 94, N = 5640): N2 % 64 != 0.  Every kernel that serves such a frame
+            # next to what served it before the ragged edge was built, in alternating rounds (the spread of a leg over the rounds is its run-to-run spread):
+            #   fp32 features   : precision "exact" (the former dispatch for f16x2 / bf16x3 at these N)        vs  pack + corr_volume_split_stream<f16x2 | bf16x3>
+            #   fp16 features   : 2-byte cells as corr_volume_h_hwc + cast (MV_H_STREAM=0 in the environment: another process)   vs  corr_volume_h_stream<out16>;
+            #                     fp32 cells run corr_volume_h_hwc either way (no ragged streaming form: it measured slower)
+            #   patch embedding : the three Conv2d layers (MIOpen) on the padded slices   vs  cost_patch_embed on the padded and on the RAW slices (fp32 cells; 16-bit cells in / tokens out)
+            import torch.nn.functional as F
+            from tools.synth import patch_embed_weights
+            a1, a2 = f1.permute(0, 2, 3, 1).contiguous().half(), f2.permute(0, 2, 3, 1).contiguous().half()
+            v16 = torch.empty((B * n, 1, h8, w8), dtype=torch.float16, device=dev)
+            Wt = [t.to(dev) for t in patch_embed_weights(0)]
+            pk = ops.PatchEmbedWeights(*Wt, operand="f16")
+            S = n                                                  # one pair's slices
+            m3 = ((h8 + 7) // 8) * ((w8 + 7) // 8)
+            raw32 = torch.randn(S, 1, h8, w8, device=dev) * 16
+            cells32 = F.pad(raw32, (0, (8 - w8 % 8) % 8, 0, (8 - h8 % 8) % 8)).contiguous()   # as PatchEmbed.forward hands them to `proj`
+            raw16 = raw32.half()
+            cells16 = cells32.half()
+            tok32, tok16 = torch.empty((S, m3, 64), dtype=torch.float32, device=dev), torch.empty((S, m3, 64), dtype=torch.float16, device=dev)
+            w16 = [t.half() for t in Wt]
+
+            def layers(x, wts):
+                y = F.relu(F.conv2d(x, wts[0], wts[1], stride=2, padding=2))
+                y = F.relu(F.conv2d(y, wts[2], wts[3], stride=2, padding=2))
+                return F.conv2d(y, wts[4], wts[5], stride=2, padding=2)
+
+            def vol16_cast():                                       # 2-byte cells without the out16 kernel: the fp32-cell volume + a cast
+                v16.copy_(ops.corr_volume(a1, a2, "hwc", out=vol))
+
+            def vol16():                                            # (MV_H_STREAM=0 switches the fp32-cell dispatch only: that process takes the cast form here too)
+                if os.environ.get("MV_H_STREAM", "1") == "0" or ops.corr_volume_out16(a1, a2, out=v16) is None:
+                    vol16_cast()
+
+            legs = [("volume fp32 exact", lambda: ops.corr_volume(f1, f2, "chw", out=vol, precision="exact")),
+                    ("volume fp32 f16x2 (pack + GEMM)", lambda: ops.corr_volume(f1, f2, "chw", out=vol, precision="f16x2")),
+                    ("volume fp32 bf16x3 (pack + GEMM)", lambda: ops.corr_volume(f1, f2, "chw", out=vol, precision="bf16x3")),
+                    ("volume fp16 hwc, fp32 cells", lambda: ops.corr_volume(a1, a2, "hwc", out=vol)),
+                    ("volume fp16 hwc, 2-byte cells", vol16),
+                    ("patch embed: Conv2d layers fp32", lambda: layers(cells32, Wt)),
+                    ("patch embed: fused, fp32 cells", lambda: ops.cost_patch_embed(cells32, pk, tokens=True, out=tok32)),
+                    ("patch embed: Conv2d layers fp16", lambda: layers(cells16, w16)),
+                    ("patch embed: fused, fp16 cells + tokens", lambda: ops.cost_patch_embed(cells16, pk, tokens=True, out=tok16)),
+                    ("patch embed: fused, RAW fp32 cells", lambda: ops.cost_patch_embed(raw32, pk, tokens=True, out=tok32)),
+                    ("patch embed: fused, RAW fp16 cells + tokens", lambda: ops.cost_patch_embed(raw16, pk, tokens=True, out=tok16))]
+            rounds, res, names = 7, {k: [] for k, _ in legs}, {}
+            for r in range(rounds):
+                for k, fn in legs:
+                    res[k].append(timeit(fn, max(3, a.iters // 10), warm=2 if r else 5)[0])
+                    if k.startswith("volume"):
+                        names[k] = ops.last_volume_kernel()
+            print(f"dataset_ab {H}x{W}: maps {h8}x{w8}, N = {n} (N % 64 = {n % 64}), B = {B}, S = {S}, MV_H_STREAM={os.environ.get('MV_H_STREAM', '1')}; us per call, median of the rounds [min .. max]")
+            for k, _ in legs:
+                v = sorted(res[k])
+                print(f"  {k:42s} {statistics.median(v):9.1f} [{v[0]:9.1f} .. {v[-1]:9.1f}]  {names.get(k, '')}")
         elif w == "volume_f16":
             for dt in (torch.float16, torch.bfloat16):
                 a1, a2 = f1.permute(0, 2, 3, 1).contiguous().to(dt), f2.permute(0, 2, 3, 1).contiguous().to(dt)
