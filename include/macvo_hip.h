@@ -649,6 +649,42 @@ int mv_body_poses(const float* pose, const float* T_BS, int T, float* out, mvStr
 int mv_motion_interpolate(float* pose, const uint8_t* need_interp, int T, double* scratch, int32_t* out_count,
                           mvStream_t stream);
 
+/* Lane-batched registration: `lanes` INDEPENDENT sequences, each into its OWN map, in one launch (one workgroup per lane).  This is what the reference's
+ * multi-sequence driver does one sequence after the other (Scripts/Experiment/Experiment_MACVO.py:55-58: every sequence runs MACVO.run_pair and keeps its own
+ * VisualMap) — per lane exactly mv_map_append: Odometry/MACVO.py:244-311,339-347 on Module/Map/VisualMap.py:15-133 + Module/Map/Graph.py:86-104,144-147,
+ * 183-186,228-229.  The tables are the frame driver's backend buffers as they lie: per-keypoint tables [lanes, cap, .], the value table [11, lanes, cap] (row
+ * stride lanes * cap, lane l at column l * cap), valid [lanes, cap] or NULL.  n_rows / time_ns are HOST arrays [lanes] (n_rows[l] <= cap; a device-driven frame
+ * passes cap and lets `valid` compact); T_BS and prior_pose are device [lanes, 7]; K, baseline, prev_frame, min_num_point are the same for every lane.
+ * stores_dev is a DEVICE array mvMapStores[lanes] (at MV_MAX_LANES x ~45 pointers the descriptors do not fit in kernel arguments); it must not be rewritten
+ * while a launch that reads it may be in flight.  Refusal (counts[4] += 1, nothing else written) is decided per lane. */
+typedef struct {
+    int32_t lanes, cap;
+    int32_t prev_frame;       /* map index of the previous keyframe (the lanes advance in lock-step), -1 for the first frame */
+    int32_t min_num_point;
+    const int32_t* n_rows;    /* HOST [lanes] */
+    const int64_t* time_ns;   /* HOST [lanes] */
+    const uint8_t* valid;     /* [lanes, cap] or NULL */
+    const float *kp0, *kp1;   /* [lanes, cap, 2] */
+    const float* vals;        /* [11, lanes, cap] */
+    const float *sigma0, *sigma1;       /* [lanes, cap, 3] */
+    const double *cov0, *cov1;          /* [lanes, cap, 9] */
+    const float* pos_Tw;      /* [lanes, cap, 3] */
+    const double* cov0_world; /* [lanes, cap, 9] */
+    const uint8_t* color;     /* [lanes, cap, 3] or NULL */
+    const float* K;           /* [9] device */
+    const float* T_BS;        /* [lanes, 7] device */
+    const float* prior_pose;  /* [lanes, 7] device or NULL (identity) */
+    float baseline;
+} mvMapFrameLanes;
+int mv_map_append_lanes(const mvMapFrameLanes* frames /* host */, const mvMapStores* stores_dev /* DEVICE [lanes] */, mvStream_t stream);
+/* mv_map_append_skipped for every lane (Odometry/MACVO.py:177-179,339-348): one need_interp row per lane with pose_dev[l] ([lanes, 7], each lane's prior) and
+ * T_BS_dev[l]; time_ns is a HOST array [lanes]. */
+int mv_map_append_skipped_lanes(const mvMapStores* stores_dev /* DEVICE [lanes] */, int lanes, const float* K_dev, const float* T_BS_dev, const float* pose_dev,
+                                float baseline, const int64_t* time_ns /* host [lanes] */, mvStream_t stream);
+/* write_graph_data (Module/Optimization/TwoFramePGO/Optimizer.py:104-108) for every lane: pose_dev [lanes, 7] over row frame_idx of each lane's frames.pose
+ * (the lanes' stores are different allocations, so one copy cannot do it).  A row outside a lane's store is left alone. */
+int mv_map_set_pose_lanes(const mvMapStores* stores_dev /* DEVICE [lanes] */, int lanes, int frame_idx, const float* pose_dev, mvStream_t stream);
+
 /* -------------------------------------------------------------------------------------------
  * Lane-batched variants: the same kernels over `lanes` INDEPENDENT frames (sequences) in ONE launch.  This is the
  * reference's batching point (Module/Frontend/Frontend.py:219-224 concatenates pairs along the batch axis) carried through
@@ -983,6 +1019,16 @@ int mv_frame_pipe_skip(mvFramePipe* p);
  * frame_idx = the map index the row receives (= frames pushed so far). */
 int mv_frame_pipe_map_skip(mvFramePipe* p, const mvMapStores* stores /* host */, int frame_idx, const float* K_dev, const float* T_BS_dev,
                            float baseline, int64_t time_ns);
+/* The two calls above for a pipe of ANY lane count (lanes >= 1), every lane into its own map (Scripts/Experiment/Experiment_MACVO.py:55-58 keeps one VisualMap
+ * per sequence; per lane Odometry/MACVO.py:244-311,339-347 and :177-179): ONE mv_map_append_lanes / mv_map_append_skipped_lanes launch on the backend stream
+ * behind the finish's e_solved / e_posed, then ONE mv_map_set_pose_lanes launch on the solve stream behind it (Optimizer.py:104-108).  stores_dev: DEVICE
+ * mvMapStores[lanes]; T_BS_dev: [lanes, 7]; time_ns: HOST [lanes]; frame_idx / prev_frame are the same for every lane (lock-step).  Same call positions as the
+ * one-lane forms.  Once mv_frame_pipe_map_append_lanes has been used, a front launch that runs on a decoder-side stream waits for the append that last read
+ * its backend slot before it rewrites the slot's tables.  A pipe that never makes these calls issues exactly the launches and waits it issued before. */
+int mv_frame_pipe_map_append_lanes(mvFramePipe* p, const mvMapStores* stores_dev /* DEVICE [lanes] */, int frame_idx, int prev_frame, const float* K_dev,
+                                   const float* T_BS_dev, float baseline, const int64_t* time_ns /* host [lanes] */);
+int mv_frame_pipe_map_skip_lanes(mvFramePipe* p, const mvMapStores* stores_dev /* DEVICE [lanes] */, int frame_idx, const float* K_dev, const float* T_BS_dev,
+                                 float baseline, const int64_t* time_ns /* host [lanes] */);
 /* Result views and slot reuse: a consumer that reads result views (mv_frame_pipe_buffer) asynchronously on its own stream
  * calls this before it finishes the next frame; the pipe then orders the kernels that recycle those buffers behind
  * everything enqueued on `stream` so far.  (Host-synchronous consumers do not need it.) */

@@ -84,6 +84,12 @@ class mvMapFrame(C.Structure):
         [("baseline", C.c_float), ("time_ns", C.c_int64), ("out_frame_idx", C.c_void_p)]
 
 
+class mvMapFrameLanes(C.Structure):
+    _fields_ = [("lanes", C.c_int32), ("cap", C.c_int32), ("prev_frame", C.c_int32), ("min_num_point", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("n_rows", "time_ns", "valid", "kp0", "kp1", "vals", "sigma0", "sigma1", "cov0", "cov1", "pos_Tw", "cov0_world",
+                                   "color", "K", "T_BS", "prior_pose")] + [("baseline", C.c_float)]
+
+
 class mvFrameInputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("fmap1", "fmap2", "coords", "flow", "logcov", "flow8", "cov8", "up_mask",
                                           "cov_mask")]
@@ -241,6 +247,12 @@ SIGNATURES = {
     "mv_frame_pipe_timeline": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "mv_frame_pipe_timeline_backend": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "mv_frame_pipe_buffer": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    # one map per lane of a batched pipe (stores: a DEVICE array mvMapStores[lanes]; time_ns: a host int64 array [lanes])
+    "mv_map_append_lanes": (C.c_int, [C.POINTER(mvMapFrameLanes), _P, _P]),
+    "mv_map_append_skipped_lanes": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_float, _P, _P]),
+    "mv_map_set_pose_lanes": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "mv_frame_pipe_map_append_lanes": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_float, _P]),
+    "mv_frame_pipe_map_skip_lanes": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_float, _P]),
 }
 
 _lib = None

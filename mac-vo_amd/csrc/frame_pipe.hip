@@ -241,6 +241,8 @@ struct mvFramePipe {
     int solve_frame = MV_SOLVE_WORLD;   // mv_frame_pipe_set_solve_frame
     bool skipped = false;               // mv_frame_pipe_skip since the newest finish
     hipEvent_t e_map;
+    hipEvent_t e_mapl[2];     // backend slot k: mv_frame_pipe_map_append_lanes has finished reading the slot's tables
+    bool mapl_valid[2];       // ... recorded (written by the caller's thread behind flush_jobs, read by whoever issues the later finishes)
     int newest_maps;
     std::deque<Pending> pending;
     // dense-mapping tail (config.mapping; lanes == 1)
@@ -584,6 +586,7 @@ extern "C" void mv_frame_pipe_destroy(mvFramePipe* p) {
     ev(p->e_packed[0]);
     ev(p->e_packed[1]);
     ev(p->e_map);
+    for (int k = 0; k < 2; ++k) ev(p->e_mapl[k]);
     ev(p->e_release);
     for (auto e : p->e_perm) ev(e);
     for (auto e : p->tv0) ev(e);
@@ -660,6 +663,10 @@ static int create_impl(mvFramePipe* p) {
     MV_HIP(mk(&p->e_packed[0]));
     MV_HIP(mk(&p->e_packed[1]));
     MV_HIP(mk(&p->e_map));
+    for (int k = 0; k < 2; ++k) {
+        MV_HIP(mk(&p->e_mapl[k]));
+        p->mapl_valid[k] = false;
+    }
     MV_HIP(mk(&p->e_release));
     const size_t N = (size_t)cap_of(c);
     for (int k = 0; k < N_PERM; ++k) {   // (a slot holds a finish's permutations [lanes, cap] or its keypoint rows [lanes, cap, 2])
@@ -1394,6 +1401,9 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     // reads views asynchronously on its own stream calls it before it asks for the next frame).
     if (p->solved_valid[k] && s != p->s_side) MV_TRY(wait_if_pending(s, p->e_solved[k]));   // (alt layout: backend and solve share one in-order stream)
     if (p->release_valid) MV_TRY(wait_if_pending(s, p->e_release));
+    // ... and by mv_frame_pipe_map_append_lanes of frame g - 2 on the backend stream: in order with a front launch that runs there, an event for one on a
+    // decoder-side stream (a 64-lane append takes longer than a one-lane one: timing does not hold this off)
+    if (p->mapl_valid[k] && s != p->s_back) MV_TRY(wait_if_pending(s, p->e_mapl[k]));
     // permutations [lanes, cap] -> pinned slot -> device (ONE copy; rows beyond a lane's n_sel are never read)
     const int ps = (int)(g % N_PERM);
     if (!j.device && p->dev_draw) MV_HIP(pass_generators());   // (a host-permuted finish)
@@ -1834,6 +1844,58 @@ extern "C" int mv_frame_pipe_map_skip(mvFramePipe* p, const mvMapStores* stores,
     // copy and would put the backend stream behind work it does not depend on.)
     if (g >= 0) MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[g & 1] : p->e_posed[g & 1], 0));
     MV_TRY(mv_map_append_skipped(stores, K_dev, T_BS_dev, prior, baseline, time_ns, p->s_back));
+    MV_HIP(hipEventRecord(p->e_map, p->s_back));
+    return MV_OK;
+}
+
+// mv_frame_pipe_map_append / _map_skip for any lane count, every lane into its own map: one launch for all lanes (mv_map_append_lanes), the optimised poses
+// behind it by one launch on the solve stream (each lane's destination is another allocation).
+extern "C" int mv_frame_pipe_map_append_lanes(mvFramePipe* p, const mvMapStores* stores_dev, int frame_idx, int prev_frame, const float* K_dev,
+                                              const float* T_BS_dev, float baseline, const int64_t* time_ns) {
+    MV_CHECK_ARG(p && stores_dev && K_dev && T_BS_dev && time_ns && p->n_fin > 0 && frame_idx >= 0);
+    MV_TRY(flush_jobs(p));
+    const mvFramePipeConfig& c = p->c;
+    const long g = p->n_fin - 1;
+    const int k = (int)(g & 1);
+    const Backend& b = p->be[k];
+    mvMapFrameLanes f{};
+    f.lanes = p->lanes;
+    f.cap = cap_of(c);
+    f.prev_frame = prev_frame;
+    f.min_num_point = c.min_num_point;
+    f.n_rows = b.n_sel;   // (device-driven frames: the upper bound, `valid` compacts)
+    f.time_ns = time_ns;
+    f.valid = b.valid;
+    f.kp0 = b.kp0f; f.kp1 = b.kp1; f.vals = b.vals; f.sigma0 = b.sigma0; f.sigma1 = b.sigma1;
+    f.cov0 = b.cov0; f.cov1 = b.cov1; f.pos_Tw = b.pos_Tw; f.cov0_world = b.cov0w;
+    f.color = nullptr;
+    f.K = K_dev; f.T_BS = T_BS_dev;
+    f.prior_pose = c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];   // push_keyframe(frame1, est_pose) (MACVO.py:282)
+    f.baseline = baseline;
+    MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[k] : p->e_posed[k], 0));   // pos_Tw / cov0_world come from the side stream
+    MV_TRY(mv_map_append_lanes(&f, stores_dev, p->s_back));
+    MV_HIP(hipEventRecord(p->e_map, p->s_back));
+    if (p->front_on_decoder) {   // what the front launch of finish g + 2 waits for where it does not run on this stream (no packet for a pipe that has none)
+        MV_HIP(hipEventRecord(p->e_mapl[k], p->s_back));
+        p->mapl_valid[k] = true;
+    }
+    // the optimised poses go in after the append wrote the priors
+    MV_HIP(hipStreamWaitEvent(p->s_side, p->e_map, 0));
+    MV_TRY(mv_map_set_pose_lanes(stores_dev, p->lanes, frame_idx, p->pose[p->pose_cur], p->s_side));
+    MV_HIP(hipEventRecord(p->e_pgo, p->s_side));
+    p->pgo_valid = true;
+    return MV_OK;
+}
+
+extern "C" int mv_frame_pipe_map_skip_lanes(mvFramePipe* p, const mvMapStores* stores_dev, int frame_idx, const float* K_dev, const float* T_BS_dev,
+                                            float baseline, const int64_t* time_ns) {
+    MV_CHECK_ARG(p && stores_dev && K_dev && T_BS_dev && time_ns && p->n_enq > 0 && frame_idx >= 1);
+    MV_TRY(flush_jobs(p));
+    const long g = p->n_fin - 1;   // the previous keyframe's finish (-1: frame 0, pushed at the poses set by mv_frame_pipe_set_pose)
+    const float* prior = g < 0 ? p->pose[p->pose_cur] : p->c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];
+    // (the same ordering argument as mv_frame_pipe_map_skip: the prior slot is written in front of finish g's solve)
+    if (g >= 0) MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[g & 1] : p->e_posed[g & 1], 0));
+    MV_TRY(mv_map_append_skipped_lanes(stores_dev, p->lanes, K_dev, T_BS_dev, prior, baseline, time_ns, p->s_back));
     MV_HIP(hipEventRecord(p->e_map, p->s_back));
     return MV_OK;
 }

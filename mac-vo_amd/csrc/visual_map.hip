@@ -120,7 +120,9 @@ __device__ __forceinline__ Se3d load_pose(const float* p) {
 }
 
 // ------------------------------------------------------------------------------------------------ registration
-__global__ __launch_bounds__(256) void map_append_kernel(mvMapFrame fr, mvMapStores st) {
+// One frame into one map, by one 256-thread workgroup: the body of map_append_kernel (one frame per launch) and of map_append_lanes_kernel (one workgroup per
+// lane).  `fr` / `st` are wave-uniform; every row offset comes from st.counts and is checked against the capacities before the first store.
+__device__ __forceinline__ void map_append_frame(const mvMapFrame& fr, const mvMapStores& st) {
     __shared__ int wave_cnt[4];
     __shared__ int base_match, base_point, frame_idx;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -236,11 +238,60 @@ __global__ __launch_bounds__(256) void map_append_kernel(mvMapFrame fr, mvMapSto
     }
 }
 
+__global__ __launch_bounds__(256) void map_append_kernel(mvMapFrame fr, mvMapStores st) { map_append_frame(fr, st); }
+
+// Lane-batched registration: `lanes` independent sequences, each with its own map, in ONE launch.  The frames' tables are the frame driver's backend buffers
+// as they lie ([lanes, cap, .] per keypoint, the value table [11, lanes, cap]); the per-lane host values ride in the kernel arguments; the maps' descriptors
+// (~45 pointers each: too many for kernel arguments at 64 lanes) are a device-resident array indexed by the lane.
+struct MapLaneFrames {
+    int32_t lanes, cap, prev_frame, min_num_point;
+    const uint8_t* valid;
+    const float *kp0, *kp1, *vals, *sigma0, *sigma1;
+    const double *cov0, *cov1;
+    const float* pos_Tw;
+    const double* cov0_world;
+    const uint8_t* color;
+    const float *K, *T_BS, *prior_pose;
+    float baseline;
+    int32_t n_rows[MV_MAX_LANES];
+    int64_t time_ns[MV_MAX_LANES];
+};
+struct MapLaneTimes {
+    int64_t t[MV_MAX_LANES];
+};
+
+__global__ __launch_bounds__(256) void map_append_lanes_kernel(MapLaneFrames a, const mvMapStores* __restrict__ stores) {
+    const int l = blockIdx.x;   // one workgroup per lane: a lane that is refused returns on its own, the others never see it
+    if (l >= a.lanes) return;
+    const size_t o = (size_t)l * a.cap;
+    mvMapFrame fr;
+    fr.n_rows = a.n_rows[l];
+    fr.table_stride = a.lanes * a.cap;   // value table [11, lanes, cap]: row stride lanes * cap, this lane's columns at l * cap
+    fr.prev_frame = a.prev_frame;
+    fr.min_num_point = a.min_num_point;
+    fr.valid = a.valid ? a.valid + o : nullptr;
+    fr.kp0 = a.kp0 + 2 * o; fr.kp1 = a.kp1 + 2 * o;
+    fr.vals = a.vals + o;
+    fr.sigma0 = a.sigma0 + 3 * o; fr.sigma1 = a.sigma1 + 3 * o;
+    fr.cov0 = a.cov0 + 9 * o; fr.cov1 = a.cov1 + 9 * o;
+    fr.pos_Tw = a.pos_Tw + 3 * o;
+    fr.cov0_world = a.cov0_world + 9 * o;
+    fr.color = a.color ? a.color + 3 * o : nullptr;
+    fr.K = a.K;
+    fr.T_BS = a.T_BS + 7 * (size_t)l;
+    fr.prior_pose = a.prior_pose ? a.prior_pose + 7 * (size_t)l : nullptr;
+    fr.baseline = a.baseline;
+    fr.time_ns = a.time_ns[l];
+    fr.out_frame_idx = nullptr;
+    const mvMapStores st = stores[l];   // (wave-uniform loads)
+    if (!st.counts) return;
+    map_append_frame(fr, st);
+}
+
 // a non-keyframe (UniformKeyframe: Odometry/MACVO.py:177-179 -> push_keyframe(frame1, pose of the previous keyframe, need_interp=True), :339-348): one frame row
 // flagged for interpolation, no match / point rows, no frame2match range; only the frame count advances (it is not a lost frame)
-__global__ void map_skip_kernel(mvMapStores st, const float* __restrict__ K, const float* __restrict__ T_BS, const float* __restrict__ pose, float baseline,
-                                int64_t time_ns) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ void map_skip_row(const mvMapStores& st, const float* __restrict__ K, const float* __restrict__ T_BS, const float* __restrict__ pose,
+                                             float baseline, int64_t time_ns) {
     int64_t* cnt = st.counts;
     const int64_t F = cnt[0];
     if (F >= st.cap_frames) {   // refused like any append when the store is full
@@ -263,6 +314,33 @@ __global__ void map_skip_kernel(mvMapStores st, const float* __restrict__ K, con
     st.frame2match_num[f] = 0;
     st.frame2map_num[f] = 0;
     cnt[0] = F + 1;
+}
+
+__global__ void map_skip_kernel(mvMapStores st, const float* __restrict__ K, const float* __restrict__ T_BS, const float* __restrict__ pose, float baseline,
+                                int64_t time_ns) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    map_skip_row(st, K, T_BS, pose, baseline, time_ns);
+}
+
+// ... of every lane: thread l writes lane l's row (its own map, its own pose and T_BS [lanes, 7], its own timestamp)
+__global__ __launch_bounds__(MV_MAX_LANES) void map_skip_lanes_kernel(const mvMapStores* __restrict__ stores, int lanes, const float* __restrict__ K,
+                                                                     const float* __restrict__ T_BS, const float* __restrict__ pose, float baseline,
+                                                                     MapLaneTimes times) {
+    const int l = threadIdx.x;
+    if (blockIdx.x != 0 || l >= lanes) return;
+    const mvMapStores st = stores[l];
+    if (!st.counts) return;
+    map_skip_row(st, K, T_BS + 7 * (size_t)l, pose + 7 * (size_t)l, baseline, times.t[l]);
+}
+
+// write_graph_data (Optimizer.py:104-108) of every lane: the optimised poses [lanes, 7] over the priors the frames were pushed with, row frame_idx of each map
+__global__ void map_set_pose_lanes_kernel(const mvMapStores* __restrict__ stores, int lanes, int frame_idx, const float* __restrict__ pose) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 7 * lanes) return;
+    const int l = i / 7;
+    float* dst = stores[l].pose;
+    if (!dst || frame_idx < 0 || (int64_t)frame_idx >= stores[l].cap_frames) return;
+    dst[7 * (size_t)frame_idx + (i - 7 * l)] = pose[i];
 }
 
 // dense-mapping tail: map_points.push + frame2map.add for the newest frame (Odometry/MACVO.py:329-337)
@@ -428,6 +506,44 @@ extern "C" int mv_map_append_skipped(const mvMapStores* stores, const float* K_d
     MV_CHECK_ARG(s.K && s.baseline && s.pose && s.T_BS && s.need_interp && s.time_ns && s.frame2match_ranges && s.frame2match_num &&
                  s.frame2map_ranges && s.frame2map_num);
     hipLaunchKernelGGL(map_skip_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, s, K_dev, T_BS_dev, pose_dev, baseline, time_ns);
+    return mv_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------ lane-batched forms (one launch for all lanes)
+extern "C" int mv_map_append_lanes(const mvMapFrameLanes* frames, const mvMapStores* stores_dev, mvStream_t stream) {
+    MV_CHECK_ARG(frames && stores_dev);
+    const mvMapFrameLanes& f = *frames;
+    MV_CHECK_ARG(f.lanes >= 1 && f.lanes <= MV_MAX_LANES && f.cap >= 0 && f.n_rows && f.time_ns && f.K && f.T_BS);
+    MV_CHECK_ARG((int64_t)f.lanes * f.cap <= INT32_MAX);
+    MapLaneFrames a{};
+    int n_max = 0;
+    for (int l = 0; l < f.lanes; ++l) {
+        MV_CHECK_ARG(f.n_rows[l] >= 0 && f.n_rows[l] <= f.cap);
+        a.n_rows[l] = f.n_rows[l];
+        a.time_ns[l] = f.time_ns[l];
+        n_max = f.n_rows[l] > n_max ? f.n_rows[l] : n_max;
+    }
+    MV_CHECK_ARG(n_max == 0 || (f.kp0 && f.kp1 && f.vals && f.sigma0 && f.sigma1 && f.cov0 && f.cov1 && f.pos_Tw && f.cov0_world));
+    a.lanes = f.lanes; a.cap = f.cap; a.prev_frame = f.prev_frame; a.min_num_point = f.min_num_point;
+    a.valid = f.valid; a.kp0 = f.kp0; a.kp1 = f.kp1; a.vals = f.vals; a.sigma0 = f.sigma0; a.sigma1 = f.sigma1;
+    a.cov0 = f.cov0; a.cov1 = f.cov1; a.pos_Tw = f.pos_Tw; a.cov0_world = f.cov0_world; a.color = f.color;
+    a.K = f.K; a.T_BS = f.T_BS; a.prior_pose = f.prior_pose; a.baseline = f.baseline;
+    hipLaunchKernelGGL(map_append_lanes_kernel, dim3(f.lanes), dim3(256), 0, (hipStream_t)stream, a, stores_dev);
+    return mv_launch_status();
+}
+
+extern "C" int mv_map_append_skipped_lanes(const mvMapStores* stores_dev, int lanes, const float* K_dev, const float* T_BS_dev, const float* pose_dev,
+                                           float baseline, const int64_t* time_ns, mvStream_t stream) {
+    MV_CHECK_ARG(stores_dev && lanes >= 1 && lanes <= MV_MAX_LANES && K_dev && T_BS_dev && pose_dev && time_ns);
+    MapLaneTimes t{};
+    for (int l = 0; l < lanes; ++l) t.t[l] = time_ns[l];
+    hipLaunchKernelGGL(map_skip_lanes_kernel, dim3(1), dim3(MV_MAX_LANES), 0, (hipStream_t)stream, stores_dev, lanes, K_dev, T_BS_dev, pose_dev, baseline, t);
+    return mv_launch_status();
+}
+
+extern "C" int mv_map_set_pose_lanes(const mvMapStores* stores_dev, int lanes, int frame_idx, const float* pose_dev, mvStream_t stream) {
+    MV_CHECK_ARG(stores_dev && lanes >= 1 && lanes <= MV_MAX_LANES && frame_idx >= 0 && pose_dev);
+    hipLaunchKernelGGL(map_set_pose_lanes_kernel, dim3(mv_ceil_div(7 * lanes, 256)), dim3(256), 0, (hipStream_t)stream, stores_dev, lanes, frame_idx, pose_dev);
     return mv_launch_status();
 }
 

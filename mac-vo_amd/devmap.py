@@ -267,3 +267,130 @@ class DeviceVisualMap:
         os.makedirs(folder, exist_ok=True)
         np.save(os.path.join(folder, "poses.npy"), self.poses_array())
         np.savez_compressed(os.path.join(folder, "tensor_map.npz"), **self.serialize())
+
+
+class DeviceVisualMaps:
+    """One :class:`DeviceVisualMap` per lane of a batched frame pipe — what the reference's multi-sequence driver keeps, one ``VisualMap`` per sequence
+    (``Scripts/Experiment/Experiment_MACVO.py:55-58``).  Every lane's frame is registered by ONE launch (``mv_map_append_lanes``: one workgroup per lane),
+    which finds the lanes' stores through a DEVICE array ``mvMapStores[lanes]`` this holder owns (64 lanes x ~45 pointers do not fit in kernel arguments).
+
+    The array names allocations: after a ``reserve`` that re-grew a store it is stale and :meth:`upload` must rewrite it — only while no launch that reads
+    it can be in flight (drain the pipe, ``reserve``, ``upload``, synchronise: ``NativeHotPath`` does exactly that).  :meth:`stores_dev` refuses a stale array
+    instead of handing out pointers into freed memory.  Capacity bookkeeping (``n_frames``, ``rows_upper``, ``last_keyframe``) stays with each map."""
+
+    def __init__(self, lanes: int | None = None, device: str | torch.device = "cuda", init_size=1024, maps: "list[DeviceVisualMap] | None" = None, **kw):
+        if maps is None:
+            sizes = list(init_size) if isinstance(init_size, (list, tuple)) else [init_size] * int(lanes)
+            if len(sizes) != lanes:
+                raise ValueError(f"init_size: {len(sizes)} sizes for {lanes} lanes")
+            maps = [DeviceVisualMap(device, init_size=s, **kw) for s in sizes]
+        self.maps = list(maps)
+        if not 1 <= len(self.maps) <= L.MV_MAX_LANES:
+            raise L.MacvoHipError(f"lanes must be in [1, {L.MV_MAX_LANES}]")
+        if lanes is not None and lanes != len(self.maps):
+            raise ValueError(f"{len(self.maps)} maps for {lanes} lanes")
+        self.lanes = len(self.maps)
+        self.dev = self.maps[0].dev
+        if any(m.dev != self.dev for m in self.maps):
+            raise L.MacvoHipError("DeviceVisualMaps: every map on the same device")
+        self.lib = L.load()
+        self._desc = torch.zeros(self.lanes * C.sizeof(L.mvMapStores), dtype=torch.uint8, device=self.dev)
+        self._uploaded: list = [None] * self.lanes
+        self.upload()
+
+    def __len__(self) -> int:
+        return self.lanes
+
+    def __getitem__(self, lane: int) -> DeviceVisualMap:
+        return self.maps[lane]
+
+    def __iter__(self):
+        return iter(self.maps)
+
+    def stale(self) -> bool:
+        return any(m.stores() is not u for m, u in zip(self.maps, self._uploaded))
+
+    def upload(self) -> None:
+        """Rewrite the device descriptor array from the members' ``stores()`` (a blocking copy on the current stream).  The caller guarantees that no launch
+        reading the array is in flight."""
+        cur = [m.stores() for m in self.maps]
+        host = (L.mvMapStores * self.lanes)(*cur)
+        self._desc.copy_(torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8))
+        self._uploaded = cur
+
+    def stores_dev(self) -> int:
+        """Device address of ``mvMapStores[lanes]``."""
+        if self.stale():
+            raise L.MacvoHipError("DeviceVisualMaps: a store was re-grown since the descriptor array was uploaded (reserve, then upload(), with the pipe drained)")
+        return self._desc.data_ptr()
+
+    def reserve(self, new_rows) -> bool:
+        """``DeviceVisualMap.reserve`` per lane (``new_rows``: one count or one per lane).  Returns whether the descriptor array went stale."""
+        rows = list(new_rows) if isinstance(new_rows, (list, tuple)) else [new_rows] * self.lanes
+        for m, n in zip(self.maps, rows):
+            m.reserve(int(n))
+        return self.stale()
+
+    def needs_growth(self, new_rows) -> bool:
+        """Whether registering one more frame with at most ``new_rows[l]`` rows would re-grow any lane's stores (``AutoScalingTensor.push`` :106-114)."""
+        rows = list(new_rows) if isinstance(new_rows, (list, tuple)) else [new_rows] * self.lanes
+        return any(m.n_frames + 1 >= m.cap["frames"] or m.rows_upper + int(n) >= m.cap["match"] for m, n in zip(self.maps, rows))
+
+    def push_frames(self, frames: "L.mvMapFrameLanes", n_rows, keep=()) -> None:
+        """Register one frame per lane from explicit lane-strided tables (``mv_map_append_lanes`` on the current stream); the frame driver uses
+        ``mv_frame_pipe_map_append_lanes`` instead.  ``frames.n_rows`` / ``frames.time_ns`` must point at host arrays the caller keeps alive."""
+        from . import ops
+
+        if self.needs_growth(list(n_rows)):
+            torch.cuda.synchronize(self.dev)
+            self.reserve(list(n_rows))
+            self.upload()
+            torch.cuda.synchronize(self.dev)
+        L.check(self.lib.mv_map_append_lanes(C.byref(frames), self.stores_dev(), ops._stream()), "mv_map_append_lanes")
+        self._keep = keep
+        for m, n in zip(self.maps, n_rows):
+            m.last_keyframe = m.n_frames
+            m.n_frames += 1
+            m.rows_upper += int(n)
+
+    def push_skipped(self, K, T_BS, baseline: float, time_ns, poses) -> None:
+        """One ``need_interp`` row per lane (``mv_map_append_skipped_lanes``): ``T_BS`` / ``poses`` ``[lanes, 7]``, ``time_ns`` one per lane."""
+        from . import ops
+
+        if self.needs_growth(0):
+            torch.cuda.synchronize(self.dev)
+            self.reserve(0)
+            self.upload()
+            torch.cuda.synchronize(self.dev)
+        f32 = torch.float32
+        Kd = ops._req(K.to(self.dev, f32).reshape(3, 3), f32, "K")
+        Td = ops._req(T_BS.to(self.dev, f32).reshape(self.lanes, 7), f32, "T_BS")
+        pd = ops._req(poses.to(self.dev, f32).reshape(self.lanes, 7), f32, "poses")
+        t = (C.c_int64 * self.lanes)(*[int(x) for x in time_ns])
+        L.check(self.lib.mv_map_append_skipped_lanes(self.stores_dev(), self.lanes, Kd.data_ptr(), Td.data_ptr(), pd.data_ptr(), float(baseline), t,
+                                                     ops._stream()), "mv_map_append_skipped_lanes")
+        self._keep = (Kd, Td, pd)
+        for m in self.maps:
+            m.n_frames += 1
+
+    def set_poses(self, frame_idx: int, poses: torch.Tensor) -> None:
+        """``write_graph_data`` (Optimizer.py:104-108) for every lane in one launch: ``poses`` ``[lanes, 7]`` over row ``frame_idx`` of each map."""
+        from . import ops
+
+        pd = ops._req(poses.to(self.dev, torch.float32).reshape(self.lanes, 7), torch.float32, "poses")
+        L.check(self.lib.mv_map_set_pose_lanes(self.stores_dev(), self.lanes, int(frame_idx), pd.data_ptr(), ops._stream()), "mv_map_set_pose_lanes")
+        self._keep_pose = pd
+
+    def serialize(self) -> "list[dict[str, np.ndarray]]":
+        return [m.serialize() for m in self.maps]
+
+    def write(self, folders, interpolate: bool = True) -> None:
+        """Finish and write every lane (once per sequence): ``MotionInterpolate`` (``Module/MapProcessor.py:52-76``) unless ``interpolate`` is off, then
+        ``poses.npy`` + ``tensor_map.npz`` (``Odometry/Interface.py:47-53``) into ``folders[l]``."""
+        folders = list(folders)
+        if len(folders) != self.lanes:
+            raise ValueError(f"{len(folders)} folders for {self.lanes} lanes")
+        for m, folder in zip(self.maps, folders):
+            if interpolate:
+                m.motion_interpolate()
+            m.write(folder)

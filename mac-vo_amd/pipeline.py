@@ -461,6 +461,8 @@ class FrameInputs:
     image: torch.Tensor | None = None
     # frame timestamp (StereoData.frame_ns) — recorded in the device-resident map when one is attached
     time_ns: int = 0
+    # batched step (stack_lanes): every lane's own timestamp, recorded in that lane's map (NativeHotPath.attach_maps); None: `time_ns` for every lane
+    lane_time_ns: "list | None" = None
     # caller-supplied keypoints of this frame: int64 (u, v) rows [n, 2] ([lanes, n, 2] for a batched step), on the host (checked) or on the device
     # (used as given: the caller keeps them cov_kernel_size // 2 inside the image).  Required by selector "explicit"; on any other selector they
     # replace the frame's own selection.  keypoint_counts: live rows per lane (default: all n).
@@ -936,8 +938,8 @@ def stack_lanes(inputs: "list[FrameInputs]") -> FrameInputs:
     for x in inputs:
         if x.ready is not None:
             torch.cuda.current_stream().wait_event(x.ready)
-    # one device map per pipe (lanes == 1), so per-lane images have no consumer in a batched step: refuse them rather than
-    # drop them silently; the lanes advance in lock-step, so the step carries lane 0's timestamp
+    # images feed the dense-mapping tail, which is one lane per pipe, so per-lane images have no consumer in a batched step: refuse them rather than
+    # drop them silently; the lanes advance in lock-step: `time_ns` stays lane 0's timestamp, `lane_time_ns` carries every lane's (one map per lane)
     assert len(inputs) == 1 or all(x.image is None for x in inputs), "stack_lanes: per-lane images are not carried"
     cat = lambda name, dim=0: (None if getattr(inputs[0], name) is None  # noqa: E731
                                else torch.cat([getattr(x, name) for x in inputs], dim=dim).contiguous())
@@ -952,7 +954,7 @@ def stack_lanes(inputs: "list[FrameInputs]") -> FrameInputs:
                        flow8=cat("flow8"), cov8=cat("cov8"), up_mask=cat("up_mask"), cov_mask=cat("cov_mask"),
                        keypoints=kps, keypoint_counts=None if kps is None else [r.shape[0] for r in rows],
                        image=inputs[0].image if len(inputs) == 1 else None, time_ns=inputs[0].time_ns,
-                       static=all(x.static for x in inputs))
+                       lane_time_ns=[int(x.time_ns) for x in inputs], static=all(x.static for x in inputs))
 
 
 class _NativeResult:
@@ -1256,11 +1258,59 @@ class NativeHotPath:
         (the reference: Odometry/MACVO.py:235-266, ~25 device-to-host copies per frame).  lanes == 1.  Call before
         :meth:`initialize`."""
         if self.lanes != 1:
-            raise ops.L.MacvoHipError("attach_map: one map per pipe, lanes must be 1")
+            raise ops.L.MacvoHipError("attach_map: one map per pipe, lanes must be 1 (attach_maps takes one map per lane)")
         self._map = devmap
+        self._maps = None
         self._map_K = K.to(self.dev, torch.float32).reshape(3, 3).contiguous()
         self._map_TBS = (torch.tensor([0, 0, 0, 0, 0, 0, 1.0]) if T_BS is None else T_BS).to(self.dev, torch.float32).reshape(7).contiguous()
         self._times: list = []
+
+    def attach_maps(self, maps, K: torch.Tensor, T_BS: torch.Tensor | None = None) -> None:
+        """:meth:`attach_map` for any lane count: lane ``l``'s finished frames go into ``maps[l]`` (a :class:`macvo_amd.devmap.DeviceVisualMaps`, or a list
+        of ``lanes`` :class:`DeviceVisualMap`) — what the reference's multi-sequence driver keeps per sequence (Scripts/Experiment/Experiment_MACVO.py:55-58),
+        registered by one launch per frame for all lanes (mv_frame_pipe_map_append_lanes), no host wait.  ``T_BS``: ``[7]`` or ``[lanes, 7]``.  All maps must
+        hold the same number of frames (the lanes advance in lock-step).  Call before :meth:`initialize`."""
+        from .devmap import DeviceVisualMaps
+
+        if self.cfg.mapping:
+            raise ops.L.MacvoHipError("attach_maps: the dense-mapping tail (mapping=True) registers through attach_map (one lane, one map)")
+        seq = maps.maps if isinstance(maps, DeviceVisualMaps) else list(maps)
+        if len(seq) != self.lanes:
+            raise ops.L.MacvoHipError(f"attach_maps: {len(seq)} map(s) for {self.lanes} lane(s)")
+        if len({(m.n_frames, m.last_keyframe) for m in seq}) != 1:
+            raise ops.L.MacvoHipError(f"attach_maps: every map must hold the same number of frames (the lanes advance in lock-step), got {[m.n_frames for m in seq]}")
+        if not isinstance(maps, DeviceVisualMaps):
+            maps = DeviceVisualMaps(maps=seq)
+        tbs = (torch.tensor([0, 0, 0, 0, 0, 0, 1.0]) if T_BS is None else T_BS).to(self.dev, torch.float32).reshape(-1, 7)
+        if tbs.shape[0] == 1:
+            tbs = tbs.expand(self.lanes, 7)
+        if tbs.shape[0] != self.lanes:
+            raise ops.L.MacvoHipError(f"attach_maps: T_BS must be [7] or [{self.lanes}, 7]")
+        self._map = None
+        self._maps = maps
+        self._map_K = K.to(self.dev, torch.float32).reshape(3, 3).contiguous()
+        self._map_TBS = tbs.contiguous()
+        self._times = []
+        if maps.stale():
+            maps.upload()
+        torch.cuda.synchronize()      # the descriptor array is read on the pipe's own streams
+
+    def _lane_times(self, x: FrameInputs):
+        """int64[lanes]: every lane's timestamp of a (stacked) step."""
+        t = x.lane_time_ns if x.lane_time_ns is not None else [x.time_ns] * self.lanes
+        if len(t) != self.lanes:
+            raise ops.L.MacvoHipError(f"lane_time_ns: {len(t)} timestamps for {self.lanes} lane(s)")
+        return (ops.C.c_int64 * self.lanes)(*[int(v) for v in t])
+
+    def _grow_maps(self, mps, n_rows) -> None:
+        """Re-growing a store re-allocates it and stales the device descriptor array: rare (capacities double), so drain the pipe, grow, upload, synchronise
+        — in that order: the array is only rewritten while no launch that reads it can be in flight (a stale descriptor is a write into freed memory)."""
+        if mps.needs_growth(n_rows):
+            self.synchronize()
+            torch.cuda.synchronize()
+            mps.reserve(n_rows)
+            mps.upload()
+            torch.cuda.synchronize()
 
     def initialize(self, x: FrameInputs, init_pose: torch.Tensor | None = None) -> None:
         """Frame 0: ``MACVO.initialize`` (:158-171) — depth only, pose = prior."""
@@ -1272,20 +1322,44 @@ class NativeHotPath:
         if getattr(self, "_map", None) is not None:   # MACVO.initialize pushes the first frame at the prior (:162-169)
             self._map.push_frame(K=self._map_K, T_BS=self._map_TBS, baseline=self.cam.baseline, time_ns=x.time_ns, prior_pose=init_pose)
             torch.cuda.current_stream().synchronize()   # later frames are appended on the pipe's streams: order them after this one
+        mps = getattr(self, "_maps", None)
+        if mps is not None:                           # ... every lane's, each at its own prior (once per sequence: the one-frame kernel per lane)
+            pri = None if init_pose is None else init_pose.detach().to(torch.float32).reshape(-1, 7)
+            times = self._lane_times(x)
+            for l, m in enumerate(mps):
+                m.push_frame(K=self._map_K, T_BS=self._map_TBS[l], baseline=self.cam.baseline, time_ns=times[l],
+                             prior_pose=None if pri is None else pri[l if pri.shape[0] > 1 else 0])
+            if mps.stale():
+                mps.upload()
+            torch.cuda.synchronize()
 
-    def skip(self, time_ns: int = 0) -> None:
-        """A non-keyframe (MACVO.py:177-179), see :meth:`HotPath.skip`: the pipe notes that the next solve's reference frame is the previous keyframe's
+    def skip(self, time_ns=0) -> None:
+        """A non-keyframe (MACVO.py:177-179), see :meth:`HotPath.skip` (``time_ns``: one timestamp, or one per lane with :meth:`attach_maps`): the pipe notes that the next solve's reference frame is the previous keyframe's
         prior (mv_frame_pipe_skip), and with an attached map the row is appended on the pipe's own stream with that prior copied on the device
         (mv_frame_pipe_map_skip) — no host wait.  Called while tracked frames are still pending (``run``), it takes effect once they have finished."""
         assert self._n_enq >= 1, "call initialize() with the first frame"
+        time_ns = [int(v) for v in time_ns] if isinstance(time_ns, (list, tuple)) else int(time_ns)
         if self._has_pending():
-            self._skip_queue.append((self._n_enq - 1, int(time_ns)))
+            self._skip_queue.append((self._n_enq - 1, time_ns))
             return
         self._skip_now(time_ns)
 
-    def _skip_now(self, time_ns: int) -> None:
+    def _skip_now(self, time_ns) -> None:
         L, lib = ops.L, self._lib
         L.check(lib.mv_frame_pipe_skip(self._pipe), "mv_frame_pipe_skip")
+        mps = getattr(self, "_maps", None)
+        if mps is not None:   # one need_interp row per lane, each at its own prior: one launch (mv_frame_pipe_map_skip_lanes)
+            t = time_ns if isinstance(time_ns, list) else [time_ns] * self.lanes
+            if len(t) != self.lanes:
+                raise L.MacvoHipError(f"skip: {len(t)} timestamps for {self.lanes} lane(s)")
+            self._grow_maps(mps, 0)
+            L.check(lib.mv_frame_pipe_map_skip_lanes(self._pipe, mps.stores_dev(), mps[0].n_frames, self._map_K.data_ptr(), self._map_TBS.data_ptr(),
+                                                     float(self.cam.baseline), (ops.C.c_int64 * self.lanes)(*t)), "mv_frame_pipe_map_skip_lanes")
+            for m in mps:
+                m.n_frames += 1
+            return
+        if isinstance(time_ns, list):
+            time_ns = time_ns[0]
         mp = getattr(self, "_map", None)
         if mp is not None:
             if mp.n_frames + 1 >= mp.cap["frames"]:
@@ -1307,7 +1381,7 @@ class NativeHotPath:
             if self._frame_index % k == 0:
                 yield x
             else:
-                self.skip(x.time_ns)
+                self.skip(x.time_ns if x.lane_time_ns is None else list(x.lane_time_ns))
 
     @traced("Frontend.estimate")
     def enqueue_frontend(self, x: FrameInputs):
@@ -1321,6 +1395,8 @@ class NativeHotPath:
             self._prev_image = x.image
         if getattr(self, "_map", None) is not None:
             self._times.append(int(x.time_ns))
+        elif getattr(self, "_maps", None) is not None:
+            self._times.append(self._lane_times(x))
         return x
 
     def _motion(self) -> None:
@@ -1483,6 +1559,17 @@ class NativeHotPath:
             mp.last_keyframe = mp.n_frames
             mp.n_frames += 1
             mp.rows_upper += n_rows
+        mps = getattr(self, "_maps", None)
+        if mps is not None:   # every lane into its own map: one launch for all lanes, then the optimised poses by one more (mv_frame_pipe_map_append_lanes)
+            n_rows = [self._cap if dd else int(self._nsel[l]) for l in range(self.lanes)]   # (device-driven: the upper bound, as above)
+            self._grow_maps(mps, n_rows)
+            L.check(lib.mv_frame_pipe_map_append_lanes(self._pipe, mps.stores_dev(), mps[0].n_frames, mps[0].last_keyframe, self._map_K.data_ptr(),
+                                                       self._map_TBS.data_ptr(), float(self.cam.baseline), self._times.pop(0)),
+                    "mv_frame_pipe_map_append_lanes")
+            for m, n in zip(mps, n_rows):
+                m.last_keyframe = m.n_frames
+                m.n_frames += 1
+                m.rows_upper += n
         map_pts = self._map_tail(mp) if self.cfg.mapping else None
         out = []
         for l in range(self.lanes):
