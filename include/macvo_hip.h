@@ -1001,7 +1001,8 @@ int mv_frame_pipe_finished_counts(mvFramePipe* p, int age, int32_t* n_cand, int3
 int mv_frame_pipe_wait_finished(mvFramePipe* p, int lag);
 /* register the newest FINISHED frame in a device-resident map (mv_map_append on the pipe's own streams, no copies; lanes = 1):
  * frame_idx = the map index the frame receives (= frames pushed so far), prev_frame = the previous keyframe's index; the
- * optimised pose is written over the frame's prior once its solve has finished */
+ * optimised pose is written over the frame's prior once its solve has finished.  The host-descriptor form (and the one that takes
+ * colours) of the one registration protocol described at mv_frame_pipe_map_append_lanes: same waits, same events. */
 int mv_frame_pipe_map_append(mvFramePipe* p, const mvMapStores* stores /* host */, int frame_idx, int prev_frame,
                              const float* K_dev, const float* T_BS_dev, float baseline, int64_t time_ns,
                              const uint8_t* color_dev /* [n_sel,3] or NULL */);
@@ -1019,12 +1020,14 @@ int mv_frame_pipe_skip(mvFramePipe* p);
  * frame_idx = the map index the row receives (= frames pushed so far). */
 int mv_frame_pipe_map_skip(mvFramePipe* p, const mvMapStores* stores /* host */, int frame_idx, const float* K_dev, const float* T_BS_dev,
                            float baseline, int64_t time_ns);
-/* The two calls above for a pipe of ANY lane count (lanes >= 1), every lane into its own map (Scripts/Experiment/Experiment_MACVO.py:55-58 keeps one VisualMap
+/* Registration for a pipe of ANY lane count (lanes >= 1), every lane into its own map (Scripts/Experiment/Experiment_MACVO.py:55-58 keeps one VisualMap
  * per sequence; per lane Odometry/MACVO.py:244-311,339-347 and :177-179): ONE mv_map_append_lanes / mv_map_append_skipped_lanes launch on the backend stream
  * behind the finish's e_solved / e_posed, then ONE mv_map_set_pose_lanes launch on the solve stream behind it (Optimizer.py:104-108).  stores_dev: DEVICE
  * mvMapStores[lanes]; T_BS_dev: [lanes, 7]; time_ns: HOST [lanes]; frame_idx / prev_frame are the same for every lane (lock-step).  Same call positions as the
- * one-lane forms.  Once mv_frame_pipe_map_append_lanes has been used, a front launch that runs on a decoder-side stream waits for the append that last read
- * its backend slot before it rewrites the slot's tables.  A pipe that never makes these calls issues exactly the launches and waits it issued before. */
+ * one-lane forms.  There is ONE protocol: the two one-lane calls above run it with a host descriptor, mv_map_append / mv_map_append_skipped and a pose copy
+ * in place of the lanes launches.  Either append records the event that guards its backend slot (one per slot, where front launches run on a decoder-side
+ * stream): the front launch of the finish two later waits for it before it rewrites the tables the append read.  A pipe that never makes these calls issues
+ * exactly the launches and waits it issued before. */
 int mv_frame_pipe_map_append_lanes(mvFramePipe* p, const mvMapStores* stores_dev /* DEVICE [lanes] */, int frame_idx, int prev_frame, const float* K_dev,
                                    const float* T_BS_dev, float baseline, const int64_t* time_ns /* host [lanes] */);
 int mv_frame_pipe_map_skip_lanes(mvFramePipe* p, const mvMapStores* stores_dev /* DEVICE [lanes] */, int frame_idx, const float* K_dev, const float* T_BS_dev,

@@ -241,7 +241,7 @@ struct mvFramePipe {
     int solve_frame = MV_SOLVE_WORLD;   // mv_frame_pipe_set_solve_frame
     bool skipped = false;               // mv_frame_pipe_skip since the newest finish
     hipEvent_t e_map;
-    hipEvent_t e_mapl[2];     // backend slot k: mv_frame_pipe_map_append_lanes has finished reading the slot's tables
+    hipEvent_t e_mapl[2];     // backend slot k: the map append (map_append_finished) has finished reading the slot's tables
     bool mapl_valid[2];       // ... recorded (written by the caller's thread behind flush_jobs, read by whoever issues the later finishes)
     int newest_maps;
     std::deque<Pending> pending;
@@ -1401,7 +1401,7 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     // reads views asynchronously on its own stream calls it before it asks for the next frame).
     if (p->solved_valid[k] && s != p->s_side) MV_TRY(wait_if_pending(s, p->e_solved[k]));   // (alt layout: backend and solve share one in-order stream)
     if (p->release_valid) MV_TRY(wait_if_pending(s, p->e_release));
-    // ... and by mv_frame_pipe_map_append_lanes of frame g - 2 on the backend stream: in order with a front launch that runs there, an event for one on a
+    // ... and by the map append (map_append_finished) of frame g - 2 on the backend stream: in order with a front launch that runs there, an event for one on a
     // decoder-side stream (a 64-lane append takes longer than a one-lane one: timing does not hold this off)
     if (p->mapl_valid[k] && s != p->s_back) MV_TRY(wait_if_pending(s, p->e_mapl[k]));
     // permutations [lanes, cap] -> pinned slot -> device (ONE copy; rows beyond a lane's n_sel are never read)
@@ -1778,43 +1778,79 @@ extern "C" int mv_frame_pipe_finish_keypoints_dev(mvFramePipe* p, const int64_t*
     return finish_uniform(p, j, table_rows(p->c), pose_sink);
 }
 
-// Register the newest FINISHED frame in a device-resident map (call right after mv_frame_pipe_finish; lanes == 1): the
-// frame's tables are handed to mv_map_append where they lie (no copies), on the backend stream behind the observation filter;
-// the optimised pose is then written over the frame's prior on the solve stream (write_graph_data, Optimizer.py:104-108).
-extern "C" int mv_frame_pipe_map_append(mvFramePipe* p, const mvMapStores* stores, int frame_idx, int prev_frame,
-                                        const float* K_dev, const float* T_BS_dev, float baseline, int64_t time_ns,
-                                        const uint8_t* color_dev) {
-    MV_CHECK_ARG(p && stores && K_dev && T_BS_dev && p->lanes == 1 && p->n_fin > 0 && frame_idx >= 0);
+// Register the newest FINISHED frame in device-resident maps (call right after a finish), the one protocol behind both entry points: the frame's tables are
+// handed to `launch` where they lie (no copies), on the backend stream behind the observation filter; `set_pose` then writes the optimised pose over the
+// frame's prior on the solve stream (write_graph_data, Optimizer.py:104-108).  `f`: mvMapFrame or mvMapFrameLanes — the fields they share are filled here.
+template <class Frame, class Launch, class SetPose>
+static int map_append_finished(mvFramePipe* p, Frame& f, int prev_frame, const float* K_dev, const float* T_BS_dev, float baseline, Launch launch,
+                               SetPose set_pose) {
     MV_TRY(flush_jobs(p));
     const mvFramePipeConfig& c = p->c;
     const long g = p->n_fin - 1;
-    const Backend& b = p->be[g & 1];
-    const int cap = cap_of(c);
-    mvMapFrame f{};
-    f.n_rows = b.n_sel[0];
-    f.table_stride = cap;
+    const int k = (int)(g & 1);
+    const Backend& b = p->be[k];
     f.prev_frame = prev_frame;
     f.min_num_point = c.min_num_point;
     f.valid = b.valid;
     f.kp0 = b.kp0f; f.kp1 = b.kp1; f.vals = b.vals; f.sigma0 = b.sigma0; f.sigma1 = b.sigma1;
     f.cov0 = b.cov0; f.cov1 = b.cov1; f.pos_Tw = b.pos_Tw; f.cov0_world = b.cov0w;
-    f.color = color_dev;
     f.K = K_dev; f.T_BS = T_BS_dev;
-    f.prior_pose = p->c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];   // push_keyframe(frame1, est_pose) (MACVO.py:282)
+    f.prior_pose = c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];   // push_keyframe(frame1, est_pose) (MACVO.py:282)
     f.baseline = baseline;
-    f.time_ns = time_ns;
-    f.out_frame_idx = nullptr;
-    MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[g & 1] : p->e_posed[g & 1], 0));   // pos_Tw / cov0_world come from the side stream
-    MV_TRY(mv_map_append(&f, stores, p->s_back));
+    MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[k] : p->e_posed[k], 0));   // pos_Tw / cov0_world come from the side stream
+    MV_TRY(launch(b));
     MV_HIP(hipEventRecord(p->e_map, p->s_back));
-    // the backend tables must outlive the append: later backends run on the same stream (ordered); the optimised pose goes
-    // in after the append wrote the prior
+    // The backend tables must outlive the append.  A front launch that runs on this stream is behind it in order; one on a decoder-side stream — the default of
+    // the one-lane device-driven pipe — waits for e_mapl[k] before finish g + 2 rewrites the slot (finish_issue).  No packet for a pipe that has no such launch.
+    if (p->front_on_decoder) {
+        MV_HIP(hipEventRecord(p->e_mapl[k], p->s_back));
+        p->mapl_valid[k] = true;
+    }
+    // the optimised pose goes in after the append wrote the prior
     MV_HIP(hipStreamWaitEvent(p->s_side, p->e_map, 0));
-    MV_HIP(hipMemcpyAsync(stores->pose + 7 * (size_t)frame_idx, p->pose[p->pose_cur], 7 * sizeof(float), hipMemcpyDeviceToDevice,
-                          p->s_side));
+    MV_TRY(set_pose(p->pose[p->pose_cur]));
     MV_HIP(hipEventRecord(p->e_pgo, p->s_side));
     p->pgo_valid = true;
     return MV_OK;
+}
+
+// The one-lane form: a host descriptor of the one map, and the frame's colours.
+extern "C" int mv_frame_pipe_map_append(mvFramePipe* p, const mvMapStores* stores, int frame_idx, int prev_frame,
+                                        const float* K_dev, const float* T_BS_dev, float baseline, int64_t time_ns,
+                                        const uint8_t* color_dev) {
+    MV_CHECK_ARG(p && stores && K_dev && T_BS_dev && p->lanes == 1 && p->n_fin > 0 && frame_idx >= 0);
+    mvMapFrame f{};
+    f.table_stride = cap_of(p->c);
+    f.color = color_dev;
+    f.time_ns = time_ns;
+    return map_append_finished(
+        p, f, prev_frame, K_dev, T_BS_dev, baseline,
+        [&](const Backend& b) {
+            f.n_rows = b.n_sel[0];
+            return mv_map_append(&f, stores, p->s_back);
+        },
+        [&](const float* pose) -> int {
+            MV_HIP(hipMemcpyAsync(stores->pose + 7 * (size_t)frame_idx, pose, 7 * sizeof(float), hipMemcpyDeviceToDevice, p->s_side));
+            return MV_OK;
+        });
+}
+
+// Any lane count, every lane into its own map (a device array of descriptors): one launch for all lanes (mv_map_append_lanes), the optimised poses behind it
+// by one launch on the solve stream (each lane's destination is another allocation).
+extern "C" int mv_frame_pipe_map_append_lanes(mvFramePipe* p, const mvMapStores* stores_dev, int frame_idx, int prev_frame, const float* K_dev,
+                                              const float* T_BS_dev, float baseline, const int64_t* time_ns) {
+    MV_CHECK_ARG(p && stores_dev && K_dev && T_BS_dev && time_ns && p->n_fin > 0 && frame_idx >= 0);
+    mvMapFrameLanes f{};
+    f.lanes = p->lanes;
+    f.cap = cap_of(p->c);
+    f.time_ns = time_ns;
+    return map_append_finished(
+        p, f, prev_frame, K_dev, T_BS_dev, baseline,
+        [&](const Backend& b) {
+            f.n_rows = b.n_sel;   // (device-driven frames: the upper bound, `valid` compacts)
+            return mv_map_append_lanes(&f, stores_dev, p->s_back);
+        },
+        [&](const float* poses) { return mv_map_set_pose_lanes(stores_dev, p->lanes, frame_idx, poses, p->s_side); });
 }
 
 // ------------------------------------------------------------------------------------------------ keyframe policy, local solve
@@ -1831,73 +1867,34 @@ extern "C" int mv_frame_pipe_skip(mvFramePipe* p) {
 }
 
 // The skipped frame's row: push_keyframe(frame1, pose row of the previous keyframe, need_interp=True) (MACVO.py:177-179).  That row still holds the prior the
-// keyframe was pushed with, so the pose is copied from the prior slot — on the backend stream, in order with the pipe's own appends.
-extern "C" int mv_frame_pipe_map_skip(mvFramePipe* p, const mvMapStores* stores, int frame_idx, const float* K_dev, const float* T_BS_dev, float baseline,
-                                      int64_t time_ns) {
-    MV_CHECK_ARG(p && stores && K_dev && T_BS_dev && p->lanes == 1 && p->n_enq > 0 && frame_idx >= 1 && frame_idx < stores->cap_frames);
+// keyframe was pushed with, so `launch` copies the pose from the prior slot — on the backend stream, in order with the pipe's own appends.  (It reads no
+// backend slot: nothing for a front launch to wait for.)
+template <class Launch>
+static int map_skip_row(mvFramePipe* p, Launch launch) {
     MV_TRY(flush_jobs(p));
     const long g = p->n_fin - 1;   // the previous keyframe's finish (-1: frame 0, pushed at the pose set by mv_frame_pipe_set_pose)
     const float* prior = g < 0 ? p->pose[p->pose_cur] : p->c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];
     // The prior slot is written on the side stream in FRONT of finish g's solve (the slot that solve started from, or the prior composed for it).  The event
-    // mv_frame_pipe_map_append made this stream wait for when it registered finish g lies behind that write, so stream order already covers it and the wait
+    // map_append_finished made this stream wait for when it registered finish g lies behind that write, so stream order already covers it and the wait
     // below adds nothing to the stream; it only keeps a caller that registers no keyframes correct.  (Not e_pgo: that is re-recorded behind the append's pose
     // copy and would put the backend stream behind work it does not depend on.)
     if (g >= 0) MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[g & 1] : p->e_posed[g & 1], 0));
-    MV_TRY(mv_map_append_skipped(stores, K_dev, T_BS_dev, prior, baseline, time_ns, p->s_back));
+    MV_TRY(launch(prior));
     MV_HIP(hipEventRecord(p->e_map, p->s_back));
     return MV_OK;
 }
 
-// mv_frame_pipe_map_append / _map_skip for any lane count, every lane into its own map: one launch for all lanes (mv_map_append_lanes), the optimised poses
-// behind it by one launch on the solve stream (each lane's destination is another allocation).
-extern "C" int mv_frame_pipe_map_append_lanes(mvFramePipe* p, const mvMapStores* stores_dev, int frame_idx, int prev_frame, const float* K_dev,
-                                              const float* T_BS_dev, float baseline, const int64_t* time_ns) {
-    MV_CHECK_ARG(p && stores_dev && K_dev && T_BS_dev && time_ns && p->n_fin > 0 && frame_idx >= 0);
-    MV_TRY(flush_jobs(p));
-    const mvFramePipeConfig& c = p->c;
-    const long g = p->n_fin - 1;
-    const int k = (int)(g & 1);
-    const Backend& b = p->be[k];
-    mvMapFrameLanes f{};
-    f.lanes = p->lanes;
-    f.cap = cap_of(c);
-    f.prev_frame = prev_frame;
-    f.min_num_point = c.min_num_point;
-    f.n_rows = b.n_sel;   // (device-driven frames: the upper bound, `valid` compacts)
-    f.time_ns = time_ns;
-    f.valid = b.valid;
-    f.kp0 = b.kp0f; f.kp1 = b.kp1; f.vals = b.vals; f.sigma0 = b.sigma0; f.sigma1 = b.sigma1;
-    f.cov0 = b.cov0; f.cov1 = b.cov1; f.pos_Tw = b.pos_Tw; f.cov0_world = b.cov0w;
-    f.color = nullptr;
-    f.K = K_dev; f.T_BS = T_BS_dev;
-    f.prior_pose = c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];   // push_keyframe(frame1, est_pose) (MACVO.py:282)
-    f.baseline = baseline;
-    MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[k] : p->e_posed[k], 0));   // pos_Tw / cov0_world come from the side stream
-    MV_TRY(mv_map_append_lanes(&f, stores_dev, p->s_back));
-    MV_HIP(hipEventRecord(p->e_map, p->s_back));
-    if (p->front_on_decoder) {   // what the front launch of finish g + 2 waits for where it does not run on this stream (no packet for a pipe that has none)
-        MV_HIP(hipEventRecord(p->e_mapl[k], p->s_back));
-        p->mapl_valid[k] = true;
-    }
-    // the optimised poses go in after the append wrote the priors
-    MV_HIP(hipStreamWaitEvent(p->s_side, p->e_map, 0));
-    MV_TRY(mv_map_set_pose_lanes(stores_dev, p->lanes, frame_idx, p->pose[p->pose_cur], p->s_side));
-    MV_HIP(hipEventRecord(p->e_pgo, p->s_side));
-    p->pgo_valid = true;
-    return MV_OK;
+extern "C" int mv_frame_pipe_map_skip(mvFramePipe* p, const mvMapStores* stores, int frame_idx, const float* K_dev, const float* T_BS_dev, float baseline,
+                                      int64_t time_ns) {
+    MV_CHECK_ARG(p && stores && K_dev && T_BS_dev && p->lanes == 1 && p->n_enq > 0 && frame_idx >= 1 && frame_idx < stores->cap_frames);
+    return map_skip_row(p, [&](const float* prior) { return mv_map_append_skipped(stores, K_dev, T_BS_dev, prior, baseline, time_ns, p->s_back); });
 }
 
 extern "C" int mv_frame_pipe_map_skip_lanes(mvFramePipe* p, const mvMapStores* stores_dev, int frame_idx, const float* K_dev, const float* T_BS_dev,
                                             float baseline, const int64_t* time_ns) {
     MV_CHECK_ARG(p && stores_dev && K_dev && T_BS_dev && time_ns && p->n_enq > 0 && frame_idx >= 1);
-    MV_TRY(flush_jobs(p));
-    const long g = p->n_fin - 1;   // the previous keyframe's finish (-1: frame 0, pushed at the poses set by mv_frame_pipe_set_pose)
-    const float* prior = g < 0 ? p->pose[p->pose_cur] : p->c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];
-    // (the same ordering argument as mv_frame_pipe_map_skip: the prior slot is written in front of finish g's solve)
-    if (g >= 0) MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[g & 1] : p->e_posed[g & 1], 0));
-    MV_TRY(mv_map_append_skipped_lanes(stores_dev, p->lanes, K_dev, T_BS_dev, prior, baseline, time_ns, p->s_back));
-    MV_HIP(hipEventRecord(p->e_map, p->s_back));
-    return MV_OK;
+    return map_skip_row(
+        p, [&](const float* prior) { return mv_map_append_skipped_lanes(stores_dev, p->lanes, K_dev, T_BS_dev, prior, baseline, time_ns, p->s_back); });
 }
 
 // ------------------------------------------------------------------------------------------------ dense-mapping tail

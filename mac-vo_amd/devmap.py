@@ -95,14 +95,9 @@ class DeviceVisualMap:
             table[k] = nt
         self._stores = None
 
-    def reserve(self, new_rows: int, new_map_points: int = 0) -> None:
-        """Make room for one more frame with at most ``new_rows`` kept observations and ``new_map_points`` dense map points
-        (``AutoScalingTensor.push`` :106-114 grows when size + n >= capacity; copies are enqueued on the current stream)."""
-        need_mp = self.map_rows_upper + new_map_points
-        if new_map_points and need_mp >= self.cap["map_points"]:
-            cap = _grow_to(need_mp)
-            self._regrow(self.map_points, list(self.map_points), cap)
-            self.cap["map_points"] = cap
+    def reserve(self, new_rows: int) -> None:
+        """Make room for one more frame with at most ``new_rows`` kept observations (``AutoScalingTensor.push`` :106-114 grows when
+        size + n >= capacity; copies are enqueued on the current stream).  Dense map points: :meth:`reserve_map_points`."""
         need_f, need_r = self.n_frames + 1, self.rows_upper + new_rows
         if need_f >= self.cap["frames"]:
             cap = _grow_to(need_f)
@@ -274,9 +269,9 @@ class DeviceVisualMaps:
     (``Scripts/Experiment/Experiment_MACVO.py:55-58``).  Every lane's frame is registered by ONE launch (``mv_map_append_lanes``: one workgroup per lane),
     which finds the lanes' stores through a DEVICE array ``mvMapStores[lanes]`` this holder owns (64 lanes x ~45 pointers do not fit in kernel arguments).
 
-    The array names allocations: after a ``reserve`` that re-grew a store it is stale and :meth:`upload` must rewrite it — only while no launch that reads
-    it can be in flight (drain the pipe, ``reserve``, ``upload``, synchronise: ``NativeHotPath`` does exactly that).  :meth:`stores_dev` refuses a stale array
-    instead of handing out pointers into freed memory.  Capacity bookkeeping (``n_frames``, ``rows_upper``, ``last_keyframe``) stays with each map."""
+    The array names allocations: after a member's ``reserve`` re-grew a store it is stale and :meth:`upload` must rewrite it — only while no launch that reads
+    it can be in flight: :meth:`grow` is the one place that does it, for this class's own pushes and for ``NativeHotPath``.  :meth:`stores_dev` refuses a stale
+    array instead of handing out pointers into freed memory.  Capacity bookkeeping (``n_frames``, ``rows_upper``, ``last_keyframe``) stays with each map."""
 
     def __init__(self, lanes: int | None = None, device: str | torch.device = "cuda", init_size=1024, maps: "list[DeviceVisualMap] | None" = None, **kw):
         if maps is None:
@@ -321,31 +316,35 @@ class DeviceVisualMaps:
     def stores_dev(self) -> int:
         """Device address of ``mvMapStores[lanes]``."""
         if self.stale():
-            raise L.MacvoHipError("DeviceVisualMaps: a store was re-grown since the descriptor array was uploaded (reserve, then upload(), with the pipe drained)")
+            raise L.MacvoHipError("DeviceVisualMaps: a store was re-grown since the descriptor array was uploaded (grow() re-grows and uploads, with the pipe drained)")
         return self._desc.data_ptr()
 
-    def reserve(self, new_rows) -> bool:
-        """``DeviceVisualMap.reserve`` per lane (``new_rows``: one count or one per lane).  Returns whether the descriptor array went stale."""
+    def grow(self, new_rows=None, new_map_points=None, drain=None) -> None:
+        """Make room for one more frame with at most ``new_rows`` rows (one count or one per lane; None: no new frame) and for ``new_map_points`` dense map
+        points per lane (None: none), where ``AutoScalingTensor.push`` (:106-114) would re-grow a store.  That re-allocates the store and stales the device
+        descriptor array: rare (capacities double), so drain the caller's pipe (``drain()``), grow, upload, synchronise — in that order: the array is only
+        rewritten while no launch that reads it can be in flight (a stale descriptor is a write into freed memory)."""
         rows = list(new_rows) if isinstance(new_rows, (list, tuple)) else [new_rows] * self.lanes
+        if not any((n is not None and (m.n_frames + 1 >= m.cap["frames"] or m.rows_upper + int(n) >= m.cap["match"]))
+                   or (new_map_points is not None and m.map_rows_upper + new_map_points >= m.cap["map_points"]) for m, n in zip(self.maps, rows)):
+            return
+        if drain is not None:
+            drain()
+        torch.cuda.synchronize(self.dev)
         for m, n in zip(self.maps, rows):
-            m.reserve(int(n))
-        return self.stale()
-
-    def needs_growth(self, new_rows) -> bool:
-        """Whether registering one more frame with at most ``new_rows[l]`` rows would re-grow any lane's stores (``AutoScalingTensor.push`` :106-114)."""
-        rows = list(new_rows) if isinstance(new_rows, (list, tuple)) else [new_rows] * self.lanes
-        return any(m.n_frames + 1 >= m.cap["frames"] or m.rows_upper + int(n) >= m.cap["match"] for m, n in zip(self.maps, rows))
+            if n is not None:
+                m.reserve(int(n))
+            if new_map_points is not None:
+                m.reserve_map_points(new_map_points)
+        self.upload()
+        torch.cuda.synchronize(self.dev)
 
     def push_frames(self, frames: "L.mvMapFrameLanes", n_rows, keep=()) -> None:
         """Register one frame per lane from explicit lane-strided tables (``mv_map_append_lanes`` on the current stream); the frame driver uses
         ``mv_frame_pipe_map_append_lanes`` instead.  ``frames.n_rows`` / ``frames.time_ns`` must point at host arrays the caller keeps alive."""
         from . import ops
 
-        if self.needs_growth(list(n_rows)):
-            torch.cuda.synchronize(self.dev)
-            self.reserve(list(n_rows))
-            self.upload()
-            torch.cuda.synchronize(self.dev)
+        self.grow(list(n_rows))
         L.check(self.lib.mv_map_append_lanes(C.byref(frames), self.stores_dev(), ops._stream()), "mv_map_append_lanes")
         self._keep = keep
         for m, n in zip(self.maps, n_rows):
@@ -357,11 +356,7 @@ class DeviceVisualMaps:
         """One ``need_interp`` row per lane (``mv_map_append_skipped_lanes``): ``T_BS`` / ``poses`` ``[lanes, 7]``, ``time_ns`` one per lane."""
         from . import ops
 
-        if self.needs_growth(0):
-            torch.cuda.synchronize(self.dev)
-            self.reserve(0)
-            self.upload()
-            torch.cuda.synchronize(self.dev)
+        self.grow(0)
         f32 = torch.float32
         Kd = ops._req(K.to(self.dev, f32).reshape(3, 3), f32, "K")
         Td = ops._req(T_BS.to(self.dev, f32).reshape(self.lanes, 7), f32, "T_BS")

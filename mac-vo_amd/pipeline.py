@@ -1255,15 +1255,13 @@ class NativeHotPath:
     def attach_map(self, devmap, K: torch.Tensor, T_BS: torch.Tensor | None = None) -> None:
         """Register every finished frame in a :class:`macvo_amd.devmap.DeviceVisualMap`: the frame's
         tables go from the tracking kernels into the map's SoA stores on the pipe's own streams — no ``.cpu()`` round trip
-        (the reference: Odometry/MACVO.py:235-266, ~25 device-to-host copies per frame).  lanes == 1.  Call before
-        :meth:`initialize`."""
+        (the reference: Odometry/MACVO.py:235-266, ~25 device-to-host copies per frame).  lanes == 1: the one-member form of
+        :meth:`attach_maps`, ``devmap`` itself is filled.  Call before :meth:`initialize`."""
+        from .devmap import DeviceVisualMaps
+
         if self.lanes != 1:
             raise ops.L.MacvoHipError("attach_map: one map per pipe, lanes must be 1 (attach_maps takes one map per lane)")
-        self._map = devmap
-        self._maps = None
-        self._map_K = K.to(self.dev, torch.float32).reshape(3, 3).contiguous()
-        self._map_TBS = (torch.tensor([0, 0, 0, 0, 0, 0, 1.0]) if T_BS is None else T_BS).to(self.dev, torch.float32).reshape(7).contiguous()
-        self._times: list = []
+        self._attach(DeviceVisualMaps(maps=[devmap]), K, T_BS)
 
     def attach_maps(self, maps, K: torch.Tensor, T_BS: torch.Tensor | None = None) -> None:
         """:meth:`attach_map` for any lane count: lane ``l``'s finished frames go into ``maps[l]`` (a :class:`macvo_amd.devmap.DeviceVisualMaps`, or a list
@@ -1279,14 +1277,14 @@ class NativeHotPath:
             raise ops.L.MacvoHipError(f"attach_maps: {len(seq)} map(s) for {self.lanes} lane(s)")
         if len({(m.n_frames, m.last_keyframe) for m in seq}) != 1:
             raise ops.L.MacvoHipError(f"attach_maps: every map must hold the same number of frames (the lanes advance in lock-step), got {[m.n_frames for m in seq]}")
-        if not isinstance(maps, DeviceVisualMaps):
-            maps = DeviceVisualMaps(maps=seq)
+        self._attach(maps if isinstance(maps, DeviceVisualMaps) else DeviceVisualMaps(maps=seq), K, T_BS)
+
+    def _attach(self, maps, K: torch.Tensor, T_BS: torch.Tensor | None) -> None:
         tbs = (torch.tensor([0, 0, 0, 0, 0, 0, 1.0]) if T_BS is None else T_BS).to(self.dev, torch.float32).reshape(-1, 7)
         if tbs.shape[0] == 1:
             tbs = tbs.expand(self.lanes, 7)
         if tbs.shape[0] != self.lanes:
             raise ops.L.MacvoHipError(f"attach_maps: T_BS must be [7] or [{self.lanes}, 7]")
-        self._map = None
         self._maps = maps
         self._map_K = K.to(self.dev, torch.float32).reshape(3, 3).contiguous()
         self._map_TBS = tbs.contiguous()
@@ -1302,16 +1300,6 @@ class NativeHotPath:
             raise ops.L.MacvoHipError(f"lane_time_ns: {len(t)} timestamps for {self.lanes} lane(s)")
         return (ops.C.c_int64 * self.lanes)(*[int(v) for v in t])
 
-    def _grow_maps(self, mps, n_rows) -> None:
-        """Re-growing a store re-allocates it and stales the device descriptor array: rare (capacities double), so drain the pipe, grow, upload, synchronise
-        — in that order: the array is only rewritten while no launch that reads it can be in flight (a stale descriptor is a write into freed memory)."""
-        if mps.needs_growth(n_rows):
-            self.synchronize()
-            torch.cuda.synchronize()
-            mps.reserve(n_rows)
-            mps.upload()
-            torch.cuda.synchronize()
-
     def initialize(self, x: FrameInputs, init_pose: torch.Tensor | None = None) -> None:
         """Frame 0: ``MACVO.initialize`` (:158-171) — depth only, pose = prior."""
         self._init_pose = init_pose
@@ -1319,11 +1307,8 @@ class NativeHotPath:
         self._skip_queue.clear()
         self._enqueue(x, False)
         self._prev_image = x.image
-        if getattr(self, "_map", None) is not None:   # MACVO.initialize pushes the first frame at the prior (:162-169)
-            self._map.push_frame(K=self._map_K, T_BS=self._map_TBS, baseline=self.cam.baseline, time_ns=x.time_ns, prior_pose=init_pose)
-            torch.cuda.current_stream().synchronize()   # later frames are appended on the pipe's streams: order them after this one
         mps = getattr(self, "_maps", None)
-        if mps is not None:                           # ... every lane's, each at its own prior (once per sequence: the one-frame kernel per lane)
+        if mps is not None:   # MACVO.initialize pushes the first frame at the prior (:162-169): every lane's, each at its own (once per sequence: the one-frame kernel per lane)
             pri = None if init_pose is None else init_pose.detach().to(torch.float32).reshape(-1, 7)
             times = self._lane_times(x)
             for l, m in enumerate(mps):
@@ -1331,12 +1316,12 @@ class NativeHotPath:
                              prior_pose=None if pri is None else pri[l if pri.shape[0] > 1 else 0])
             if mps.stale():
                 mps.upload()
-            torch.cuda.synchronize()
+            torch.cuda.synchronize()   # later frames are appended on the pipe's streams: order them after this one
 
     def skip(self, time_ns=0) -> None:
         """A non-keyframe (MACVO.py:177-179), see :meth:`HotPath.skip` (``time_ns``: one timestamp, or one per lane with :meth:`attach_maps`): the pipe notes that the next solve's reference frame is the previous keyframe's
         prior (mv_frame_pipe_skip), and with an attached map the row is appended on the pipe's own stream with that prior copied on the device
-        (mv_frame_pipe_map_skip) — no host wait.  Called while tracked frames are still pending (``run``), it takes effect once they have finished."""
+        (mv_frame_pipe_map_skip_lanes) — no host wait.  Called while tracked frames are still pending (``run``), it takes effect once they have finished."""
         assert self._n_enq >= 1, "call initialize() with the first frame"
         time_ns = [int(v) for v in time_ns] if isinstance(time_ns, (list, tuple)) else int(time_ns)
         if self._has_pending():
@@ -1352,23 +1337,11 @@ class NativeHotPath:
             t = time_ns if isinstance(time_ns, list) else [time_ns] * self.lanes
             if len(t) != self.lanes:
                 raise L.MacvoHipError(f"skip: {len(t)} timestamps for {self.lanes} lane(s)")
-            self._grow_maps(mps, 0)
+            mps.grow(0, drain=self.synchronize)
             L.check(lib.mv_frame_pipe_map_skip_lanes(self._pipe, mps.stores_dev(), mps[0].n_frames, self._map_K.data_ptr(), self._map_TBS.data_ptr(),
                                                      float(self.cam.baseline), (ops.C.c_int64 * self.lanes)(*t)), "mv_frame_pipe_map_skip_lanes")
             for m in mps:
                 m.n_frames += 1
-            return
-        if isinstance(time_ns, list):
-            time_ns = time_ns[0]
-        mp = getattr(self, "_map", None)
-        if mp is not None:
-            if mp.n_frames + 1 >= mp.cap["frames"]:
-                self.synchronize()
-                mp.reserve(0)
-                torch.cuda.synchronize()
-            L.check(lib.mv_frame_pipe_map_skip(self._pipe, ops.C.byref(mp.stores()), mp.n_frames, self._map_K.data_ptr(), self._map_TBS.data_ptr(),
-                                               float(self.cam.baseline), int(time_ns)), "mv_frame_pipe_map_skip")
-            mp.n_frames += 1
 
     def _keyframes_of(self, frames):
         """:meth:`HotPath._keyframes_of`: the keyframes of ``frames``; the frames in between are skipped as they are passed."""
@@ -1393,9 +1366,7 @@ class NativeHotPath:
         if self.cfg.mapping:
             self._images.append(self._prev_image)
             self._prev_image = x.image
-        if getattr(self, "_map", None) is not None:
-            self._times.append(int(x.time_ns))
-        elif getattr(self, "_maps", None) is not None:
+        if getattr(self, "_maps", None) is not None:
             self._times.append(self._lane_times(x))
         return x
 
@@ -1509,7 +1480,7 @@ class NativeHotPath:
             L.check(lib.mv_frame_pipe_finish_keypoints(self._pipe, self._kp.data_ptr(), self._nsel, sink), "mv_frame_pipe_finish_keypoints")
         return self._finished(host_counts=True)
 
-    def _map_tail(self, mp):
+    def _map_tail(self, mps):
         """Dense-mapping tail of the frame just finished (Odometry/MACVO.py:303-337): the reference maps only when tracking
         succeeded — so the frame's observation count has to reach the host first (one blocking wait per frame: mapping mode gives
         up the driver's run-ahead, as the reference's own `.cpu()` calls do) — and then draws its SECOND randperm of the frame from
@@ -1524,14 +1495,11 @@ class NativeHotPath:
         perm = (torch.randperm(nm.value) if g is None else torch.randperm(nm.value, generator=g))[: c.map_num_point]
         n = perm.numel()
         img = None if image0 is None else ops._req(image0.reshape(3, self.cam.H, self.cam.W), torch.float32, "image")
-        if mp is not None:
-            if mp.map_rows_upper + n >= mp.cap["map_points"]:
-                self.synchronize()
-                mp.reserve_map_points(n)
-                torch.cuda.synchronize()
-            mp.map_rows_upper += n
+        if mps is not None:   # (growth re-allocates the store member 0's host descriptor names, and stales the holder's device array with it)
+            mps.grow(new_map_points=n, drain=self.synchronize)
+            mps[0].map_rows_upper += n
         L.check(lib.mv_frame_pipe_map_points(self._pipe, perm.data_ptr() if n else None, n, None if img is None else img.data_ptr(),
-                                             None if mp is None else ops.C.byref(mp.stores())), "mv_frame_pipe_map_points")
+                                             None if mps is None else ops.C.byref(mps[0].stores())), "mv_frame_pipe_map_points")
         self._map_keep = img
         f32 = torch.float32
         v = lambda name, dt, tail: self._view(name, 0, dt, (n,) + tail)  # noqa: E731
@@ -1545,24 +1513,11 @@ class NativeHotPath:
         self._n_fin += 1
         if self._kps:
             self._kps.pop(0)
-        mp = getattr(self, "_map", None)
         dd = self.device_driven and not host_counts
-        if mp is not None:
-            n_rows = self._cap if dd else int(self._nsel[0])   # (device-driven: an upper bound; the append compacts by the `valid` mask)
-            if mp.n_frames + 1 >= mp.cap["frames"] or mp.rows_upper + n_rows >= mp.cap["match"]:
-                self.synchronize()                          # growth re-allocates the stores: rare (capacity doubles), so simply drain
-                mp.reserve(n_rows)
-                torch.cuda.synchronize()
-            L.check(lib.mv_frame_pipe_map_append(self._pipe, ops.C.byref(mp.stores()), mp.n_frames, mp.last_keyframe,
-                                                 self._map_K.data_ptr(), self._map_TBS.data_ptr(), float(self.cam.baseline),
-                                                 self._times.pop(0), None), "mv_frame_pipe_map_append")
-            mp.last_keyframe = mp.n_frames
-            mp.n_frames += 1
-            mp.rows_upper += n_rows
         mps = getattr(self, "_maps", None)
         if mps is not None:   # every lane into its own map: one launch for all lanes, then the optimised poses by one more (mv_frame_pipe_map_append_lanes)
-            n_rows = [self._cap if dd else int(self._nsel[l]) for l in range(self.lanes)]   # (device-driven: the upper bound, as above)
-            self._grow_maps(mps, n_rows)
+            n_rows = [self._cap if dd else int(self._nsel[l]) for l in range(self.lanes)]   # (device-driven: an upper bound; the append compacts by the `valid` mask)
+            mps.grow(n_rows, drain=self.synchronize)
             L.check(lib.mv_frame_pipe_map_append_lanes(self._pipe, mps.stores_dev(), mps[0].n_frames, mps[0].last_keyframe, self._map_K.data_ptr(),
                                                        self._map_TBS.data_ptr(), float(self.cam.baseline), self._times.pop(0)),
                     "mv_frame_pipe_map_append_lanes")
@@ -1570,7 +1525,7 @@ class NativeHotPath:
                 m.last_keyframe = m.n_frames
                 m.n_frames += 1
                 m.rows_upper += n
-        map_pts = self._map_tail(mp) if self.cfg.mapping else None
+        map_pts = self._map_tail(mps) if self.cfg.mapping else None
         out = []
         for l in range(self.lanes):
             res = _NativeResult(self, l, None if dd else self._nsel[l], None if dd else self._ncand[l])

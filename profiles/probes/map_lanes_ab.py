@@ -7,6 +7,7 @@
         Prints HIP-event times per frame; run it under `rocprofv3 --kernel-trace --stats` for the kernels' own durations.
     python profiles/probes/map_lanes_ab.py pipe [--variants plain,maps --lanes 32 --steps 300 --repeats 3] [--tree DIR]
         frames/s of a 32-lane pipe at 640 x 480 with and without maps attached, alternating in one process, a fresh pipe per measurement.
+        Variant `map` attaches through attach_map instead of attach_maps (one map, --lanes 1).
         --tree DIR: import the package from another checkout (e.g. the parent commit, `--variants plain`) — same script, same frames, same call.
 One JSON line per measurement."""
 import argparse
@@ -112,12 +113,17 @@ def pipe(args, torch, root):
         hot = NativeHotPath(Camera(**cam), HotPathConfig(graph_type="disp", volume_precision=ops.default_volume_precision()), dev, lanes=lanes,
                             generators=[7 + l for l in range(lanes)])
         mps = None
-        if variant == "maps":
-            from macvo_amd.devmap import DeviceVisualMaps
+        if variant in ("map", "maps"):
+            from macvo_amd.devmap import DeviceVisualMap, DeviceVisualMaps
 
             rows = (args.steps + args.warmup + 2) * 200
-            mps = DeviceVisualMaps(lanes, dev, init_size=1 << (rows + 1).bit_length())     # (no re-growth inside the timed region)
-            hot.attach_maps(mps, K)
+            size = 1 << (rows + 1).bit_length()                                            # (no re-growth inside the timed region)
+            if variant == "map":                                                           # the one-map call: --lanes 1
+                mps = [DeviceVisualMap(dev, init_size=size)]
+                hot.attach_map(mps[0], K)
+            else:
+                mps = DeviceVisualMaps(lanes, dev, init_size=size)
+                hot.attach_maps(mps, K)
         hot.initialize(batches[0])
         sink = torch.zeros(args.steps, lanes, 7, device=dev)
         for _ in hot.run(batches[(1 + k) % pool] for k in range(args.warmup)):

@@ -6,7 +6,8 @@ map_set_pose_lanes_kernel, devmap.DeviceVisualMaps, NativeHotPath.attach_maps).
   different capacities that re-grow at different frames;
 * refusal is per lane: a lane whose match store is one row short is refused (``counts[4]``), nothing of it is written, the other lanes are complete;
 * the driver: every lane of a 3-lane pipe leaves, bit for bit, what a one-lane pipe with ``attach_map`` leaves for that lane's sequence;
-* pipes without maps are unchanged, and ``attach_maps([m])`` on a one-lane pipe equals ``attach_map(m)``.
+* pipes without maps are unchanged, and ``attach_maps([m])`` on a one-lane pipe equals ``attach_map(m)``;
+* the one-lane C entry points (``mv_frame_pipe_map_append`` / ``_map_skip``), called by hand, leave what ``attach_maps([m])`` leaves.
 
 Every comparison is exact (``np.array_equal``): the kernels copy rows, nothing is rounded."""
 import ctypes as C
@@ -368,3 +369,46 @@ def test_unattached_pipes_are_unchanged_and_one_lane_forms_agree(gpu, sequences,
         hp.close()
     _same(sers[1][0], sers[0][0], "attach_maps([m]) vs attach_map(m)")
     assert np.array_equal(sers[0][1], sers[1][1]) and sers[0][2] == sers[1][2]
+
+
+def test_one_lane_c_entry_points_equal_the_lanes_path(gpu, sequences):
+    """mv_frame_pipe_map_append / mv_frame_pipe_map_skip — the host-descriptor form of the one registration protocol, which Python no longer calls — made by
+    hand on a pipe without maps, against the same run with ``attach_maps([m])``: lane 2's sequence, every other frame a keyframe, so both calls run."""
+    from macvo_amd import _lib as L
+    from macvo_amd.devmap import DeviceVisualMap
+    from macvo_amd.pipeline import Camera, HotPathConfig, NativeHotPath
+
+    cam, ins = sequences
+    seq, K, tbs, start = ins[2], _K(cam).to(gpu).contiguous(), T_BS[2].to(gpu).contiguous(), STARTS[2]
+    sers = []
+    for by_hand in (False, True):
+        hp = NativeHotPath(Camera(**cam), HotPathConfig(graph_type="icp", keyframe_freq=2), gpu, generators=[33])
+        m = DeviceVisualMap(gpu, init_size=4096)              # room for the whole run: no growth logic here
+        if by_hand:                                           # frame 0 as initialize pushes it
+            m.push_frame(K=K, T_BS=tbs, baseline=cam["baseline"], time_ns=_time(2, 0), prior_pose=start)
+            torch.cuda.synchronize()
+        else:
+            hp.attach_maps([m], K, tbs)
+        hp.initialize(seq[0], init_pose=start)
+        lib, pipe, args = hp._lib, hp._pipe, (K.data_ptr(), tbs.data_ptr(), float(cam["baseline"]))
+        for t in range(1, N_FRAMES):
+            if t % 2 == 0:
+                hp.step(seq[t])                               # (no finish is pending when the calls below come in)
+                if by_hand:
+                    L.check(lib.mv_frame_pipe_map_append(pipe, C.byref(m.stores()), m.n_frames, m.last_keyframe, *args, _time(2, t), None), "mv_frame_pipe_map_append")
+                    m.last_keyframe = m.n_frames
+                    m.n_frames += 1
+            elif by_hand:
+                L.check(lib.mv_frame_pipe_skip(pipe), "mv_frame_pipe_skip")
+                L.check(lib.mv_frame_pipe_map_skip(pipe, C.byref(m.stores()), m.n_frames, *args, _time(2, t)), "mv_frame_pipe_map_skip")
+                m.n_frames += 1
+            else:
+                hp.skip(_time(2, t))
+        hp.sync_all()
+        torch.cuda.synchronize()
+        assert m.cap["match"] == 4096 and m.n_frames == N_FRAMES
+        sers.append((m.serialize(), m.poses_array(), m.counts.cpu().tolist()))
+        hp.close()
+    _same(sers[1][0], sers[0][0], "mv_frame_pipe_map_append / _map_skip vs attach_maps([m])")
+    assert np.array_equal(sers[0][1], sers[1][1]) and sers[0][2] == sers[1][2]
+    assert sers[0][0]["frames//need_interp"].tolist() == _want_flags(2, 2) and sers[0][0]["match//pixel1_uv"].shape[0] > 100
