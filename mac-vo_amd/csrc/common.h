@@ -59,6 +59,38 @@ __device__ __forceinline__ void mv_epilogue_pixel(const mvEpiArgs& a, int plane,
         a.match_cov[2 * plane + i] = 0.f;
     }
 }
+// mv_epilogue_pixel in two halves for a caller that wants a pixel's six input loads in flight early (kp_nms_kernel<true> issues those of
+// its four pixels in front of its record reservation): the loads — flow and logcov are [2, 2, H, W], every plane is read —, then the same
+// expressions and stores as above.
+struct mvEpiPixel { float fx0, lc0, f2, f3, l0, l1; };
+__device__ __forceinline__ mvEpiPixel mv_epilogue_load(const mvEpiArgs& a, int plane, int i) {
+    return mvEpiPixel{a.flow[i], a.logcov[i], a.flow[2 * plane + i], a.flow[3 * plane + i], a.logcov[2 * plane + i], a.logcov[3 * plane + i]};
+}
+__device__ __forceinline__ void mv_epilogue_store(const mvEpiArgs& a, int plane, int i, const mvEpiPixel& v) {
+    const float fx0 = v.fx0;
+    const float lc0 = v.lc0;
+    const float dcov = a.cov_is_log ? expf(lc0 * 2.f) : lc0;
+    const float d = fabsf(fx0);
+    if (a.disparity) a.disparity[i] = d;
+    if (a.disparity_cov) a.disparity_cov[i] = dcov;
+    if (a.depth) a.depth[i] = a.bl_fx * (1.f / d);
+    if (a.depth_cov) {
+        const float d2 = d * d;
+        const float err2 = dcov * (1.f / d2);
+        a.depth_cov[i] = a.bl_fx_sq * (err2 / d2);
+    }
+    if (a.bad_mask) a.bad_mask[i] = fx0 <= 0.f;
+    if (a.match_flow) {
+        a.match_flow[i] = v.f2;
+        a.match_flow[plane + i] = v.f3;
+    }
+    if (a.match_cov) {
+        const float l0 = v.l0, l1 = v.l1;
+        a.match_cov[i] = a.cov_is_log ? expf(l0 * 2.f) : l0;
+        a.match_cov[plane + i] = a.cov_is_log ? expf(l1 * 2.f) : l1;
+        a.match_cov[2 * plane + i] = 0.f;
+    }
+}
 // mv_epilogue_pixel of a frontend that lacks the depth model's covariance (D = false), the matcher's (M = false) or both (StereoDepth.py:121-128,
 // Matching.py:142-147: `cov` / `disparity_uncertainty` are None).  Only the covariance planes of a pair whose flag is set are read and written; `logcov`
 // may be null when neither is.  Same expressions as above for everything that is written.

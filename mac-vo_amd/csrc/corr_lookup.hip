@@ -18,59 +18,151 @@
 //     and (query, j) for y: 2K values per query instead of 2*K*K.  Lanes [0, 2K) of an "axis pass" evaluate them for one
 //     query, the next 2K lanes for the next query, ... (true division, same fp32 op order as grid_sample) and write the
 //     (weight, cell) entries to LDS.  Results are bit-identical to the per-tap form.
-//   * taps (round 6): the wave's QPW * K*K (tap, query) PAIRS are dealt over its lanes (324 pairs = 6 rounds for four
-//     queries; "lane = tap, query after query" took 8, every second one with 17 live lanes); a pair reads its two axis
-//     entries (two 8-byte LDS reads; rounds 1-5: four ds_bpermute), 4 cells, and forms the ATen bilinear sum.
-//   * output [B, K*K, H1, W1] is channel-major: results are transposed through LDS (aliasing the staging buffer) so
-//     every channel row is written as one QPB*4-byte segment.
+//   * taps: the wave's QPW * K*K (tap, query) PAIRS are dealt over its lanes (four queries: 324 pairs in 6 rounds; "lane = tap, query
+//     after query" took 8, every second one with 17 live lanes); a pair reads its two axis entries (two 8-byte LDS reads), 4 cells, and
+//     forms the ATen bilinear sum.  For r = 4 the deal and the block strides are chosen so that a 32-lane group reads 32 different LDS
+//     banks (tap_phase below; CPU model: profiles/probes/lookup_lds_bank_model.py — 34.5 % of the kernel's LDS-array cycles were
+//     conflicts, 0 now for the row-major block, the rest of the tiled block's is its staging stores).
+//   * output [B, K*K, H1, W1] is channel-major: results are transposed through LDS so every channel row is written as one QPB*4-byte
+//     segment.  A wave parks its results in a strip that aliases ITS OWN staged blocks.
+//   * ONE workgroup barrier, in front of the transposed store (the only place where a wave reads what another wave wrote).  Staging ->
+//     taps and taps -> strip are hand-overs inside one wave (wave_lds_handover: in-order LDS, no instruction); before, every wave of
+//     the workgroup waited at two more barriers for the slowest wave's cell loads and tap reads.
+//   * static LDS per workgroup (r = 4): 11 648 B for 16 queries (8 waves x 2 blocks of 146 floats + 2 304 B of axis entries; 11 520 B
+//     before), 23 680 B for 32; tiled blocks (16 x 20 + 18 floats): 23 936 B / 48 256 B.  Beside one f16x2 GEMM workgroup per CU
+//     (304 of 512 registers per SIMD, 96 KB of LDS) the 16-query workgroup (31 registers -> 2 x 32 per SIMD) is limited by the 208 free
+//     registers to three workgroups (64 registers per SIMD each; at the 33 -> 40 registers before: two) and by LDS to five.  Beside the 144-KB ring of the
+//     bf16x3 GEMM (16 KB free) one workgroup fits, as before — which is why the strip aliases the blocks rather than adding
+//     81 x 17 floats of its own.
 #include "common.h"
 
 namespace {
 
 // One axis entry of a query — what RAFT's normalise + ATen's un-normalise make of (coordinate + offset): the bilinear weight and the clamped
 // cell offset in the staged block | (1 << 8) when the tap's 2-cell span lies inside the block.  The axis passes write the 2 K entries of
-// every query of the wave into LDS; the tap phase reads them back per (tap, query) PAIR.
-struct AxisEntry { float w; int c; };
+// every query of the wave into LDS; the tap phase reads them back per (tap, query) PAIR (8-byte aligned: one ds_read_b64 each).
+struct alignas(8) AxisEntry { float w; int c; };
 
-// Tap phase shared by the lookup kernels (round 6): the wave's QPW * K * K (tap, query) pairs are dealt over its lanes — 324 pairs = 6 rounds
-// of 64 for four queries where "lane = tap, one query after the other" takes 8 rounds of which every second one has 17 live lanes — and a
-// pair fetches its two axis entries with two 8-byte LDS reads where the lane = tap form used four ds_bpermute.  The arithmetic per pair is
-// the ATen bilinear sum of before, term for term.
+// Hand-over of LDS contents between the lanes of ONE wave: the LDS unit executes a wave's operations in order, so all that is needed is
+// that the compiler keeps the order too (it reasons per thread and would otherwise be free to move a read above another lane's write).
+// Emits no instruction and no wait; NOT a workgroup barrier.
+__device__ __forceinline__ void wave_lds_handover() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One tap: the ATen bilinear sum, term for term (every expression and its order as in every earlier form of this file)
+template <int K, int STRIDE>
+__device__ __forceinline__ float tap_one(const float* qblk, const AxisEntry* qax, int ti, int tj) {
+    const AxisEntry X = qax[ti], Y = qax[K + tj];
+    const float w = X.w, n = Y.w;
+    const bool inblk = ((X.c & Y.c) & 256) != 0;
+    const float* p = &qblk[(Y.c & 255) * STRIDE + (X.c & 255)];
+    const float e = 1.f - w, so = 1.f - n;
+    const float vnw = inblk ? p[0] : 0.f, vne = inblk ? p[1] : 0.f;
+    const float vsw = inblk ? p[STRIDE] : 0.f, vse = inblk ? p[STRIDE + 1] : 0.f;
+    // ATen: (nw_val*nw + ne_val*ne) + sw_val*sw + se_val*se with nw = s*e, ne = s*w, sw = n*e, se = n*w
+    float r0 = vnw * (so * e);
+    r0 = r0 + vne * (so * w);
+    r0 = r0 + vsw * (n * e);
+    r0 = r0 + vse * (n * w);
+    return r0;
+}
+
+// A wave's output strip holds the results of its query s at strip[s * strip_pitch + u], u < K K; the strips of the workgroup's waves are
+// wave_floats apart.  For K = 9 the pitch and the distance are chosen so that the transposed store's LDS reads — 32 lanes = 32 queries of
+// one row u (four-query waves) or 16 queries of two rows (two-query waves) — touch 32 different banks: 8 waves x 20 (resp. 4) banks apart,
+// queries 83 (resp. 82) floats apart.
+template <int K, int QPW>
+constexpr int strip_pitch() { return K * K + ((K == 9 && QPW == 4) ? 2 : 1); }
+template <int K, int QPW, int CELLS>
+constexpr int wave_floats() { return QPW * CELLS + ((K == 9 && QPW == 4) ? 12 : 0); }
+
+// Row u of a wave's output strip holds channel tap_channel(u).  K = 9: u enumerates the 8 x 9 body of the window (u = 8 ti + tj,
+// tj < 8), then the row tj = 8 (u = 72 + ti) — the order the taps are dealt in; any other K: u = channel.
+template <int K>
+__device__ __forceinline__ int tap_channel(int u) {
+    if constexpr (K == 9) return u < 72 ? u + (u >> 3) : 9 * (u - 72) + 8;
+    else return u;
+}
+
+// Tap phase shared by the lookup kernels: the wave's QPW * K * K (tap, query) pairs are dealt over its lanes, a pair reads its two axis
+// entries (two 8-byte LDS reads) and 4 cells and forms the bilinear sum; the sums then go to the wave's OWN output strip
+// strip[s * strip_pitch + u], which aliases the wave's staged blocks — only this wave ever read those, so the hand-over is wave-local.
+// (s, ti, tj) and the strip address are derived once per round, without a division.
+//
+// K = 9 (radius 4, every hot path).  The cell of tap (ti, tj) sits at STRIDE * (tj + cy) + ti + cx of its query's block; with
+// STRIDE = 12 (row-major) or 20 (tiled) that is bank 4 * (3 tj mod 8) + ti resp. 4 * (5 tj mod 8) + ti (+ a per-query constant): the 4 x 8
+// taps ti0 .. ti0 + 3, tj 0 .. 7 of ONE query cover the 32 banks exactly once.  Hence (profiles/probes/lookup_lds_bank_model.py):
+//   * rounds 0 .. QPW - 1: round r = query r, lane = 8 ti + tj over ti, tj in 0 .. 7: each 32-lane group is one such 4 x 8 patch — the
+//     four cell reads and both axis reads are conflict-free, and (s, ti, tj) cost one shift and one mask for all rounds;
+//   * QPW / 2 rounds for what is left of two queries each (17 taps per query): lanes 0 .. 15 the column ti = 8 (tj 0 .. 7) of both,
+//     lanes 32 .. 49 the row tj = 8 (ti 0 .. 8) of both.  A query's block starts CELLS = 18 mod 32 banks behind its neighbour's, which
+//     keeps the two columns (banks 0 mod 4 | 2 mod 4) and the two rows (9 consecutive banks each, 18 apart) disjoint as long as both
+//     queries sit at the same offset in their blocks (always in the row-major block; the tiled block adds (x mod 4, y mod 4)).
+//   The same number of rounds as dealing 64 consecutive pairs per round (3 for two queries, 6 for four), which put rows tj = 0 and
+//   tj = 8 of every column on one bank: two-way conflicts in every group of every cell read.
+// Any other K: 64 consecutive pairs per round, (s, ti, tj) advanced by 64 as a three-digit number in base K.
 template <int K, int QPW, int STRIDE, int CELLS>
-__device__ __forceinline__ void tap_pairs(const float* blk, const AxisEntry (*ax)[2 * K], int lane, float (&res)[(QPW * K * K + 63) / 64]) {
-    constexpr int KK = K * K, NPAIR = QPW * KK, NR = (NPAIR + 63) / 64;
+__device__ __forceinline__ void tap_phase(float* blk, const AxisEntry (*ax)[2 * K], int lane) {
+    constexpr int KK = K * K, P = strip_pitch<K, QPW>();
+    static_assert(P <= CELLS, "the output strip must fit in the wave's staged blocks");
+    if constexpr (K == 9) {
+        static_assert(QPW % 2 == 0, "the leftover rounds pair queries");
+        constexpr int NL = QPW / 2;
+        float res[QPW + NL];
+        const int ti0 = lane >> 3, tj0 = lane & 7;
 #pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const int pair = min(r * 64 + lane, NPAIR - 1);
-        const int s = pair / KK, tap = pair - s * KK;
-        const int ti = tap / K, tj = tap - ti * K;
-        const AxisEntry X = ax[s][ti], Y = ax[s][K + tj];
-        const float w = X.w, n = Y.w;
-        const bool inblk = ((X.c & Y.c) & 256) != 0;
-        const float* p = &blk[s * CELLS + (Y.c & 255) * STRIDE + (X.c & 255)];
-        const float e = 1.f - w, so = 1.f - n;
-        const float vnw = inblk ? p[0] : 0.f, vne = inblk ? p[1] : 0.f;
-        const float vsw = inblk ? p[STRIDE] : 0.f, vse = inblk ? p[STRIDE + 1] : 0.f;
-        // ATen: (nw_val*nw + ne_val*ne) + sw_val*sw + se_val*se with nw = s*e, ne = s*w, sw = n*e, se = n*w
-        float r0 = vnw * (so * e);
-        r0 = r0 + vne * (so * w);
-        r0 = r0 + vsw * (n * e);
-        r0 = r0 + vse * (n * w);
-        res[r] = r0;
+        for (int r = 0; r < QPW; ++r) res[r] = tap_one<K, STRIDE>(blk + r * CELLS, ax[r], ti0, tj0);
+        const int l = lane & 31;
+        const bool rowh = lane >= 32;                                   // upper half: the row tj = 8; lower half: the column ti = 8
+        const int sl = rowh ? (l >= 9 ? 1 : 0) : ((l >> 3) & 1);        // which query of the pair
+        const int ti = rowh ? min(l - 9 * sl, 8) : 8, tj = rowh ? 8 : (l & 7);   // (idle lanes repeat a live lane's tap)
+        const bool live = rowh ? l < 18 : l < 16;
+        const int ul = sl * P + (rowh ? 72 + ti : 64 + tj);
+#pragma unroll
+        for (int m = 0; m < NL; ++m) res[QPW + m] = tap_one<K, STRIDE>(blk + (2 * m + sl) * CELLS, ax[2 * m + sl], ti, tj);
+        wave_lds_handover();   // every read of the staged blocks precedes the strip that overwrites them
+#pragma unroll
+        for (int r = 0; r < QPW; ++r) blk[r * P + lane] = res[r];
+#pragma unroll
+        for (int m = 0; m < NL; ++m)
+            if (live) blk[2 * m * P + ul] = res[QPW + m];
+    } else {
+        constexpr int NPAIR = QPW * KK, NR = (NPAIR + 63) / 64;
+        constexpr int D0 = 64 % K, D1 = (64 / K) % K, D2 = 64 / KK;     // 64 in base K
+        float res[NR];
+        int oaddr[NR];
+        int s = lane / KK, ti = (lane - s * KK) / K, tj = lane - s * KK - ti * K;   // round 0 (constant divisors, lane < 64)
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const int sc = min(s, QPW - 1);                            // (lanes past the last pair repeat a tap of the last query)
+            res[r] = tap_one<K, STRIDE>(blk + sc * CELLS, ax[sc], ti, tj);
+            oaddr[r] = s < QPW ? s * P + ti * K + tj : -1;
+            tj += D0;
+            const int c0 = tj >= K ? 1 : 0;
+            tj -= c0 * K;
+            ti += D1 + c0;
+            const int c1 = ti >= K ? 1 : 0;
+            ti -= c1 * K;
+            s += D2 + c1;
+        }
+        wave_lds_handover();
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            if (oaddr[r] >= 0) blk[oaddr[r]] = res[r];
     }
 }
 
-// ... and its results into the transpose buffer: outs[tap][query of the workgroup]
-template <int K, int QPW, int QPB>
-__device__ __forceinline__ void tap_pairs_out(float (*outs)[QPB + 1], int wave, int lane, const float (&res)[(QPW * K * K + 63) / 64]) {
-    constexpr int KK = K * K, NPAIR = QPW * KK, NR = (NPAIR + 63) / 64;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const int pair = r * 64 + lane;
-        if (pair < NPAIR) {
-            const int s = pair / KK, tap = pair - s * KK;
-            outs[tap][wave * QPW + s] = res[r];
-        }
+// ... and the transposed store: every channel row of the workgroup = QPB consecutive queries = one contiguous segment; the value of
+// (row u, query c) is read from the strip of the wave that owns query c
+template <int K, int QPW, int QPB, int BLK_STRIDE>
+__device__ __forceinline__ void store_tokens(const float* smem, float* __restrict__ out, int b, int q0, int N1, int t) {
+    constexpr int KK = K * K, P = strip_pitch<K, QPW>(), NTHR = 64 * (QPB / QPW);
+    for (int idx = t; idx < KK * QPB; idx += NTHR) {
+        const int u = idx / QPB, c = idx - u * QPB;
+        if (q0 + c < N1) out[((size_t)b * KK + tap_channel<K>(u)) * N1 + q0 + c] = smem[(c / QPW) * BLK_STRIDE + (c % QPW) * P + u];
     }
 }
 
@@ -82,11 +174,9 @@ __global__ __launch_bounds__(64 * (QPB / QPW)) void corr_lookup_kernel(const VT*
                                                                         const float* __restrict__ coords,
                                                                         float* __restrict__ out, int N1, int H2, int W2) {
     constexpr int K = 2 * R + 1;
-    constexpr int KK = K * K;
     constexpr int BS = K + 3;            // staged block edge (12 for r = 4)
-    constexpr int CELLS = BS * BS;       // 144
+    constexpr int CELLS = BS * BS + (K == 9 ? 2 : 0);   // floats per staged block: 144 cells (+ 2 for r = 4: consecutive blocks 18 banks apart, see tap_phase)
     constexpr int NWAVE = QPB / QPW;     // waves per workgroup, QPW queries each
-    constexpr int NTHR = 64 * NWAVE;
     constexpr int RPR = 64 / BS;         // block rows one wave-wide load covers (5 for r = 4)
     constexpr int LPR = RPR * BS;        // active lanes of such a load (60)
     constexpr int NROUND = (BS + RPR - 1) / RPR;    // loads per query (3)
@@ -102,13 +192,10 @@ __global__ __launch_bounds__(64 * (QPB / QPW)) void corr_lookup_kernel(const VT*
     constexpr int APASS = (QPW + QPA - 1) / QPA;
     static_assert(QPW <= 32 && (QPW & (QPW - 1)) == 0 && QPB % QPW == 0, "bad lookup tiling");
 
-    // one LDS region, two lives: staged cell blocks (read by the tap phase), then the transposed outputs
-    constexpr int BLK_STRIDE = QPW * CELLS;
-    constexpr int BLK_FLOATS = NWAVE * BLK_STRIDE;
-    constexpr int OUT_FLOATS = KK * (QPB + 1);
-    __shared__ float smem[BLK_FLOATS > OUT_FLOATS ? BLK_FLOATS : OUT_FLOATS];
+    // one LDS region per WAVE, two lives: the wave's staged cell blocks (written and read by this wave only), then its output strip
+    constexpr int BLK_STRIDE = wave_floats<K, QPW, CELLS>();
+    __shared__ float smem[NWAVE * BLK_STRIDE];
     float* blk = smem + (threadIdx.x >> 6) * BLK_STRIDE;
-    float (*outs)[QPB + 1] = reinterpret_cast<float (*)[QPB + 1]>(smem);
 
     MV_SMALL_KERNEL_PRIO();
     const int b = blockIdx.y;
@@ -198,23 +285,18 @@ __global__ __launch_bounds__(64 * (QPB / QPW)) void corr_lookup_kernel(const VT*
         } else {
 #pragma unroll
             for (int k = 0; k < NROUND; ++k)
-                if (lane < LPR && k * LPR + lane < CELLS) blk[s * CELLS + k * LPR + lane] = v[s][k];
+                if (lane < LPR && k * LPR + lane < BS * BS) blk[s * CELLS + k * LPR + lane] = v[s][k];
         }
     }
-    __syncthreads();
+    // no workgroup barrier: the tap phase of a wave reads the blocks and axis entries that this same wave wrote
+    wave_lds_handover();
 
-    // ---- taps: (tap, query) pairs over the lanes
-    float res[(QPW * KK + 63) / 64];
-    tap_pairs<K, QPW, BS, CELLS>(blk, ax, lane, res);
-    __syncthreads();   // every wave is done reading the staged blocks: the region becomes the output transpose buffer
-    tap_pairs_out<K, QPW, QPB>(outs, wave, lane, res);
-    __syncthreads();
+    // ---- taps: (tap, query) pairs over the lanes, results into the wave's output strip
+    tap_phase<K, QPW, BS, CELLS>(blk, ax, lane);
+    __syncthreads();   // the kernel's only barrier: the transposed store reads every wave's strip
 
     // ---- transposed store: each channel row = QPB consecutive queries
-    for (int idx = t; idx < KK * QPB; idx += NTHR) {
-        const int k = idx / QPB, c = idx - k * QPB;
-        if (q0 + c < N1) out[((size_t)b * KK + k) * N1 + q0 + c] = outs[k][c];
-    }
+    store_tokens<K, QPW, QPB, BLK_STRIDE>(smem, out, b, q0, N1, t);
 }
 
 
@@ -237,18 +319,15 @@ template <int QPW, int QPB, typename VT = float>
 __global__ __launch_bounds__(64 * (QPB / QPW)) void corr_lookup_tiled_kernel(const VT* __restrict__ vol,
                                                                               const float* __restrict__ coords,
                                                                               float* __restrict__ out, int N1, int H2, int W2) {
-    constexpr int R = 4, K = 9, KK = 81;
+    constexpr int R = 4, K = 9;
     constexpr int BS = 16;                     // staged block: 4 x 4 tiles of 4 x 4 cells ...
-    constexpr int BSP = 18, CELLS = BS * BSP;  // ... at a row stride of 18 floats: the 9 rows a wave's taps read sit in 9 different banks (16: rows y, y + 2 collide)
-    constexpr int NWAVE = QPB / QPW, NTHR = 64 * NWAVE;
+    constexpr int BSP = 20, CELLS = BS * BSP + 18;  // ... at a row stride of 20 floats, blocks 18 banks apart: 4 x 8 taps of a query cover the 32 banks once (tap_phase)
+    constexpr int NWAVE = QPB / QPW;
     constexpr int QPA = 64 / (2 * K);
     constexpr int APASS = (QPW + QPA - 1) / QPA;
-    constexpr int BLK_STRIDE = QPW * CELLS;
-    constexpr int BLK_FLOATS = NWAVE * BLK_STRIDE;
-    constexpr int OUT_FLOATS = KK * (QPB + 1);
-    __shared__ float smem[BLK_FLOATS > OUT_FLOATS ? BLK_FLOATS : OUT_FLOATS];
+    constexpr int BLK_STRIDE = wave_floats<K, QPW, CELLS>();
+    __shared__ __attribute__((aligned(16))) float smem[NWAVE * BLK_STRIDE];   // per wave: its staged blocks, then its output strip
     float* blk = smem + (threadIdx.x >> 6) * BLK_STRIDE;
-    float (*outs)[QPB + 1] = reinterpret_cast<float (*)[QPB + 1]>(smem);
 
     MV_SMALL_KERNEL_PRIO();
     const int b = blockIdx.y;
@@ -333,17 +412,11 @@ __global__ __launch_bounds__(64 * (QPB / QPW)) void corr_lookup_tiled_kernel(con
             else
                 blk[s * CELLS + (4 * k + (cell >> 2)) * BSP + 4 * ti + (cell & 3)] = v[s][k];
         }
-    __syncthreads();
+    wave_lds_handover();   // (wave-local, as in corr_lookup_kernel)
 
-    float res[(QPW * KK + 63) / 64];
-    tap_pairs<K, QPW, BSP, CELLS>(blk, ax, lane, res);
+    tap_phase<K, QPW, BSP, CELLS>(blk, ax, lane);
     __syncthreads();
-    tap_pairs_out<K, QPW, QPB>(outs, wave, lane, res);
-    __syncthreads();
-    for (int idx = t; idx < KK * QPB; idx += NTHR) {
-        const int k = idx / QPB, c = idx - k * QPB;
-        if (q0 + c < N1) out[((size_t)b * KK + k) * N1 + q0 + c] = outs[k][c];
-    }
+    store_tokens<K, QPW, QPB, BLK_STRIDE>(smem, out, b, q0, N1, t);
 }
 
 }  // namespace

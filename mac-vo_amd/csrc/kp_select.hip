@@ -14,10 +14,17 @@
 //            before the first LDS store), SEPARABLE NaN-propagating min (k + k LDS reads per pixel instead of k*k),
 //            equality test, one 64-bit __ballot word per 64-pixel row segment for the threshold-independent part of
 //            the mask.  Every NMS pixel also emits a 12-byte record {bit address | candidate flag, flow quality,
-//            depth0 variance}; a workgroup reserves its record range with ONE global atomic (LDS-aggregated).  That
-//            atomic is the kernel's longest dependency (measured: ~6 of its 13 us are 300 workgroups waiting for the
-//            return value of a same-address device-scope atomic); removing it needs per-workgroup record regions and a
-//            re-indexing pass in kernel 2 that costs about half of what it saves — left as is.
+//            depth0 variance}; a workgroup reserves its record range with ONE global atomic.  The return of that
+//            same-address device-scope atomic is the kernel's longest dependency (~6 of 13 us alone when 300 workgroups
+//            wait for it with nothing else to do), so it is issued as early as the count exists and consumed as late as
+//            possible: the NMS decisions (LDS only) come first, the workgroup's count is taken from the wave ballots
+//            (popcounts in scalar registers + four per-wave totals in LDS: no same-address LDS atomics), one thread
+//            issues the global atomic, and in the fused form the epilogue pixels (their 6 loads each issued in front of
+//            the reservation, then 9 stores each), the mask reads and the candidate words run while it is in flight; only
+//            the record stores wait for the base.  The
+//            form without the epilogue has nothing to put there and keeps decisions -> count -> atomic -> records.
+//            Records of a workgroup are in (wave, row, lane) order, workgroups in the order their atomics land — kernel
+//            2 does not depend on either (see the record stores below).
 //   kernel 2 (one 1024-thread workgroup; 256 / 512 threads measured 3x / 1.4x slower): every global read is issued
 //            up front (records -> registers, candidate words -> registers -> dynamic LDS); lower (nan)median(s) by
 //            BUCKET REFINEMENT on order-preserving keys (min/max -> 2048 linear buckets over the population's own range
@@ -103,14 +110,13 @@ __global__ __launch_bounds__(256) void kp_nms_kernel(const float* __restrict__ f
     }
     __shared__ float tile[TILE_H + 2 * MAX_R][TILE_W + 2 * MAX_R + 1];
     __shared__ float hmin[TILE_H + 2 * MAX_R][TILE_W + 1];
-    __shared__ int wg_count, wg_base;
+    __shared__ int wave_cnt[4], wg_base;
     const int H = p.H, W = p.W, plane = H * W;
     const int r = p.kernel_size >> 1;
     const int x0 = blockIdx.x * TILE_W, y0 = blockIdx.y * TILE_H;
     const int tx = threadIdx.x, ty = threadIdx.y;  // tx = lane (0..63), ty = wave (0..3)
     const int tid = ty * 64 + tx;
     const bool mapping = p.mode == MV_KP_MAPPING;
-    if (tid == 0) wg_count = 0;
 
     if (!mapping) {
         const int tw = TILE_W + 2 * r, th = TILE_H + 2 * r;
@@ -156,30 +162,55 @@ __global__ __launch_bounds__(256) void kp_nms_kernel(const float* __restrict__ f
     }
     __syncthreads();
 
-    bool nms_px[TILE_H / 4];
-    bool cand_px[TILE_H / 4];
-    float q_px[TILE_H / 4];
-    int my_nms = 0;
+    constexpr int NPX = TILE_H / 4;   // pixels per thread: rows ty * 4 .. ty * 4 + 3 of the tile, column tx
+    const int gx = x0 + tx;
+
+    // ---- NMS decision of the thread's pixels: LDS only
+    bool nms_px[NPX];
+    float q_px[NPX];
+    unsigned long long nms_word[NPX];   // wave-uniform: the row's NMS pixels
 #pragma unroll
-    for (int it = 0; it < TILE_H / 4; ++it) {
-        const int ly = ty * (TILE_H / 4) + it;
-        const int gx = x0 + tx, gy = y0 + ly;
+    for (int it = 0; it < NPX; ++it) {
+        const int ly = ty * NPX + it;
+        bool nms = false;
+        float q = 0.f;
+        if (!mapping && gx < W && y0 + ly < H) {
+            q = tile[ly + r][tx + r];
+            float m = hmin[ly][tx];
+            for (int dy = 1; dy <= 2 * r; ++dy) m = nanmin(m, hmin[ly + dy][tx]);
+            nms = (q == m);  // false whenever the window holds a NaN (m is NaN then) or q itself is NaN
+        }
+        nms_px[it] = nms;
+        q_px[it] = q;
+        nms_word[it] = __ballot(nms);
+    }
+
+    // ---- fused: the epilogue inputs of the thread's pixels, all loads in flight here — in front of the reservation, so that the wave
+    //      which issues the atomic can consume them while the atomic is still out (loads and returning atomics complete in issue order)
+    mvEpiPixel epi[NPX] = {};
+    if (FUSE) {
+#pragma unroll
+        for (int it = 0; it < NPX; ++it) {
+            const int gy = y0 + ty * NPX + it;
+            if (gx < W && gy < H) epi[it] = mv_epilogue_load(ef, plane, gy * W + gx);
+        }
+    }
+
+    // ---- the rest of a pixel: (fused) its epilogue outputs, the candidate decision, the row's candidate word
+    bool cand_px[NPX];
+    auto pixel_rest = [&](int it) {
+        const int gy = y0 + ty * NPX + it;
         const bool inimg = gx < W && gy < H;
         const int idx = gy * W + gx;
-        bool nms = false, cand = false;
-        float q = 0.f;
-        if (FUSE && inimg) mv_epilogue_pixel(ef, plane, idx);
+        bool cand = false;
+        if (FUSE && inimg) mv_epilogue_store(ef, plane, idx, epi[it]);
         if (inimg) {
             const bool border = p.mask_width > 0 && gx >= p.mask_width && gx < W - p.mask_width &&
                                 gy >= p.mask_width && gy < H - p.mask_width;
             if (mapping) {
                 cand = border && (d0[idx] < p.max_depth) && (d0c[idx] < p.max_depth_cov);
             } else {
-                q = tile[ly + r][tx + r];
-                float m = hmin[ly][tx];
-                for (int dy = 1; dy <= 2 * r; ++dy) m = nanmin(m, hmin[ly + dy][tx]);
-                nms = (q == m);  // false whenever the window holds a NaN (m is NaN then) or q itself is NaN
-                cand = nms && border;
+                cand = nms_px[it] && border;
                 if (cand && p.mode == MV_KP_FULL) cand = (d0[idx] < p.max_depth) && (d1[idx] < p.max_depth);
             }
             if (cand && mask_a) cand = mask_a[idx] != 0;
@@ -187,38 +218,59 @@ __global__ __launch_bounds__(256) void kp_nms_kernel(const float* __restrict__ f
         }
         const unsigned long long cand_word = __ballot(cand);
         if (tx == 0 && gy < H) ws.cand_bits[(size_t)gy * words_per_row + blockIdx.x] = cand_word;
-        nms_px[it] = nms;
         cand_px[it] = cand;
-        q_px[it] = q;
-        my_nms += nms;
-    }
-    if (mapping) return;
-
-    // ---- records: LDS-aggregated reservation, one global atomic per workgroup
-    int my_off = 0;
-    if (my_nms) my_off = atomicAdd(&wg_count, my_nms);
-    __syncthreads();
-#ifdef MV_KP_FAKE_ATOMIC
-    if (tid == 0) wg_base = (blockIdx.y * gridDim.x + blockIdx.x) * 16;   // timing experiment only (wrong results)
-#else
-    if (tid == 0) wg_base = wg_count ? atomicAdd(&ws.counters[0], wg_count) : 0;
-#endif
-    __syncthreads();
-    int pos = wg_base + my_off;
+    };
+    if (!FUSE) {
 #pragma unroll
-    for (int it = 0; it < TILE_H / 4; ++it) {
+        for (int it = 0; it < NPX; ++it) pixel_rest(it);
+        if (mapping) return;
+    }
+
+    // ---- records: the workgroup's count from the ballots (scalar popcounts, one LDS word per wave), ONE global atomic per workgroup
+    int wave_n = 0;
+#pragma unroll
+    for (int it = 0; it < NPX; ++it) wave_n += __popcll(nms_word[it]);
+    if (tx == 0) wave_cnt[ty] = wave_n;
+    __syncthreads();
+    const int n0 = wave_cnt[0], n1 = wave_cnt[1], n2 = wave_cnt[2], n3 = wave_cnt[3];
+    const int wg_n = n0 + n1 + n2 + n3;
+    int base = 0;
+#ifdef MV_KP_FAKE_ATOMIC
+    if (tid == 0) base = (blockIdx.y * gridDim.x + blockIdx.x) * 16;   // timing experiment only (wrong results)
+#else
+    // Issued here, consumed behind the pixel work below.  The counter is addressed through an offset of zero that the compiler cannot
+    // see through: for an atomic at a wave-uniform address it would build the wave-aggregated form, whose v_readfirstlane of the
+    // returned value forces the wait for the atomic right here, in front of the loads that are meant to overlap it.
+    int opaque_zero = 0;
+    asm volatile("" : "+v"(opaque_zero));
+    if (tid == 0 && wg_n) base = atomicAdd(ws.counters + opaque_zero, wg_n);
+#endif
+    if (FUSE) {
+#pragma unroll
+        for (int it = 0; it < NPX; ++it) pixel_rest(it);
+    }
+    if (tid == 0) wg_base = base;
+    __syncthreads();
+    // Record order: inside the workgroup (wave, row, lane) — a pixel's slot is the popcount of the NMS bits in front of it; across
+    // workgroups whatever order the atomics landed in.  kp_finish_body depends on neither: the medians are those of the record
+    // POPULATION, failing records clear their bit by ADDRESS, and the candidate list is compacted from the bit words by position.
+    int pos = wg_base + (ty > 0 ? n0 : 0) + (ty > 1 ? n1 : 0) + (ty > 2 ? n2 : 0);
+#pragma unroll
+    for (int it = 0; it < NPX; ++it) {
         if (nms_px[it]) {
-            const int gx = x0 + tx, gy = y0 + ty * (TILE_H / 4) + it;
+            const int gy = y0 + ty * NPX + it;
             const int idx = gy * W + gx;
-            ws.rec_idx[pos] = (unsigned)(((gy * words_per_row + blockIdx.x) << 6) | tx) | (cand_px[it] ? CAND_FLAG : 0u);
+            const int at = pos + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(nms_word[it] >> 32),
+                                                                __builtin_amdgcn_mbcnt_lo((unsigned)nms_word[it], 0u));
+            ws.rec_idx[at] = (unsigned)(((gy * words_per_row + blockIdx.x) << 6) | tx) | (cand_px[it] ? CAND_FLAG : 0u);
             if (p.mode == MV_KP_NODEPTH) {
-                ws.rec_q[pos] = q_px[it];
+                ws.rec_q[at] = q_px[it];
             } else {
-                ws.rec_q[pos] = fc ? flow_quality(fc, plane, idx) : 0.f;
-                ws.rec_d[pos] = d0c[idx];
+                ws.rec_q[at] = fc ? flow_quality(fc, plane, idx) : 0.f;
+                ws.rec_d[at] = d0c[idx];
             }
-            ++pos;
         }
+        pos += __popcll(nms_word[it]);
     }
 }
 
