@@ -228,6 +228,18 @@ int mv_convex_upsample(const float* flow, const float* mask, float* out, int B, 
  * the mask head runs under autocast and no `.float()` copy of the 11 MB mask is made).  flow and out stay fp32. */
 int mv_convex_upsample_m(const float* flow, const void* mask, int mask_dtype, float* out, int B, int h, int w,
                          float mask_scale, int exp2_out, mvStream_t stream);
+/* Frames whose sides are no multiples of 8.  The network pads such a frame, centred, before its encoders and un-pads its dense outputs (FlowFormerCov.inference,
+ * flownet.py:37-44: `InputPadder(image1.shape)`, the public RAFT / FlowFormer padder in its default "sintel" mode — the FlowFormer submodule is unpinned in the
+ * reference checkout; tools/flowformer_host.py states the padder).  mv_input_pad writes pad = {left, right, top, bottom} with left = ((-W) % 8) / 2 and
+ * top = ((-H) % 8) / 2: the 1/8 maps are (H + top + bottom) / 8 x (W + left + right) / 8, frame pixel (y, x) is pixel (y + top, x + left) of the padded frame. */
+void mv_input_pad(int H, int W, int32_t pad[4]);
+/* mv_convex_upsample(_m) that stores only the window rows [y0, y0 + H) x columns [x0, x0 + W) of the 8h x 8w result (0 <= y0, y0 + H <= 8h, likewise x): the network's
+ * `unpad` inside the kernel.  out [B, 2, H, W] fp32, dense (row pitch W), 4-byte aligned — nothing more is assumed, an odd H * W is fine;
+ * out[b, c, y, x] has the bits mv_convex_upsample_m gives at (y + y0, x + x0).  Nothing outside `out` is written. */
+int mv_convex_upsample_crop(const float* flow, const float* mask, float* out, int B, int h, int w, int y0, int x0, int H, int W,
+                            float mask_scale, int exp2_out, mvStream_t stream);
+int mv_convex_upsample_crop_m(const float* flow, const void* mask, int mask_dtype, float* out, int B, int h, int w, int y0, int x0,
+                              int H, int W, float mask_scale, int exp2_out, mvStream_t stream);
 
 /* -------------------------------------------------------------------------------------------
  * A10/A11 + MappingPointSelector  candidate generation for the covariance-aware keypoint selectors.
@@ -799,7 +811,8 @@ int mv_obs_filter_lanes(const uint8_t* inbound, const double* cov1, const double
 typedef struct mvFramePipe mvFramePipe;
 
 typedef struct {
-    int32_t H, W;              /* image size, multiples of 8 */
+    int32_t H, W;              /* image size: any with H % 8 != 1 and W % 8 != 1 (a pad of 7 stays refused) (mv_input_pad: the 1/8 maps below are h8 x w8 = ceil(H / 8) x ceil(W / 8), the network's centred pad; with
+                                  flow8 / cov8 the pipe upsamples straight into the un-padded H x W window, mv_convex_upsample_crop) */
     int32_t C;                 /* feature channels (% 16 == 0) */
     int32_t pairs;             /* volume batch = 2 * lanes (<= 2 * MV_MAX_LANES): pair 2l stereo, 2l + 1 temporal of lane l */
     int32_t iters;             /* decoder iterations = window lookups per frame (12) */
@@ -851,15 +864,15 @@ enum { MV_MOTION_STATIC = 0, MV_MOTION_TARTAN = 1 };
 
 /* what the learned layers hand over for one estimate_pair (device pointers, fp32 unless noted) */
 typedef struct {
-    const void* fmap1;      /* [pairs, C, H/8, W/8] (CHW) or [pairs, H/8, W/8, C] (HWC), feat_dtype */
+    const void* fmap1;      /* [pairs, C, h8, w8] (CHW) or [pairs, h8, w8, C] (HWC), feat_dtype; h8 x w8 = ceil(H / 8) x ceil(W / 8) */
     const void* fmap2;
-    const float* coords;    /* [iters, pairs, 2, H/8, W/8]: coords1 entering each decoder iteration (covhead.py:85-92) */
-    const float* flow;      /* [pairs, 2, H, W] last upsampled flow        } either these two ...            */
+    const float* coords;    /* [iters, pairs, 2, h8, w8]: coords1 entering each decoder iteration (covhead.py:85-92) */
+    const float* flow;      /* [pairs, 2, H, W] last upsampled flow        } either these two (un-padded, as `inference` returns them) ... */
     const float* logcov;    /* [pairs, 2, H, W] last upsampled log-sigma   }  (logcov / cov8 / cov_mask: only the pairs  */
-    const float* flow8;     /* [pairs, 2, H/8, W/8]   } ... or the 1/8-resolution fields + convex-upsampling */
-    const float* cov8;      /* [pairs, 2, H/8, W/8]   }     masks of the last iteration (covhead.py:119-135); (whose covariance the   */
-    const float* up_mask;   /* [pairs, 576, H/8, W/8] }     up_mask BEFORE its 0.25 scale, cov_mask after      */
-    const float* cov_mask;  /* [pairs, 576, H/8, W/8] }   (frontend provides are read; NULL with both MV_NOCOV_* bits set)           */
+    const float* flow8;     /* [pairs, 2, h8, w8]   } ... or the 1/8-resolution fields + convex-upsampling */
+    const float* cov8;      /* [pairs, 2, h8, w8]   }     masks of the last iteration (covhead.py:119-135); (whose covariance the   */
+    const float* up_mask;   /* [pairs, 576, h8, w8] }     up_mask BEFORE its 0.25 scale, cov_mask after      */
+    const float* cov_mask;  /* [pairs, 576, h8, w8] }   (frontend provides are read; NULL with both MV_NOCOV_* bits set)           */
 } mvFrameInputs;
 
 /* buffers reported by mv_frame_pipe_buffer (element counts, not bytes; MV_FB_VOLUME's element is the volume CELL: fp32, or fp16 — 2 bytes —

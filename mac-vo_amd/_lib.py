@@ -128,6 +128,9 @@ SIGNATURES = {
                                        _P, _P, _P, _P, _P, _P, _P, _P]),
     "mv_convex_upsample": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     "mv_convex_upsample_m": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    "mv_input_pad": (None, [C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "mv_convex_upsample_crop": (C.c_int, [_P, _P, _P] + [C.c_int] * 7 + [C.c_float, C.c_int, _P]),
+    "mv_convex_upsample_crop_m": (C.c_int, [_P, _P, C.c_int, _P] + [C.c_int] * 7 + [C.c_float, C.c_int, _P]),
     "mv_kp_select_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mv_kp_select": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(mvKpSelectParams), _P, C.c_size_t,
                                _P, _P, _P, _P]),

@@ -484,9 +484,29 @@ static void describe_backend(mvFramePipe* p) {
     }
 }
 
+// The 1/8-resolution grid of an H x W frame and where the frame sits in its 8x upsampling.  The network pads a frame to multiples of 8, centred (the public
+// InputPadder's "sintel" mode, which FlowFormerCov.inference selects: flownet.py:37-44), works on (H + hp) / 8 x (W + pw) / 8 maps and un-pads its dense outputs:
+// frame pixel (y, x) is pixel (y + hp / 2, x + pw / 2) of the padded one.  Everything follows from H and W — no configuration; a multiple of 8 has no pad.
+struct Eighth { int h8, w8, y0, x0; };
+static Eighth eighth_dims(int H, int W) {
+    int32_t pad[4];   // {left, right, top, bottom}
+    mv_input_pad(H, W, pad);
+    return Eighth{(H + pad[2] + pad[3]) / 8, (W + pad[0] + pad[1]) / 8, pad[2], pad[0]};
+}
+
+// convex upsampling into the pipe's H x W planes: the aligned kernel when the frame has no pad (the launches of every earlier build), the window form otherwise
+static int upsample_frame(const mvFramePipe* p, const float* f8, const float* mask, float* out, int B, float mask_scale, int exp2_out, hipStream_t s) {
+    const Eighth e = eighth_dims(p->c.H, p->c.W);
+    if (8 * e.h8 == p->c.H && 8 * e.w8 == p->c.W) return mv_convex_upsample(f8, mask, out, B, p->h8, p->w8, mask_scale, exp2_out, s);
+    return mv_convex_upsample_crop(f8, mask, out, B, p->h8, p->w8, e.y0, e.x0, p->c.H, p->c.W, mask_scale, exp2_out, s);
+}
+
 static int check_config(const mvFramePipeConfig* c) {
     MV_CHECK_ARG(c);
-    MV_CHECK_ARG(c->H > 0 && c->W > 0 && c->H % 8 == 0 && c->W % 8 == 0);
+    MV_CHECK_ARG(c->H > 0 && c->W > 0 && c->H <= (1 << 14) && c->W <= (1 << 14));   // (eighth_dims; what a stage needs of H, W is checked with that stage below)
+    // A side one above a multiple of 8 (a pad of 7: seven of the last coarse row's eight rows are replicas) stays an invalid configuration, as it has always been:
+    // tests/test_abi_and_host.py pins H = 481 as refused.  Pads 0 .. 6 are taken; the kernels themselves handle 7 (tests/test_gpu_upsample_crop.py).
+    MV_CHECK_ARG(c->H % 8 != 1 && c->W % 8 != 1);
     MV_CHECK_ARG(c->C > 0 && c->C % 16 == 0 && c->iters >= 0);
     MV_CHECK_ARG(c->pairs >= 2 && c->pairs % 2 == 0 && c->pairs / 2 <= MV_MAX_LANES);   // lane l = pairs 2l (stereo), 2l + 1 (temporal)
     MV_CHECK_ARG(c->radius >= 1 && c->radius <= 4);
@@ -527,8 +547,8 @@ extern "C" size_t mv_frame_pipe_arena_bytes(const mvFramePipeConfig* cfg) {
     mvFramePipe tmp{};
     tmp.c = *cfg;
     tmp.plane = cfg->H * cfg->W;
-    tmp.h8 = cfg->H / 8;
-    tmp.w8 = cfg->W / 8;
+    tmp.h8 = eighth_dims(cfg->H, cfg->W).h8;
+    tmp.w8 = eighth_dims(cfg->H, cfg->W).w8;
     tmp.n8 = tmp.h8 * tmp.w8;
     tmp.KK = (2 * cfg->radius + 1) * (2 * cfg->radius + 1);
     tmp.lanes = cfg->pairs / 2;
@@ -703,8 +723,8 @@ extern "C" int mv_frame_pipe_create(const mvFramePipeConfig* cfg, void* arena, s
     if (!p) return MV_ERR_WORKSPACE;
     p->c = *cfg;
     p->plane = cfg->H * cfg->W;
-    p->h8 = cfg->H / 8;
-    p->w8 = cfg->W / 8;
+    p->h8 = eighth_dims(cfg->H, cfg->W).h8;
+    p->w8 = eighth_dims(cfg->H, cfg->W).w8;
     p->n8 = p->h8 * p->w8;
     p->KK = (2 * cfg->radius + 1) * (2 * cfg->radius + 1);
     p->lanes = cfg->pairs / 2;
@@ -985,16 +1005,15 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
     constexpr bool fuse_epi = true;   // epilogue + the selector's first kernel in one launch (the separate form was an A/B knob of rounds 2-4)
     const int nocov = c.frontend_nocov;
     if (up) {
-        MV_TRY(mv_convex_upsample(in->flow8, in->up_mask, p->up_flow, B, p->h8, p->w8, 0.25f, 0, s));
+        MV_TRY(upsample_frame(p, in->flow8, in->up_mask, p->up_flow, B, 0.25f, 0, s));
         if (!nocov) {
-            MV_TRY(mv_convex_upsample(in->cov8, in->cov_mask, p->up_cov, B, p->h8, p->w8, 1.0f, 1, s));
+            MV_TRY(upsample_frame(p, in->cov8, in->cov_mask, p->up_cov, B, 1.0f, 1, s));
         } else if (nocov != (MV_NOCOV_DEPTH | MV_NOCOV_MATCH)) {
             // one side only: the covariance field of THAT pair of every lane (pair 2l = lane l's stereo pair, 2l + 1 its temporal pair); the other pair's
             // planes of cov8 / cov_mask / up_cov are neither read nor written
             for (int l = 0; l < p->lanes; ++l) {
                 const size_t pr = 2 * (size_t)l + ((nocov & MV_NOCOV_DEPTH) ? 1 : 0);
-                MV_TRY(mv_convex_upsample(in->cov8 + pr * 2 * p->n8, in->cov_mask + pr * 576 * p->n8, p->up_cov + pr * 2 * p->plane, 1, p->h8, p->w8,
-                                          1.0f, 1, s));
+                MV_TRY(upsample_frame(p, in->cov8 + pr * 2 * p->n8, in->cov_mask + pr * 576 * p->n8, p->up_cov + pr * 2 * p->plane, 1, 1.0f, 1, s));
             }
         }
         MV_TRY(mv_frontend_epilogue_lanes(p->up_flow, p->up_cov, 0, c.H, c.W, c.bl_fx, c.bl_fx_sq, mp.disparity,

@@ -62,11 +62,17 @@ __device__ __forceinline__ float exp_nonpos(float x) {
 }
 
 // grid: x = groups of 64*PX coarse pixels, y = (8 sub-rows x 8/NSX sub-column groups) / 4 waves, z = sample
-template <int DT, int PX, int NSX>
+//
+// CROP (mv_convex_upsample_crop_m: the network's `unpad`, flownet.py:43-44, inside the kernel): the same arithmetic, but only the window rows [y0, y0 + H) x columns
+// [x0, x0 + W) of the 8h x 8w result are stored, into a dense [B, 2, H, W] output of row pitch W.  Nothing is assumed about that output beyond 4-byte alignment (an odd
+// H * W puts every second plane on an odd float offset, a row of 315 floats starts anywhere): one predicated dword store per element — a lane's NSX-wide group can
+// straddle either column edge.  A wave whose sub-row lies outside the window for every coarse row it owns (sub-rows sy < y0 of the top coarse row, the bottom pad's of
+// the last one) leaves before its loads.  The window parameters trail the aligned form's: CROP = false reads none of them and is the code it was without them.
+template <int DT, int PX, int NSX, bool CROP>
 __global__ __launch_bounds__(256) void convex_upsample_kernel(const float* __restrict__ flow,
                                                                const typename MaskElem<DT>::T* __restrict__ mask,
                                                                float* __restrict__ out, int h, int w, float mask_scale,
-                                                               int exp2_out) {
+                                                               int exp2_out, int y0, int x0, int H, int W) {
     typedef typename MaskElem<DT>::T T;
     typedef PixVec<T, PX> V;
     constexpr int SPLIT = 8 / NSX;
@@ -76,6 +82,14 @@ __global__ __launch_bounds__(256) void convex_upsample_kernel(const float* __res
     const int sy = wv / SPLIT, sx0 = (wv % SPLIT) * NSX;
     const int p0 = (blockIdx.x * 64 + threadIdx.x) * PX;   // first coarse pixel of this lane (row-major)
     const int pl = min(p0, hw - PX);                        // tail lanes: clamped loads, no stores
+    if constexpr (CROP) {
+        // coarse rows whose sub-row sy is inside the window: 0 <= 8 r + sy - y0 < H  <=>  r_lo <= r <= r_hi (arithmetic shifts: floor); the wave owns rows r_a .. r_b
+        const int swv = __builtin_amdgcn_readfirstlane(wv);
+        const int ssy = swv / SPLIT;
+        const int r_lo = (y0 - ssy + 7) >> 3, r_hi = (y0 + H - 1 - ssy) >> 3;
+        const int q_a = blockIdx.x * 64 * PX, q_b = min(q_a + 64 * PX, hw) - 1;
+        if (max(q_a / w, r_lo) > min(q_b / w, r_hi)) return;
+    }
 
     // every mask value this lane needs: 9 taps x NSX sub-columns (x PX pixels), issued back to back
     const T* mk = mask + (size_t)b * 576 * hw + (size_t)(sy * 8 + sx0) * hw + pl;
@@ -140,7 +154,18 @@ __global__ __launch_bounds__(256) void convex_upsample_kernel(const float* __res
             o[0][sx] = exp2_out ? expf(a0 * 2.f) : a0;
             o[1][sx] = exp2_out ? expf(a1 * 2.f) : a1;
         }
-        if (p0 + j < hw) {
+        if constexpr (CROP) {
+            const int Y = 8 * py[j] + sy - y0, X = 8 * px[j] + sx0 - x0;   // window coordinates of the group's first element
+            if (p0 + j < hw && Y >= 0 && Y < H) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    float* dst = out + ((size_t)(b * 2 + c) * H + Y) * W;
+#pragma unroll
+                    for (int sx = 0; sx < NSX; ++sx)
+                        if (X + sx >= 0 && X + sx < W) dst[X + sx] = o[c][sx];
+                }
+            }
+        } else if (p0 + j < hw) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 float* dst = out + ((size_t)(b * 2 + c) * 8 * h + (8 * py[j] + sy)) * W8 + 8 * px[j] + sx0;
@@ -156,12 +181,14 @@ __global__ __launch_bounds__(256) void convex_upsample_kernel(const float* __res
     }
 }
 
-template <int DT, int PX, int NSX>
-int launch(const float* flow, const void* mask, float* out, int B, int h, int w, float mask_scale, int exp2_out,
+struct Window { int y0, x0, H, W; };
+
+template <int DT, int PX, int NSX, bool CROP>
+int launch(const float* flow, const void* mask, float* out, int B, int h, int w, float mask_scale, int exp2_out, const Window& win,
            hipStream_t stream) {
     dim3 grid(mv_ceil_div(h * w, 64 * PX), 8 * (8 / NSX) / 4, B), block(64, 4);
-    hipLaunchKernelGGL((convex_upsample_kernel<DT, PX, NSX>), grid, block, 0, stream, flow,
-                       (const typename MaskElem<DT>::T*)mask, out, h, w, mask_scale, exp2_out);
+    hipLaunchKernelGGL((convex_upsample_kernel<DT, PX, NSX, CROP>), grid, block, 0, stream, flow,
+                       (const typename MaskElem<DT>::T*)mask, out, h, w, mask_scale, exp2_out, win.y0, win.x0, win.H, win.W);
     return mv_launch_status();
 }
 
@@ -169,11 +196,23 @@ int launch(const float* flow, const void* mask, float* out, int B, int h, int w,
 //   fp32 mask   60x80: NSX 2 / 4 / 8 = 7.1 / 7.4 / 8.1 us;  90x160: 16.8 / 18.9 / 18.2 us    -> NSX = 2 (4800 waves at 60x80: 4.7 per SIMD)
 //   16-bit mask 60x80: NSX 2 / 4 = 7.4-7.8 / 7.4 us;        90x160: 15.4-16.8 / 15.1-15.6 us -> NSX = 4
 //   two pixels per lane with dword loads of a 16-bit mask (half the waves, the same loads per wave): 9.3-9.5 us / 17.5-21.9 us -> not built in
-template <int DT>
-int dispatch(const float* flow, const void* mask, float* out, int B, int h, int w, float mask_scale, int exp2_out,
+// The window form keeps each mask type's NSX: its stores are dwords either way, and the loads and the arithmetic are what the table above measured.
+template <int DT, bool CROP>
+int dispatch(const float* flow, const void* mask, float* out, int B, int h, int w, float mask_scale, int exp2_out, const Window& win,
              hipStream_t stream) {
-    if constexpr (DT == MV_F32) return launch<DT, 1, 2>(flow, mask, out, B, h, w, mask_scale, exp2_out, stream);
-    else return launch<DT, 1, 4>(flow, mask, out, B, h, w, mask_scale, exp2_out, stream);
+    if constexpr (DT == MV_F32) return launch<DT, 1, 2, CROP>(flow, mask, out, B, h, w, mask_scale, exp2_out, win, stream);
+    else return launch<DT, 1, 4, CROP>(flow, mask, out, B, h, w, mask_scale, exp2_out, win, stream);
+}
+
+template <bool CROP>
+int dispatch_dtype(const float* flow, const void* mask, int mask_dtype, float* out, int B, int h, int w, float mask_scale, int exp2_out,
+                   const Window& win, mvStream_t stream) {
+    switch (mask_dtype) {
+        case MV_F32: return dispatch<MV_F32, CROP>(flow, mask, out, B, h, w, mask_scale, exp2_out, win, (hipStream_t)stream);
+        case MV_F16: return dispatch<MV_F16, CROP>(flow, mask, out, B, h, w, mask_scale, exp2_out, win, (hipStream_t)stream);
+        case MV_BF16: return dispatch<MV_BF16, CROP>(flow, mask, out, B, h, w, mask_scale, exp2_out, win, (hipStream_t)stream);
+        default: return MV_ERR_UNSUPPORTED;
+    }
 }
 
 }  // namespace
@@ -184,15 +223,32 @@ extern "C" int mv_convex_upsample_m(const float* flow, const void* mask, int mas
     MV_CHECK_ARG(((uintptr_t)out & 15) == 0);
     MV_CHECK_ARG(((uintptr_t)mask & (mask_dtype == MV_F32 ? 3 : 1)) == 0);
     if (B > 65535) return MV_ERR_UNSUPPORTED;
-    switch (mask_dtype) {
-        case MV_F32: return dispatch<MV_F32>(flow, mask, out, B, h, w, mask_scale, exp2_out, (hipStream_t)stream);
-        case MV_F16: return dispatch<MV_F16>(flow, mask, out, B, h, w, mask_scale, exp2_out, (hipStream_t)stream);
-        case MV_BF16: return dispatch<MV_BF16>(flow, mask, out, B, h, w, mask_scale, exp2_out, (hipStream_t)stream);
-        default: return MV_ERR_UNSUPPORTED;
-    }
+    return dispatch_dtype<false>(flow, mask, mask_dtype, out, B, h, w, mask_scale, exp2_out, Window{0, 0, 8 * h, 8 * w}, stream);
 }
 
 extern "C" int mv_convex_upsample(const float* flow, const float* mask, float* out, int B, int h, int w,
                                   float mask_scale, int exp2_out, mvStream_t stream) {
     return mv_convex_upsample_m(flow, mask, MV_F32, out, B, h, w, mask_scale, exp2_out, stream);
+}
+
+extern "C" void mv_input_pad(int H, int W, int32_t pad[4]) {
+    const int pw = (8 - W % 8) % 8, hp = (8 - H % 8) % 8;
+    pad[0] = pw / 2, pad[1] = pw - pw / 2, pad[2] = hp / 2, pad[3] = hp - hp / 2;
+}
+
+// The window [y0, y0 + H) x [x0, x0 + W) of the same result, dense: out[b, c, y, x] = padded[b, c, y + y0, x + x0].  `out` needs 4-byte alignment only.
+extern "C" int mv_convex_upsample_crop_m(const float* flow, const void* mask, int mask_dtype, float* out, int B, int h, int w, int y0, int x0,
+                                         int H, int W, float mask_scale, int exp2_out, mvStream_t stream) {
+    MV_CHECK_ARG(flow && mask && out && B > 0 && h > 0 && w > 0);
+    MV_CHECK_ARG(h <= (1 << 24) / w);                                   // (8h * 8w and every window coordinate stay far inside an int)
+    MV_CHECK_ARG(y0 >= 0 && x0 >= 0 && H > 0 && W > 0 && H <= 8 * h - y0 && W <= 8 * w - x0);
+    MV_CHECK_ARG(((uintptr_t)out & 3) == 0);
+    MV_CHECK_ARG(((uintptr_t)mask & (mask_dtype == MV_F32 ? 3 : 1)) == 0);
+    if (B > 65535) return MV_ERR_UNSUPPORTED;
+    return dispatch_dtype<true>(flow, mask, mask_dtype, out, B, h, w, mask_scale, exp2_out, Window{y0, x0, H, W}, stream);
+}
+
+extern "C" int mv_convex_upsample_crop(const float* flow, const float* mask, float* out, int B, int h, int w, int y0, int x0, int H, int W,
+                                       float mask_scale, int exp2_out, mvStream_t stream) {
+    return mv_convex_upsample_crop_m(flow, mask, MV_F32, out, B, h, w, y0, x0, H, W, mask_scale, exp2_out, stream);
 }

@@ -326,10 +326,36 @@ def frontend_epilogue(flow: torch.Tensor, cov: torch.Tensor | None, baseline: fl
     return FrontendMaps(depth, depth_cov, disparity, disparity_cov, bad, mflow, mcov)
 
 
-def convex_upsample(flow8: torch.Tensor, mask: torch.Tensor, mask_scale: float = 1.0, exp2_out: bool = False) -> torch.Tensor:
+def input_pad(H: int, W: int) -> tuple:
+    """``(left, right, top, bottom)``: the centred pad to multiples of 8 that ``FlowFormerCov.inference`` applies to an ``H x W`` frame before its encoders
+    and removes from its dense outputs (flownet.py:37-44, ``InputPadder(image1.shape)`` — the public padder's default "sintel" mode; the FlowFormer submodule is
+    unpinned in the reference checkout, ``tools/flowformer_host.py`` states the padder).  The rule of ``mv_input_pad``, which the frame driver follows."""
+    pad = (C.c_int32 * 4)()
+    L.load().mv_input_pad(int(H), int(W), pad)
+    return tuple(int(v) for v in pad)
+
+
+def eighth_shape(H: int, W: int) -> tuple:
+    """``(h8, w8)`` of the 1/8-resolution maps of an ``H x W`` frame: ``ceil(H / 8), ceil(W / 8)`` (:func:`input_pad`)."""
+    left, right, top, bottom = input_pad(H, W)
+    return (H + top + bottom) // 8, (W + left + right) // 8
+
+
+def unpad_window(H: int, W: int) -> "tuple | None":
+    """The ``crop=`` of :func:`convex_upsample` that un-pads the upsampled maps of an ``H x W`` frame; None for a frame without pad."""
+    left, right, top, bottom = input_pad(H, W)
+    return (top, left, H, W) if (left or right or top or bottom) else None
+
+
+def convex_upsample(flow8: torch.Tensor, mask: torch.Tensor, mask_scale: float = 1.0, exp2_out: bool = False,
+                    crop: "tuple | None" = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """RAFT / FlowFormer ``upsample_flow`` (covhead.py:124-126,133-135): ``[B,2,h,w], [B,576,h,w] -> [B,2,8h,8w]``;
     ``exp2_out`` fuses the ``exp(2 * cov)`` of flownet.py:44.  ``mask`` may be fp32, fp16 or bf16 (the decoder's autocast type in Fast mode);
-    the result is the fp32 formula on the widened values."""
+    the result is the fp32 formula on the widened values.
+
+    ``crop=(y0, x0, H, W)``: only that window of the result, ``[B,2,H,W]`` dense — the bits of ``convex_upsample(...)[..., y0:y0+H, x0:x0+W]`` without the
+    padded intermediate and the slice copy (``mv_convex_upsample_crop_m``; the network's ``unpad``, see :func:`unpad_window`).  ``out`` (crop only): a contiguous
+    fp32 ``[B,2,H,W]`` tensor to write, at any 4-byte-aligned address."""
     lib = L.load()
     flow8 = _req(flow8, torch.float32, "flow8")
     if mask.dtype not in _DT:
@@ -337,6 +363,18 @@ def convex_upsample(flow8: torch.Tensor, mask: torch.Tensor, mask_scale: float =
     mask = _req(mask, mask.dtype, "mask")       # a 16-bit mask is read as it is (no widened copy) and widened in registers
     B, two, h, w = flow8.shape
     assert two == 2 and mask.shape == (B, 576, h, w)
+    if crop is not None:
+        y0, x0, H, W = (int(v) for v in crop)
+        if not (0 <= y0 and 0 <= x0 and H > 0 and W > 0 and y0 + H <= 8 * h and x0 + W <= 8 * w):
+            raise ValueError(f"crop {tuple(crop)} is no window of the {8 * h} x {8 * w} result")
+        if out is None:
+            out = torch.empty((B, 2, H, W), dtype=torch.float32, device=flow8.device)
+        elif out.shape != (B, 2, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != flow8.device:
+            raise ValueError("out: a contiguous fp32 [B, 2, H, W] tensor on the inputs' device expected")
+        L.check(lib.mv_convex_upsample_crop_m(flow8.data_ptr(), mask.data_ptr(), _DT[mask.dtype], out.data_ptr(), B, h, w, y0, x0, H, W,
+                                              float(mask_scale), int(exp2_out), _stream()), "mv_convex_upsample_crop_m")
+        return out
+    assert out is None, "out= belongs to the crop form"
     out = torch.empty((B, 2, 8 * h, 8 * w), dtype=torch.float32, device=flow8.device)
     L.check(lib.mv_convex_upsample_m(flow8.data_ptr(), mask.data_ptr(), _DT[mask.dtype], out.data_ptr(), B, h, w, float(mask_scale),
                                      int(exp2_out), _stream()), "mv_convex_upsample_m")

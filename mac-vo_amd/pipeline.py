@@ -432,10 +432,14 @@ def _randint_rows(num_point: int, H: int, W: int, mask: int, g) -> torch.Tensor:
 class FrameInputs:
     """What the learned layers hand to the hot path for one ``estimate_pair`` (all GPU-resident).
 
-    fmap1 / fmap2 : ``[2, C, H/8, W/8]`` (layout "chw") or ``[2, H/8, W/8, C]`` ("hwc"); pair 0 = stereo
+    fmap1 / fmap2 : ``[2, C, h8, w8]`` (layout "chw") or ``[2, h8, w8, C]`` ("hwc"); pair 0 = stereo
                     (L_t2 vs R_t2), pair 1 = temporal (L_t1 vs L_t2)  (Frontend.py:219-220)
-    coords        : ``[iters, 2, 2, H/8, W/8]`` fp32 — coords1 entering each decoder iteration (covhead.py:85-92)
-    flow, logcov  : ``[2, 2, H, W]`` fp32 — last upsampled flow / log-sigma predictions (covhead.py:140)
+    coords        : ``[iters, 2, 2, h8, w8]`` fp32 — coords1 entering each decoder iteration (covhead.py:85-92)
+    flow, logcov  : ``[2, 2, H, W]`` fp32 — last upsampled flow / log-sigma predictions (covhead.py:140), un-padded as ``inference`` returns them
+
+    ``H x W`` is the camera's frame, of any size but one: a side one above a multiple of 8 (a pad of 7) is an invalid configuration for the native driver; ``h8, w8 = ops.eighth_shape(H, W) = ceil(H / 8), ceil(W / 8)`` is the grid the network works on after
+    its centred pad to multiples of 8 (``ops.input_pad``; flownet.py:37-44 — KITTI's 376 x 780 frames give 47 x 98 maps).  ``flow8`` / ``cov8`` and the masks
+    live on that grid too; the hot path upsamples them straight into the un-padded ``H x W`` window.
 
     With ``HotPathConfig.frontend_cov`` not ``(True, True)`` only the covariance samples of a side that provides one are read (sample 0 = depth
     model, sample 1 = matcher); ``logcov`` / ``cov8`` / ``cov_mask`` are None when neither does (plain FlowFormer has no covariance head).
@@ -450,10 +454,10 @@ class FrameInputs:
     cov_is_log: bool = True
     # alternative to flow/logcov: the last decoder iteration's 1/8-resolution fields and convex
     # upsampling masks (covhead.py:119-135); the hot path then runs mv_convex_upsample (+ fused exp(2*cov)) itself
-    flow8: torch.Tensor | None = None        # [2, 2, H/8, W/8]  coords1 - coords0
-    cov8: torch.Tensor | None = None         # [2, 2, H/8, W/8]  cov_coords1 - cov_coords0
-    up_mask: torch.Tensor | None = None      # [2, 576, H/8, W/8] flow branch mask BEFORE the 0.25 scale (:121)
-    cov_mask: torch.Tensor | None = None     # [2, 576, H/8, W/8] log-sigma branch mask (0.25 already applied, :41)
+    flow8: torch.Tensor | None = None        # [2, 2, h8, w8]  coords1 - coords0
+    cov8: torch.Tensor | None = None         # [2, 2, h8, w8]  cov_coords1 - cov_coords0
+    up_mask: torch.Tensor | None = None      # [2, 576, h8, w8] flow branch mask BEFORE the 0.25 scale (:121)
+    cov_mask: torch.Tensor | None = None     # [2, 576, h8, w8] log-sigma branch mask (0.25 already applied, :41)
     # event recorded by whoever produced fmap1/fmap2 (None = already complete, e.g. resident inputs): the volume GEMM
     # runs on its own stream and must not start before its operands exist
     ready: "torch.cuda.Event | None" = None
@@ -471,6 +475,21 @@ class FrameInputs:
     # promise that every tensor above lives at a fixed address for the lifetime of the HotPath (e.g. the static output
     # buffers of a graph-captured network, as in the reference's CUDAGraph frontend): allows hipGraph replay
     static: bool = False
+
+
+def check_frame_shapes(x: "FrameInputs", cam: "Camera") -> None:
+    """The 1/8-resolution inputs live on ``ops.eighth_shape(H, W)``, the full-resolution ones on the un-padded ``H x W`` frame."""
+    h8, w8 = ops.eighth_shape(cam.H, cam.W)
+    if tuple(x.coords.shape[-2:]) != (h8, w8):
+        raise ops.L.MacvoHipError(f"coords are {tuple(x.coords.shape[-2:])} but a {cam.H} x {cam.W} frame has {h8} x {w8} maps at 1/8 resolution")
+    for name in ("flow8", "cov8", "up_mask", "cov_mask"):
+        t = getattr(x, name)
+        if t is not None and tuple(t.shape[-2:]) != (h8, w8):
+            raise ops.L.MacvoHipError(f"{name} is {tuple(t.shape[-2:])}, expected {h8} x {w8}")
+    for name in ("flow", "logcov"):
+        t = getattr(x, name)
+        if t is not None and x.flow8 is None and tuple(t.shape[-2:]) != (cam.H, cam.W):
+            raise ops.L.MacvoHipError(f"{name} is {tuple(t.shape[-2:])}, expected the un-padded {cam.H} x {cam.W} frame")
 
 
 @dataclass
@@ -576,18 +595,21 @@ class HotPath:
         for it in range(x.coords.shape[0]):
             tok = ops.corr_lookup(vol, x.coords[it], c.radius, out=tok)
         fd, fm = self._fcov
+        win = ops.unpad_window(cam.H, cam.W) if x.flow8 is not None else None   # (a frame with a pad: the un-padded window only, as the native driver does)
+        if win is not None:
+            check_frame_shapes(x, cam)
         if x.flow8 is not None and fd and fm:
-            flow = ops.convex_upsample(x.flow8, x.up_mask, mask_scale=0.25)
-            cov = ops.convex_upsample(x.cov8, x.cov_mask, mask_scale=1.0, exp2_out=True)     # exp(2*cov) fused
+            flow = ops.convex_upsample(x.flow8, x.up_mask, mask_scale=0.25, crop=win)
+            cov = ops.convex_upsample(x.cov8, x.cov_mask, mask_scale=1.0, exp2_out=True, crop=win)     # exp(2*cov) fused
             maps = ops.frontend_epilogue(flow, cov, cam.baseline, cam.fx, cov_is_log=False)
         elif x.flow8 is not None:
             # a side without covariance: no covariance upsampling for its pair (pair 0 = the depth model's, pair 1 = the matcher's)
-            flow = ops.convex_upsample(x.flow8, x.up_mask, mask_scale=0.25)
+            flow = ops.convex_upsample(x.flow8, x.up_mask, mask_scale=0.25, crop=win)
             cov = None
             if fd or fm:
                 k = 0 if fd else 1
                 cov = torch.empty_like(flow)
-                cov[k: k + 1] = ops.convex_upsample(x.cov8[k: k + 1], x.cov_mask[k: k + 1], mask_scale=1.0, exp2_out=True)
+                cov[k: k + 1] = ops.convex_upsample(x.cov8[k: k + 1], x.cov_mask[k: k + 1], mask_scale=1.0, exp2_out=True, crop=win)
             maps = ops.frontend_epilogue(flow, cov, cam.baseline, cam.fx, cov_is_log=False, provide_cov=(fd, fm))
         elif not (fd and fm):
             maps = ops.frontend_epilogue(x.flow, x.logcov if (fd or fm) else None, cam.baseline, cam.fx, cov_is_log=x.cov_is_log, provide_cov=(fd, fm))
@@ -1114,6 +1136,7 @@ class NativeHotPath:
         if pairs != 2 * self.lanes:
             raise L.MacvoHipError(f"inputs carry {pairs} pairs but the pipe has {self.lanes} lane(s) (2 pairs per lane)")
         chans = x.fmap1.shape[-1] if hwc else x.fmap1.shape[1]
+        check_frame_shapes(x, cam)
         dt = {torch.float32: L.MV_F32, torch.float16: L.MV_F16, torch.bfloat16: L.MV_BF16}[x.fmap1.dtype]
         bl_fx = float(cam.baseline) * float(cam.fx)
         max_depth = cam.fx * cam.baseline if c.max_depth == "auto" else float(c.max_depth)
@@ -1217,9 +1240,9 @@ class NativeHotPath:
 
     @property
     def last_tokens(self) -> torch.Tensor:
-        """Window-lookup output of the newest frame's last decoder iteration ``[pairs, (2r+1)^2, H/8, W/8]``."""
+        """Window-lookup output of the newest frame's last decoder iteration ``[pairs, (2r+1)^2, h8, w8]`` (``ops.eighth_shape``)."""
         k = 2 * self.cfg.radius + 1
-        return self._view("TOKENS", 0, torch.float32, (self._pc.pairs, k * k, self.cam.H // 8, self.cam.W // 8))
+        return self._view("TOKENS", 0, torch.float32, (self._pc.pairs, k * k) + ops.eighth_shape(self.cam.H, self.cam.W))
 
     def maps(self, age: int = 0, lane: int = 0) -> "ops.FrontendMaps":
         H, W = self.cam.H, self.cam.W

@@ -258,6 +258,31 @@ def main():
                 torch.cuda.synchronize()
                 us = e0.elapsed_time(e1) * 1e3 / reps
                 print(f"convex_upsample B={B} mask {str(mdt)[6:]} {us:8.2f} us back to back  {byts / us / 1e3:7.1f} GB/s  {byts / us / 1e3 / 8000 * 100:.1f}% of HBM peak ({byts / 1e6:.1f} MB)")
+        elif w == "upsample_crop":
+            # --H / --W of any size (376 x 780, 237 x 315): the window form against what a caller needed before it — the padded kernel and the
+            # `.contiguous()` copy of the un-padded slice.  Back to back on one stream; under `rocprofv3 --kernel-trace --stats` the three kernels show by name.
+            ch8, cw8 = ops.eighth_shape(H, W)
+            win = ops.unpad_window(H, W) or (0, 0, H, W)
+            y0, x0 = win[0], win[1]
+            cfl = torch.randn(B, 2, ch8, cw8, generator=g).to(dev)
+            cmk = torch.randn(B, 576, ch8, cw8, generator=g).to(dev)
+            cout = torch.empty(B, 2, H, W, device=dev)
+            legs = {"padded": lambda: ops.convex_upsample(cfl, cmkd, 1.0, True),
+                    "padded + slice copy": lambda: ops.convex_upsample(cfl, cmkd, 1.0, True)[..., y0: y0 + H, x0: x0 + W].contiguous(),
+                    "crop": lambda: ops.convex_upsample(cfl, cmkd, 1.0, True, crop=(y0, x0, H, W), out=cout)}
+            for mdt in (torch.float32, torch.bfloat16):
+                cmkd = cmk.to(mdt)
+                for name, fn in legs.items():
+                    for _ in range(5):
+                        fn()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    reps = 4 * a.iters
+                    e0.record()
+                    for _ in range(reps):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    print(f"convex_upsample {ch8}x{cw8} -> {H}x{W} B={B} mask {str(mdt)[6:]:8s} {name:20s} {e0.elapsed_time(e1) * 1e3 / reps:8.2f} us back to back")
         elif w == "select":
             fc = synth.flow_cov_maps(H, W, 2).to(dev)
             d0, d0c = [t.to(dev) for t in synth.depth_maps(H, W, 3)]
