@@ -463,9 +463,56 @@ MV_HD double quality_point(const PointLin& lin, const double (&D)[6]) {
     return lin.s2 * q;
 }
 
+// A D = b, b = -gw, for an A that is not positive definite: Gaussian elimination with partial pivoting.  The reference's solver is PINV
+// (Optimizer.py:71), and the pseudo-inverse of a non-singular A is its inverse whatever the signs of its eigenvalues, so an indefinite A — which
+// indefinite pixel covariances (s_uv^2 > s_uu s_vv) give J^T W J — is a step like any other there, not a failure.  Only chol_solve6 comes here, after
+// its factorisation has met a non-positive pivot; the rows are exchanged by selects over unrolled loops (no dynamically indexed registers).
+// Returns false for a zero or non-finite pivot.
+MV_HD bool gauss_solve6(const double* Aw, const double (&dg6)[6], const double* gw, double (&D)[6]) {
+    double M[6][7];
+    MV_UNROLL
+    for (int j = 0; j < 6; ++j) {
+        MV_UNROLL
+        for (int k = 0; k < 6; ++k) M[j][k] = (j == k) ? dg6[j] : Aw[(j < k) ? tri(j, k) : tri(k, j)];
+        M[j][6] = -gw[j];
+    }
+    bool ok = true;
+    MV_UNROLL
+    for (int c = 0; c < 6; ++c) {
+        MV_UNROLL
+        for (int r = c + 1; r < 6; ++r) {   // the largest |M[r][c]|, r >= c, ends in row c
+            const bool sw = fabs(M[r][c]) > fabs(M[c][c]);
+            MV_UNROLL
+            for (int k = c; k < 7; ++k) {
+                const double a = M[c][k], b = M[r][k];
+                M[c][k] = sw ? b : a;
+                M[r][k] = sw ? a : b;
+            }
+        }
+        ok = ok && (fabs(M[c][c]) > 0.0) && (fabs(M[c][c]) < INFINITY);
+        const double inv = 1.0 / M[c][c];
+        MV_UNROLL
+        for (int r = c + 1; r < 6; ++r) {
+            const double f = M[r][c] * inv;
+            MV_UNROLL
+            for (int k = c + 1; k < 7; ++k) M[r][k] = fma(-f, M[c][k], M[r][k]);
+        }
+    }
+    if (!ok) return false;
+    MV_UNROLL
+    for (int j = 5; j >= 0; --j) {
+        double sacc = M[j][6];
+        MV_UNROLL
+        for (int k = j + 1; k < 6; ++k) sacc = fma(-M[j][k], D[k], sacc);
+        D[j] = sacc / M[j][j];
+    }
+    return true;
+}
+
 // solve A D = b, b = -gw, by Cholesky (A = L L^T) with the diagonal of A taken from `dg6` (the damped one); every thread solves
 // redundantly (uniform control flow).  One reciprocal square root per pivot (l_jj = dd / sqrt(dd) to ~1 ulp), the substitutions
-// multiply by the reciprocal pivots.  Returns false where PyPose reports "Linear solver failed".
+// multiply by the reciprocal pivots.  An A that is not positive definite goes to gauss_solve6; returns false where neither can solve
+// (NaN, a singular A), which is where PyPose reports "Linear solver failed".
 MV_HD bool chol_solve6(const double* Aw, const double (&dg6)[6], const double* gw, double (&D)[6]) {
     double L[6][6], linv[6];
     bool ok = true;
@@ -486,7 +533,7 @@ MV_HD bool chol_solve6(const double* Aw, const double (&dg6)[6], const double* g
             L[i2][j] = sacc * inv;
         }
     }
-    if (!ok) return false;
+    if (!ok) return gauss_solve6(Aw, dg6, gw, D);
     double yv[6];
     MV_UNROLL
     for (int j = 0; j < 6; ++j) {

@@ -1,5 +1,5 @@
 """mv_convex_upsample_crop_m: convex 8x upsampling that stores only the un-padded window.  The arithmetic is the aligned kernel's, so the bar is bit
-equality with the slice of `mv_convex_upsample_m` on the same inputs (whose parity with oracle.frontend.upsample_flow tests/test_gpu_kernels.py pins) — and
+equality with the slice of `mv_convex_upsample_m` on the same inputs (whose parity with oracle.frontend.upsample_flow tests/test_gpu_corr.py::test_convex_upsample pins) — and
 nothing outside the output may be written: the output is a view at an odd float offset into a NaN-filled buffer whose 64 floats on either side stay NaN."""
 import pytest
 import torch
