@@ -60,7 +60,7 @@ __device__ __forceinline__ void mv_epilogue_pixel(const mvEpiArgs& a, int plane,
     }
 }
 // mv_epilogue_pixel in two halves for a caller that wants a pixel's six input loads in flight early (kp_nms_kernel<true> issues those of
-// its four pixels in front of its record reservation): the loads — flow and logcov are [2, 2, H, W], every plane is read —, then the same
+// its four pixels at entry, in one burst with its staging loads, and stores the outputs in front of its NMS phases): the loads — flow and logcov are [2, 2, H, W], every plane is read —, then the same
 // expressions and stores as above.
 struct mvEpiPixel { float fx0, lc0, f2, f3, l0, l1; };
 __device__ __forceinline__ mvEpiPixel mv_epilogue_load(const mvEpiArgs& a, int plane, int i) {

@@ -17,12 +17,17 @@
 //            depth0 variance}; a workgroup reserves its record range with ONE global atomic.  The return of that
 //            same-address device-scope atomic is the kernel's longest dependency (~6 of 13 us alone when 300 workgroups
 //            wait for it with nothing else to do), so it is issued as early as the count exists and consumed as late as
-//            possible: the NMS decisions (LDS only) come first, the workgroup's count is taken from the wave ballots
-//            (popcounts in scalar registers + four per-wave totals in LDS: no same-address LDS atomics), one thread
-//            issues the global atomic, and in the fused form the epilogue pixels (their 6 loads each issued in front of
-//            the reservation, then 9 stores each), the mask reads and the candidate words run while it is in flight; only
-//            the record stores wait for the base.  The
-//            form without the epilogue has nothing to put there and keeps decisions -> count -> atomic -> records.
+//            possible.  Order of events in a workgroup of the fused form (the epilogue rides along), which makes ONE round
+//            trip to memory for everything it reads: (1) every load of the thread in one burst — the log-sigma pairs of
+//            its staged elements from clamped addresses without a branch around them, and the six epilogue inputs of each
+//            of its four pixels; (2) expf, LDS stores; (3) the 9 epilogue stores of each pixel, 13 MB per frame, whose
+//            acknowledgements nothing waits for until the reservation returns: they drain under (4)-(7) instead of behind
+//            the kernel's last instruction; (4) barrier, horizontal pass, barrier, NMS decisions (LDS only); (5) the
+//            workgroup's count from the wave ballots (popcounts in scalar registers + four per-wave totals in LDS: no
+//            same-address LDS atomics), barrier; (6) one thread issues the global atomic, and the mask reads and the
+//            candidate words run while it is in flight; (7) the record stores, which alone wait for the base.  The
+//            un-fused form has nothing to store early: staging (FULL: the two depths of its own pixels requested there as
+//            well) -> decisions -> candidate words -> count -> atomic -> records.
 //            Records of a workgroup are in (wave, row, lane) order, workgroups in the order their atomics land — kernel
 //            2 does not depend on either (see the record stores below).
 //   kernel 2 (one 1024-thread workgroup; 256 / 512 threads measured 3x / 1.4x slower): every global read is issued
@@ -116,40 +121,102 @@ __global__ __launch_bounds__(256) void kp_nms_kernel(const float* __restrict__ f
     const int x0 = blockIdx.x * TILE_W, y0 = blockIdx.y * TILE_H;
     const int tx = threadIdx.x, ty = threadIdx.y;  // tx = lane (0..63), ty = wave (0..3)
     const int tid = ty * 64 + tx;
-    const bool mapping = p.mode == MV_KP_MAPPING;
+    const bool mapping = !FUSE && p.mode == MV_KP_MAPPING;   // the fused entry point takes MV_KP_NODEPTH only
+    constexpr int NPX = TILE_H / 4;   // pixels per thread: rows ty * 4 .. ty * 4 + 3 of the tile, column tx
+    const int gx = x0 + tx;
+    mvEpiPixel epi[NPX] = {};   // fused: the epilogue inputs of the thread's pixels
+    float dv0[NPX] = {}, dv1[NPX] = {};   // un-fused FULL: depth0 / depth1 of the thread's pixels (the candidate test behind the NMS)
 
     if (!mapping) {
         const int tw = TILE_W + 2 * r, th = TILE_H + 2 * r;
         // stage the quality tile + halo: all global loads of a thread are issued before the first LDS store
-        constexpr int NST = ((TILE_W + 2 * MAX_R) * (TILE_H + 2 * MAX_R) + 255) / 256;   // 9 for the 78 x 30 maximum
+        constexpr int NST = ((TILE_W + 2 * MAX_R) * (TILE_H + 2 * MAX_R) + 255) / 256;   // 10 for the 78 x 30 maximum
         float qv[NST];
+        if (FUSE) {
+            // Element i of the thread: where its inputs are read — an address clamped into the image, so that no condition stands around the loads
+            // — and whether it is a pixel at all.  Written as `if (inside) q = f(expf(load), expf(load))` the compiler wraps each element in a
+            // branch and waits for its loads inside it: ten dependent round trips where one was meant (read off the ISA; so it was before this
+            // order, and so the un-fused form below still is: alone, where the maps sit in L2, hoisting its loads the same way measured no gain).
+            auto staged_at = [&](int i, bool& inside) {
+                const int e = i * 256 + tid;
+                const int ly = e / tw, lx = e - ly * tw;
+                const int sx = x0 + lx - r, sy = y0 + ly - r;
+                const bool staged = e < tw * th;   // past the staged area: the tile's first pixel, one address for the whole wave
+                inside = staged && sx >= 0 && sx < W && sy >= 0 && sy < H;
+                return (staged ? min(max(sy, 0), H - 1) : y0) * W + (staged ? min(max(sx, 0), W - 1) : x0);
+            };
+            float l0v[NST], l1v[NST];
+            bool inside;
 #pragma unroll
-        for (int i = 0; i < NST; ++i) {
-            const int e = i * 256 + tid;
-            const int ly = e / tw, lx = e - ly * tw;
-            const int gx = x0 + lx - r, gy = y0 + ly - r;
-            float q = INFINITY;  // out-of-image == -inf padding of max_pool2d(-q): never the minimum
-            if (e < tw * th && gx >= 0 && gx < W && gy >= 0 && gy < H) {
-                const int idx = gy * W + gx;
-                if (FUSE) {
-                    // flow_quality of (c0, c1, 0): (c0 + c1) - 2 * 0 = c0 + c1 exactly
-                    const float l0 = ef.logcov[2 * plane + idx], l1 = ef.logcov[3 * plane + idx];
-                    const float c0 = ef.cov_is_log ? expf(l0 * 2.f) : l0, c1 = ef.cov_is_log ? expf(l1 * 2.f) : l1;
-                    q = (c0 + c1) - 2.f * 0.f;
-                } else if (p.mode == MV_KP_NODEPTH) {
-                    q = flow_quality(fc, plane, idx);
-                } else {
-                    q = d0c[idx] + d1c[idx];
-                    if (fc) q = q * flow_quality(fc, plane, idx);
+            for (int i = 0; i < NST; ++i) {
+                const int ci = staged_at(i, inside);
+                l0v[i] = ef.logcov[2 * plane + ci];
+                l1v[i] = ef.logcov[3 * plane + ci];
+            }
+            // ... and in the same burst the six epilogue inputs of each of the thread's own pixels, which depend on nothing computed here (a pixel
+            // past the ragged edge reads the edge pixel and stores nothing): one memory round trip for everything the kernel reads
+#pragma unroll
+            for (int it = 0; it < NPX; ++it)
+                epi[it] = mv_epilogue_load(ef, plane, min(y0 + ty * NPX + it, H - 1) * W + min(gx, W - 1));
+#pragma unroll
+            for (int i = 0; i < NST; ++i) {
+                staged_at(i, inside);
+                // flow_quality of (c0, c1, 0): (c0 + c1) - 2 * 0 = c0 + c1 exactly
+                const float c0 = ef.cov_is_log ? expf(l0v[i] * 2.f) : l0v[i], c1 = ef.cov_is_log ? expf(l1v[i] * 2.f) : l1v[i];
+                const float q = (c0 + c1) - 2.f * 0.f;
+                qv[i] = inside ? q : INFINITY;   // out-of-image == -inf padding of max_pool2d(-q): never the minimum
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NST; ++i) {
+                const int e = i * 256 + tid;
+                const int ly = e / tw, lx = e - ly * tw;
+                const int gx = x0 + lx - r, gy = y0 + ly - r;
+                float q = INFINITY;  // out-of-image == -inf padding of max_pool2d(-q): never the minimum
+                if (e < tw * th && gx >= 0 && gx < W && gy >= 0 && gy < H) {
+                    const int idx = gy * W + gx;
+                    if (p.mode == MV_KP_NODEPTH) {
+                        q = flow_quality(fc, plane, idx);
+                    } else {
+                        q = d0c[idx] + d1c[idx];
+                        if (fc) q = q * flow_quality(fc, plane, idx);
+                    }
+                }
+                qv[i] = q;
+            }
+            // FULL: the two depths of the thread's own pixels, which the candidate test behind the NMS wants, are requested here as well
+            if (p.mode == MV_KP_FULL) {
+#pragma unroll
+                for (int it = 0; it < NPX; ++it) {
+                    const int gy = y0 + ty * NPX + it;
+                    if (gx < W && gy < H) {
+                        dv0[it] = d0[gy * W + gx];
+                        dv1[it] = d1[gy * W + gx];
+                    }
                 }
             }
-            qv[i] = q;
         }
 #pragma unroll
         for (int i = 0; i < NST; ++i) {
             const int e = i * 256 + tid;
             const int ly = e / tw, lx = e - ly * tw;
             if (e < tw * th) tile[ly][lx] = qv[i];
+        }
+        // fused: the epilogue outputs of the thread's pixels (9 stores each) leave here, in front of both LDS phases, the count, the reservation
+        // and the record stores, which all run while these stores are acknowledged (a workgroup barrier does not wait for them)
+        if (FUSE) {
+            // Every epilogue input is named as used here, outside any condition.  The stores below sit behind null-pointer and in-image branches;
+            // were a loaded register first read inside one of them, the compiler would have to assume the load still pending on the path around
+            // it, and the next reuse of that register — in the horizontal pass — would get an s_waitcnt vmcnt(0), which by then means "all 36
+            // stores acknowledged" (loads and stores share the in-order counter).  Behind this point no load is outstanding.
+#pragma unroll
+            for (int it = 0; it < NPX; ++it)
+                asm volatile("" :: "v"(epi[it].fx0), "v"(epi[it].lc0), "v"(epi[it].f2), "v"(epi[it].f3), "v"(epi[it].l0), "v"(epi[it].l1));
+#pragma unroll
+            for (int it = 0; it < NPX; ++it) {
+                const int gy = y0 + ty * NPX + it;
+                if (gx < W && gy < H) mv_epilogue_store(ef, plane, gy * W + gx, epi[it]);
+            }
         }
         __syncthreads();
         // horizontal pass: hmin[ly][x] = nanmin over tile[ly][x .. x+2r]
@@ -161,9 +228,6 @@ __global__ __launch_bounds__(256) void kp_nms_kernel(const float* __restrict__ f
         }
     }
     __syncthreads();
-
-    constexpr int NPX = TILE_H / 4;   // pixels per thread: rows ty * 4 .. ty * 4 + 3 of the tile, column tx
-    const int gx = x0 + tx;
 
     // ---- NMS decision of the thread's pixels: LDS only
     bool nms_px[NPX];
@@ -185,25 +249,13 @@ __global__ __launch_bounds__(256) void kp_nms_kernel(const float* __restrict__ f
         nms_word[it] = __ballot(nms);
     }
 
-    // ---- fused: the epilogue inputs of the thread's pixels, all loads in flight here — in front of the reservation, so that the wave
-    //      which issues the atomic can consume them while the atomic is still out (loads and returning atomics complete in issue order)
-    mvEpiPixel epi[NPX] = {};
-    if (FUSE) {
-#pragma unroll
-        for (int it = 0; it < NPX; ++it) {
-            const int gy = y0 + ty * NPX + it;
-            if (gx < W && gy < H) epi[it] = mv_epilogue_load(ef, plane, gy * W + gx);
-        }
-    }
-
-    // ---- the rest of a pixel: (fused) its epilogue outputs, the candidate decision, the row's candidate word
+    // ---- the rest of a pixel: the candidate decision, the row's candidate word
     bool cand_px[NPX];
     auto pixel_rest = [&](int it) {
         const int gy = y0 + ty * NPX + it;
         const bool inimg = gx < W && gy < H;
         const int idx = gy * W + gx;
         bool cand = false;
-        if (FUSE && inimg) mv_epilogue_store(ef, plane, idx, epi[it]);
         if (inimg) {
             const bool border = p.mask_width > 0 && gx >= p.mask_width && gx < W - p.mask_width &&
                                 gy >= p.mask_width && gy < H - p.mask_width;
@@ -211,7 +263,7 @@ __global__ __launch_bounds__(256) void kp_nms_kernel(const float* __restrict__ f
                 cand = border && (d0[idx] < p.max_depth) && (d0c[idx] < p.max_depth_cov);
             } else {
                 cand = nms_px[it] && border;
-                if (cand && p.mode == MV_KP_FULL) cand = (d0[idx] < p.max_depth) && (d1[idx] < p.max_depth);
+                if (!FUSE && cand && p.mode == MV_KP_FULL) cand = (dv0[it] < p.max_depth) && (dv1[it] < p.max_depth);
             }
             if (cand && mask_a) cand = mask_a[idx] != 0;
             if (cand && mask_b) cand = mask_b[idx] != 0;
@@ -240,7 +292,7 @@ __global__ __launch_bounds__(256) void kp_nms_kernel(const float* __restrict__ f
 #else
     // Issued here, consumed behind the pixel work below.  The counter is addressed through an offset of zero that the compiler cannot
     // see through: for an atomic at a wave-uniform address it would build the wave-aggregated form, whose v_readfirstlane of the
-    // returned value forces the wait for the atomic right here, in front of the loads that are meant to overlap it.
+    // returned value forces the wait for the atomic right here, in front of the candidate words that are meant to overlap it.
     int opaque_zero = 0;
     asm volatile("" : "+v"(opaque_zero));
     if (tid == 0 && wg_n) base = atomicAdd(ws.counters + opaque_zero, wg_n);
@@ -263,7 +315,7 @@ __global__ __launch_bounds__(256) void kp_nms_kernel(const float* __restrict__ f
             const int at = pos + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(nms_word[it] >> 32),
                                                                 __builtin_amdgcn_mbcnt_lo((unsigned)nms_word[it], 0u));
             ws.rec_idx[at] = (unsigned)(((gy * words_per_row + blockIdx.x) << 6) | tx) | (cand_px[it] ? CAND_FLAG : 0u);
-            if (p.mode == MV_KP_NODEPTH) {
+            if (FUSE || p.mode == MV_KP_NODEPTH) {
                 ws.rec_q[at] = q_px[it];
             } else {
                 ws.rec_q[at] = fc ? flow_quality(fc, plane, idx) : 0.f;
