@@ -1070,6 +1070,58 @@ int mv_frame_pipe_timeline_backend(mvFramePipe* p, float* ms, int cap_frames, in
 /* where a result lives inside the arena; age 0 = newest frame that passed that stage, 1 = the one before */
 int mv_frame_pipe_buffer(mvFramePipe* p, int which, int age, void** ptr, size_t* count);
 
+/* ---- Frontend evaluation (Evaluation/EvalFlow.py, Evaluation/EvalDepth.py): one lane = one frame (B = 1, as every caller of the reference assumes),
+ * lanes <= MV_MAX_LANES, any H, W >= 1 with H * W <= 2^22 (torch's fp32 quantile position q * (n - 1) is exact up to there; MV_ERR_INVALID_ARG beyond).
+ * All launches go on `stream`; nothing synchronises with the host.  One fp32 row per lane is written to rows[lane][row_index][COLS] of a caller-owned
+ * device table rows[lanes][rows_per_lane][COLS]; no other row is touched, so a pass over a sequence fills a table that is read back once.  Means are
+ * fp64 sums of the fp32 per-pixel terms, reduced in an order that depends on (H, W) only, over the non-NaN terms (nanmean); an empty population gives a
+ * NaN mean and a zero count (the reference raises there and skips the frame, EvalDepth.py:28-37).  Counts are exact integers stored as fp32.
+ * Quantiles follow torch.nanquantile bit for bit: n non-NaN values, r = fp32(q) * fp32(n - 1), a = v[floor r], b = v[ceil r], w = r - floor r, d = b - a,
+ * w < 0.5 ? a + w * d : b - d * (1 - w) (two +inf order statistics give NaN); the order statistics come from an exact radix select (-0.0 and +0.0 are equal
+ * values, either may be returned).  workspace: mv_eval_workspace_bytes(lanes, H, W) bytes, 16-byte aligned, private to the call until it has finished
+ * (0 = unsupported arguments). */
+size_t mv_eval_workspace_bytes(int lanes, int H, int W);
+/* EvalFlow.py:29-47 (evaluate_flow) and :82-127 (evaluate_flowcov).  Per pixel: eu = est_u - gt_u, ev = est_v - gt_v, epe = sqrtf(eu * eu + ev * ev);
+ * mask = [apply_max_flow: est_u < max_flow && est_v < max_flow (signed, NaN compares false, :36-37)] && [valid: valid != 0].  apply_max_flow is off when
+ * the caller passes the ground-truth mask (:32-34).  N_MASK = |mask|, N_MASK_FINITE = non-NaN epe inside it, N_FINITE = non-NaN epe of the lane;
+ * MASKED_EPE = nanmean(epe[mask]), EPE = nanmean(epe), PXk = mean over the mask of (epe < k): a NaN epe inside the mask is a miss there.
+ * est_cov (or NULL): planes sigma_uu and sigma_vv, cov_plane_stride floats apart (a third plane is ignored, as est_cov[:, :2] does, :78).  Then
+ * det = cu * cv (= torch.det of the diagonal 2 x 2), pinv(c) = |c| > 1e-15f * max(|cu|, |cv|) ? 1 / c : 0 (Tensor.pinverse's rcond),
+ * m = (eu * pinv(cu)) * eu + (ev * pinv(cv)) * ev, nll = logf(det) + square(sqrtf(m)) (:101, Utility/Math.py:146), uncertainty = det (:107);
+ * T25 / T50 / T75 = nanquantile(uncertainty) over ALL pixels of the lane (:108-110); MASKED_NLL = nanmean(nll[mask]) over N_MASK_NLL terms,
+ * Qxx_NLL = nanmean(nll[uncertainty < Txx]) (strict; the mask is not intersected, :115-117), N_Qxx = |uncertainty < Txx|.  The reference's own SVD raises
+ * on a non-finite covariance; here a NaN covariance gives a NaN nll, which the means drop — that case is ours and is not pinned by the reference.
+ * Without est_cov the NLL and threshold columns are NaN and N_Q* are 0.
+ * grids (or NULL; needs est_cov): uint32 [lanes][2][100][100], (eu^2, cu) and (ev^2, cv) over ALL pixels (:120-127, GridRecorder.py:24-36): bin =
+ * (int)(v * 4.0f) truncated toward zero, a pixel counts when both bins are in [0, 100); NaN and +-inf are not counted.  The grids ACCUMULATE (+=): the
+ * caller zeroes them once per sequence.  epe_out / nll_out (or NULL): the per-pixel planes [lanes][H * W] (nll_out is written only with est_cov). */
+enum {
+    MV_EVAL_FLOW_MASKED_EPE = 0, MV_EVAL_FLOW_EPE, MV_EVAL_FLOW_PX1, MV_EVAL_FLOW_PX3, MV_EVAL_FLOW_PX5, MV_EVAL_FLOW_MASKED_NLL,
+    MV_EVAL_FLOW_Q25_NLL, MV_EVAL_FLOW_Q50_NLL, MV_EVAL_FLOW_Q75_NLL, MV_EVAL_FLOW_T25, MV_EVAL_FLOW_T50, MV_EVAL_FLOW_T75,
+    MV_EVAL_FLOW_N_MASK, MV_EVAL_FLOW_N_MASK_FINITE, MV_EVAL_FLOW_N_FINITE, MV_EVAL_FLOW_N_Q25, MV_EVAL_FLOW_N_Q50, MV_EVAL_FLOW_N_Q75,
+    MV_EVAL_FLOW_N_MASK_NLL, MV_EVAL_FLOW_COLS
+};
+int mv_eval_flow_lanes(int lanes, int H, int W, const float* est_flow /* [2,H,W] per lane */, int64_t est_lane_stride,
+                       const float* gt_flow /* [2,H,W] per lane */, int64_t gt_lane_stride, const float* est_cov /* or NULL */,
+                       int64_t cov_plane_stride, int64_t cov_lane_stride, const uint8_t* valid /* [H,W] per lane or NULL */, int64_t valid_lane_stride,
+                       float max_flow, int apply_max_flow, float* rows, int rows_per_lane, int row_index, uint32_t* grids /* or NULL */,
+                       float* epe_out /* or NULL */, float* nll_out /* or NULL */, void* workspace, size_t workspace_bytes, mvStream_t stream);
+/* EvalDepth.py:22-34 (evaluate_depth) and :57-82 (evaluate_depthcov).  err = |est - gt|, mask = est < max_depth; MASKED_ERR = nanmean(err[mask]),
+ * ERR_25 / ERR_75 = nanquantile(err[mask]), ERR_50 = nanmedian(err[mask]) = the lower middle element, not the interpolated quantile.  est_cov [H,W]
+ * (or NULL): e = est - gt, pinv(c) = c != 0 ? 1 / c : 0, nll = logf(c) + square(sqrtf((e * pinv(c)) * e)), uncertainty = c; thresholds, means and
+ * counts as for flow.  grid (or NULL; needs est_cov): uint32 [lanes][100][100] of (e^2, c) with bin = (int)(v * 2.0f) (0 ... 50 in steps of 0.5),
+ * accumulating.  err_out / nll_out as above. */
+enum {
+    MV_EVAL_DEPTH_MASKED_ERR = 0, MV_EVAL_DEPTH_ERR_25, MV_EVAL_DEPTH_ERR_50, MV_EVAL_DEPTH_ERR_75, MV_EVAL_DEPTH_MASKED_NLL,
+    MV_EVAL_DEPTH_Q25_NLL, MV_EVAL_DEPTH_Q50_NLL, MV_EVAL_DEPTH_Q75_NLL, MV_EVAL_DEPTH_T25, MV_EVAL_DEPTH_T50, MV_EVAL_DEPTH_T75,
+    MV_EVAL_DEPTH_N_MASK, MV_EVAL_DEPTH_N_MASK_FINITE, MV_EVAL_DEPTH_N_FINITE, MV_EVAL_DEPTH_N_Q25, MV_EVAL_DEPTH_N_Q50, MV_EVAL_DEPTH_N_Q75,
+    MV_EVAL_DEPTH_N_MASK_NLL, MV_EVAL_DEPTH_COLS
+};
+int mv_eval_depth_lanes(int lanes, int H, int W, const float* est_depth /* [H,W] per lane */, int64_t est_lane_stride,
+                        const float* gt_depth /* [H,W] per lane */, int64_t gt_lane_stride, const float* est_cov /* [H,W] per lane or NULL */,
+                        int64_t cov_lane_stride, float max_depth, float* rows, int rows_per_lane, int row_index, uint32_t* grid /* or NULL */,
+                        float* err_out /* or NULL */, float* nll_out /* or NULL */, void* workspace, size_t workspace_bytes, mvStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,13 @@ MV_SOLVE_WORLD, MV_SOLVE_LOCAL = 0, 1
 MV_NOCOV_DEPTH, MV_NOCOV_MATCH = 1, 2
 ABI_VERSION = 8
 MV_MAX_LANES = 64        # include/macvo_hip.h
+# row columns of mv_eval_flow_lanes / mv_eval_depth_lanes (enum order of the header)
+EVAL_FLOW_COLS = ("masked_epe", "epe", "px1", "px3", "px5", "masked_nll", "q25_nll", "q50_nll", "q75_nll", "t25", "t50", "t75",
+                  "n_mask", "n_mask_finite", "n_finite", "n_q25", "n_q50", "n_q75", "n_mask_nll")
+EVAL_DEPTH_COLS = ("masked_err", "err_25", "err_50", "err_75", "masked_nll", "q25_nll", "q50_nll", "q75_nll", "t25", "t50", "t75",
+                   "n_mask", "n_mask_finite", "n_finite", "n_q25", "n_q50", "n_q75", "n_mask_nll")
+EVAL_GRID = 100          # GridRecorder((0, 25, .25), ...) / ((0, 50, .5), ...): 100 x 100 bins
+EVAL_MAX_PIXELS = 1 << 22
 
 
 class mvKpSelectParams(C.Structure):
@@ -256,6 +263,12 @@ SIGNATURES = {
     "mv_map_set_pose_lanes": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "mv_frame_pipe_map_append_lanes": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_float, _P]),
     "mv_frame_pipe_map_skip_lanes": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_float, _P]),
+    # frontend evaluation (EvalFlow.py / EvalDepth.py): rows[lanes][rows_per_lane][COLS] on the device, one row per lane and call
+    "mv_eval_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mv_eval_flow_lanes": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_float, C.c_int,
+                                     _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    "mv_eval_depth_lanes": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_float, _P, C.c_int, C.c_int, _P, _P, _P,
+                                      _P, C.c_size_t, _P]),
 }
 
 _lib = None

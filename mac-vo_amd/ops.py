@@ -1073,3 +1073,122 @@ def pose_exp_compose(prev: torch.Tensor, raw: torch.Tensor, norm: torch.Tensor |
     L.check(lib.mv_pose_exp_compose(n, prev.data_ptr(), raw.data_ptr(), 6, nrm.data_ptr(), out.data_ptr(), _stream()),
             "mv_pose_exp_compose")
     return out.reshape(7) if single else out
+
+
+# ------------------------------------------------------------------------------------------- frontend evaluation
+@dataclass
+class EvalResult:
+    """What ``eval_flow`` / ``eval_depth`` leave on the device: ``row`` = this call's ``[lanes, COLS]`` view of the table ``rows``
+    (columns: ``_lib.EVAL_FLOW_COLS`` / ``EVAL_DEPTH_COLS``), the recorder grid(s) and the optional per-pixel planes.  Nothing here is a
+    Python number: reading one is the caller's synchronisation."""
+    row: torch.Tensor
+    rows: torch.Tensor
+    grids: torch.Tensor | None
+    err: torch.Tensor | None
+    nll: torch.Tensor | None
+
+
+def _eval_workspace(lanes: int, H: int, W: int, device) -> torch.Tensor:
+    # the kernels zero what they need per call, so launches may share a workspace when they are ordered: one per stream
+    key = ("eval", lanes, H, W, str(device), _stream())
+    ws = _ws_cache.get(key)
+    if ws is None:
+        nbytes = L.load().mv_eval_workspace_bytes(lanes, H, W)
+        if nbytes == 0:
+            raise L.MacvoHipError(f"eval: {lanes} lanes of {H}x{W} are not supported (lanes <= {L.MV_MAX_LANES}, H * W <= 2^22)")
+        ws = _ws_cache[key] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    return ws
+
+
+def _eval_lanes(t: torch.Tensor, planes: int, name: str) -> torch.Tensor:
+    """``[planes,H,W]`` or ``[L,planes,H,W]`` (``planes = 0``: ``[H,W]``, ``[L,H,W]`` or ``[L,1,H,W]``) -> contiguous fp32 ``[L,planes or 1,H,W]``."""
+    t = _req(t, torch.float32, name)
+    if planes == 0:
+        if t.dim() == 4 and t.shape[1] != 1:
+            raise L.MacvoHipError(f"{name}: expected [L,1,H,W], got {tuple(t.shape)}")
+        if t.dim() not in (2, 3, 4):
+            raise L.MacvoHipError(f"{name}: expected [H,W], [L,H,W] or [L,1,H,W], got {tuple(t.shape)}")
+        return t.reshape(-1, 1, t.shape[-2], t.shape[-1]) if t.dim() != 2 else t.reshape(1, 1, *t.shape)
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    if t.dim() != 4 or t.shape[1] < planes:
+        raise L.MacvoHipError(f"{name}: expected [L,{planes},H,W], got {tuple(t.shape)}")
+    return t
+
+
+def _eval_tables(kind: str, lanes: int, ncols: int, ngrids: int, rows, row: int, grids, has_cov: bool, device):
+    if rows is None:
+        rows = torch.full((lanes, row + 1, ncols), float("nan"), dtype=torch.float32, device=device)
+    if (rows.dim() != 3 or rows.shape[0] != lanes or rows.shape[2] != ncols or rows.dtype != torch.float32 or not rows.is_cuda
+            or not rows.is_contiguous()):
+        raise L.MacvoHipError(f"{kind}: rows must be a contiguous fp32 GPU tensor [{lanes}, n_rows, {ncols}]")
+    if not 0 <= row < rows.shape[1]:
+        raise L.MacvoHipError(f"{kind}: row {row} outside a table of {rows.shape[1]} rows")
+    if has_cov:
+        shape = (lanes, ngrids, L.EVAL_GRID, L.EVAL_GRID) if ngrids > 1 else (lanes, L.EVAL_GRID, L.EVAL_GRID)
+        if grids is None:
+            grids = torch.zeros(shape, dtype=torch.int32, device=device)
+        if tuple(grids.shape) != shape or grids.dtype not in (torch.int32, torch.uint32) or not grids.is_cuda or not grids.is_contiguous():
+            raise L.MacvoHipError(f"{kind}: grids must be a contiguous int32 GPU tensor {shape} (it accumulates: zero it once per sequence)")
+    elif grids is not None:
+        raise L.MacvoHipError(f"{kind}: grids need a covariance")
+    return rows, grids
+
+
+def eval_flow(est_flow: torch.Tensor, gt_flow: torch.Tensor, est_cov: torch.Tensor | None = None, valid: torch.Tensor | None = None,
+              max_flow: float = 128.0, apply_max_flow: bool = True, rows: torch.Tensor | None = None, row: int = 0,
+              grids: torch.Tensor | None = None, planes: bool = False) -> EvalResult:
+    """One frame per lane of ``evaluate_flow`` / ``evaluate_flowcov`` (EvalFlow.py:29-47, 82-127; ``mv_eval_flow_lanes``).  ``est_flow``, ``gt_flow``:
+    ``[2,H,W]`` or ``[L,2,H,W]``; ``est_cov``: ``[L,2 or 3,H,W]`` (planes uu, vv; a third is ignored) or None; ``valid``: bool / uint8 ``[H,W]``, ``[L,H,W]``
+    or ``[L,1,H,W]``, nonzero = valid.  ``rows`` (``[L, n_rows, len(EVAL_FLOW_COLS)]``) / ``row`` / ``grids`` (int32 ``[L,2,100,100]``): accumulate on the
+    device over a sequence; allocated (grids zeroed) when absent.  ``planes=True`` also returns the per-pixel epe / nll maps."""
+    lib = L.load()
+    est = _eval_lanes(est_flow, 2, "est_flow")
+    gt = _eval_lanes(gt_flow, 2, "gt_flow")
+    lanes, _, H, W = est.shape
+    if est.shape[1] != 2 or tuple(gt.shape) != tuple(est.shape):
+        raise L.MacvoHipError(f"eval_flow: est_flow and gt_flow must both be [L,2,H,W] (got {tuple(est.shape)}, {tuple(gt.shape)})")
+    cov = None
+    if est_cov is not None:
+        cov = _eval_lanes(est_cov, 2, "est_cov")
+        if cov.shape[0] != lanes or tuple(cov.shape[2:]) != (H, W):
+            raise L.MacvoHipError(f"eval_flow: est_cov {tuple(cov.shape)} does not match the flow {tuple(est.shape)}")
+    vm = _u8(valid)
+    if vm is not None and vm.numel() != lanes * H * W:
+        raise L.MacvoHipError(f"eval_flow: valid has {vm.numel()} elements for {lanes} lanes of {H}x{W}")
+    dev = est.device
+    rows, grids = _eval_tables("eval_flow", lanes, len(L.EVAL_FLOW_COLS), 2, rows, row, grids, cov is not None, dev)
+    epe = torch.empty((lanes, H, W), dtype=torch.float32, device=dev) if planes else None
+    nll = torch.empty((lanes, H, W), dtype=torch.float32, device=dev) if planes and cov is not None else None
+    ws = _eval_workspace(lanes, H, W, dev)
+    n = H * W
+    L.check(lib.mv_eval_flow_lanes(lanes, H, W, est.data_ptr(), 2 * n, gt.data_ptr(), 2 * n, _ptr(cov), n, 0 if cov is None else cov.shape[1] * n,
+                                   _ptr(vm), n, float(max_flow), int(bool(apply_max_flow)), rows.data_ptr(), rows.shape[1], row, _ptr(grids),
+                                   _ptr(epe), _ptr(nll), ws.data_ptr(), ws.numel() * 8, _stream()), "mv_eval_flow_lanes")
+    return EvalResult(rows[:, row], rows, grids, epe, nll)
+
+
+def eval_depth(est_depth: torch.Tensor, gt_depth: torch.Tensor, est_cov: torch.Tensor | None = None, max_depth: float = 80.0,
+               rows: torch.Tensor | None = None, row: int = 0, grids: torch.Tensor | None = None, planes: bool = False) -> EvalResult:
+    """One frame per lane of ``evaluate_depth`` / ``evaluate_depthcov`` (EvalDepth.py:22-34, 57-82; ``mv_eval_depth_lanes``).  Maps are ``[H,W]``,
+    ``[L,H,W]`` or ``[L,1,H,W]``; ``grids``: int32 ``[L,100,100]``.  Otherwise as ``eval_flow``."""
+    lib = L.load()
+    est = _eval_lanes(est_depth, 0, "est_depth")
+    gt = _eval_lanes(gt_depth, 0, "gt_depth")
+    lanes, _, H, W = est.shape
+    if tuple(gt.shape) != tuple(est.shape):
+        raise L.MacvoHipError(f"eval_depth: est_depth {tuple(est.shape)} and gt_depth {tuple(gt.shape)} differ")
+    cov = None
+    if est_cov is not None:
+        cov = _eval_lanes(est_cov, 0, "est_cov")
+        if tuple(cov.shape) != tuple(est.shape):
+            raise L.MacvoHipError(f"eval_depth: est_cov {tuple(cov.shape)} does not match the depth {tuple(est.shape)}")
+    dev = est.device
+    rows, grids = _eval_tables("eval_depth", lanes, len(L.EVAL_DEPTH_COLS), 1, rows, row, grids, cov is not None, dev)
+    err = torch.empty((lanes, H, W), dtype=torch.float32, device=dev) if planes else None
+    nll = torch.empty((lanes, H, W), dtype=torch.float32, device=dev) if planes and cov is not None else None
+    ws = _eval_workspace(lanes, H, W, dev)
+    n = H * W
+    L.check(lib.mv_eval_depth_lanes(lanes, H, W, est.data_ptr(), n, gt.data_ptr(), n, _ptr(cov), n, float(max_depth), rows.data_ptr(), rows.shape[1],
+                                    row, _ptr(grids), _ptr(err), _ptr(nll), ws.data_ptr(), ws.numel() * 8, _stream()), "mv_eval_depth_lanes")
+    return EvalResult(rows[:, row], rows, grids, err, nll)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Stand-alone timing of individual C-ABI kernels on the GPU box (HIP events, median of N launches).
 
-    python tools/kernel_bench.py [volume_f32 volume_f16 lookup select cov pgo ...] [--iters 50]
+    python tools/kernel_bench.py [volume_f32 volume_f16 lookup select cov pgo eval ...] [--iters 50]
 
 Used for A/B tuning and as the target of `rocprofv3 --pmc ...` runs (one kernel family per process).
 """
@@ -283,6 +283,103 @@ def main():
                     e1.record()
                     torch.cuda.synchronize()
                     print(f"convex_upsample {ch8}x{cw8} -> {H}x{W} B={B} mask {str(mdt)[6:]:8s} {name:20s} {e0.elapsed_time(e1) * 1e3 / reps:8.2f} us back to back")
+        elif w == "eval":
+            # ops.eval_flow / ops.eval_depth with covariance (csrc/eval_metrics.hip) next to the same closed form in torch on the same device and inputs
+            # (no SVD, no host read-back, masked means as where(...).nanmean()), lanes 1 and 32, in alternating rounds of back-to-back calls
+            # (>= 200 calls per leg; the spread over the rounds is the run-to-run spread).  Under `rocprofv3 --kernel-trace --stats` the kernels show by name.
+            def torch_grid(grid, a0, a1, scale):
+                i0, i1 = (a0 * scale).to(torch.int64), (a1 * scale).to(torch.int64)      # NaN / inf -> INT64_MIN: outside, as numpy's astype(int)
+                ok = (i0 >= 0) & (i0 < 100) & (i1 >= 0) & (i1 < 100)
+                lane = torch.arange(a0.shape[0], device=a0.device)[:, None].expand_as(i0)
+                grid.view(-1).index_add_(0, torch.where(ok, lane * 10000 + i0 * 100 + i1, 0).reshape(-1), ok.reshape(-1).to(grid.dtype))
+
+            def torch_cov_fields(nll, unc, mask):
+                nanv = torch.full_like(nll, float("nan"))
+                out = [torch.where(mask, nll, nanv).nanmean(1)]
+                qs = torch.nanquantile(unc, torch.tensor([0.25, 0.5, 0.75], device=unc.device), dim=1)
+                return out + [torch.where(unc < qs[i][:, None], nll, nanv).nanmean(1) for i in range(3)] + [qs[0], qs[1], qs[2]]
+
+            def torch_flow(est, gt, cov, valid, max_flow, gu, gv):
+                L_ = est.shape[0]
+                e = (est - gt).reshape(L_, 2, -1)
+                eu, ev = e[:, 0], e[:, 1]
+                epe = (eu * eu + ev * ev).sqrt()
+                mask = (est[:, 0] < max_flow).reshape(L_, -1) & (est[:, 1] < max_flow).reshape(L_, -1) & valid.reshape(L_, -1)
+                nanv = torch.full_like(epe, float("nan"))
+                me = torch.where(mask, epe, nanv)
+                nm = mask.sum(1).float()
+                out = [me.nanmean(1), epe.nanmean(1)] + [((me < k).sum(1).float() / nm) for k in (1, 3, 5)]
+                cu, cv = cov[:, 0].reshape(L_, -1), cov[:, 1].reshape(L_, -1)
+                det = cu * cv
+                cut = torch.maximum(cu.abs(), cv.abs()) * 1e-15
+                pu, pv = torch.where(cu.abs() > cut, 1.0 / cu, 0.0), torch.where(cv.abs() > cut, 1.0 / cv, 0.0)
+                r = ((eu * pu) * eu + (ev * pv) * ev).sqrt()
+                out += torch_cov_fields(det.log() + r * r, det, mask)
+                torch_grid(gu, eu * eu, cu, 4.0)
+                torch_grid(gv, ev * ev, cv, 4.0)
+                return torch.stack(out, 1)
+
+            def torch_depth(est, gt, cov, max_depth, gd):
+                L_ = est.shape[0]
+                est, gt, c = est.reshape(L_, -1), gt.reshape(L_, -1), cov.reshape(L_, -1)
+                e = est - gt
+                mask = est < max_depth
+                me = torch.where(mask, e.abs(), torch.full_like(e, float("nan")))
+                out = [me.nanmean(1), torch.nanquantile(me, 0.25, dim=1), me.nanmedian(1).values, torch.nanquantile(me, 0.75, dim=1)]
+                r = ((e * torch.where(c != 0, 1.0 / c, 0.0)) * e).sqrt()
+                out += torch_cov_fields(c.log() + r * r, c, mask)
+                torch_grid(gd, e * e, c, 2.0)
+                return torch.stack(out, 1)
+
+            for lanes in (1, 32):
+                gt_f = torch.randn(lanes, 2, H, W, generator=g) * 4
+                est_f = (gt_f + torch.randn(lanes, 2, H, W, generator=g) * torch.exp(torch.randn(lanes, 2, H, W, generator=g))).to(dev)
+                cov_f = torch.exp(torch.randn(lanes, 2, H, W, generator=g) * 1.5).to(dev)
+                valid = (torch.rand(lanes, 1, H, W, generator=g) > 0.15).to(dev)
+                gt_d = torch.rand(lanes, 1, H, W, generator=g) * 40 + 0.5
+                est_d = (gt_d + torch.randn(lanes, 1, H, W, generator=g)).to(dev)
+                cov_d = torch.exp(torch.randn(lanes, 1, H, W, generator=g) * 1.5).to(dev)
+                gt_f[torch.rand(lanes, 2, H, W, generator=g) < 0.03] = float("nan")
+                gt_f, gt_d = gt_f.to(dev), gt_d.to(dev)
+                from macvo_amd import _lib as L_
+
+                frows = torch.empty(lanes, 1, len(L_.EVAL_FLOW_COLS), device=dev)
+                drows = torch.empty(lanes, 1, len(L_.EVAL_DEPTH_COLS), device=dev)
+                fgr = torch.zeros(lanes, 2, 100, 100, dtype=torch.int32, device=dev)
+                dgr = torch.zeros(lanes, 100, 100, dtype=torch.int32, device=dev)
+                tg = [torch.zeros(lanes, 100, 100, dtype=torch.int32, device=dev) for _ in range(3)]
+                legs = [("eval_flow  HIP", lambda: ops.eval_flow(est_f, gt_f, cov_f, valid, 8.0, True, rows=frows, row=0, grids=fgr)),
+                        ("eval_flow  torch closed form", lambda: torch_flow(est_f, gt_f, cov_f, valid, 8.0, tg[0], tg[1])),
+                        ("eval_depth HIP", lambda: ops.eval_depth(est_d, gt_d, cov_d, 30.0, rows=drows, row=0, grids=dgr)),
+                        ("eval_depth torch closed form", lambda: torch_depth(est_d, gt_d, cov_d, 30.0, tg[2]))]
+                # same answers first (the HIP side is tested bit for bit elsewhere; this guards the comparator)
+                hf, tf = legs[0][1]().row[:, :12], legs[1][1]()
+                hd, td = legs[2][1]().row[:, :11], legs[3][1]()
+                torch.cuda.synchronize()
+                print(f"lanes {lanes}: max |HIP - torch| over the row fields: flow {float((hf - tf).abs().nan_to_num().max()):.3e} depth {float((hd - td).abs().nan_to_num().max()):.3e}")
+                rounds, per = 5, max(8, (4 * a.iters) // 5)
+                res = {k: [] for k, _ in legs}
+                for k, fn in legs:
+                    for _ in range(5):
+                        fn()
+                torch.cuda.synchronize()
+                for _ in range(rounds):
+                    for k, fn in legs:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(per):
+                            fn()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        res[k].append(e0.elapsed_time(e1) * 1e3 / per)
+                nb_f, nb_d = lanes * (H * W * (6 * 4 + 1) + 19 * 4 + 2 * 40000), lanes * (H * W * 3 * 4 + 18 * 4 + 40000)
+                for k, _ in legs:
+                    v = res[k]
+                    print(f"{k:30s} {H}x{W} lanes {lanes:2d}: median {statistics.median(v):9.1f} us / call (rounds {min(v):.1f} .. {max(v):.1f}; {rounds * per} calls)")
+                for kind, nb in (("flow", nb_f), ("depth", nb_d)):
+                    h, t_ = statistics.median(res[f"eval_{kind:5s} HIP"]), statistics.median(res[f"eval_{kind:5s} torch closed form"])
+                    print(f"eval_{kind}: torch / HIP = {t_ / h:.2f}x; algorithmic bytes {nb / 1e6:.2f} MB = {nb / 8e6:.2f} us at 8 TB/s; "
+                          "launches per HIP call: 1 memset + 4 kernels")
         elif w == "select":
             fc = synth.flow_cov_maps(H, W, 2).to(dev)
             d0, d0c = [t.to(dev) for t in synth.depth_maps(H, W, 3)]

@@ -114,6 +114,9 @@ CHECKS = [
      "LM solve, local-frame ICP form: at the 512-register limit, at most the 2 registers spilled outside the LM loop (DESIGN section 7)"),
     (r"^kp_nms_kernel<|^kp_finish_kernel<(1024, 16, 5|512, 16, 10)", lambda r: r["private_segment_fixed_size"] == 0,
      "selector at 640 x 480: no scratch (the 24-rows-per-thread finishing variant for larger images spills 61-74 registers)"),
+    (r"^eval_(pixel|select|qmean)_kernel<", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and regs(r) <= 128 and
+     r.get("group_segment_fixed_size", 0) <= 60 * 1024,
+     "evaluation metrics: no scratch, four waves per SIMD, the LDS-privatised recorder grids + digit histograms within the 64 KB static limit (two workgroups per CU)"),
 ]
 
 
