@@ -159,6 +159,50 @@ struct Carver {   // bump allocator over the arena (or a size counter when base 
     }
 };
 
+// One sync edge of the driver: the event and whether it holds a record of the current generation.  Nothing waits for an edge that holds none: the three
+// waits then return MV_OK without a HIP call.  The state is a relaxed atomic because the backend launch thread records edges the caller's thread waits for:
+// all of those reads but one are ordered by `mu` (wait_issued / flush_jobs); the lean chain's volume release in issue_volume is not.
+struct Ev {
+    hipEvent_t e = nullptr;
+    std::atomic<bool> rec{false};
+    Ev() = default;
+    Ev(Ev&& o) noexcept : e(o.e), rec(o.recorded()) { o.e = nullptr; }   // (movable, not copyable: the timing events live in vectors)
+    ~Ev() { if (e) (void)hipEventDestroy(e); }
+    int create(unsigned flags = hipEventDisableTiming) {   // (hipEventDefault: a timing event, as hipEventCreate makes it)
+        return (flags == hipEventDefault ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, flags)) == hipSuccess ? MV_OK : MV_ERR_LAUNCH;
+    }
+    bool recorded() const { return rec.load(std::memory_order_relaxed); }
+    void skip() { rec.store(false, std::memory_order_relaxed); }   // this generation is deliberately not recorded (the event may hold an older one)
+    int record(hipStream_t s) {
+        if (hipEventRecord(e, s) != hipSuccess) return MV_ERR_LAUNCH;
+        rec.store(true, std::memory_order_relaxed);
+        return MV_OK;
+    }
+    int wait(hipStream_t s) const {   // always a barrier packet
+        return !recorded() || hipStreamWaitEvent(s, e, 0) == hipSuccess ? MV_OK : MV_ERR_LAUNCH;
+    }
+    // ... and when the event has already fired no barrier packet is queued at all (every hipStreamWaitEvent costs the waiting queue a few microseconds
+    // even for a long-fired event)
+    int wait_if_pending(hipStream_t s) const {
+        if (!recorded()) return MV_OK;
+        const hipError_t q = hipEventQuery(e);
+        if (q == hipSuccess) return MV_OK;
+        if (q != hipErrorNotReady) return MV_ERR_LAUNCH;
+        return hipStreamWaitEvent(s, e, 0) == hipSuccess ? MV_OK : MV_ERR_LAUNCH;
+    }
+    int sync() const { return !recorded() || hipEventSynchronize(e) == hipSuccess ? MV_OK : MV_ERR_LAUNCH; }
+};
+template <int N>
+int create_all(Ev (&a)[N]) {
+    for (Ev& e : a) MV_TRY(e.create());
+    return MV_OK;
+}
+template <int N>
+struct EvRing {   // one edge per running frame / finish number: generation g lives in slot g % N
+    Ev slot[N];
+    Ev& operator[](long g) { return slot[g % N]; }
+};
+
 }  // namespace
 
 struct mvFramePipe {
@@ -184,8 +228,8 @@ struct mvFramePipe {
                        // (the driver owns both the producer and the consumer of the volume; MV_FB_VOLUME then shows that layout)
     int pack_on;       // 0 = on the GEMM's stream (in front of it), 1 = backend stream, 2 = decoder-side stream
     int sel_on_back;   // 1: upsampling / epilogue / selector / count copy of a frame run on the backend stream behind its lookups
-    hipEvent_t e_lk[N_CAND];   // a frame's last lookup (decoder-side stream)
-    hipEvent_t e_packed[2];
+    Ev e_lk[N_CAND];   // a frame's last lookup (decoder-side stream)
+    Ev e_packed[2];
     float *up_flow, *up_cov;
     Maps maps[N_MAPS];
     void* kp_ws;
@@ -208,41 +252,41 @@ struct mvFramePipe {
     int n_lk;
     int alt;                     // the two-decoder-stream layout: see mv_frame_pipe_create
     int free_cus;                // CUs the volume GEMM leaves without a persistent workgroup (mv_corr_volume_packed_shared)
-    hipEvent_t e_seg[N_INEV];    // alt: end of frame f's selector segment, slot f % N_INEV (the next frame's segment runs on the other decoder-side stream)
-    bool seg_valid[N_INEV];
+    EvRing<N_INEV> e_seg;        // alt: end of frame f's selector segment (the next frame's segment runs on the other decoder-side stream)
     int alt_indep;               // alt: consecutive frames' segments may overlap (own selector workspace each; NODEPTH selector, no upsampling)
     void* kp_ws2;                // ... the odd frames' workspace
     int lean_chain;              // device-driven frames with the front launch on the decoder side: fewer packets on the frame's chain — no e_cand / e_seg markers behind
                                  // the selector (nobody waits for them: the front launch follows in order), the volume buffer is released by the front launch's event
                                  // instead of a marker behind the lookups.  A marker costs the queue ~6 us, a cross-queue barrier ~10 (rocprofv3 trace, r06_chain_gaps.log)
-    bool cand_recorded[N_CAND];  // e_cand[k] holds this frame's selector segment (lean chain: recorded only when somebody asks)
-    hipEvent_t vol_free_ev[MAX_VOL];   // what the GEMM that rewrites volume buffer k waits for (e_vol_free[k], or the ring event of the frame's front launch)
+    Ev* vol_free_ev[MAX_VOL];    // what the GEMM that rewrites volume buffer k waits for (e_vol_free[k], or the ring event of the frame's front launch; null: nothing)
     int front_on_decoder;        // device-driven alt layout: a frame's front launch (draw + gathers + covariances) runs on the frame's decoder-side stream right
                                  // behind its selector segment (no cross-queue barrier in front of it); the backend stream carries the solves only
 
     hipStream_t s_sel;   // MV_PIPE_SELECTOR_ON=own: a fifth stream for the selector segment (nullptr otherwise)
     SelSeg deferred;     // MV_PIPE_SELECTOR_ON=vol: the newest frame's selector segment, not issued yet
     bool deferred_valid;
-    hipEvent_t e_rest[N_INEV];   // inputs of the decoder side (coords, flow, ...) when the GEMM was issued ahead of them
-    hipEvent_t e_in[N_INEV], e_vol_done[MAX_VOL], e_vol_free[MAX_VOL], e_cand[N_CAND], e_backend[N_BEV], e_pgo, e_perm[N_PERM];
-    hipEvent_t e_kpin[N_BEV]; // finish g (slot g % N_BEV): the caller's stream when mv_frame_pipe_finish_keypoints_dev was called
-    hipEvent_t e_release;     // the consumer's reads of result views enqueued so far (mv_frame_pipe_release)
-    bool release_valid;
-    hipEvent_t e_posed[2];    // backend slot k: world-frame tables written (side stream, in front of the solve)
-    hipEvent_t e_solved[2];   // backend slot k: its solve has finished reading the tables
-    bool vol_free_valid[MAX_VOL], backend_valid[N_BEV], pgo_valid, perm_valid[N_PERM], solved_valid[2];
+    EvRing<N_INEV> e_rest;    // inputs of the decoder side (coords, flow, ...) when the GEMM was issued ahead of them
+    EvRing<N_INEV> e_in;
+    Ev e_vol_done[MAX_VOL], e_vol_free[MAX_VOL], e_pgo;
+    Ev e_cand[N_CAND];        // slot k holds this frame's selector segment (lean chain: recorded only when somebody asks)
+    EvRing<N_BEV> e_backend;
+    EvRing<N_PERM> e_perm;
+    EvRing<N_BEV> e_kpin;     // finish g: the caller's stream when mv_frame_pipe_finish_keypoints_dev was called
+    Ev e_release;             // the consumer's reads of result views enqueued so far (mv_frame_pipe_release)
+    Ev e_posed[2];            // backend slot k: world-frame tables written (side stream, in front of the solve)
+    Ev e_solved[2];           // backend slot k: its solve has finished reading the tables
     // state
     long n_enq, n_fin;
     long n_vol;            // volume GEMMs issued (n_enq <= n_vol <= n_enq + 1: at most one GEMM ahead of its frame's decoder side)
-    hipEvent_t e_in_of[MAX_VOL];   // per volume buffer: the input-ready event its GEMM waited for (the decoder side re-uses it)
+    Ev* e_in_of[MAX_VOL];  // per volume buffer: the input-ready event its GEMM waited for (the decoder side re-uses it)
     int lookups_on_main;   // default 1; MV_PIPE_LOOKUPS_ON=vol is the measured alternative
     int pose_cur;
     int prior_slot;        // pose slot the newest finished frame started from (its motion-model prior)
     int solve_frame = MV_SOLVE_WORLD;   // mv_frame_pipe_set_solve_frame
     bool skipped = false;               // mv_frame_pipe_skip since the newest finish
-    hipEvent_t e_map;
-    hipEvent_t e_mapl[2];     // backend slot k: the map append (map_append_finished) has finished reading the slot's tables
-    bool mapl_valid[2];       // ... recorded (written by the caller's thread behind flush_jobs, read by whoever issues the later finishes)
+    Ev e_map;
+    Ev e_mapl[2];             // backend slot k: the map append (map_append_finished) has finished reading the slot's tables
+                              // (recorded by the caller's thread behind flush_jobs, waited for by whoever issues the later finishes)
     int newest_maps;
     std::deque<Pending> pending;
     // dense-mapping tail (config.mapping; lanes == 1)
@@ -251,15 +295,13 @@ struct mvFramePipe {
     float* stats_m[N_CAND];
     int32_t* h_count_m[N_CAND];    // pinned
     int32_t* h_nvalid[2];          // pinned: observation count of backend slot k
-    hipEvent_t e_nvalid[2];
-    bool nvalid_valid[2];
+    Ev e_nvalid[2];
     int64_t *mp_perm, *mp_uv;      // [map_num_point], [map_num_point, 2]
     float *mp_uvf, *mp_d, *mp_sdd, *mp_sigma, *mp_Tc, *mp_Tw;
     double* mp_cov;
     uint8_t* mp_color;
     int64_t* h_perm_m;             // pinned
-    hipEvent_t e_maptail;          // the map tail's last kernel (buffers + pinned permutation reusable)
-    bool maptail_valid;
+    Ev e_maptail;                  // the map tail's last kernel (buffers + pinned permutation reusable)
     int mp_rows;                   // rows of the newest map tail (0: none for the newest finished frame)
     int last_maps_prev, last_cand;   // of the newest finished frame
     // native keypoint permutations (mv_frame_pipe_seed_lanes): one MT19937 per lane, the engine behind torch's CPU generator
@@ -275,8 +317,8 @@ struct mvFramePipe {
     long last_backend_frame = -1;   // frame index of the newest backend issued with keypoints (launch-thread / inline issuer only)
     // optional timing of the dominant kernel (bench.py roofline): event pairs around each volume GEMM on its stream
     int vol_timed[MAX_VOL];      // timing slot of the GEMM that filled each volume buffer (-1: not timed)
-    std::vector<hipEvent_t> tv0, tv1, tv2, tv3;   // GEMM start / end, last lookup done, selector done (timeline hook)
-    std::vector<hipEvent_t> tv4, tv5, tv6, tv7;   // backend start / end (backend stream), pose_apply start / solve end (solve stream)
+    std::vector<Ev> tv0, tv1, tv2, tv3;   // GEMM start / end, last lookup done, selector done (timeline hook)
+    std::vector<Ev> tv4, tv5, tv6, tv7;   // backend start / end (backend stream), pose_apply start / solve end (solve stream)
     int n_timed, timed_cap;
     int time_detail;   // 1 (default): a timed frame also records the six timeline events tv2..tv7 on three streams; 0: only the pair around its GEMM
     // Backend launch thread (round 3).  A one-lane stream is bound by the HOST: ~38 launches per frame at ~4 us each on one thread
@@ -309,24 +351,13 @@ struct mvFramePipe {
     // the caller's stream (e_motion_set), the finish composes prev pose @ Exp(raw * pose_norm) on the solve's stream (e_motion_used) into `prior`, which the
     // solve starts from and mv_frame_pipe_map_append registers.  A slot is rewritten only behind the events of its previous user.
     float* motion_in[N_MAPS];
-    hipEvent_t e_motion_in[N_MAPS], e_motion_read[N_MAPS];
-    bool motion_in_valid[N_MAPS], motion_read_valid[N_MAPS];
+    EvRing<N_MAPS> e_motion_in, e_motion_read;
     float* motion_raw[N_MOT];
     float* prior[N_MOT];
     float* pose_norm;       // [6] fp32
-    hipEvent_t e_motion_set[N_MOT], e_motion_used[N_MOT];
-    bool motion_used_valid[N_MOT];
+    EvRing<N_MOT> e_motion_set, e_motion_used;
     long motion_g[N_MOT];   // finish index whose raw motion the slot holds (-1: none)
 };
-
-// cross-stream dependency; when the event has already fired no barrier packet is queued at all (every
-// hipStreamWaitEvent costs the waiting queue a few microseconds even for a long-fired event)
-static int wait_if_pending(hipStream_t s, hipEvent_t e) {
-    const hipError_t q = hipEventQuery(e);
-    if (q == hipSuccess) return MV_OK;
-    if (q != hipErrorNotReady) return MV_ERR_LAUNCH;
-    return hipStreamWaitEvent(s, e, 0) == hipSuccess ? MV_OK : MV_ERR_LAUNCH;
-}
 
 static int affinity_cores() {
 #if defined(__linux__)
@@ -584,39 +615,9 @@ extern "C" void mv_frame_pipe_destroy(mvFramePipe* p) {
     (void)hipStreamSynchronize(p->s_back);
     (void)hipStreamSynchronize(p->s_side);
     if (p->s_sel) (void)hipStreamSynchronize(p->s_sel);
-    auto ev = [](hipEvent_t e) { if (e) (void)hipEventDestroy(e); };
-    for (auto e : p->e_in) ev(e);
-    for (auto e : p->e_rest) ev(e);
-    for (int k = 0; k < MAX_VOL; ++k) { ev(p->e_vol_done[k]); ev(p->e_vol_free[k]); }
-    for (int k = 0; k < N_CAND; ++k) ev(p->e_cand[k]);
-    for (int k = 0; k < 2; ++k) { ev(p->e_posed[k]); ev(p->e_solved[k]); }
-    for (auto e : p->e_backend) ev(e);
-    for (auto e : p->e_kpin) ev(e);
-    for (auto e : p->e_motion_in) ev(e);
-    for (auto e : p->e_motion_read) ev(e);
-    for (auto e : p->e_motion_set) ev(e);
-    for (auto e : p->e_motion_used) ev(e);
-    ev(p->e_pgo);
-    for (int k = 0; k < N_CAND; ++k) ev(p->e_lk[k]);
-    for (auto e : p->e_seg) ev(e);
-    ev(p->e_maptail);
-    for (int k = 0; k < 2; ++k) { ev(p->e_nvalid[k]); if (p->h_nvalid[k]) (void)hipHostFree(p->h_nvalid[k]); }
+    for (int k = 0; k < 2; ++k) if (p->h_nvalid[k]) (void)hipHostFree(p->h_nvalid[k]);
     for (int k = 0; k < N_CAND; ++k) if (p->h_count_m[k]) (void)hipHostFree(p->h_count_m[k]);
     if (p->h_perm_m) (void)hipHostFree(p->h_perm_m);
-    ev(p->e_packed[0]);
-    ev(p->e_packed[1]);
-    ev(p->e_map);
-    for (int k = 0; k < 2; ++k) ev(p->e_mapl[k]);
-    ev(p->e_release);
-    for (auto e : p->e_perm) ev(e);
-    for (auto e : p->tv0) ev(e);
-    for (auto e : p->tv1) ev(e);
-    for (auto e : p->tv2) ev(e);
-    for (auto e : p->tv3) ev(e);
-    for (auto e : p->tv4) ev(e);
-    for (auto e : p->tv5) ev(e);
-    for (auto e : p->tv6) ev(e);
-    for (auto e : p->tv7) ev(e);
     for (int k = 0; k < N_CAND; ++k) if (p->h_count[k]) (void)hipHostFree(p->h_count[k]);
     for (auto h : p->h_perm) if (h) (void)hipHostFree(h);
     if (p->s_vol) (void)hipStreamDestroy(p->s_vol);
@@ -624,7 +625,7 @@ extern "C" void mv_frame_pipe_destroy(mvFramePipe* p) {
     if (p->s_back && p->s_back != p->s_side) (void)hipStreamDestroy(p->s_back);
     if (p->s_side) (void)hipStreamDestroy(p->s_side);
     if (p->s_sel) (void)hipStreamDestroy(p->s_sel);
-    delete p;
+    delete p;   // (every Ev destroys its event: the streams were synchronised above)
 }
 
 static int create_impl(mvFramePipe* p) {
@@ -644,55 +645,38 @@ static int create_impl(mvFramePipe* p) {
     MV_HIP(hipStreamCreateWithPriority(&p->s_side, hipStreamNonBlocking, hi));
     if (p->alt) p->s_back = p->s_side;   // backend + solve of a frame in order on ONE stream: the fourth queue belongs to the odd frames' decoder side
     if (p->sel_on_back == 2) MV_HIP(hipStreamCreateWithPriority(&p->s_sel, hipStreamNonBlocking, hi));
-    auto mk = [](hipEvent_t* e) { return hipEventCreateWithFlags(e, hipEventDisableTiming); };
-    for (auto& e : p->e_in) MV_HIP(mk(&e));
-    for (auto& e : p->e_rest) MV_HIP(mk(&e));
-    for (int k = 0; k < MAX_VOL; ++k) {
-        MV_HIP(mk(&p->e_vol_done[k]));
-        MV_HIP(mk(&p->e_vol_free[k]));
-    }
-    for (int k = 0; k < N_CAND; ++k) {
-        MV_HIP(mk(&p->e_cand[k]));
-        MV_HIP(hipHostMalloc((void**)&p->h_count[k], (size_t)p->lanes * 4 * sizeof(int32_t), hipHostMallocDefault));
-    }
-    for (auto& e : p->e_backend) MV_HIP(mk(&e));
-    for (auto& e : p->e_kpin) MV_HIP(mk(&e));
+    MV_TRY(create_all(p->e_in.slot));
+    MV_TRY(create_all(p->e_rest.slot));
+    MV_TRY(create_all(p->e_vol_done));
+    MV_TRY(create_all(p->e_vol_free));
+    MV_TRY(create_all(p->e_cand));
+    MV_TRY(create_all(p->e_backend.slot));
+    MV_TRY(create_all(p->e_kpin.slot));
     if (c.motion_model == MV_MOTION_TARTAN) {
-        for (auto& e : p->e_motion_in) MV_HIP(mk(&e));
-        for (auto& e : p->e_motion_read) MV_HIP(mk(&e));
-        for (auto& e : p->e_motion_set) MV_HIP(mk(&e));
-        for (auto& e : p->e_motion_used) MV_HIP(mk(&e));
+        MV_TRY(create_all(p->e_motion_in.slot));
+        MV_TRY(create_all(p->e_motion_read.slot));
+        MV_TRY(create_all(p->e_motion_set.slot));
+        MV_TRY(create_all(p->e_motion_used.slot));
     }
     for (auto& g : p->motion_g) g = -1;
-    for (int k = 0; k < 2; ++k) {
-        MV_HIP(mk(&p->e_posed[k]));
-        MV_HIP(mk(&p->e_solved[k]));
-    }
-    MV_HIP(mk(&p->e_pgo));
-    for (int k = 0; k < N_CAND; ++k) MV_HIP(mk(&p->e_lk[k]));
-    for (auto& e : p->e_seg) MV_HIP(mk(&e));
-    MV_HIP(mk(&p->e_maptail));
-    for (int k = 0; k < 2; ++k) {
-        MV_HIP(mk(&p->e_nvalid[k]));
-        MV_HIP(hipHostMalloc((void**)&p->h_nvalid[k], (size_t)p->lanes * sizeof(int32_t), hipHostMallocDefault));
-    }
+    MV_TRY(create_all(p->e_posed));
+    MV_TRY(create_all(p->e_solved));
+    MV_TRY(create_all(p->e_lk));
+    MV_TRY(create_all(p->e_seg.slot));
+    MV_TRY(create_all(p->e_nvalid));
+    MV_TRY(create_all(p->e_packed));
+    MV_TRY(create_all(p->e_mapl));
+    MV_TRY(create_all(p->e_perm.slot));
+    for (Ev* e : {&p->e_pgo, &p->e_maptail, &p->e_map, &p->e_release}) MV_TRY(e->create());
+    for (int k = 0; k < N_CAND; ++k) MV_HIP(hipHostMalloc((void**)&p->h_count[k], (size_t)p->lanes * 4 * sizeof(int32_t), hipHostMallocDefault));
+    for (int k = 0; k < 2; ++k) MV_HIP(hipHostMalloc((void**)&p->h_nvalid[k], (size_t)p->lanes * sizeof(int32_t), hipHostMallocDefault));
     if (c.mapping) {
         for (int k = 0; k < N_CAND; ++k) MV_HIP(hipHostMalloc((void**)&p->h_count_m[k], 4 * sizeof(int32_t), hipHostMallocDefault));
         MV_HIP(hipHostMalloc((void**)&p->h_perm_m, (size_t)c.map_num_point * sizeof(int64_t), hipHostMallocDefault));
     }
-    MV_HIP(mk(&p->e_packed[0]));
-    MV_HIP(mk(&p->e_packed[1]));
-    MV_HIP(mk(&p->e_map));
-    for (int k = 0; k < 2; ++k) {
-        MV_HIP(mk(&p->e_mapl[k]));
-        p->mapl_valid[k] = false;
-    }
-    MV_HIP(mk(&p->e_release));
     const size_t N = (size_t)cap_of(c);
-    for (int k = 0; k < N_PERM; ++k) {   // (a slot holds a finish's permutations [lanes, cap] or its keypoint rows [lanes, cap, 2])
-        MV_HIP(mk(&p->e_perm[k]));
+    for (int k = 0; k < N_PERM; ++k)   // (a slot holds a finish's permutations [lanes, cap] or its keypoint rows [lanes, cap, 2])
         MV_HIP(hipHostMalloc((void**)&p->h_perm[k], (size_t)p->lanes * N * 2 * sizeof(int64_t), hipHostMallocDefault));
-    }
     // constants: selector workspace zeroed once (mv_kp_select leaves it zeroed), identity pose, PGO scalars, offsets table
     MV_HIP(hipMemsetAsync(p->kp_ws, 0, p->kp_ws_bytes, p->s_main));
     if (p->kp_ws2) MV_HIP(hipMemsetAsync(p->kp_ws2, 0, p->kp_ws_bytes, p->s_main));
@@ -776,7 +760,6 @@ extern "C" int mv_frame_pipe_create(const mvFramePipeConfig* cfg, void* arena, s
     }
     describe_backend(p);
     p->newest_maps = -1;
-    for (auto& r : p->cand_recorded) r = true;
     {
         const char* e = getenv("MV_PIPE_LOOKUPS_ON");
         p->lookups_on_main = (e && strcmp(e, "vol") == 0) ? 0 : 1;
@@ -838,7 +821,7 @@ extern "C" int mv_frame_pipe_create(const mvFramePipeConfig* cfg, void* arena, s
 extern "C" int mv_frame_pipe_set_pose(mvFramePipe* p, const float* pose7_host) {
     MV_CHECK_ARG(p && pose7_host);
     MV_TRY(flush_jobs(p));
-    if (p->pgo_valid) MV_HIP(hipEventSynchronize(p->e_pgo));
+    MV_TRY(p->e_pgo.sync());
     MV_HIP(hipMemcpy(p->pose[p->pose_cur], pose7_host, (size_t)p->lanes * 7 * sizeof(float), hipMemcpyHostToDevice));
     return MV_OK;
 }
@@ -863,20 +846,20 @@ static int issue_volume(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_s
     const int k = (int)(f % p->n_volbuf);
     const int B = c.pairs;
     // inputs were produced on the caller's stream
-    hipEvent_t e_in = p->e_in[f % N_INEV];
-    MV_HIP(hipEventRecord(e_in, (hipStream_t)in_stream));
-    p->e_in_of[k] = e_in;
-    MV_TRY(wait_if_pending(p->s_vol, e_in));
-    if (p->vol_free_valid[k]) MV_TRY(wait_if_pending(p->s_vol, p->vol_free_ev[k] ? p->vol_free_ev[k] : p->e_vol_free[k]));
+    Ev& e_in = p->e_in[f];
+    MV_TRY(e_in.record((hipStream_t)in_stream));
+    p->e_in_of[k] = &e_in;
+    MV_TRY(e_in.wait_if_pending(p->s_vol));
+    if (p->vol_free_ev[k]) MV_TRY(p->vol_free_ev[k]->wait_if_pending(p->s_vol));
     const bool timed = p->n_timed < p->timed_cap;
-    if (timed && !p->packed) MV_HIP(hipEventRecord(p->tv0[p->n_timed], p->s_vol));
+    if (timed && !p->packed) MV_TRY(p->tv0[p->n_timed].record(p->s_vol));
     if (p->packed) {
         void** pk = p->pk[f & 1];
         hipStream_t sp = p->pack_on == 0 ? p->s_vol : p->pack_on == 1 ? p->s_back : p->pack_on == 2 ? p->s_main : p->s_side;
         if (sp != p->s_vol) {
-            MV_TRY(wait_if_pending(sp, e_in));
+            MV_TRY(e_in.wait_if_pending(sp));
             // this operand set was last read by the GEMM of frame f - 2 (same stream order as the volume buffers' events)
-            if (f >= 2) MV_TRY(wait_if_pending(sp, p->e_vol_done[(f - 2) % p->n_volbuf]));
+            if (f >= 2) MV_TRY(p->e_vol_done[(f - 2) % p->n_volbuf].wait_if_pending(sp));
         }
         if (p->tiled)
             MV_TRY(mv_volume_pack_tiled((const float*)in->fmap1, (const float*)in->fmap2, pk[0], pk[1], B, c.C, p->n8, p->h8, p->w8,
@@ -885,11 +868,11 @@ static int issue_volume(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_s
             MV_TRY(mv_volume_pack((const float*)in->fmap1, (const float*)in->fmap2, pk[0], pk[1], B, c.C, p->n8, p->n8, c.layout,
                                   c.volume_split, sp));
         if (sp != p->s_vol) {
-            MV_HIP(hipEventRecord(p->e_packed[f & 1], sp));
-            MV_HIP(hipStreamWaitEvent(p->s_vol, p->e_packed[f & 1], 0));
+            MV_TRY(p->e_packed[f & 1].record(sp));
+            MV_TRY(p->e_packed[f & 1].wait(p->s_vol));
         }
         // (round-4 A/B, removed: the GEMM waiting for the previous frame's lookups — each then has the chip to itself — cost 21 % of the frame rate)
-        if (timed) MV_HIP(hipEventRecord(p->tv0[p->n_timed], p->s_vol));   // the GEMM alone: behind the pack, wherever that ran
+        if (timed) MV_TRY(p->tv0[p->n_timed].record(p->s_vol));   // the GEMM alone: behind the pack, wherever that ran
         MV_TRY(mv_corr_volume_packed_shared(pk[0], pk[1], p->vol[k], B, c.C, p->n8, p->n8, c.volume_split, p->free_cus, p->s_vol));
     } else if (c.volume_split == 2 || c.volume_split == 3) {
         const size_t nel = (size_t)B * p->n8 * c.C;
@@ -908,8 +891,8 @@ static int issue_volume(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_s
         MV_TRY(mv_corr_volume(in->fmap1, in->fmap2, p->vol[k], B, c.C, p->n8, p->n8, c.feat_dtype, c.layout, p->s_vol));
     }
     p->vol_timed[k] = timed ? p->n_timed : -1;
-    if (timed) MV_HIP(hipEventRecord(p->tv1[p->n_timed++], p->s_vol));
-    MV_HIP(hipEventRecord(p->e_vol_done[k], p->s_vol));
+    if (timed) MV_TRY(p->tv1[p->n_timed++].record(p->s_vol));
+    MV_TRY(p->e_vol_done[k].record(p->s_vol));
     p->n_vol = f + 1;
     return MV_OK;
 }
@@ -933,14 +916,8 @@ extern "C" int mv_frame_pipe_enqueue_volume(mvFramePipe* p, const mvFrameInputs*
 // lean chain: the markers behind frame f's selector segment were not recorded; whoever needs them (a host-permuted finish, mv_frame_pipe_wait_candidates, a
 // selector segment that depends on the previous one) records them now, on the frame's decoder-side stream — a later point of the same in-order stream
 static int ensure_chain_events(mvFramePipe* p, long f, int cand_slot) {
-    if (cand_slot >= 0 && !p->cand_recorded[cand_slot]) {
-        MV_HIP(hipEventRecord(p->e_cand[cand_slot], p->s_lk[f % p->n_lk]));
-        p->cand_recorded[cand_slot] = true;
-    }
-    if (p->alt && f >= 0 && !p->seg_valid[f % N_INEV]) {
-        MV_HIP(hipEventRecord(p->e_seg[f % N_INEV], p->s_lk[f % p->n_lk]));
-        p->seg_valid[f % N_INEV] = true;
-    }
+    if (cand_slot >= 0 && !p->e_cand[cand_slot].recorded()) MV_TRY(p->e_cand[cand_slot].record(p->s_lk[f % p->n_lk]));
+    if (p->alt && f >= 0 && !p->e_seg[f].recorded()) MV_TRY(p->e_seg[f].record(p->s_lk[f % p->n_lk]));
     return MV_OK;
 }
 
@@ -948,13 +925,11 @@ static int ensure_chain_events(mvFramePipe* p, long f, int cand_slot) {
 // caller's PoseNet of frame f - N_MAPS (event of its mv_frame_pipe_set_motion, recorded on the caller's thread before this segment was described).
 static int issue_motion_input(mvFramePipe* p, int m, hipStream_t s) {
     const mvFramePipeConfig& c = p->c;
-    if (p->motion_read_valid[m]) MV_TRY(wait_if_pending(s, p->e_motion_read[m]));
+    MV_TRY(p->e_motion_read[m].wait_if_pending(s));
     const Maps& mp = p->maps[m];
     MV_TRY(mv_motion_input_lanes(p->lanes, c.H, c.W, mp.match_flow, 2LL * p->plane, mp.depth, (long long)p->plane, c.fx, c.fy, c.cx, c.cy, c.bl_fx,
                                  p->motion_in[m], s));
-    MV_HIP(hipEventRecord(p->e_motion_in[m], s));
-    p->motion_in_valid[m] = true;
-    return MV_OK;
+    return p->e_motion_in[m].record(s);
 }
 
 static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
@@ -965,7 +940,7 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
     hipStream_t s = p->s_lk[d.f % p->n_lk];   // (same stream as the frame's lookups: in order behind them)
     if (p->sel_on_back) {   // everything behind the lookups continues on another stream (in order with the backends it must follow)
         s = p->sel_on_back == 2 ? p->s_sel : p->sel_on_back == 3 ? p->s_vol : p->s_back;   // (1 and 4: the backend stream)
-        MV_HIP(hipStreamWaitEvent(s, p->e_lk[k], 0));
+        MV_TRY(p->e_lk[k].wait(s));
     }
     // maps slot m and candidate slot k were last read by the backend of frame f - 2 (f - 3 for the maps) on `back`
     // (the newest backend event covers the older one: same stream)
@@ -985,12 +960,12 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
         // (device-driven frame: a finish is issued right behind its frame's enqueue, so "the newest issued backend" would be the PREVIOUS frame's and the
         // segments would run one after the other; the ring holds the exact finish — frame f - 4's, long done — instead)
         const long w = p->dev_draw ? d.need_issued - 1 : issued - 1;
-        if (w >= 0 && w < issued) MV_TRY(wait_if_pending(s, p->e_backend[w % N_BEV]));
+        if (w >= 0 && w < issued) MV_TRY(p->e_backend[w].wait_if_pending(s));
     } else if (p->n_fin > 0) {
         const long w = p->dev_draw ? d.need_issued - 1 : p->n_fin - 1;
-        if (w >= 0 && p->backend_valid[w % N_BEV]) MV_TRY(wait_if_pending(s, p->e_backend[w % N_BEV]));
+        if (w >= 0) MV_TRY(p->e_backend[w].wait_if_pending(s));
     }
-    if (p->release_valid) MV_TRY(wait_if_pending(s, p->e_release));   // ... and by consumers of result views (mv_frame_pipe_release)
+    MV_TRY(p->e_release.wait_if_pending(s));   // ... and by consumers of result views (mv_frame_pipe_release)
     // alt: the previous frame's segment ran on the OTHER decoder-side stream; this one reads its maps (FULL selector, and the backend's gathers
     // behind e_cand) and shares the selector workspace / upsampling buffers with it
     // (alt_indep: NODEPTH selector without upsampling reads nothing of the previous frame and has its own workspace — the segments may overlap and
@@ -998,7 +973,7 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
     const bool indep = p->alt_indep && !up && (c.selector_mode == MV_KP_NODEPTH || kp_new_mode(c.selector_mode));
     if (p->alt && !indep && d.f > 0) {
         MV_TRY(ensure_chain_events(p, d.f - 1, -1));
-        MV_TRY(wait_if_pending(s, p->e_seg[(d.f - 1) % N_INEV]));
+        MV_TRY(p->e_seg[d.f - 1].wait_if_pending(s));
     }
     void* const kp_ws = (indep && (d.f & 1)) ? p->kp_ws2 : p->kp_ws;
     Maps& mp = p->maps[m];
@@ -1063,16 +1038,15 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
         // lean chain (device-driven, front launch in order behind this segment, segments independent): no marker here — e_cand is recorded on demand
         // (ensure_cand_event) and nothing waits for e_seg
         const bool lean = p->lean_chain && p->dev_draw && p->front_on_decoder && indep && !p->sel_on_back && !c.mapping;
-        p->cand_recorded[k] = !lean;
-        if (!lean) MV_HIP(hipEventRecord(p->e_cand[k], s));
-        if (timed) MV_HIP(hipEventRecord(p->tv3[ti], s));
+        if (lean) p->e_cand[k].skip();
+        else MV_TRY(p->e_cand[k].record(s));
+        if (timed) MV_TRY(p->tv3[ti].record(s));
         if (p->alt) {
-            if (!lean) MV_HIP(hipEventRecord(p->e_seg[d.f % N_INEV], s));
-            p->seg_valid[d.f % N_INEV] = !lean;
+            if (lean) p->e_seg[d.f].skip();
+            else MV_TRY(p->e_seg[d.f].record(s));
         }
     } else if (p->alt) {
-        MV_HIP(hipEventRecord(p->e_seg[d.f % N_INEV], s));
-        p->seg_valid[d.f % N_INEV] = true;
+        MV_TRY(p->e_seg[d.f].record(s));
     }
     return MV_OK;
 }
@@ -1121,37 +1095,35 @@ extern "C" int mv_frame_pipe_enqueue(mvFramePipe* p, const mvFrameInputs* in, mv
     hipStream_t s = p->s_lk[lk];
     float* const* tok = p->tok + 2 * lk;
     if (ahead) {   // the GEMM's input event predates this call: order the decoder side after the caller's stream as of NOW
-        hipEvent_t e = p->e_rest[f % N_INEV];
-        MV_HIP(hipEventRecord(e, (hipStream_t)in_stream));
-        MV_TRY(wait_if_pending(s, e));
+        MV_TRY(p->e_rest[f].record((hipStream_t)in_stream));
+        MV_TRY(p->e_rest[f].wait_if_pending(s));
     }
     if (p->lookups_on_main) {
-        MV_HIP(hipStreamWaitEvent(s, p->e_vol_done[kv], 0));   // also orders `s` after e_in (the GEMM stream waited for it)
+        MV_TRY(p->e_vol_done[kv].wait(s));   // also orders `s` after e_in (the GEMM stream waited for it)
         for (int it = 0; it < c.iters; ++it)
             MV_TRY(lookup_of(p)(p->vol[kv], in->coords + it * coord_stride, tok[it & 1], B, p->h8, p->w8, p->h8, p->w8, c.radius, s));
         // lean chain: this frame's front launch (same stream, behind the lookups) releases the buffer — its ring event exists before the GEMM that rewrites the
         // buffer is issued (that GEMM belongs to frame f + n_volbuf, enqueued only after this frame has been finished: MAX_PENDING < n_volbuf)
         const bool lean = p->lean_chain && p->dev_draw && with_selector && c.num_point > 0 && p->n_volbuf > MAX_PENDING;
         if (lean) {
-            p->vol_free_ev[kv] = p->e_backend[(p->n_fin + (long)p->pending.size()) % N_BEV];
+            p->vol_free_ev[kv] = &p->e_backend[p->n_fin + (long)p->pending.size()];
         } else {
-            MV_HIP(hipEventRecord(p->e_vol_free[kv], s));
-            p->vol_free_ev[kv] = p->e_vol_free[kv];
+            MV_TRY(p->e_vol_free[kv].record(s));
+            p->vol_free_ev[kv] = &p->e_vol_free[kv];
         }
-        p->vol_free_valid[kv] = true;
-        if (timed) MV_HIP(hipEventRecord(p->tv2[ti], s));
+        if (timed) MV_TRY(p->tv2[ti].record(s));
     } else {
         for (int it = 0; it < c.iters; ++it)
             MV_TRY(lookup_of(p)(p->vol[kv], in->coords + it * coord_stride, tok[it & 1], B, p->h8, p->w8, p->h8, p->w8, c.radius, p->s_vol));
-        MV_HIP(hipEventRecord(p->e_vol_done[kv], p->s_vol));   // volume AND its lookups done
-        MV_HIP(hipStreamWaitEvent(s, p->e_vol_done[kv], 0));   // also orders `s` after e_in
-        p->vol_free_valid[kv] = false;                         // vol[k] / tok are only touched on s_vol: stream order suffices
+        MV_TRY(p->e_vol_done[kv].record(p->s_vol));   // volume AND its lookups done
+        MV_TRY(p->e_vol_done[kv].wait(s));            // also orders `s` after e_in
+        p->vol_free_ev[kv] = nullptr;                 // vol[k] / tok are only touched on s_vol: stream order suffices
     }
 
     const double t_hs1 = p->host_stats ? now_us() : 0.0;
     SelSeg d{*in, f, k, m, ti, p->newest_maps, timed, with_selector != 0, up,
              p->n_fin - MAX_PENDING + (long)p->pending.size()};
-    if (p->sel_on_back) MV_HIP(hipEventRecord(p->e_lk[k], s));   // the segment continues on another stream behind the last lookup
+    if (p->sel_on_back) MV_TRY(p->e_lk[k].record(s));   // the segment continues on another stream behind the last lookup
     // MV_PIPE_SELECTOR_ON=late: with two unfinished frames in front of it (the steady state of a 3-deep pipeline) the segment is
     // handed to the NEXT finish, which issues it right behind that frame's backend: the backend stream then holds
     // backend(f - 2), selector(f), backend(f - 1), selector(f + 1) ... — a backend waits behind ONE queued selector segment (whose
@@ -1182,9 +1154,8 @@ extern "C" int mv_frame_pipe_wait_motion_input(mvFramePipe* p, mvStream_t stream
     if (sj >= 0) MV_TRY(wait_issued(p, sj + 1));
     else MV_TRY(flush_deferred(p));
     const int m = (int)((p->n_enq - 1) % N_MAPS);
-    MV_CHECK_ARG(p->motion_in_valid[m]);
-    MV_HIP(hipStreamWaitEvent((hipStream_t)stream, p->e_motion_in[m], 0));
-    return MV_OK;
+    MV_CHECK_ARG(p->e_motion_in[m].recorded());
+    return p->e_motion_in[m].wait((hipStream_t)stream);
 }
 
 extern "C" int mv_frame_pipe_set_motion(mvFramePipe* p, const float* motion_dev, mvStream_t stream) {
@@ -1193,17 +1164,14 @@ extern "C" int mv_frame_pipe_set_motion(mvFramePipe* p, const float* motion_dev,
     const int k = (int)(g % N_MOT);
     hipStream_t s = (hipStream_t)stream;
     // the slot's previous user, finish g - N_MOT, composed its prior on the solve's stream: that launch must have been ISSUED before its event means anything
-    if (p->motion_used_valid[k]) {
+    if (p->e_motion_used[g].recorded()) {
         MV_TRY(wait_issued(p, g - N_MOT + 1));
-        MV_HIP(hipStreamWaitEvent(s, p->e_motion_used[k], 0));
+        MV_TRY(p->e_motion_used[g].wait(s));
     }
     MV_HIP(hipMemcpyAsync(p->motion_raw[k], motion_dev, (size_t)p->lanes * 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    MV_HIP(hipEventRecord(p->e_motion_set[k], s));   // recorded before the frame's finish is queued: its solve waits for it
+    MV_TRY(p->e_motion_set[g].record(s));   // recorded before the frame's finish is queued: its solve waits for it
     p->motion_g[k] = g;
-    const int m = (int)((p->n_enq - 1) % N_MAPS);     // ... and the PoseNet's reads of this frame's input are behind this point of `stream`
-    MV_HIP(hipEventRecord(p->e_motion_read[m], s));
-    p->motion_read_valid[m] = true;
-    return MV_OK;
+    return p->e_motion_read[p->n_enq - 1].record(s);   // ... and the PoseNet's reads of this frame's input are behind this point of `stream`
 }
 
 extern "C" int mv_frame_pipe_wait_candidates(mvFramePipe* p, int32_t* n_cand) {
@@ -1212,11 +1180,11 @@ extern "C" int mv_frame_pipe_wait_candidates(mvFramePipe* p, int32_t* n_cand) {
     const Pending& pd = p->pending.front();
     MV_TRY(ensure_chain_events(p, pd.f, pd.cand));
     if (kp_new_mode(p->c.selector_mode)) {   // no candidate list: the frame's row count is known (the mapping selector's count still travels behind e_cand)
-        if (p->c.mapping) MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));
+        if (p->c.mapping) MV_TRY(p->e_cand[pd.cand].sync());
         for (int l = 0; l < p->lanes; ++l) n_cand[l] = frame_rows(p->c);
         return MV_OK;
     }
-    MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));
+    MV_TRY(p->e_cand[pd.cand].sync());
     if (p->dev_draw)   // (the device-driven pipe has no per-frame count copy)
         MV_HIP(hipMemcpy(p->h_count[pd.cand], p->count[pd.cand], (size_t)p->lanes * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int l = 0; l < p->lanes; ++l) n_cand[l] = p->h_count[pd.cand][4 * l];
@@ -1388,10 +1356,9 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     const bool motion = c.motion_model == MV_MOTION_TARTAN;
     float* const prior = motion ? p->prior[g % N_MOT] : nullptr;
     if (motion) {   // prior = previous pose @ Exp(raw * pose_norm), on the solve's stream behind the previous solve and the caller's set_motion
-        MV_HIP(hipStreamWaitEvent(p->s_side, p->e_motion_set[g % N_MOT], 0));
+        MV_TRY(p->e_motion_set[g].wait(p->s_side));
         MV_TRY(mv_pose_exp_compose(L, p->pose[j.pose_from], p->motion_raw[g % N_MOT], 6, p->pose_norm, prior, p->s_side));
-        MV_HIP(hipEventRecord(p->e_motion_used[g % N_MOT], p->s_side));
-        p->motion_used_valid[g % N_MOT] = true;
+        MV_TRY(p->e_motion_used[g].record(p->s_side));
     }
     if (n_max == 0) {   // nothing to track in any lane: the poses stay at the motion-model prior (MACVO.py:303-307)
         // The pose slots still rotate (MV_FB_POSE age a = the pose after the a-th newest finish) and the slot's events are
@@ -1401,15 +1368,12 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
                               p->s_side));
         if (j.pose_sink)
             MV_HIP(hipMemcpyAsync(j.pose_sink, p->pose[j.pose_to], (size_t)L * 7 * sizeof(float), hipMemcpyDeviceToDevice, p->s_side));
-        MV_HIP(hipEventRecord(p->e_posed[k], p->s_side));
-        MV_HIP(hipEventRecord(p->e_pgo, p->s_side));
-        MV_HIP(hipEventRecord(p->e_solved[k], p->s_side));
-        MV_TRY(wait_if_pending(s, p->e_cand[pd.cand]));   // (lean chain: this frame's ring event also releases its volume buffer — not before its lookups are through)
-        MV_HIP(hipEventRecord(p->e_backend[g % N_BEV], s));
-        p->pgo_valid = true;
-        p->solved_valid[k] = true;
-        p->backend_valid[g % N_BEV] = true;
-        p->nvalid_valid[k] = false;   // (mv_frame_pipe_wait_tracked then reports 0 observations: no mapping either)
+        MV_TRY(p->e_posed[k].record(p->s_side));
+        MV_TRY(p->e_pgo.record(p->s_side));
+        MV_TRY(p->e_solved[k].record(p->s_side));
+        MV_TRY(p->e_cand[pd.cand].wait_if_pending(s));   // (lean chain: this frame's ring event also releases its volume buffer — not before its lookups are through)
+        MV_TRY(p->e_backend[g].record(s));
+        p->e_nvalid[k].skip();   // (mv_frame_pipe_wait_tracked then reports 0 observations: no mapping either)
         return MV_OK;
     }
     const mvFrontMaps fm{p->maps[pd.maps].match_flow, p->maps[pd.maps].match_cov, p->maps[pd.maps_prev].dm, p->maps[pd.maps].dm};
@@ -1418,40 +1382,39 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     // Slot reuse.  This backend slot's tables were last read by the solve of frame g - 2 (side stream) and by whoever looked at
     // that frame's result views: the former has its event, the latter the event of mv_frame_pipe_release (a consumer that
     // reads views asynchronously on its own stream calls it before it asks for the next frame).
-    if (p->solved_valid[k] && s != p->s_side) MV_TRY(wait_if_pending(s, p->e_solved[k]));   // (alt layout: backend and solve share one in-order stream)
-    if (p->release_valid) MV_TRY(wait_if_pending(s, p->e_release));
+    if (s != p->s_side) MV_TRY(p->e_solved[k].wait_if_pending(s));   // (alt layout: backend and solve share one in-order stream)
+    MV_TRY(p->e_release.wait_if_pending(s));
     // ... and by the map append (map_append_finished) of frame g - 2 on the backend stream: in order with a front launch that runs there, an event for one on a
     // decoder-side stream (a 64-lane append takes longer than a one-lane one: timing does not hold this off)
-    if (p->mapl_valid[k] && s != p->s_back) MV_TRY(wait_if_pending(s, p->e_mapl[k]));
+    if (s != p->s_back) MV_TRY(p->e_mapl[k].wait_if_pending(s));
     // permutations [lanes, cap] -> pinned slot -> device (ONE copy; rows beyond a lane's n_sel are never read)
     const int ps = (int)(g % N_PERM);
     if (!j.device && p->dev_draw) MV_HIP(pass_generators());   // (a host-permuted finish)
     const bool host_rows = !j.device && (j.kp == KPJ_PERM || j.kp == KPJ_HOST);   // a permutation or (u, v) rows from the host
     const size_t rw = j.kp == KPJ_HOST ? 2 : 1;                                     // int64 words per row
     if (host_rows) {
-        if (p->perm_valid[ps]) MV_HIP(hipEventSynchronize(p->e_perm[ps]));   // long done; keeps the slot reuse provably safe
+        MV_TRY(p->e_perm[g].sync());   // long done; keeps the slot reuse provably safe
         for (int l = 0; l < L; ++l)
             memcpy(p->h_perm[ps] + (size_t)l * cap * rw, perm_host + (size_t)l * cap * rw, (size_t)n_sel[l] * rw * sizeof(int64_t));
     }
-    if (j.kp == KPJ_DEV) MV_HIP(hipStreamWaitEvent(s, p->e_kpin[g % N_BEV], 0));   // the caller's stream as of mv_frame_pipe_finish_keypoints_dev
-    if (!on_dec) MV_TRY(wait_if_pending(s, p->e_cand[pd.cand]));   // fired: the host has just read this frame's count (device-driven: a pending barrier)
-    else if (g > 0 && p->backend_valid[(g - 1) % N_BEV]) MV_TRY(wait_if_pending(s, p->e_backend[(g - 1) % N_BEV]));
+    if (j.kp == KPJ_DEV) MV_TRY(p->e_kpin[g].wait(s));   // the caller's stream as of mv_frame_pipe_finish_keypoints_dev
+    if (!on_dec) MV_TRY(p->e_cand[pd.cand].wait_if_pending(s));   // fired: the host has just read this frame's count (device-driven: a pending barrier)
+    else if (g > 0) MV_TRY(p->e_backend[g - 1].wait_if_pending(s));
     // alt layout: the previous frame's maps (gathers below) were written by a segment on the other decoder-side stream, which e_cand does not cover.
     // (Slot f - 1 of e_seg is re-recorded by frame f - 1 + N_INEV, far beyond the frames in flight.)
     // ... unless the previous frame's backend ran on THIS stream and waited for that segment itself (its e_cand is recorded at the same point): stream order
     // then covers it, and a pending cross-queue barrier less sits in front of the backend (device-driven frames are issued long before their selector is done;
     // every unsatisfied barrier at the head of a queue costs the other queues dispatch latency, profiles/r06_device_draw_ab.log)
     const bool prev_here = p->alt && p->last_backend_frame == pd.f - 1;   // (on_dec: the previous front launch's event, waited for above, covers it too)
-    if (p->alt && pd.f > 0 && !prev_here) MV_TRY(wait_if_pending(s, p->e_seg[(pd.f - 1) % N_INEV]));
+    if (p->alt && pd.f > 0 && !prev_here) MV_TRY(p->e_seg[pd.f - 1].wait_if_pending(s));
     p->last_backend_frame = pd.f;
     const int ti = pd.ti;
-    if (ti >= 0) MV_HIP(hipEventRecord(p->tv4[ti], s));
+    if (ti >= 0) MV_TRY(p->tv4[ti].record(s));
     const bool perm_in_args = j.kp == KPJ_PERM && L == 1 && n_max <= 256;   // one lane: the permutation rides in the kernel arguments (no pinned staging copy, no H2D node)
     if (!perm_in_args && host_rows) {   // (keypoint rows go straight into the frame's kp0 table, which the front launch then reads in place)
         const size_t perm_bytes = ((size_t)(L - 1) * cap + n_sel[L - 1]) * rw * sizeof(int64_t);
         MV_HIP(hipMemcpyAsync(j.kp == KPJ_HOST ? b.kp0 : b.perm, p->h_perm[ps], perm_bytes, hipMemcpyHostToDevice, s));
-        MV_HIP(hipEventRecord(p->e_perm[ps], s));
-        p->perm_valid[ps] = true;
+        MV_TRY(p->e_perm[g].record(s));
     }
     // Pose-INDEPENDENT part first: it overlaps the previous frames' solves.  The chain solve(t-1) -> backend(t) -> solve(t) is the
     // sequential dependency of visual odometry and, beside a GEMM that never pauses, it was the period of a single-sequence
@@ -1486,19 +1449,17 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     }
     if (c.mapping) {   // the mapping decision of this frame (MACVO.py:303-307) needs the observation count on the host
         MV_HIP(hipMemcpyAsync(p->h_nvalid[k], b.n_valid, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        MV_HIP(hipEventRecord(p->e_nvalid[k], s));
-        p->nvalid_valid[k] = true;
+        MV_TRY(p->e_nvalid[k].record(s));
     }
-    MV_HIP(hipEventRecord(p->e_backend[g % N_BEV], s));
-    p->backend_valid[g % N_BEV] = true;
-    if (ti >= 0) MV_HIP(hipEventRecord(p->tv5[ti], s));
+    MV_TRY(p->e_backend[g].record(s));
+    if (ti >= 0) MV_TRY(p->tv5[ti].record(s));
 
     // ---- side stream: world-frame tables from the previous solve's pose (same stream: no event), then the LM solves of all
     // lanes in ONE launch (problem l = rows [l * cap, (l + 1) * cap), dead rows masked by `valid`); the optimised poses become
     // the next frame's priors (StaticMotionModel)
     hipStream_t ss = p->s_side;
-    if (ss != s) MV_HIP(hipStreamWaitEvent(ss, p->e_backend[g % N_BEV], 0));   // (alt layout: backend + solve share one in-order stream)
-    if (ti >= 0) MV_HIP(hipEventRecord(p->tv6[ti], ss));
+    if (ss != s) MV_TRY(p->e_backend[g].wait(ss));   // (alt layout: backend + solve share one in-order stream)
+    if (ti >= 0) MV_TRY(p->tv6[ti].record(ss));
     mvPosedSolve sv = b.solve;
     sv.init_pose = p->pose[j.pose_from];
     sv.out_pose_f32 = p->pose[j.pose_to];
@@ -1520,7 +1481,7 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
         MV_TRY(mv_posed_solve(sv, ss));
     } else {
         MV_TRY(mv_pose_apply_lanes(sv.init_pose, sv.pos_Tc, sv.cov_Tc, L, n_sel, cap, sv.pos_Tw, sv.out_rot, sv.cov_Tw, ss));
-        MV_HIP(hipEventRecord(p->e_posed[k], ss));
+        MV_TRY(p->e_posed[k].record(ss));
         if (sv.ref_pose)
             MV_TRY(mv_pgo_solve_local(L, sv.offsets, sv.graph_type, motion ? prior : sv.init_pose, sv.ref_pose, sv.intrinsics, sv.baseline, sv.pos_Tw, sv.cov_Tw,
                                       sv.pixel2_uv, sv.pixel2_d, sv.pixel2_disp, sv.pixel2_disp_cov, sv.pixel2_uv_cov, sv.obs2_covTc, sv.valid, sv.min_points,
@@ -1532,11 +1493,9 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
         if (j.pose_sink)
             MV_HIP(hipMemcpyAsync(j.pose_sink, p->pose[j.pose_to], (size_t)L * 7 * sizeof(float), hipMemcpyDeviceToDevice, ss));
     }
-    MV_HIP(hipEventRecord(p->e_solved[k], ss));   // (two adjacent records on one in-order stream, nothing between them: both fire behind the solve, in either order)
-    MV_HIP(hipEventRecord(p->e_pgo, ss));
-    if (ti >= 0) MV_HIP(hipEventRecord(p->tv7[ti], ss));
-    p->pgo_valid = true;
-    p->solved_valid[k] = true;
+    MV_TRY(p->e_solved[k].record(ss));   // (two adjacent records on one in-order stream, nothing between them: both fire behind the solve, in either order)
+    MV_TRY(p->e_pgo.record(ss));
+    if (ti >= 0) MV_TRY(p->tv7[ti].record(ss));
     return MV_OK;
 }
 
@@ -1638,7 +1597,7 @@ static int finish_prologue(mvFramePipe* p, bool markers, bool map_count) {
         MV_TRY(ensure_chain_events(p, pd.f, pd.cand));
         if (pd.f > 0) MV_TRY(ensure_chain_events(p, pd.f - 1, -1));
     }
-    if (map_count && p->c.mapping) MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));
+    if (map_count && p->c.mapping) MV_TRY(p->e_cand[pd.cand].sync());
     return MV_OK;
 }
 static FinishJob new_job(const mvFramePipe* p, int kp, bool seeded, bool device) {
@@ -1678,7 +1637,7 @@ extern "C" int mv_frame_pipe_finish_seeded(mvFramePipe* p, float* pose_sink, int
     MV_TRY(finish_prologue(p, false, false));
     const Pending& pd = p->pending.front();
     const double t_w0 = p->host_stats ? now_us() : 0.0;
-    MV_HIP(hipEventSynchronize(p->e_cand[pd.cand]));
+    MV_TRY(p->e_cand[pd.cand].sync());
     FinishJob j = new_job(p, KPJ_PERM, true, false);
     if (p->host_stats) p->st_wait += j.t_count - t_w0;
     int32_t nsel[MV_MAX_LANES];
@@ -1721,7 +1680,7 @@ extern "C" int mv_frame_pipe_finished_counts(mvFramePipe* p, int age, int32_t* n
         return MV_OK;
     }
     const long g = p->n_fin - 1 - age;
-    MV_HIP(hipEventSynchronize(p->e_backend[g % N_BEV]));
+    MV_TRY(p->e_backend[g].sync());
     std::vector<int32_t> h(2 * (size_t)p->lanes);
     MV_HIP(hipMemcpy(h.data(), p->be[g & 1].live_dev, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int l = 0; l < p->lanes; ++l) {
@@ -1738,8 +1697,7 @@ extern "C" int mv_frame_pipe_wait_finished(mvFramePipe* p, int lag) {
     if (g < 0) return MV_OK;
     MV_TRY(wait_issued(p, g + 1));
     // (polling with hipEventQuery before blocking was measured: no difference — the wait is 10-40 us per frame and two frames back, profiles/r06_chain_gaps.log)
-    MV_HIP(hipEventSynchronize(p->e_backend[g % N_BEV]));
-    return MV_OK;
+    return p->e_backend[g].sync();
 }
 
 // Host-only probe of the driver's permutation generator (no GPU, no pipe): `calls` successive `torch.randperm(n[i])[:k]` of one
@@ -1793,7 +1751,7 @@ extern "C" int mv_frame_pipe_finish_keypoints_dev(mvFramePipe* p, const int64_t*
     FinishJob j = new_job(p, KPJ_DEV, false, false);
     j.kp_dev = kp_uv_dev;
     j.nsel_dev = n_sel_dev;
-    MV_HIP(hipEventRecord(p->e_kpin[p->n_fin % N_BEV], (hipStream_t)stream));   // recorded before the job is queued
+    MV_TRY(p->e_kpin[p->n_fin].record((hipStream_t)stream));   // recorded before the job is queued
     return finish_uniform(p, j, table_rows(p->c), pose_sink);
 }
 
@@ -1816,21 +1774,16 @@ static int map_append_finished(mvFramePipe* p, Frame& f, int prev_frame, const f
     f.K = K_dev; f.T_BS = T_BS_dev;
     f.prior_pose = c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];   // push_keyframe(frame1, est_pose) (MACVO.py:282)
     f.baseline = baseline;
-    MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[k] : p->e_posed[k], 0));   // pos_Tw / cov0_world come from the side stream
+    MV_TRY((p->fuse_backend ? p->e_solved[k] : p->e_posed[k]).wait(p->s_back));   // pos_Tw / cov0_world come from the side stream
     MV_TRY(launch(b));
-    MV_HIP(hipEventRecord(p->e_map, p->s_back));
+    MV_TRY(p->e_map.record(p->s_back));
     // The backend tables must outlive the append.  A front launch that runs on this stream is behind it in order; one on a decoder-side stream — the default of
     // the one-lane device-driven pipe — waits for e_mapl[k] before finish g + 2 rewrites the slot (finish_issue).  No packet for a pipe that has no such launch.
-    if (p->front_on_decoder) {
-        MV_HIP(hipEventRecord(p->e_mapl[k], p->s_back));
-        p->mapl_valid[k] = true;
-    }
+    if (p->front_on_decoder) MV_TRY(p->e_mapl[k].record(p->s_back));
     // the optimised pose goes in after the append wrote the prior
-    MV_HIP(hipStreamWaitEvent(p->s_side, p->e_map, 0));
+    MV_TRY(p->e_map.wait(p->s_side));
     MV_TRY(set_pose(p->pose[p->pose_cur]));
-    MV_HIP(hipEventRecord(p->e_pgo, p->s_side));
-    p->pgo_valid = true;
-    return MV_OK;
+    return p->e_pgo.record(p->s_side);
 }
 
 // The one-lane form: a host descriptor of the one map, and the frame's colours.
@@ -1897,10 +1850,9 @@ static int map_skip_row(mvFramePipe* p, Launch launch) {
     // map_append_finished made this stream wait for when it registered finish g lies behind that write, so stream order already covers it and the wait
     // below adds nothing to the stream; it only keeps a caller that registers no keyframes correct.  (Not e_pgo: that is re-recorded behind the append's pose
     // copy and would put the backend stream behind work it does not depend on.)
-    if (g >= 0) MV_HIP(hipStreamWaitEvent(p->s_back, p->fuse_backend ? p->e_solved[g & 1] : p->e_posed[g & 1], 0));
+    if (g >= 0) MV_TRY((p->fuse_backend ? p->e_solved[g & 1] : p->e_posed[g & 1]).wait(p->s_back));
     MV_TRY(launch(prior));
-    MV_HIP(hipEventRecord(p->e_map, p->s_back));
-    return MV_OK;
+    return p->e_map.record(p->s_back);
 }
 
 extern "C" int mv_frame_pipe_map_skip(mvFramePipe* p, const mvMapStores* stores, int frame_idx, const float* K_dev, const float* T_BS_dev, float baseline,
@@ -1921,12 +1873,12 @@ extern "C" int mv_frame_pipe_wait_tracked(mvFramePipe* p, int32_t* n_valid, int3
     MV_CHECK_ARG(p && n_valid && p->c.mapping && p->n_fin > 0);
     MV_TRY(flush_jobs(p));
     const int k = (int)((p->n_fin - 1) & 1);
-    if (!p->nvalid_valid[k]) {          // a frame without keypoints: nothing was tracked
+    if (!p->e_nvalid[k].recorded()) {   // a frame without keypoints: nothing was tracked
         *n_valid = 0;
         if (n_cand_map) *n_cand_map = 0;
         return MV_OK;
     }
-    MV_HIP(hipEventSynchronize(p->e_nvalid[k]));
+    MV_TRY(p->e_nvalid[k].sync());
     *n_valid = p->h_nvalid[k][0];
     if (n_cand_map) *n_cand_map = p->h_count_m[p->last_cand][0];   // (its copy preceded e_cand, which the host waited for before finish)
     return MV_OK;
@@ -1939,14 +1891,14 @@ extern "C" int mv_frame_pipe_map_points(mvFramePipe* p, const int64_t* perm_host
     const mvFramePipeConfig& c = p->c;
     hipStream_t s = p->s_back;
     const Maps& m0 = p->maps[p->last_maps_prev];
-    if (p->maptail_valid) MV_HIP(hipEventSynchronize(p->e_maptail));   // pinned permutation + map buffers of the previous tail (long done)
-    if (p->release_valid) MV_TRY(wait_if_pending(s, p->e_release));    // ... and consumers of its result views
+    MV_TRY(p->e_maptail.sync());               // pinned permutation + map buffers of the previous tail (long done)
+    MV_TRY(p->e_release.wait_if_pending(s));   // ... and consumers of its result views
     if (n_sel > 0) {
         memcpy(p->h_perm_m, perm_host, (size_t)n_sel * sizeof(int64_t));
         MV_HIP(hipMemcpyAsync(p->mp_perm, p->h_perm_m, (size_t)n_sel * sizeof(int64_t), hipMemcpyHostToDevice, s));
         MV_TRY(mv_kp_gather(p->cand_m[p->last_cand], p->mp_perm, n_sel, c.W, p->mp_uv, s));
         // prev_pose.Act (MACVO.py:334): the pose the frame started from = the previous frame's optimised pose
-        MV_TRY(wait_if_pending(s, p->e_pgo));   // (the solve that produced it; the newest solve is recorded later on `side`: also fine)
+        MV_TRY(p->e_pgo.wait_if_pending(s));   // (the solve that produced it; the newest solve is recorded later on `side`: also fine)
         MV_TRY(mv_map_points(p->mp_uv, n_sel, m0.depth, m0.depth_cov, image_dev, c.H, c.W, c.fx, c.fy, c.cx, c.cy,
                              p->pose[p->prior_slot], c.match_cov_default, p->mp_uvf, p->mp_d, p->mp_sdd, p->mp_sigma, p->mp_Tc, p->mp_Tw,
                              image_dev ? p->mp_color : nullptr, s));
@@ -1958,17 +1910,13 @@ extern "C" int mv_frame_pipe_map_points(mvFramePipe* p, const int64_t* perm_host
         MV_TRY(mv_map_append_points(stores, n_sel, p->mp_Tw, p->mp_cov, image_dev ? p->mp_color : nullptr, s));
     }
     p->mp_rows = n_sel;
-    MV_HIP(hipEventRecord(p->e_maptail, s));
-    p->maptail_valid = true;
-    MV_HIP(hipEventRecord(p->e_backend[(p->n_fin - 1) % N_BEV], s));   // the previous frame's maps stay in use until here (the next enqueue waits for this event)
-    return MV_OK;
+    MV_TRY(p->e_maptail.record(s));
+    return p->e_backend[p->n_fin - 1].record(s);   // the previous frame's maps stay in use until here (the next enqueue waits for this event)
 }
 
 extern "C" int mv_frame_pipe_release(mvFramePipe* p, mvStream_t stream) {
     MV_CHECK_ARG(p);
-    MV_HIP(hipEventRecord(p->e_release, (hipStream_t)stream));
-    p->release_valid = true;
-    return MV_OK;
+    return p->e_release.record((hipStream_t)stream);
 }
 
 extern "C" int mv_frame_pipe_sync(mvFramePipe* p, mvStream_t stream, int block_host) {
@@ -1976,8 +1924,7 @@ extern "C" int mv_frame_pipe_sync(mvFramePipe* p, mvStream_t stream, int block_h
     MV_TRY(flush_deferred(p));
     MV_TRY(flush_jobs(p));   // everything finished so far has been issued
     if (block_host == 2) {   // results of the newest FINISHED frame only: its solve (which ran behind its backend kernels)
-        if (p->pgo_valid) MV_HIP(hipStreamWaitEvent((hipStream_t)stream, p->e_pgo, 0));
-        return MV_OK;
+        return p->e_pgo.wait((hipStream_t)stream);
     }
     if (block_host) {
         MV_HIP(hipStreamSynchronize(p->s_vol));
@@ -1988,39 +1935,27 @@ extern "C" int mv_frame_pipe_sync(mvFramePipe* p, mvStream_t stream, int block_h
         return MV_OK;
     }
     // make `stream` wait for everything enqueued so far
-    hipEvent_t e;
-    MV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    Ev e;
+    MV_TRY(e.create());
     hipStream_t all[4 + MAX_LK] = {p->s_vol, p->s_back, p->s_side, p->s_sel};
     for (int k = 0; k < p->n_lk; ++k) all[4 + k] = p->s_lk[k];
     int rc = MV_OK;
     for (hipStream_t q : all) {
         if (!q) continue;
-        if (hipEventRecord(e, q) != hipSuccess || hipStreamWaitEvent((hipStream_t)stream, e, 0) != hipSuccess) rc = MV_ERR_LAUNCH;
+        if (e.record(q) != MV_OK || e.wait((hipStream_t)stream) != MV_OK) rc = MV_ERR_LAUNCH;
     }
-    (void)hipEventDestroy(e);
     return rc;
 }
 
 extern "C" int mv_frame_pipe_time_volume(mvFramePipe* p, int max_launches) {
     MV_CHECK_ARG(p && max_launches >= 0 && max_launches <= (1 << 20));
     MV_TRY(flush_jobs(p));   // finish_issue on the launch thread records into tv3..tv7 (which may reallocate below)
-    while ((int)p->tv0.size() < max_launches) {
-        hipEvent_t a, b;
-        MV_HIP(hipEventCreate(&a));
-        p->tv0.push_back(a);
-        MV_HIP(hipEventCreate(&b));
-        p->tv1.push_back(b);
-        hipEvent_t c2, c3;
-        MV_HIP(hipEventCreate(&c2));
-        p->tv2.push_back(c2);
-        MV_HIP(hipEventCreate(&c3));
-        p->tv3.push_back(c3);
-        for (auto* v : {&p->tv4, &p->tv5, &p->tv6, &p->tv7}) {
-            hipEvent_t e;
-            MV_HIP(hipEventCreate(&e));
-            v->push_back(e);
+    for (auto* v : {&p->tv0, &p->tv1, &p->tv2, &p->tv3, &p->tv4, &p->tv5, &p->tv6, &p->tv7})
+        while ((int)v->size() < max_launches) {
+            Ev e;
+            MV_TRY(e.create(hipEventDefault));   // (timing enabled)
+            v->push_back(std::move(e));
         }
-    }
     p->n_timed = 0;
     p->timed_cap = max_launches;
     return MV_OK;
@@ -2038,7 +1973,7 @@ extern "C" int mv_frame_pipe_volume_times(mvFramePipe* p, float* ms, int cap, in
     MV_TRY(flush_jobs(p));
     MV_HIP(hipStreamSynchronize(p->s_vol));
     const int m = p->n_timed < cap ? p->n_timed : cap;
-    for (int i = 0; i < m; ++i) MV_HIP(hipEventElapsedTime(&ms[i], p->tv0[i], p->tv1[i]));
+    for (int i = 0; i < m; ++i) MV_HIP(hipEventElapsedTime(&ms[i], p->tv0[i].e, p->tv1[i].e));
     *n = m;
     return MV_OK;
 }
@@ -2050,7 +1985,7 @@ extern "C" int mv_frame_pipe_volume_starts(mvFramePipe* p, float* ms, int cap, i
     MV_TRY(flush_jobs(p));
     MV_HIP(hipStreamSynchronize(p->s_vol));
     const int m = p->n_timed < cap ? p->n_timed : cap;
-    for (int i = 0; i < m; ++i) MV_HIP(hipEventElapsedTime(&ms[i], p->tv0[0], p->tv0[i]));
+    for (int i = 0; i < m; ++i) MV_HIP(hipEventElapsedTime(&ms[i], p->tv0[0].e, p->tv0[i].e));
     *n = m;
     return MV_OK;
 }
@@ -2067,9 +2002,9 @@ extern "C" int mv_frame_pipe_timeline(mvFramePipe* p, float* ms, int cap_frames,
     if (p->s_sel) MV_HIP(hipStreamSynchronize(p->s_sel));
     const int m = p->n_timed < cap_frames ? p->n_timed : cap_frames;
     for (int i = 0; i < m; ++i) {
-        hipEvent_t evs[4] = {p->tv0[i], p->tv1[i], p->tv2[i], p->tv3[i]};
+        hipEvent_t evs[4] = {p->tv0[i].e, p->tv1[i].e, p->tv2[i].e, p->tv3[i].e};
         for (int j = 0; j < 4; ++j)
-            if (hipEventElapsedTime(&ms[4 * i + j], p->tv0[0], evs[j]) != hipSuccess) ms[4 * i + j] = -1.f;
+            if (hipEventElapsedTime(&ms[4 * i + j], p->tv0[0].e, evs[j]) != hipSuccess) ms[4 * i + j] = -1.f;
     }
     *n = m;
     return MV_OK;
@@ -2086,9 +2021,9 @@ extern "C" int mv_frame_pipe_timeline_backend(mvFramePipe* p, float* ms, int cap
     for (int k = 0; k < p->n_lk; ++k) MV_HIP(hipStreamSynchronize(p->s_lk[k]));   // (device-driven frames run the front launch on the decoder side)
     const int m = p->n_timed < cap_frames ? p->n_timed : cap_frames;
     for (int i = 0; i < m; ++i) {
-        hipEvent_t evs[4] = {p->tv4[i], p->tv5[i], p->tv6[i], p->tv7[i]};
+        hipEvent_t evs[4] = {p->tv4[i].e, p->tv5[i].e, p->tv6[i].e, p->tv7[i].e};
         for (int j = 0; j < 4; ++j)
-            if (hipEventElapsedTime(&ms[4 * i + j], p->tv0[0], evs[j]) != hipSuccess) ms[4 * i + j] = -1.f;
+            if (hipEventElapsedTime(&ms[4 * i + j], p->tv0[0].e, evs[j]) != hipSuccess) ms[4 * i + j] = -1.f;
     }
     *n = m;
     return MV_OK;
