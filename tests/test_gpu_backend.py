@@ -148,6 +148,17 @@ def test_match_cov(gpu, n, float_kp):
 
 
 def test_match_cov_pair_equals_two_calls(gpu):
+    _match_cov_pair_equals_two_calls(gpu, (160.0, 160.0, 160.0, 120.0))
+
+
+def test_match_cov_pair_equals_two_calls_anisotropic_camera(gpu):
+    from tests import cameras
+
+    assert cameras.ANISO_SMALL.fx != cameras.ANISO_SMALL.fy
+    _match_cov_pair_equals_two_calls(gpu, cameras.ANISO_SMALL.K)
+
+
+def _match_cov_pair_equals_two_calls(gpu, K):
     from macvo_amd import ops
 
     H, W, n = 240, 320, 150
@@ -160,7 +171,6 @@ def test_match_cov_pair_equals_two_calls(gpu):
     s0[:, 2] = 0
     s1 = torch.rand(n, 3, generator=g) * 0.5
     s1[:, 2] = 0
-    K = (160.0, 160.0, 160.0, 120.0)
     R = torch.linalg.qr(torch.randn(3, 3, generator=g, dtype=torch.float64))[0].to(gpu)
     a0, a1 = s0.clone().to(gpu), s1.clone().to(gpu)
     c0, c0w = ops.match_cov(d0.to(gpu), k0.to(gpu), a0, None, *K, rot=R)

@@ -42,10 +42,27 @@ class _Frames(dict):
 @pytest.mark.parametrize("parallel", [False, True])
 @pytest.mark.parametrize("graph", ["disp", "icp"])
 def test_hip_two_frame_pgo_plugin_protocol(gpu, parallel, graph):
+    from oracle import pgo
+
+    _plugin_protocol(parallel, graph, pgo.make_synthetic_problem(n=150, seed=12)[0])
+
+
+@pytest.mark.parametrize("graph", ["disp", "reproj", "icp"])
+def test_hip_two_frame_pgo_plugin_protocol_anisotropic_camera(gpu, graph):
+    """``images_intrinsic`` = the ANISO matrix (fx != fy, off-centre principal point) and a baseline that is not 0.25, at the same bounds."""
+    from oracle import pgo
+    from tests import cameras
+
+    c = cameras.ANISO
+    prob, _ = pgo.make_synthetic_problem(n=150, seed=12, K=c.K, baseline=0.4, W=c.W, H=c.H)
+    assert prob.K[0, 0] != prob.K[1, 1]
+    _plugin_protocol(False, graph, prob)
+
+
+def _plugin_protocol(parallel, graph, prob):
     from macvo_amd.plugins import HIP_TwoFrame_PGO
     from oracle import pgo, se3
 
-    prob, _ = pgo.make_synthetic_problem(n=150, seed=12)
     cfg = SimpleNamespace(device="cpu", vectorize=True, parallel=parallel, graph_type=graph, autodiff=False)
     HIP_TwoFrame_PGO.is_valid_config(cfg)
     opt = HIP_TwoFrame_PGO(cfg)

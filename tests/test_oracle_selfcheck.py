@@ -56,7 +56,20 @@ def test_se3_exp_identities():
 @pytest.mark.parametrize("graph", [0, 1, 2])
 def test_analytic_jacobian_vs_finite_differences(graph):
     """mirrors AnalyticModule.verify_jacobian (PyposeOptimizers.py:60-73)"""
-    prob, _ = pgo.make_synthetic_problem(n=20, seed=3)
+    _jacobian_vs_finite_differences(graph)
+
+
+@pytest.mark.parametrize("graph", [0, 1, 2])
+def test_analytic_jacobian_vs_finite_differences_anisotropic(graph):
+    """the same check, same bound, on a camera with fx != fy and an off-centre principal point (tests/cameras.ANISO)"""
+    from tests import cameras
+
+    c = cameras.ANISO
+    _jacobian_vs_finite_differences(graph, K=c.K, baseline=c.baseline, W=c.W, H=c.H)
+
+
+def _jacobian_vs_finite_differences(graph, **camera):
+    prob, _ = pgo.make_synthetic_problem(n=20, seed=3, **camera)
     g = pgo._Graph(prob, graph)
     g.T = se3.se3_exp(torch.tensor([0.1, -0.2, 0.05, 0.02, -0.03, 0.01], dtype=torch.float64))
     g.forward()

@@ -138,8 +138,9 @@ def make_camera(H=480, W=640):
 
 
 def make_sequence(n_frames=4, H=480, W=640, C=256, iters=12, seed=0, feat_dtype=torch.float32, pool=2,
-                  noise=0.3, device="cpu", closed_loop=False):
-    """Returns (cam dict, list of frame dicts, list of true poses [7] float64).
+                  noise=0.3, device="cpu", closed_loop=False, cam=None):
+    """Returns (cam dict, list of frame dicts, list of true poses [7] float64).  ``cam`` (a dict with the keys of ``make_camera``) replaces the
+    default camera ``make_camera(H, W)``; its H and W must be the ones given here.
 
     Frame dict keys = FrameInputs fields: fmap1, fmap2 [2,C,H/8,W/8]; coords [iters,2,2,H/8,W/8]; flow, logcov
     [2,2,H,W].  flow[0,0] = -disparity of the frame (stereo pair), flow[1] = temporal flow (t-1 -> t) sampled on
@@ -151,7 +152,8 @@ def make_sequence(n_frames=4, H=480, W=640, C=256, iters=12, seed=0, feat_dtype=
 
     dev = torch.device(device)
     g = torch.Generator().manual_seed(seed)
-    cam = make_camera(H, W)
+    cam = make_camera(H, W) if cam is None else dict(cam)
+    assert (cam["H"], cam["W"]) == (H, W), (cam, H, W)
     fx, fy, cx, cy, bl = cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["baseline"]
     h8, w8 = H // 8, W // 8
     if closed_loop:
