@@ -110,6 +110,13 @@ FB_NAMES = ("VOLUME", "TOKENS", "DISPARITY", "DISPARITY_COV", "DEPTH", "DEPTH_CO
 FB = {n: i for i, n in enumerate(FB_NAMES)}
 
 _P = C.c_void_p
+# the four window lookups: vol, coords, out, B, H1, W1, H2, W2, radius, stream
+_LOOKUP = [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]
+# the six posed solves: (nprob, offsets, n_live, cap, graph_type) or (nprob, offsets, n_live_dev, n_live_stride, cap, graph_type), then the poses and tables
+# (14 pointers, one more per extra pose), then filter_flags ... stream
+_POSED_HOST = [C.c_int, _P, _P, C.c_int, C.c_int]
+_POSED_DEV = [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int]
+_POSED_TAIL = [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int, C.POINTER(mvLMParams)] + [_P] * 5
 # name -> (restype, argtypes): every symbol include/macvo_hip.h declares
 SIGNATURES = {
     "mv_abi_version": (C.c_int, []),
@@ -122,10 +129,10 @@ SIGNATURES = {
     "mv_corr_volume_packed_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mv_corr_volume_packed": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mv_corr_volume_packed_shared": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
-    "mv_corr_lookup": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
-    "mv_corr_lookup_tiled": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
-    "mv_corr_lookup_vol16": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
-    "mv_corr_lookup_tiled_vol16": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mv_corr_lookup": (C.c_int, _LOOKUP),
+    "mv_corr_lookup_tiled": (C.c_int, _LOOKUP),
+    "mv_corr_lookup_vol16": (C.c_int, _LOOKUP),
+    "mv_corr_lookup_tiled_vol16": (C.c_int, _LOOKUP),
     "mv_fmap_tile_rows16": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mv_tiled_slice_cells": (C.c_int, [C.c_int, C.c_int]),
     "mv_corr_volume_out16_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -151,25 +158,19 @@ SIGNATURES = {
     "mv_obs_cov_pair_nomatch_lanes": (C.c_int, [C.c_int, C.c_int32] + [_P] * 11 + [C.c_float, _P, C.POINTER(mvMatchCovParams), C.c_int, _P, C.c_int, _P]),
     "mv_motion_input_lanes": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_longlong, _P, C.c_longlong] + [C.c_float] * 5 + [_P, _P]),
     "mv_pose_exp_compose": (C.c_int, [C.c_int, _P, _P, C.c_longlong, _P, _P, _P]),
-    "mv_pgo_solve_posed_motion": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int] + [_P] * 15 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int,
-                                                                                         C.POINTER(mvLMParams)] + [_P] * 5),
-    "mv_pgo_solve_posed_motion_dev": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int] + [_P] * 15 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P,
-                                                                                                         C.c_int, C.POINTER(mvLMParams)] + [_P] * 5),
+    "mv_pgo_solve_posed_motion": (C.c_int, _POSED_HOST + [_P] * 15 + _POSED_TAIL),
+    "mv_pgo_solve_posed_motion_dev": (C.c_int, _POSED_DEV + [_P] * 15 + _POSED_TAIL),
     "mv_frame_pipe_wait_motion_input": (C.c_int, [_P, _P]),
     "mv_frame_pipe_set_motion": (C.c_int, [_P, _P, _P]),
     "mv_lm_default_params": (None, [C.POINTER(mvLMParams)]),
     "mv_pgo_solve": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int,
                                C.POINTER(mvLMParams), _P, _P, _P, _P]),
-    "mv_pgo_solve_posed": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int] + [_P] * 14 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int,
-                                     C.POINTER(mvLMParams)] + [_P] * 5),
-    "mv_pgo_solve_posed_dev": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int] + [_P] * 14 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int,
-                                         C.POINTER(mvLMParams)] + [_P] * 5),
+    "mv_pgo_solve_posed": (C.c_int, _POSED_HOST + [_P] * 14 + _POSED_TAIL),
+    "mv_pgo_solve_posed_dev": (C.c_int, _POSED_DEV + [_P] * 14 + _POSED_TAIL),
     "mv_pgo_solve_local": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int,
                                      C.POINTER(mvLMParams), _P, _P, _P, _P]),
-    "mv_pgo_solve_posed_local": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int] + [_P] * 16 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int,
-                                           C.POINTER(mvLMParams)] + [_P] * 5),
-    "mv_pgo_solve_posed_local_dev": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int] + [_P] * 16 + [C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int,
-                                               C.POINTER(mvLMParams)] + [_P] * 5),
+    "mv_pgo_solve_posed_local": (C.c_int, _POSED_HOST + [_P] * 16 + _POSED_TAIL),
+    "mv_pgo_solve_posed_local_dev": (C.c_int, _POSED_DEV + [_P] * 16 + _POSED_TAIL),
     "mv_backend_front_draw_lanes": (C.c_int, [_P, C.c_size_t, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int] + [_P] * 10 +
                                     [C.c_int, C.c_float, C.POINTER(mvMatchCovParams)] + [_P] * 13),
     "mv_backend_front_lanes": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_int, _P, C.c_int] + [_P] * 10 + [C.c_int, C.c_float, C.POINTER(mvMatchCovParams)] +

@@ -83,7 +83,29 @@ struct mvPosedSolve {   // mv_pgo_solve_posed*'s arguments; the plain mv_pgo_sol
     const mvLMParams* params;
     double *out_pose, *out_info;
     float *out_pose_f32, *pose_sink;
-    const float* ref_pose;       // (optional, last: the positional initialisers leave it null) T_o2w [nprob, 7]: solve in its frame (Local_TwoFrame_PGO)
+    const float* ref_pose;       // (optional) T_o2w [nprob, 7]: solve in its frame (Local_TwoFrame_PGO)
+};
+
+struct mvCovKeypoints {   // one keypoint set of a covariance launch (CovSet of match_cov_dev.h): tables [lanes, cap, .], depth_map [lanes, H, W], rot [lanes, 9]
+    const float *depth_map, *kp_uv;
+    float* flow_cov;          // clamped in place
+    const float* depth_cov;   // per-keypoint depth variance (optional: the patch statistic otherwise)
+    const double* rot;
+    double *out_cov, *out_cov_rot;
+    float* out_stats;
+};
+struct mvObsCovLaunch {   // mv_match_cov* / mv_obs_cov*'s arguments: one launch of match_cov_kernel, obs_cov_kernel or obs_cov_nomatch_kernel
+    int model;
+    int32_t modifiers;
+    const mvMatchCovParams* params;
+    int lanes;
+    const int32_t* n_live;   // host [lanes]
+    int cap;
+    mvCovKeypoints set0, set1;
+    bool pair;               // set1 given: a frame's two calls (kp0 on depth0, kp1 on depth1) in one launch; both need params->use_patch_var
+    const float *depth_cov_map0, *depth_cov_map1;   // dense depth variance [lanes, H, W] (MV_COV_GMM)
+    bool no_match_cov;       // (pair) set 1 without match covariance: sigma (c, c, 0) with c = model_match_cov_default, its flow_cov is not read
+    float model_match_cov_default;
 };
 
 // (hidden: the library exports the C entry points of macvo_hip.h only)
@@ -92,3 +114,10 @@ __attribute__((visibility("hidden"))) int mv_backend_front(const mvKpSource& src
                                                            const mvFrontTables& t, mvStream_t stream);
 // pgo_solve.hip — filters + rotation into the world frame + LM solve in one launch (pgo_solve_kernel with the prologue)
 __attribute__((visibility("hidden"))) int mv_posed_solve(const mvPosedSolve& d, mvStream_t stream);
+// ... and the same launch without the prologue (mv_pgo_solve, mv_pgo_solve_local): d.pos_Tc null, pos_Tw / cov_Tw / valid are inputs
+__attribute__((visibility("hidden"))) int mv_plain_solve(const mvPosedSolve& d, mvStream_t stream);
+// match_cov.hip — the covariance model of one or both keypoint sets of a frame, the argument checks of every mv_match_cov* / mv_obs_cov* entry point
+__attribute__((visibility("hidden"))) int mv_obs_cov_launch(const mvObsCovLaunch& d, mvStream_t stream);
+// corr_lookup.hip — the window lookup on a volume of fp32 or (cells16) fp16 cells, row-major or (tiled) in 4 x 4-cell tiles
+__attribute__((visibility("hidden"))) int mv_lookup(const void* vol, bool cells16, bool tiled, const float* coords, float* out, int B, int H1, int W1,
+                                                    int H2, int W2, int radius, mvStream_t stream);

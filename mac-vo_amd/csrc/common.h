@@ -159,6 +159,18 @@ static inline int mv_launch_status() {
 
 static inline int mv_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// the live-row counts of a lane-batched call (host [lanes], each within [0, cap]) as the kernel argument, and the largest of them
+static inline int check_lanes(int lanes, const int32_t* n_live, int cap, mvLaneCounts& c, int& n_max) {
+    MV_CHECK_ARG(lanes >= 1 && lanes <= MV_MAX_LANES && n_live && cap >= 0);
+    n_max = 0;
+    for (int l = 0; l < lanes; ++l) {
+        MV_CHECK_ARG(n_live[l] >= 0 && n_live[l] <= cap);
+        c.n[l] = n_live[l];
+        n_max = n_live[l] > n_max ? n_live[l] : n_max;
+    }
+    return MV_OK;
+}
+
 // modifier chain of mv_obs_cov (MV_COVMOD_*): 4 bits per step, innermost first, 0 = end; at most 4 steps, nothing after the end
 static inline bool mv_cov_modifiers_ok(int32_t m) {
     bool ended = false;

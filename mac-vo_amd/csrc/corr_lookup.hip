@@ -433,88 +433,82 @@ static int lookup_small_threshold() {
     return v;
 }
 
-extern "C" int mv_corr_lookup(const float* vol, const float* coords, float* out, int B, int H1, int W1,
-                              int H2, int W2, int radius, mvStream_t stream) {
-    MV_CHECK_ARG(vol && coords && out);
-    MV_CHECK_ARG(B > 0 && H1 > 0 && W1 > 0 && H2 > 1 && W2 > 1);
-    if (radius < 1 || radius > 4) return MV_ERR_UNSUPPORTED;
-    if (B > 65535) return MV_ERR_UNSUPPORTED;
-    const int N1 = H1 * W1;
-    hipStream_t s = (hipStream_t)stream;
-    // small launches (one frame: 9600 queries for 256 CUs) are latency-bound -> 16-query workgroups of 8 waves (600
-    // workgroups, 5.96 us vs 7.15 us for 32-query ones); large batches (B = 32: 58.5 us, ~2.4 TB/s) are throughput-bound ->
-    // 4 queries per wave amortise the per-wave setup, 32-query (128-B) output segments
-    const bool small = (size_t)B * N1 <= (size_t)lookup_small_threshold();
+// small launches (one frame: 9600 queries for 256 CUs) are latency-bound -> 16-query workgroups of 8 waves (600
+// workgroups, 5.96 us vs 7.15 us for 32-query ones); large batches (B = 32: 58.5 us, ~2.4 TB/s) are throughput-bound ->
+// 4 queries per wave amortise the per-wave setup, 32-query (128-B) output segments
+template <auto SMALL, auto LARGE, typename VT>
+static void launch_lookup(bool small, const VT* vol, const float* coords, float* out, int B, int N1, int H2, int W2, hipStream_t s) {
+    if (small)
+        hipLaunchKernelGGL(SMALL, dim3(mv_ceil_div(N1, 16), B), dim3(512), 0, s, vol, coords, out, N1, H2, W2);
+    else
+        hipLaunchKernelGGL(LARGE, dim3(mv_ceil_div(N1, 32), B), dim3(512), 0, s, vol, coords, out, N1, H2, W2);
+}
+
+static int lookup_small_qpb() {
     static int small_qpb = -1;   // MV_LOOKUP_QPB=8: 256-thread workgroups of 8 queries (A/B knob for the co-running case)
     if (small_qpb < 0) { const char* e = getenv("MV_LOOKUP_QPB"); small_qpb = (e && atoi(e) == 8) ? 8 : 16; }
-#define MV_LOOKUP(R)                                                                                                  \
-    if (small && small_qpb == 8)                                                                                      \
-        hipLaunchKernelGGL((corr_lookup_kernel<R, 2, 8>), dim3(mv_ceil_div(N1, 8), B), dim3(256), 0, s, vol, coords,  \
-                           out, N1, H2, W2);                                                                          \
-    else if (small)                                                                                                   \
-        hipLaunchKernelGGL((corr_lookup_kernel<R, 2, 16>), dim3(mv_ceil_div(N1, 16), B), dim3(512), 0, s, vol, coords, \
-                           out, N1, H2, W2);                                                                          \
-    else                                                                                                              \
-        hipLaunchKernelGGL((corr_lookup_kernel<R, 4, 32>), dim3(mv_ceil_div(N1, 32), B), dim3(512), 0, s, vol, coords, \
-                           out, N1, H2, W2)
-    switch (radius) {
-        case 1: MV_LOOKUP(1); break;
-        case 2: MV_LOOKUP(2); break;
-        case 3: MV_LOOKUP(3); break;
-        default: MV_LOOKUP(4); break;
+    return small_qpb;
+}
+
+// row-major fp32 cells, any radius
+template <int R>
+static void launch_lookup_f32(bool small, const float* vol, const float* coords, float* out, int B, int N1, int H2, int W2, hipStream_t s) {
+    if (small && lookup_small_qpb() == 8)
+        hipLaunchKernelGGL((corr_lookup_kernel<R, 2, 8>), dim3(mv_ceil_div(N1, 8), B), dim3(256), 0, s, vol, coords, out, N1, H2, W2);
+    else
+        launch_lookup<corr_lookup_kernel<R, 2, 16>, corr_lookup_kernel<R, 4, 32>>(small, vol, coords, out, B, N1, H2, W2, s);
+}
+
+// The window lookup on any of the four volume forms.  cells16: the volume is stored as fp16 (mv_corr_volume_out16): half the bytes per cell; tokens are
+// fp32.  tiled: its slices are stored in 4 x 4-cell tiles (fp32: mv_volume_pack_tiled + mv_corr_volume_packed; fp16: mv_fmap_tile_rows16 on operand 2 +
+// mv_corr_volume_out16).  Row-major fp32 takes radius 1..4, the other forms radius 4; tiles need W2 (fp32: and H2) a multiple of 4.
+int mv_lookup(const void* vol, bool cells16, bool tiled, const float* coords, float* out, int B, int H1, int W1, int H2, int W2, int radius,
+              mvStream_t stream) {
+    MV_CHECK_ARG(vol && coords && out);
+    MV_CHECK_ARG(B > 0 && H1 > 0 && W1 > 0 && H2 > 1 && W2 > 1);
+    MV_CHECK_ARG(!(tiled && cells16) || ((uintptr_t)vol & 31) == 0);     // a tile = one 32-byte sector
+    if (radius > 4 || radius < (cells16 || tiled ? 4 : 1) || B > 65535) return MV_ERR_UNSUPPORTED;
+    if (tiled && ((W2 % 4) || (!cells16 && (H2 % 4)))) return MV_ERR_UNSUPPORTED;
+    const int N1 = H1 * W1;
+    hipStream_t s = (hipStream_t)stream;
+    const bool small = (size_t)B * N1 <= (size_t)lookup_small_threshold();
+    const float* v32 = reinterpret_cast<const float*>(vol);
+    const _Float16* v16 = reinterpret_cast<const _Float16*>(vol);
+    if (!cells16 && !tiled) {
+        switch (radius) {
+            case 1: launch_lookup_f32<1>(small, v32, coords, out, B, N1, H2, W2, s); break;
+            case 2: launch_lookup_f32<2>(small, v32, coords, out, B, N1, H2, W2, s); break;
+            case 3: launch_lookup_f32<3>(small, v32, coords, out, B, N1, H2, W2, s); break;
+            default: launch_lookup_f32<4>(small, v32, coords, out, B, N1, H2, W2, s); break;
+        }
+    } else if (!tiled) {
+        launch_lookup<corr_lookup_kernel<4, 2, 16, _Float16>, corr_lookup_kernel<4, 4, 32, _Float16>>(small, v16, coords, out, B, N1, H2, W2, s);
+    } else if (!cells16) {
+        launch_lookup<corr_lookup_tiled_kernel<2, 16>, corr_lookup_tiled_kernel<4, 32>>(small, v32, coords, out, B, N1, H2, W2, s);
+    } else {
+        launch_lookup<corr_lookup_tiled_kernel<2, 16, _Float16>, corr_lookup_tiled_kernel<4, 32, _Float16>>(small, v16, coords, out, B, N1, H2, W2, s);
     }
-#undef MV_LOOKUP
     return mv_launch_status();
 }
 
-// the same lookup on a volume stored as fp16 (mv_corr_volume_out16): half the bytes per cell; tokens are fp32
+extern "C" int mv_corr_lookup(const float* vol, const float* coords, float* out, int B, int H1, int W1,
+                              int H2, int W2, int radius, mvStream_t stream) {
+    return mv_lookup(vol, false, false, coords, out, B, H1, W1, H2, W2, radius, stream);
+}
+
 extern "C" int mv_corr_lookup_vol16(const void* vol, const float* coords, float* out, int B, int H1, int W1, int H2, int W2, int radius,
                                     mvStream_t stream) {
-    MV_CHECK_ARG(vol && coords && out);
-    MV_CHECK_ARG(B > 0 && H1 > 0 && W1 > 0 && H2 > 1 && W2 > 1);
-    if (radius != 4 || B > 65535) return MV_ERR_UNSUPPORTED;
-    const int N1 = H1 * W1;
-    hipStream_t s = (hipStream_t)stream;
-    const _Float16* v = reinterpret_cast<const _Float16*>(vol);
-    if ((size_t)B * N1 <= (size_t)lookup_small_threshold())
-        hipLaunchKernelGGL((corr_lookup_kernel<4, 2, 16, _Float16>), dim3(mv_ceil_div(N1, 16), B), dim3(512), 0, s, v, coords, out, N1, H2, W2);
-    else
-        hipLaunchKernelGGL((corr_lookup_kernel<4, 4, 32, _Float16>), dim3(mv_ceil_div(N1, 32), B), dim3(512), 0, s, v, coords, out, N1, H2, W2);
-    return mv_launch_status();
+    return mv_lookup(vol, true, false, coords, out, B, H1, W1, H2, W2, radius, stream);
 }
 
-// the same on a volume whose slices are stored in 4 x 4-cell tiles (mv_volume_pack_tiled + mv_corr_volume_packed); radius 4, H2 and W2
-// multiples of 4
 extern "C" int mv_corr_lookup_tiled(const float* vol, const float* coords, float* out, int B, int H1, int W1, int H2, int W2,
                                     int radius, mvStream_t stream) {
-    MV_CHECK_ARG(vol && coords && out);
-    MV_CHECK_ARG(B > 0 && H1 > 0 && W1 > 0 && H2 > 1 && W2 > 1);
-    if (radius != 4 || (H2 % 4) || (W2 % 4) || B > 65535) return MV_ERR_UNSUPPORTED;
-    const int N1 = H1 * W1;
-    hipStream_t s = (hipStream_t)stream;
-    if ((size_t)B * N1 <= (size_t)lookup_small_threshold())
-        hipLaunchKernelGGL((corr_lookup_tiled_kernel<2, 16>), dim3(mv_ceil_div(N1, 16), B), dim3(512), 0, s, vol, coords, out, N1, H2, W2);
-    else
-        hipLaunchKernelGGL((corr_lookup_tiled_kernel<4, 32>), dim3(mv_ceil_div(N1, 32), B), dim3(512), 0, s, vol, coords, out, N1, H2, W2);
-    return mv_launch_status();
+    return mv_lookup(vol, false, true, coords, out, B, H1, W1, H2, W2, radius, stream);
 }
 
-
-// ... and on a TILED volume of fp16 cells: mv_fmap_tile_rows16 on operand 2 + mv_corr_volume_out16 (radius 4, H2 and W2 multiples of 4)
 extern "C" int mv_corr_lookup_tiled_vol16(const void* vol, const float* coords, float* out, int B, int H1, int W1, int H2, int W2, int radius,
                                           mvStream_t stream) {
-    MV_CHECK_ARG(vol && coords && out);
-    MV_CHECK_ARG(B > 0 && H1 > 0 && W1 > 0 && H2 > 1 && W2 > 1);
-    MV_CHECK_ARG(((uintptr_t)vol & 31) == 0);                            // a tile = one 32-byte sector
-    if (radius != 4 || (W2 % 4) || B > 65535) return MV_ERR_UNSUPPORTED;
-    const int N1 = H1 * W1;
-    hipStream_t s = (hipStream_t)stream;
-    const _Float16* v = reinterpret_cast<const _Float16*>(vol);
-    if ((size_t)B * N1 <= (size_t)lookup_small_threshold())
-        hipLaunchKernelGGL((corr_lookup_tiled_kernel<2, 16, _Float16>), dim3(mv_ceil_div(N1, 16), B), dim3(512), 0, s, v, coords, out, N1, H2, W2);
-    else
-        hipLaunchKernelGGL((corr_lookup_tiled_kernel<4, 32, _Float16>), dim3(mv_ceil_div(N1, 32), B), dim3(512), 0, s, v, coords, out, N1, H2, W2);
-    return mv_launch_status();
+    return mv_lookup(vol, true, true, coords, out, B, H1, W1, H2, W2, radius, stream);
 }
 
 // The pixel rows of a 16-bit HWC feature map [B, H, W, C] in 4 x 4-tile order: out[b][(ty * W/4 + tx) * 16 + (y % 4) * 4 + x % 4][:] =

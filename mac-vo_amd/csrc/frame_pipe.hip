@@ -500,18 +500,25 @@ static size_t carve(mvFramePipe* p, char* base) {
 // Backend slot's tables.  THE place where a slot's table pointers are spelled out; finish_issue names a slot.
 static void describe_backend(mvFramePipe* p) {
     const mvFramePipeConfig& c = p->c;
-    p->cov = mvCovConfig{c.cov_model, c.cov_modifiers, {c.H, c.W, c.cov_kernel_size, 1, c.fx, c.fy, c.cx, c.cy, c.min_flow_cov_sq, c.min_depth_cov},
-                         c.edgewidth, c.match_cov_default, c.frontend_nocov, c.cov_match_cov_default};
+    mvCovConfig& cv = p->cov = {};
+    cv.model = c.cov_model; cv.modifiers = c.cov_modifiers;
+    cv.cp = mvMatchCovParams{c.H, c.W, c.cov_kernel_size, 1, c.fx, c.fy, c.cx, c.cy, c.min_flow_cov_sq, c.min_depth_cov};
+    cv.edge = c.edgewidth; cv.match_cov_default = c.match_cov_default;
+    cv.nocov = c.frontend_nocov; cv.model_match_cov_default = c.cov_match_cov_default;
     for (Maps& m : p->maps) m.dm = mvDepthMaps{m.depth, m.disparity, m.disparity_cov, m.depth_cov};
     const int cap = cap_of(c);
     const size_t LN = (size_t)p->lanes * cap;   // value table is [11, lanes, cap]: each of its rows is one concatenated per-point column
     for (Backend& b : p->be) {
         b.front = mvFrontTables{b.kp0, b.kp0f, b.kp1, b.inbound, b.vals, b.sigma0, b.sigma1, b.pos_Tc, b.cov0, b.cov1};
         // (the observation filters: prologue of the solve's launch; mapping mode needs the count on the host first and keeps the launch)
-        b.solve = mvPosedSolve{p->lanes, p->offs, cap, c.graph_type, nullptr, nullptr, p->intr, p->bl, b.pos_Tc, b.cov0, b.pos_Tw, b.cov0w, b.rot,
-                               b.kp1, b.vals + 4 * LN, b.vals + 5 * LN, b.vals + 6 * LN, b.sigma1, b.cov1, nullptr, nullptr, 0,
-                               c.mapping ? -1 : c.filters, c.filter_min_depth, c.max_depth, b.inbound, b.vals, b.valid, b.n_valid, c.min_num_point, &c.lm,
-                               b.pose64, b.info, nullptr, nullptr};
+        mvPosedSolve& sv = b.solve = {};
+        sv.nprob = p->lanes; sv.offsets = p->offs; sv.cap = cap; sv.graph_type = c.graph_type; sv.intrinsics = p->intr; sv.baseline = p->bl;
+        sv.pos_Tc = b.pos_Tc; sv.cov_Tc = b.cov0; sv.pos_Tw = b.pos_Tw; sv.cov_Tw = b.cov0w; sv.out_rot = b.rot;
+        sv.pixel2_uv = b.kp1; sv.pixel2_d = b.vals + 4 * LN; sv.pixel2_disp = b.vals + 5 * LN; sv.pixel2_disp_cov = b.vals + 6 * LN;
+        sv.pixel2_uv_cov = b.sigma1; sv.obs2_covTc = b.cov1;
+        sv.filter_flags = c.mapping ? -1 : c.filters; sv.filter_min_depth = c.filter_min_depth; sv.filter_max_depth = c.max_depth;
+        sv.inbound = b.inbound; sv.vals = b.vals; sv.valid = b.valid; sv.count_out = b.n_valid; sv.min_points = c.min_num_point; sv.params = &c.lm;
+        sv.out_pose = b.pose64; sv.out_info = b.info;
     }
 }
 
@@ -827,18 +834,6 @@ extern "C" int mv_frame_pipe_set_pose(mvFramePipe* p, const float* pose7_host) {
 }
 
 // ------------------------------------------------------------------------------------------------ frontend half
-typedef int (*mvLookupFn)(const float*, const float*, float*, int, int, int, int, int, int, mvStream_t);
-static int lookup_vol16_as_float_ptr(const float* vol, const float* coords, float* out, int B, int H1, int W1, int H2, int W2, int radius, mvStream_t s) {
-    return mv_corr_lookup_vol16(vol, coords, out, B, H1, W1, H2, W2, radius, s);      // (the arena pointer is typed float*; the cells are fp16)
-}
-static int lookup_tiled_vol16_as_float_ptr(const float* vol, const float* coords, float* out, int B, int H1, int W1, int H2, int W2, int radius, mvStream_t s) {
-    return mv_corr_lookup_tiled_vol16(vol, coords, out, B, H1, W1, H2, W2, radius, s);
-}
-static mvLookupFn lookup_of(const mvFramePipe* p) {
-    if (p->vol16) return p->tiled ? lookup_tiled_vol16_as_float_ptr : lookup_vol16_as_float_ptr;
-    return p->tiled ? mv_corr_lookup_tiled : mv_corr_lookup;
-}
-
 // volume GEMM of frame n_vol on its own stream; a buffer is rewritten only after the lookups that read it have finished
 static int issue_volume(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_stream) {
     const mvFramePipeConfig& c = p->c;
@@ -1101,7 +1096,7 @@ extern "C" int mv_frame_pipe_enqueue(mvFramePipe* p, const mvFrameInputs* in, mv
     if (p->lookups_on_main) {
         MV_TRY(p->e_vol_done[kv].wait(s));   // also orders `s` after e_in (the GEMM stream waited for it)
         for (int it = 0; it < c.iters; ++it)
-            MV_TRY(lookup_of(p)(p->vol[kv], in->coords + it * coord_stride, tok[it & 1], B, p->h8, p->w8, p->h8, p->w8, c.radius, s));
+            MV_TRY(mv_lookup(p->vol[kv], p->vol16, p->tiled, in->coords + it * coord_stride, tok[it & 1], B, p->h8, p->w8, p->h8, p->w8, c.radius, s));
         // lean chain: this frame's front launch (same stream, behind the lookups) releases the buffer — its ring event exists before the GEMM that rewrites the
         // buffer is issued (that GEMM belongs to frame f + n_volbuf, enqueued only after this frame has been finished: MAX_PENDING < n_volbuf)
         const bool lean = p->lean_chain && p->dev_draw && with_selector && c.num_point > 0 && p->n_volbuf > MAX_PENDING;
@@ -1114,7 +1109,7 @@ extern "C" int mv_frame_pipe_enqueue(mvFramePipe* p, const mvFrameInputs* in, mv
         if (timed) MV_TRY(p->tv2[ti].record(s));
     } else {
         for (int it = 0; it < c.iters; ++it)
-            MV_TRY(lookup_of(p)(p->vol[kv], in->coords + it * coord_stride, tok[it & 1], B, p->h8, p->w8, p->h8, p->w8, c.radius, p->s_vol));
+            MV_TRY(mv_lookup(p->vol[kv], p->vol16, p->tiled, in->coords + it * coord_stride, tok[it & 1], B, p->h8, p->w8, p->h8, p->w8, c.radius, p->s_vol));
         MV_TRY(p->e_vol_done[kv].record(p->s_vol));   // volume AND its lookups done
         MV_TRY(p->e_vol_done[kv].wait(s));            // also orders `s` after e_in
         p->vol_free_ev[kv] = nullptr;                 // vol[k] / tok are only touched on s_vol: stream order suffices
@@ -1438,13 +1433,18 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
                                  c.match_cov_default, c.fx, c.fy, c.cx, c.cy, t.kp0_uv, t.kp0, t.kp1, t.inbound, t.vals, t.sigma0, t.sigma1, t.pos_Tc, s));
     }
     if (!fused) {   // (behind a fused front launch — keypoint rows — the covariances are computed again: same bits)
-        if (c.frontend_nocov & MV_NOCOV_MATCH)   // (set 1: the model's own sigma, the depth variance the tracking gathered at kp1 — value row 7)
-            MV_TRY(mv_obs_cov_pair_nomatch_lanes(c.cov_model, c.cov_modifiers, fm.f0.depth, fm.f0.sdd, t.kp0, t.sigma0, nullptr, t.cov0, nullptr, fm.f1.depth,
-                                                 fm.f1.sdd, t.kp1, fm.f1.sdd ? t.vals + 7 * (size_t)L * cap : nullptr, c.cov_match_cov_default, t.cov1,
-                                                 &p->cov.cp, L, n_sel, cap, s));
-        else
-            MV_TRY(mv_obs_cov_pair_lanes(c.cov_model, c.cov_modifiers, fm.f0.depth, fm.f0.sdd, t.kp0, t.sigma0, nullptr, t.cov0, nullptr, fm.f1.depth,
-                                         fm.f1.sdd, t.kp1, t.sigma1, t.cov1, &p->cov.cp, L, n_sel, cap, s));
+        mvObsCovLaunch d{};
+        d.model = p->cov.model; d.modifiers = p->cov.modifiers; d.params = &p->cov.cp; d.lanes = L; d.n_live = n_sel; d.cap = cap;
+        d.pair = true;
+        d.set0.depth_map = fm.f0.depth; d.set0.kp_uv = t.kp0; d.set0.flow_cov = t.sigma0; d.set0.out_cov = t.cov0;
+        d.set1.depth_map = fm.f1.depth; d.set1.kp_uv = t.kp1; d.set1.flow_cov = t.sigma1; d.set1.out_cov = t.cov1;
+        d.depth_cov_map0 = fm.f0.sdd; d.depth_cov_map1 = fm.f1.sdd;
+        if (c.frontend_nocov & MV_NOCOV_MATCH) {   // (set 1: the model's own sigma, the depth variance the tracking gathered at kp1 — value row 7)
+            d.no_match_cov = true; d.model_match_cov_default = p->cov.model_match_cov_default;
+            d.set1.flow_cov = nullptr;
+            d.set1.depth_cov = fm.f1.sdd ? t.vals + 7 * (size_t)L * cap : nullptr;
+        }
+        MV_TRY(mv_obs_cov_launch(d, s));
         MV_TRY(obs_filter());
     }
     if (c.mapping) {   // the mapping decision of this frame (MACVO.py:303-307) needs the observation count on the host
@@ -1482,14 +1482,9 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     } else {
         MV_TRY(mv_pose_apply_lanes(sv.init_pose, sv.pos_Tc, sv.cov_Tc, L, n_sel, cap, sv.pos_Tw, sv.out_rot, sv.cov_Tw, ss));
         MV_TRY(p->e_posed[k].record(ss));
-        if (sv.ref_pose)
-            MV_TRY(mv_pgo_solve_local(L, sv.offsets, sv.graph_type, motion ? prior : sv.init_pose, sv.ref_pose, sv.intrinsics, sv.baseline, sv.pos_Tw, sv.cov_Tw,
-                                      sv.pixel2_uv, sv.pixel2_d, sv.pixel2_disp, sv.pixel2_disp_cov, sv.pixel2_uv_cov, sv.obs2_covTc, sv.valid, sv.min_points,
-                                      sv.params, sv.out_pose, sv.out_info, sv.out_pose_f32, ss));
-        else
-        MV_TRY(mv_pgo_solve(L, sv.offsets, sv.graph_type, motion ? prior : sv.init_pose, sv.intrinsics, sv.baseline, sv.pos_Tw, sv.cov_Tw, sv.pixel2_uv,
-                            sv.pixel2_d, sv.pixel2_disp, sv.pixel2_disp_cov, sv.pixel2_uv_cov, sv.obs2_covTc, sv.valid, sv.min_points, sv.params,
-                            sv.out_pose, sv.out_info, sv.out_pose_f32, ss));
+        sv.pos_Tc = nullptr;   // the plain solve (mv_pgo_solve; with ref_pose mv_pgo_solve_local): the world-frame tables and `valid` are inputs by now
+        if (motion) sv.init_pose = prior;
+        MV_TRY(mv_plain_solve(sv, ss));
         if (j.pose_sink)
             MV_HIP(hipMemcpyAsync(j.pose_sink, p->pose[j.pose_to], (size_t)L * 7 * sizeof(float), hipMemcpyDeviceToDevice, ss));
     }
@@ -1902,8 +1897,7 @@ extern "C" int mv_frame_pipe_map_points(mvFramePipe* p, const int64_t* perm_host
         MV_TRY(mv_map_points(p->mp_uv, n_sel, m0.depth, m0.depth_cov, image_dev, c.H, c.W, c.fx, c.fy, c.cx, c.cy,
                              p->pose[p->prior_slot], c.match_cov_default, p->mp_uvf, p->mp_d, p->mp_sdd, p->mp_sigma, p->mp_Tc, p->mp_Tw,
                              image_dev ? p->mp_color : nullptr, s));
-        mvMatchCovParams cp{c.H, c.W, c.cov_kernel_size, 1, c.fx, c.fy, c.cx, c.cy, c.min_flow_cov_sq, c.min_depth_cov};
-        MV_TRY(mv_obs_cov(c.cov_model, c.cov_modifiers, m0.depth, m0.depth_cov, p->mp_uvf, p->mp_sigma, p->mp_sdd, nullptr, &cp, n_sel, p->mp_cov,
+        MV_TRY(mv_obs_cov(c.cov_model, c.cov_modifiers, m0.depth, m0.depth_cov, p->mp_uvf, p->mp_sigma, p->mp_sdd, nullptr, &p->cov.cp, n_sel, p->mp_cov,
                           nullptr, nullptr, s));   // the same ObsCovModel (MACVO.py:324)
     }
     if (stores) {   // map_points.push + frame2map.add (also for n_sel == 0: the reference adds the empty range), behind the frame's registration

@@ -510,17 +510,6 @@ void launch_backend_front_pm(int pm, Args... args) {
 
 }  // namespace
 
-static inline int check_lanes(int lanes, const int32_t* n_live, int cap, mvLaneCounts& c, int& n_max) {
-    MV_CHECK_ARG(lanes >= 1 && lanes <= MV_MAX_LANES && n_live && cap >= 0);
-    n_max = 0;
-    for (int l = 0; l < lanes; ++l) {
-        MV_CHECK_ARG(n_live[l] >= 0 && n_live[l] <= cap);
-        c.n[l] = n_live[l];
-        n_max = n_live[l] > n_max ? n_live[l] : n_max;
-    }
-    return MV_OK;
-}
-
 extern "C" int mv_frontend_epilogue_lanes(const float* flow, const float* logcov, int cov_is_log, int H, int W,
                                           float bl_fx, float bl_fx_sq, float* disparity, float* disparity_cov,
                                           float* depth, float* depth_cov, uint8_t* bad_mask, float* match_flow,

@@ -879,14 +879,11 @@ extern "C" int mv_kp_select(const float* flow_cov, const float* depth0, const fl
 
 extern "C" int mv_kp_gather_lanes(const int32_t* cand, size_t cand_lane_stride, const int64_t* perm, int lanes,
                                   const int32_t* n_live, int cap, int W, int64_t* out_uv, mvStream_t stream) {
-    MV_CHECK_ARG(lanes >= 1 && lanes <= MV_MAX_LANES && n_live && cap >= 0 && W > 0);
+    MV_CHECK_ARG(W > 0);
     mvLaneCounts c{};
     int n_max = 0;
-    for (int l = 0; l < lanes; ++l) {
-        MV_CHECK_ARG(n_live[l] >= 0 && n_live[l] <= cap);
-        c.n[l] = n_live[l];
-        n_max = n_live[l] > n_max ? n_live[l] : n_max;
-    }
+    const int rc = check_lanes(lanes, n_live, cap, c, n_max);
+    if (rc != MV_OK) return rc;
     if (n_max == 0) return MV_OK;
     MV_CHECK_ARG(cand && perm && out_uv);
     hipLaunchKernelGGL(kp_gather_kernel, dim3(mv_ceil_div(n_max, 256), lanes), dim3(256), 0, (hipStream_t)stream, cand, perm,

@@ -85,22 +85,84 @@ int launch_obs_cov(int model, int32_t mods, dim3 grid, hipStream_t st, const Cov
 
 }  // namespace
 
+// Every covariance entry point ends here: the one copy of the argument checks, of CovSet and of the grid.  A single form is lanes = 1, cap = N, one set.
+int mv_obs_cov_launch(const mvObsCovLaunch& d, mvStream_t stream) {
+    MV_CHECK_ARG(d.model >= MV_COV_MATCH && d.model <= MV_COV_NONE && mv_cov_modifiers_ok(d.modifiers) && d.params);
+    mvLaneCounts c{};
+    int n_max = 0;
+    const int rc = check_lanes(d.lanes, d.n_live, d.cap, c, n_max);
+    if (rc != MV_OK) return rc;
+    if (n_max == 0) return MV_OK;
+    const mvCovKeypoints &k0 = d.set0, &k1 = d.pair ? d.set1 : d.set0;
+    MV_CHECK_ARG(k0.depth_map && k0.kp_uv && k0.flow_cov && k0.out_cov && k1.depth_map && k1.kp_uv && (k1.flow_cov || d.no_match_cov) && k1.out_cov);
+    const mvMatchCovParams p = *d.params;
+    MV_CHECK_ARG(p.H > 0 && p.W > 0 && p.kernel_size >= 1 && (p.kernel_size & 1));
+    // (an oversized kernel is "unsupported", not "invalid": the single forms say so before they look at the depth variances, the pair forms behind that)
+    if (!d.pair && p.kernel_size > MAX_K) return MV_ERR_UNSUPPORTED;
+    MV_CHECK_ARG(p.use_patch_var || (!d.pair && k0.depth_cov));
+    // the mixture model needs the depth model's variance: both dense maps and, for a set without match covariance, the one gathered at its keypoints
+    MV_CHECK_ARG(d.model != MV_COV_GMM || (d.depth_cov_map0 && d.depth_cov_map1 && (!d.no_match_cov || k1.depth_cov)));
+    if (p.kernel_size > MAX_K) return MV_ERR_UNSUPPORTED;
+    MV_CHECK_ARG(!k0.out_cov_rot || k0.rot);
+    const CovSet s0{k0.depth_map, k0.kp_uv, k0.flow_cov, k0.depth_cov, k0.rot, k0.out_cov, k0.out_cov_rot, k0.out_stats};
+    const CovSet s1{k1.depth_map, k1.kp_uv, k1.flow_cov, k1.depth_cov, k1.rot, k1.out_cov, k1.out_cov_rot, k1.out_stats};
+    const dim3 grid(mv_ceil_div(n_max, 4), d.pair ? 2 : 1, d.lanes);
+    hipStream_t st = (hipStream_t)stream;
+    if (!d.no_match_cov) return launch_obs_cov(d.model, d.modifiers, grid, st, s0, s1, p, d.cap, c, d.depth_cov_map0, d.depth_cov_map1);
+    const bool m = d.modifiers != 0;
+    if (d.model == MV_COV_MATCH)
+        launch_nomatch<MV_COV_MATCH>(m, grid, st, s0, s1, p, d.cap, c, d.modifiers, d.depth_cov_map0, d.depth_cov_map1, d.model_match_cov_default);
+    else if (d.model == MV_COV_GMM)
+        launch_nomatch<MV_COV_GMM>(m, grid, st, s0, s1, p, d.cap, c, d.modifiers, d.depth_cov_map0, d.depth_cov_map1, d.model_match_cov_default);
+    else
+        launch_nomatch<MV_COV_NONE>(m, grid, st, s0, s1, p, d.cap, c, d.modifiers, d.depth_cov_map0, d.depth_cov_map1, d.model_match_cov_default);
+    return mv_launch_status();
+}
+
+extern "C" int mv_obs_cov(int model, int32_t modifiers, const float* depth_map, const float* depth_cov_map, const float* kp_uv, float* flow_cov,
+                          const float* depth_cov, const double* rot, const mvMatchCovParams* params, int N, double* out_cov, double* out_cov_rot,
+                          float* out_stats, mvStream_t stream) {
+    const int32_t n = N;
+    mvObsCovLaunch d{};
+    d.model = model; d.modifiers = modifiers; d.params = params; d.lanes = 1; d.n_live = &n; d.cap = N;
+    d.set0 = mvCovKeypoints{depth_map, kp_uv, flow_cov, depth_cov, rot, out_cov, out_cov_rot, out_stats};
+    d.depth_cov_map0 = d.depth_cov_map1 = depth_cov_map;
+    return mv_obs_cov_launch(d, stream);
+}
+
+extern "C" int mv_obs_cov_pair_lanes(int model, int32_t modifiers, const float* depth_map0, const float* depth_cov_map0, const float* kp_uv0,
+                                     float* flow_cov0, const double* rot0, double* out_cov0, double* out_cov_rot0, const float* depth_map1,
+                                     const float* depth_cov_map1, const float* kp_uv1, float* flow_cov1, double* out_cov1,
+                                     const mvMatchCovParams* params, int lanes, const int32_t* n_live, int cap, mvStream_t stream) {
+    mvObsCovLaunch d{};
+    d.model = model; d.modifiers = modifiers; d.params = params; d.lanes = lanes; d.n_live = n_live; d.cap = cap;
+    d.pair = true;
+    d.set0 = mvCovKeypoints{depth_map0, kp_uv0, flow_cov0, nullptr, rot0, out_cov0, out_cov_rot0, nullptr};
+    d.set1 = mvCovKeypoints{depth_map1, kp_uv1, flow_cov1, nullptr, nullptr, out_cov1, nullptr, nullptr};
+    d.depth_cov_map0 = depth_cov_map0; d.depth_cov_map1 = depth_cov_map1;
+    return mv_obs_cov_launch(d, stream);
+}
+
+extern "C" int mv_obs_cov_pair_nomatch_lanes(int model, int32_t modifiers, const float* depth_map0, const float* depth_cov_map0, const float* kp_uv0,
+                                             float* flow_cov0, const double* rot0, double* out_cov0, double* out_cov_rot0, const float* depth_map1,
+                                             const float* depth_cov_map1, const float* kp_uv1, const float* depth_cov1, float model_match_cov_default,
+                                             double* out_cov1, const mvMatchCovParams* params, int lanes, const int32_t* n_live, int cap,
+                                             mvStream_t stream) {
+    mvObsCovLaunch d{};
+    d.model = model; d.modifiers = modifiers; d.params = params; d.lanes = lanes; d.n_live = n_live; d.cap = cap;
+    d.pair = true;
+    d.set0 = mvCovKeypoints{depth_map0, kp_uv0, flow_cov0, nullptr, rot0, out_cov0, out_cov_rot0, nullptr};
+    d.set1 = mvCovKeypoints{depth_map1, kp_uv1, nullptr, depth_cov1, nullptr, out_cov1, nullptr, nullptr};
+    d.depth_cov_map0 = depth_cov_map0; d.depth_cov_map1 = depth_cov_map1;
+    d.no_match_cov = true; d.model_match_cov_default = model_match_cov_default;
+    return mv_obs_cov_launch(d, stream);
+}
+
+// MatchCovariance without modifiers: (MV_COV_MATCH, 0) is what launch_obs_cov sends to match_cov_kernel
 extern "C" int mv_match_cov(const float* depth_map, const float* kp_uv, float* flow_cov, const float* depth_cov,
                             const double* rot, const mvMatchCovParams* params, int N, double* out_cov,
                             double* out_cov_rot, float* out_stats, mvStream_t stream) {
-    MV_CHECK_ARG(params && N >= 0);
-    if (N == 0) return MV_OK;
-    MV_CHECK_ARG(depth_map && kp_uv && flow_cov && out_cov);
-    const mvMatchCovParams p = *params;
-    MV_CHECK_ARG(p.H > 0 && p.W > 0 && p.kernel_size >= 1 && (p.kernel_size & 1));
-    if (p.kernel_size > MAX_K) return MV_ERR_UNSUPPORTED;
-    MV_CHECK_ARG(p.use_patch_var || depth_cov);
-    MV_CHECK_ARG(!out_cov_rot || rot);
-    const CovSet s0{depth_map, kp_uv, flow_cov, depth_cov, rot, out_cov, out_cov_rot, out_stats};
-    mvLaneCounts c{};
-    c.n[0] = N;
-    hipLaunchKernelGGL(match_cov_kernel, dim3(mv_ceil_div(N, 4), 1, 1), dim3(256), 0, (hipStream_t)stream, s0, s0, p, N, c);
-    return mv_launch_status();
+    return mv_obs_cov(MV_COV_MATCH, 0, depth_map, nullptr, kp_uv, flow_cov, depth_cov, rot, params, N, out_cov, out_cov_rot, out_stats, stream);
 }
 
 extern "C" int mv_match_cov_pair_lanes(const float* depth_map0, const float* kp_uv0, float* flow_cov0, const double* rot0,
@@ -108,25 +170,8 @@ extern "C" int mv_match_cov_pair_lanes(const float* depth_map0, const float* kp_
                                        const float* kp_uv1, float* flow_cov1, double* out_cov1,
                                        const mvMatchCovParams* params, int lanes, const int32_t* n_live, int cap,
                                        mvStream_t stream) {
-    MV_CHECK_ARG(params && lanes >= 1 && lanes <= MV_MAX_LANES && n_live && cap >= 0);
-    mvLaneCounts c{};
-    int n_max = 0;
-    for (int l = 0; l < lanes; ++l) {
-        MV_CHECK_ARG(n_live[l] >= 0 && n_live[l] <= cap);
-        c.n[l] = n_live[l];
-        n_max = n_live[l] > n_max ? n_live[l] : n_max;
-    }
-    if (n_max == 0) return MV_OK;
-    MV_CHECK_ARG(depth_map0 && kp_uv0 && flow_cov0 && out_cov0 && depth_map1 && kp_uv1 && flow_cov1 && out_cov1);
-    const mvMatchCovParams p = *params;
-    MV_CHECK_ARG(p.H > 0 && p.W > 0 && p.kernel_size >= 1 && (p.kernel_size & 1) && p.use_patch_var);
-    if (p.kernel_size > MAX_K) return MV_ERR_UNSUPPORTED;
-    MV_CHECK_ARG(!out_cov_rot0 || rot0);
-    const CovSet s0{depth_map0, kp_uv0, flow_cov0, nullptr, rot0, out_cov0, out_cov_rot0, nullptr};
-    const CovSet s1{depth_map1, kp_uv1, flow_cov1, nullptr, nullptr, out_cov1, nullptr, nullptr};
-    hipLaunchKernelGGL(match_cov_kernel, dim3(mv_ceil_div(n_max, 4), 2, lanes), dim3(256), 0, (hipStream_t)stream, s0, s1, p,
-                       cap, c);
-    return mv_launch_status();
+    return mv_obs_cov_pair_lanes(MV_COV_MATCH, 0, depth_map0, nullptr, kp_uv0, flow_cov0, rot0, out_cov0, out_cov_rot0, depth_map1, nullptr, kp_uv1,
+                                 flow_cov1, out_cov1, params, lanes, n_live, cap, stream);
 }
 
 extern "C" int mv_match_cov_pair(const float* depth_map0, const float* kp_uv0, float* flow_cov0, const double* rot0,
@@ -139,80 +184,3 @@ extern "C" int mv_match_cov_pair(const float* depth_map0, const float* kp_uv0, f
                                    out_cov1, params, 1, &n, N, stream);
 }
 
-extern "C" int mv_obs_cov(int model, int32_t modifiers, const float* depth_map, const float* depth_cov_map, const float* kp_uv, float* flow_cov,
-                          const float* depth_cov, const double* rot, const mvMatchCovParams* params, int N, double* out_cov, double* out_cov_rot,
-                          float* out_stats, mvStream_t stream) {
-    MV_CHECK_ARG(params && N >= 0 && model >= MV_COV_MATCH && model <= MV_COV_NONE && mv_cov_modifiers_ok(modifiers));
-    if (N == 0) return MV_OK;
-    MV_CHECK_ARG(depth_map && kp_uv && flow_cov && out_cov);
-    const mvMatchCovParams p = *params;
-    MV_CHECK_ARG(p.H > 0 && p.W > 0 && p.kernel_size >= 1 && (p.kernel_size & 1));
-    if (p.kernel_size > MAX_K) return MV_ERR_UNSUPPORTED;
-    MV_CHECK_ARG(p.use_patch_var || depth_cov);
-    MV_CHECK_ARG(model != MV_COV_GMM || depth_cov_map);
-    MV_CHECK_ARG(!out_cov_rot || rot);
-    const CovSet s0{depth_map, kp_uv, flow_cov, depth_cov, rot, out_cov, out_cov_rot, out_stats};
-    mvLaneCounts c{};
-    c.n[0] = N;
-    return launch_obs_cov(model, modifiers, dim3(mv_ceil_div(N, 4), 1, 1), (hipStream_t)stream, s0, s0, p, N, c, depth_cov_map, depth_cov_map);
-}
-
-extern "C" int mv_obs_cov_pair_lanes(int model, int32_t modifiers, const float* depth_map0, const float* depth_cov_map0, const float* kp_uv0,
-                                     float* flow_cov0, const double* rot0, double* out_cov0, double* out_cov_rot0, const float* depth_map1,
-                                     const float* depth_cov_map1, const float* kp_uv1, float* flow_cov1, double* out_cov1,
-                                     const mvMatchCovParams* params, int lanes, const int32_t* n_live, int cap, mvStream_t stream) {
-    MV_CHECK_ARG(model >= MV_COV_MATCH && model <= MV_COV_NONE && mv_cov_modifiers_ok(modifiers));
-    MV_CHECK_ARG(params && lanes >= 1 && lanes <= MV_MAX_LANES && n_live && cap >= 0);
-    mvLaneCounts c{};
-    int n_max = 0;
-    for (int l = 0; l < lanes; ++l) {
-        MV_CHECK_ARG(n_live[l] >= 0 && n_live[l] <= cap);
-        c.n[l] = n_live[l];
-        n_max = n_live[l] > n_max ? n_live[l] : n_max;
-    }
-    if (n_max == 0) return MV_OK;
-    MV_CHECK_ARG(depth_map0 && kp_uv0 && flow_cov0 && out_cov0 && depth_map1 && kp_uv1 && flow_cov1 && out_cov1);
-    MV_CHECK_ARG(model != MV_COV_GMM || (depth_cov_map0 && depth_cov_map1));
-    const mvMatchCovParams p = *params;
-    MV_CHECK_ARG(p.H > 0 && p.W > 0 && p.kernel_size >= 1 && (p.kernel_size & 1) && p.use_patch_var);
-    if (p.kernel_size > MAX_K) return MV_ERR_UNSUPPORTED;
-    MV_CHECK_ARG(!out_cov_rot0 || rot0);
-    const CovSet s0{depth_map0, kp_uv0, flow_cov0, nullptr, rot0, out_cov0, out_cov_rot0, nullptr};
-    const CovSet s1{depth_map1, kp_uv1, flow_cov1, nullptr, nullptr, out_cov1, nullptr, nullptr};
-    return launch_obs_cov(model, modifiers, dim3(mv_ceil_div(n_max, 4), 2, lanes), (hipStream_t)stream, s0, s1, p, cap, c, depth_cov_map0,
-                          depth_cov_map1);
-}
-
-extern "C" int mv_obs_cov_pair_nomatch_lanes(int model, int32_t modifiers, const float* depth_map0, const float* depth_cov_map0, const float* kp_uv0,
-                                             float* flow_cov0, const double* rot0, double* out_cov0, double* out_cov_rot0, const float* depth_map1,
-                                             const float* depth_cov_map1, const float* kp_uv1, const float* depth_cov1, float model_match_cov_default,
-                                             double* out_cov1, const mvMatchCovParams* params, int lanes, const int32_t* n_live, int cap,
-                                             mvStream_t stream) {
-    MV_CHECK_ARG(model >= MV_COV_MATCH && model <= MV_COV_NONE && mv_cov_modifiers_ok(modifiers));
-    MV_CHECK_ARG(params && lanes >= 1 && lanes <= MV_MAX_LANES && n_live && cap >= 0);
-    mvLaneCounts c{};
-    int n_max = 0;
-    for (int l = 0; l < lanes; ++l) {
-        MV_CHECK_ARG(n_live[l] >= 0 && n_live[l] <= cap);
-        c.n[l] = n_live[l];
-        n_max = n_live[l] > n_max ? n_live[l] : n_max;
-    }
-    if (n_max == 0) return MV_OK;
-    MV_CHECK_ARG(depth_map0 && kp_uv0 && flow_cov0 && out_cov0 && depth_map1 && kp_uv1 && out_cov1);
-    MV_CHECK_ARG(model != MV_COV_GMM || (depth_cov_map0 && depth_cov_map1 && depth_cov1));   // the mixture model needs the depth model's variance
-    const mvMatchCovParams p = *params;
-    MV_CHECK_ARG(p.H > 0 && p.W > 0 && p.kernel_size >= 1 && (p.kernel_size & 1) && p.use_patch_var);
-    if (p.kernel_size > MAX_K) return MV_ERR_UNSUPPORTED;
-    MV_CHECK_ARG(!out_cov_rot0 || rot0);
-    const CovSet s0{depth_map0, kp_uv0, flow_cov0, nullptr, rot0, out_cov0, out_cov_rot0, nullptr};
-    const CovSet s1{depth_map1, kp_uv1, nullptr, depth_cov1, nullptr, out_cov1, nullptr, nullptr};
-    const dim3 grid(mv_ceil_div(n_max, 4), 2, lanes);
-    const bool m = modifiers != 0;
-    if (model == MV_COV_MATCH)
-        launch_nomatch<MV_COV_MATCH>(m, grid, (hipStream_t)stream, s0, s1, p, cap, c, modifiers, depth_cov_map0, depth_cov_map1, model_match_cov_default);
-    else if (model == MV_COV_GMM)
-        launch_nomatch<MV_COV_GMM>(m, grid, (hipStream_t)stream, s0, s1, p, cap, c, modifiers, depth_cov_map0, depth_cov_map1, model_match_cov_default);
-    else
-        launch_nomatch<MV_COV_NONE>(m, grid, (hipStream_t)stream, s0, s1, p, cap, c, modifiers, depth_cov_map0, depth_cov_map1, model_match_cov_default);
-    return mv_launch_status();
-}

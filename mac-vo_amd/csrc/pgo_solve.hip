@@ -652,7 +652,7 @@ extern "C" void mv_lm_default_params(mvLMParams* p) {
 }
 
 // One pgo_solve_kernel launch.  d.pos_Tc given (mv_posed_solve): the pose-dependent remainder of the backend is the launch's prologue.
-static int pgo_solve_impl(const mvPosedSolve& d, mvStream_t stream) {
+int mv_plain_solve(const mvPosedSolve& d, mvStream_t stream) {
     const int nprob = d.nprob;
     const mvLMParams* params = d.params;
     MV_CHECK_ARG(nprob >= 0 && params);
@@ -726,19 +726,30 @@ static int pgo_solve_impl(const mvPosedSolve& d, mvStream_t stream) {
     return mv_launch_status();
 }
 
-extern "C" int mv_pgo_solve(int nprob, const int32_t* offsets, int graph_type, const float* init_pose,
-                            const float* intrinsics, const float* baseline, const float* pos_Tw, const double* cov_Tw,
-                            const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp,
-                            const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
-                            const uint8_t* valid, int min_points, const mvLMParams* params, double* out_pose,
-                            double* out_info, float* out_pose_f32, mvStream_t stream) {
+// mv_pgo_solve's arguments as a descriptor: no prologue (pos_Tc null, no filters), the world-frame tables and `valid` are inputs
+static mvPosedSolve plain_solve_desc(int nprob, const int32_t* offsets, int graph_type, const float* init_pose, const float* intrinsics,
+                                     const float* baseline, const float* pos_Tw, const double* cov_Tw, const float* pixel2_uv, const float* pixel2_d,
+                                     const float* pixel2_disp, const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
+                                     const uint8_t* valid, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
+                                     float* out_pose_f32) {
     mvPosedSolve d{};
     d.nprob = nprob; d.offsets = offsets; d.graph_type = graph_type; d.init_pose = init_pose; d.intrinsics = intrinsics; d.baseline = baseline;
     d.pos_Tw = const_cast<float*>(pos_Tw); d.cov_Tw = const_cast<double*>(cov_Tw);   // (read only without pos_Tc)
     d.pixel2_uv = pixel2_uv; d.pixel2_d = pixel2_d; d.pixel2_disp = pixel2_disp; d.pixel2_disp_cov = pixel2_disp_cov; d.pixel2_uv_cov = pixel2_uv_cov;
     d.obs2_covTc = obs2_covTc; d.filter_flags = -1; d.valid = const_cast<uint8_t*>(valid); d.min_points = min_points; d.params = params;
     d.out_pose = out_pose; d.out_info = out_info; d.out_pose_f32 = out_pose_f32;
-    return pgo_solve_impl(d, stream);
+    return d;
+}
+
+extern "C" int mv_pgo_solve(int nprob, const int32_t* offsets, int graph_type, const float* init_pose,
+                            const float* intrinsics, const float* baseline, const float* pos_Tw, const double* cov_Tw,
+                            const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp,
+                            const float* pixel2_disp_cov, const float* pixel2_uv_cov, const double* obs2_covTc,
+                            const uint8_t* valid, int min_points, const mvLMParams* params, double* out_pose,
+                            double* out_info, float* out_pose_f32, mvStream_t stream) {
+    return mv_plain_solve(plain_solve_desc(nprob, offsets, graph_type, init_pose, intrinsics, baseline, pos_Tw, cov_Tw, pixel2_uv, pixel2_d, pixel2_disp,
+                                           pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, params, out_pose, out_info, out_pose_f32),
+                          stream);
 }
 
 // The posed solve: filters + rotation into the world frame with init_pose (the previous pose) + LM solve.  Live rows of problem l: n_live[l] (host) or —
@@ -748,8 +759,32 @@ extern "C" int mv_pgo_solve(int nprob, const int32_t* offsets, int graph_type, c
 int mv_posed_solve(const mvPosedSolve& d, mvStream_t stream) {
     MV_CHECK_ARG(d.pos_Tc && d.pos_Tw && (d.n_live || (d.n_live_dev && d.n_live_stride >= 1)) && (!d.cov_Tc || d.cov_Tw));
     MV_CHECK_ARG(d.nprob < 512);   // (the 256-thread solve variant: the filter body is written for it)
-    return pgo_solve_impl(d, stream);
+    return mv_plain_solve(d, stream);
 }
+
+// What the six mv_pgo_solve_posed* share, as a descriptor; each of them adds its poses (start_pose, ref_pose) and where the live-row counts are
+static mvPosedSolve posed_solve_desc(int nprob, const int32_t* offsets, int cap, int graph_type, const float* init_pose, const float* intrinsics,
+                                     const float* baseline, const float* pos_Tc, const double* cov_Tc, float* pos_Tw, double* cov_Tw, double* out_rot,
+                                     const float* pixel2_uv, const float* pixel2_d, const float* pixel2_disp, const float* pixel2_disp_cov,
+                                     const float* pixel2_uv_cov, const double* obs2_covTc, int filter_flags, float filter_min_depth,
+                                     float filter_max_depth, const uint8_t* inbound, const float* vals, uint8_t* valid, int32_t* count_out,
+                                     int min_points, const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32,
+                                     float* pose_sink) {
+    mvPosedSolve d{};
+    d.nprob = nprob; d.offsets = offsets; d.cap = cap; d.graph_type = graph_type; d.init_pose = init_pose; d.intrinsics = intrinsics; d.baseline = baseline;
+    d.pos_Tc = pos_Tc; d.cov_Tc = cov_Tc; d.pos_Tw = pos_Tw; d.cov_Tw = cov_Tw; d.out_rot = out_rot;
+    d.pixel2_uv = pixel2_uv; d.pixel2_d = pixel2_d; d.pixel2_disp = pixel2_disp; d.pixel2_disp_cov = pixel2_disp_cov; d.pixel2_uv_cov = pixel2_uv_cov;
+    d.obs2_covTc = obs2_covTc;
+    d.filter_flags = filter_flags; d.filter_min_depth = filter_min_depth; d.filter_max_depth = filter_max_depth; d.inbound = inbound; d.vals = vals;
+    d.valid = valid; d.count_out = count_out; d.min_points = min_points; d.params = params;
+    d.out_pose = out_pose; d.out_info = out_info; d.out_pose_f32 = out_pose_f32; d.pose_sink = pose_sink;
+    return d;
+}
+// (the arguments of posed_solve_desc under the names every mv_pgo_solve_posed* gives them)
+#define MV_POSED_COMMON                                                                                                                                    \
+    nprob, offsets, cap, graph_type, init_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot, pixel2_uv, pixel2_d, pixel2_disp,          \
+        pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params, \
+        out_pose, out_info, out_pose_f32, pose_sink
 
 extern "C" int mv_pgo_solve_posed(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type,
                                   const float* init_pose, const float* intrinsics, const float* baseline, const float* pos_Tc, const double* cov_Tc,
@@ -758,10 +793,9 @@ extern "C" int mv_pgo_solve_posed(int nprob, const int32_t* offsets, const int32
                                   int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
                                   uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
                                   float* out_pose_f32, float* pose_sink, mvStream_t stream) {
-    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, nullptr, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
-                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, n_live, nullptr, 0,
-                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
-                           out_pose, out_info, out_pose_f32, pose_sink}, stream);
+    mvPosedSolve d = posed_solve_desc(MV_POSED_COMMON);
+    d.n_live = n_live;
+    return mv_posed_solve(d, stream);
 }
 
 extern "C" int mv_pgo_solve_posed_dev(int nprob, const int32_t* offsets, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
@@ -771,10 +805,9 @@ extern "C" int mv_pgo_solve_posed_dev(int nprob, const int32_t* offsets, const i
                                       int filter_flags, float filter_min_depth, float filter_max_depth, const uint8_t* inbound, const float* vals,
                                       uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
                                       float* out_pose_f32, float* pose_sink, mvStream_t stream) {
-    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, nullptr, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
-                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, nullptr, n_live_dev, n_live_stride,
-                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
-                           out_pose, out_info, out_pose_f32, pose_sink}, stream);
+    mvPosedSolve d = posed_solve_desc(MV_POSED_COMMON);
+    d.n_live_dev = n_live_dev; d.n_live_stride = n_live_stride;
+    return mv_posed_solve(d, stream);
 }
 
 extern "C" int mv_pgo_solve_posed_motion(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type,
@@ -785,10 +818,9 @@ extern "C" int mv_pgo_solve_posed_motion(int nprob, const int32_t* offsets, cons
                                          uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
                                          float* out_pose_f32, float* pose_sink, mvStream_t stream) {
     MV_CHECK_ARG(n_live && start_pose);
-    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
-                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, n_live, nullptr, 0,
-                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
-                           out_pose, out_info, out_pose_f32, pose_sink}, stream);
+    mvPosedSolve d = posed_solve_desc(MV_POSED_COMMON);
+    d.start_pose = start_pose; d.n_live = n_live;
+    return mv_posed_solve(d, stream);
 }
 
 extern "C" int mv_pgo_solve_posed_motion_dev(int nprob, const int32_t* offsets, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
@@ -799,10 +831,9 @@ extern "C" int mv_pgo_solve_posed_motion_dev(int nprob, const int32_t* offsets, 
                                              uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose, double* out_info,
                                              float* out_pose_f32, float* pose_sink, mvStream_t stream) {
     MV_CHECK_ARG(n_live_dev && start_pose);
-    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
-                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, nullptr, n_live_dev, n_live_stride,
-                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
-                           out_pose, out_info, out_pose_f32, pose_sink}, stream);
+    mvPosedSolve d = posed_solve_desc(MV_POSED_COMMON);
+    d.start_pose = start_pose; d.n_live_dev = n_live_dev; d.n_live_stride = n_live_stride;
+    return mv_posed_solve(d, stream);
 }
 
 // The local-frame forms (Local_TwoFrame_PGO, Module/Optimization/TwoFramePGO/Optimizer.py:111-150): the same launches with ref_pose [nprob, 7] (T_o2w) —
@@ -814,13 +845,10 @@ extern "C" int mv_pgo_solve_local(int nprob, const int32_t* offsets, int graph_t
                                   const uint8_t* valid, int min_points, const mvLMParams* params, double* out_pose,
                                   double* out_info, float* out_pose_f32, mvStream_t stream) {
     MV_CHECK_ARG(ref_pose);
-    mvPosedSolve d{};
-    d.nprob = nprob; d.offsets = offsets; d.graph_type = graph_type; d.init_pose = init_pose; d.intrinsics = intrinsics; d.baseline = baseline;
-    d.pos_Tw = const_cast<float*>(pos_Tw); d.cov_Tw = const_cast<double*>(cov_Tw);   // (read only without pos_Tc)
-    d.pixel2_uv = pixel2_uv; d.pixel2_d = pixel2_d; d.pixel2_disp = pixel2_disp; d.pixel2_disp_cov = pixel2_disp_cov; d.pixel2_uv_cov = pixel2_uv_cov;
-    d.obs2_covTc = obs2_covTc; d.filter_flags = -1; d.valid = const_cast<uint8_t*>(valid); d.min_points = min_points; d.params = params;
-    d.out_pose = out_pose; d.out_info = out_info; d.out_pose_f32 = out_pose_f32; d.ref_pose = ref_pose;
-    return pgo_solve_impl(d, stream);
+    mvPosedSolve d = plain_solve_desc(nprob, offsets, graph_type, init_pose, intrinsics, baseline, pos_Tw, cov_Tw, pixel2_uv, pixel2_d, pixel2_disp,
+                                      pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, valid, min_points, params, out_pose, out_info, out_pose_f32);
+    d.ref_pose = ref_pose;
+    return mv_plain_solve(d, stream);
 }
 
 extern "C" int mv_pgo_solve_posed_local(int nprob, const int32_t* offsets, const int32_t* n_live, int cap, int graph_type,
@@ -831,10 +859,9 @@ extern "C" int mv_pgo_solve_posed_local(int nprob, const int32_t* offsets, const
                                         const float* vals, uint8_t* valid, int32_t* count_out, int min_points, const mvLMParams* params, double* out_pose,
                                         double* out_info, float* out_pose_f32, float* pose_sink, mvStream_t stream) {
     MV_CHECK_ARG(n_live && ref_pose);
-    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
-                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, n_live, nullptr, 0,
-                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
-                           out_pose, out_info, out_pose_f32, pose_sink, ref_pose}, stream);
+    mvPosedSolve d = posed_solve_desc(MV_POSED_COMMON);
+    d.start_pose = start_pose; d.ref_pose = ref_pose; d.n_live = n_live;
+    return mv_posed_solve(d, stream);
 }
 
 extern "C" int mv_pgo_solve_posed_local_dev(int nprob, const int32_t* offsets, const int32_t* n_live_dev, int n_live_stride, int cap, int graph_type,
@@ -846,8 +873,9 @@ extern "C" int mv_pgo_solve_posed_local_dev(int nprob, const int32_t* offsets, c
                                             int min_points, const mvLMParams* params, double* out_pose, double* out_info, float* out_pose_f32,
                                             float* pose_sink, mvStream_t stream) {
     MV_CHECK_ARG(n_live_dev && ref_pose);
-    return mv_posed_solve({nprob, offsets, cap, graph_type, init_pose, start_pose, intrinsics, baseline, pos_Tc, cov_Tc, pos_Tw, cov_Tw, out_rot,
-                           pixel2_uv, pixel2_d, pixel2_disp, pixel2_disp_cov, pixel2_uv_cov, obs2_covTc, nullptr, n_live_dev, n_live_stride,
-                           filter_flags, filter_min_depth, filter_max_depth, inbound, vals, valid, count_out, min_points, params,
-                           out_pose, out_info, out_pose_f32, pose_sink, ref_pose}, stream);
+    mvPosedSolve d = posed_solve_desc(MV_POSED_COMMON);
+    d.start_pose = start_pose; d.ref_pose = ref_pose; d.n_live_dev = n_live_dev; d.n_live_stride = n_live_stride;
+    return mv_posed_solve(d, stream);
 }
+#undef MV_POSED_COMMON
+

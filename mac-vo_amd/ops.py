@@ -696,31 +696,8 @@ def match_cov(depth_map: torch.Tensor, kp_uv: torch.Tensor, flow_cov: torch.Tens
     """MAC-VO covariance model (Project2to3.py:124-181,377-433; Math.py:43-63).  ``flow_cov [N,3]`` is clamped IN
     PLACE like the reference.  Returns ``cov [N,3,3] float64`` (GPU) and, if ``rot [3,3] float64`` is given,
     ``R cov R^T`` (MACVO.py:273-281)."""
-    lib = L.load()
-    depth_map = _req(depth_map, torch.float32, "depth_map")
-    H, W = depth_map.shape[-2:]
-    if kp_uv.dtype != torch.float32:
-        kp_uv = kp_uv.to(torch.float32)
-    kp_uv = _req(kp_uv, torch.float32, "kp_uv")
-    if flow_cov.dtype != torch.float32 or not flow_cov.is_contiguous() or not flow_cov.is_cuda:
-        raise L.MacvoHipError("match_cov: flow_cov must be a contiguous float32 GPU tensor (it is clamped in place)")
-    N = kp_uv.shape[0]
-    dev = depth_map.device
-    dc = None if depth_cov is None else _req(depth_cov, torch.float32, "depth_cov")
-    r = None if rot is None else _req(rot.to(dev), torch.float64, "rot")
-    out = torch.empty((N, 3, 3), dtype=torch.float64, device=dev)
-    out_rot = torch.empty((N, 3, 3), dtype=torch.float64, device=dev) if r is not None else None
-    stats = torch.empty((N, 2), dtype=torch.float32, device=dev) if want_stats else None
-    p = L.mvMatchCovParams(H, W, kernel_size, int(use_patch_var or dc is None), fx, fy, cx, cy, min_flow_cov ** 2,
-                           min_depth_cov)
-    L.check(lib.mv_match_cov(depth_map.data_ptr(), kp_uv.data_ptr(), flow_cov.data_ptr(), _ptr(dc), _ptr(r),
-                             C.byref(p), N, out.data_ptr(), _ptr(out_rot), _ptr(stats), _stream()), "mv_match_cov")
-    res = (out,)
-    if out_rot is not None:
-        res += (out_rot,)
-    if want_stats:
-        res += (stats,)
-    return res[0] if len(res) == 1 else res
+    return obs_cov("match", depth_map, kp_uv, flow_cov, depth_cov, fx, fy, cx, cy, None, (), kernel_size, min_flow_cov, min_depth_cov, use_patch_var,
+                   rot, want_stats)
 
 
 def match_cov_pair(depth0: torch.Tensor, kp0_uv: torch.Tensor, sigma0: torch.Tensor, depth1: torch.Tensor,
@@ -728,24 +705,8 @@ def match_cov_pair(depth0: torch.Tensor, kp0_uv: torch.Tensor, sigma0: torch.Ten
                    rot: torch.Tensor | None = None, kernel_size: int = 31, min_flow_cov: float = 0.25,
                    min_depth_cov: float = 0.05):
     """Both covariance-model calls of a frame (MACVO.py:241-242) in one launch -> (cov0, cov0_world | None, cov1)."""
-    lib = L.load()
-    d0, d1 = _req(depth0, torch.float32, "depth0"), _req(depth1, torch.float32, "depth1")
-    H, W = d0.shape[-2:]
-    k0, k1 = _req(kp0_uv, torch.float32, "kp0_uv"), _req(kp1_uv, torch.float32, "kp1_uv")
-    for t_, nm in ((sigma0, "sigma0"), (sigma1, "sigma1")):
-        if t_.dtype != torch.float32 or not t_.is_contiguous() or not t_.is_cuda:
-            raise L.MacvoHipError(f"match_cov_pair: {nm} must be a contiguous float32 GPU tensor (clamped in place)")
-    N, dev = k0.shape[0], d0.device
-    assert k1.shape[0] == N
-    r = None if rot is None else _req(rot.to(dev), torch.float64, "rot")
-    c0 = torch.empty((N, 3, 3), dtype=torch.float64, device=dev)
-    c1 = torch.empty((N, 3, 3), dtype=torch.float64, device=dev)
-    c0w = torch.empty((N, 3, 3), dtype=torch.float64, device=dev) if r is not None else None
-    p = L.mvMatchCovParams(H, W, kernel_size, 1, fx, fy, cx, cy, min_flow_cov ** 2, min_depth_cov)
-    L.check(lib.mv_match_cov_pair(d0.data_ptr(), k0.data_ptr(), sigma0.data_ptr(), _ptr(r), c0.data_ptr(), _ptr(c0w),
-                                  d1.data_ptr(), k1.data_ptr(), sigma1.data_ptr(), c1.data_ptr(), C.byref(p), N, _stream()),
-            "mv_match_cov_pair")
-    return c0, c0w, c1
+    return obs_cov_pair("match", depth0, kp0_uv, sigma0, depth1, kp1_uv, sigma1, fx, fy, cx, cy, None, None, (), rot, kernel_size, min_flow_cov,
+                        min_depth_cov)
 
 
 COV_MODELS = {"match": L.MV_COV_MATCH, "gmm": L.MV_COV_GMM, "none": L.MV_COV_NONE}
@@ -755,6 +716,8 @@ COV_MODIFIERS = {"diag": L.MV_COVMOD_DIAG, "normalize": L.MV_COVMOD_NORMALIZE}
 def cov_modifier_chain(modifiers) -> int:
     """``("diag", "normalize", ...)`` (innermost first, at most 4) -> the packed int32 chain of ``mv_obs_cov``."""
     mods = tuple(modifiers)
+    if not mods:   # (the common case, on the per-frame path of HotPath)
+        return 0
     if len(mods) > 4:
         raise ValueError(f"at most 4 covariance modifiers, got {mods}")
     chain = 0
@@ -983,11 +946,8 @@ def map_points(uv: torch.Tensor, depth: torch.Tensor, depth_cov: torch.Tensor, K
                               *[float(k) for k in K4], pose_c.data_ptr(), float(match_cov_default), uvf.data_ptr(),
                               d.data_ptr(), sdd.data_ptr(), sig.data_ptr(), Tc.data_ptr(), Tw.data_ptr(), _ptr(col), _stream()),
             "mv_map_points")
-    if cov_model == "match" and not tuple(cov_modifiers):
-        cov = match_cov(depth, uvf, sig, sdd, *K4, kernel_size=kernel_size, min_flow_cov=min_flow_cov, min_depth_cov=min_depth_cov)
-    else:
-        cov = obs_cov(cov_model, depth, uvf, sig, sdd, *K4, depth_cov_map=depth_cov, modifiers=cov_modifiers, kernel_size=kernel_size,
-                      min_flow_cov=min_flow_cov, min_depth_cov=min_depth_cov)
+    cov = obs_cov(cov_model, depth, uvf, sig, sdd, *K4, depth_cov_map=depth_cov, modifiers=cov_modifiers, kernel_size=kernel_size,
+                  min_flow_cov=min_flow_cov, min_depth_cov=min_depth_cov)
     return MapPoints(uvf, d, sdd, Tc, Tw, cov, col)
 
 

@@ -831,23 +831,15 @@ class HotPath:
 
             tr = ops.kp_track(kp0, maps1.flow, maps1.flow_cov, maps0, maps1, c.edgewidth, c.match_cov_default)
             pos0_Tc, pos_Tw, rot = ops.backproject(tr.kp0_uv, tr.vals[0], cam.K4, prev_pose, want_rot=True)
-            if not self._fcov[1]:
-                # the matcher gives no covariance: tr.sigma1 holds the -1 placeholders, the second call is the model with flow_cov=None
-                cov0, cov0_w, cov1 = ops.obs_cov_pair(c.cov_model, maps0.depth, tr.kp0_uv, tr.sigma0, maps1.depth, tr.kp1_uv, None,
-                                                      *cam.K4, depth_cov_map0=maps0.depth_cov, depth_cov_map1=maps1.depth_cov,
-                                                      modifiers=c.cov_modifiers, rot=rot, kernel_size=c.cov_kernel_size,
-                                                      min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov, no_match_cov=True,
-                                                      match_cov_default=c.cov_match_cov_default,
-                                                      depth_cov1=tr.vals[7] if self._fcov[0] else None)
-            elif c.cov_model == "match" and not tuple(c.cov_modifiers):
-                cov0, cov0_w, cov1 = ops.match_cov_pair(maps0.depth, tr.kp0_uv, tr.sigma0, maps1.depth, tr.kp1_uv, tr.sigma1,
-                                                        *cam.K4, rot=rot, kernel_size=c.cov_kernel_size,
-                                                        min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov)
-            else:
-                cov0, cov0_w, cov1 = ops.obs_cov_pair(c.cov_model, maps0.depth, tr.kp0_uv, tr.sigma0, maps1.depth, tr.kp1_uv, tr.sigma1,
-                                                      *cam.K4, depth_cov_map0=maps0.depth_cov, depth_cov_map1=maps1.depth_cov,
-                                                      modifiers=c.cov_modifiers, rot=rot, kernel_size=c.cov_kernel_size,
-                                                      min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov)
+            # a matcher that gives no covariance: tr.sigma1 holds the -1 placeholders, the second call is the model with flow_cov=None
+            no_match_cov = not self._fcov[1]
+            cov0, cov0_w, cov1 = ops.obs_cov_pair(c.cov_model, maps0.depth, tr.kp0_uv, tr.sigma0, maps1.depth, tr.kp1_uv,
+                                                  None if no_match_cov else tr.sigma1, *cam.K4,
+                                                  depth_cov_map0=maps0.depth_cov, depth_cov_map1=maps1.depth_cov,
+                                                  modifiers=c.cov_modifiers, rot=rot, kernel_size=c.cov_kernel_size,
+                                                  min_flow_cov=c.min_flow_cov, min_depth_cov=c.min_depth_cov, no_match_cov=no_match_cov,
+                                                  match_cov_default=c.cov_match_cov_default,
+                                                  depth_cov1=tr.vals[7] if no_match_cov and self._fcov[0] else None)
             valid, n_valid = ops.obs_filter(tr.inbound, cov0, cov1, tr.vals, c.filters, c.filter_min_depth, self._max_depth)
             if motion_ev is not None:
                 prior = compose()

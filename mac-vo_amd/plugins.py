@@ -204,7 +204,7 @@ def _obs_cov_device(model: str, config, frame, kp, depth_est, depth_cov, flow_co
         assert depth_est.cov is not None
     none = model == "none"
     res = ops.obs_cov(model, depth_est.depth.to(dev), kp.to(dev), work, None if depth_cov is None else depth_cov.to(dev),
-                      frame.fx, frame.fy, frame.cx, frame.cy, depth_cov_map=None if depth_est.cov is None else depth_est.cov.to(dev),
+                      frame.fx, frame.fy, frame.cx, frame.cy, depth_cov_map=depth_est.cov.to(dev) if model == "gmm" else None,   # (only the mixture reads it)
                       modifiers=modifiers, kernel_size=31 if none else config.kernel_size,
                       min_flow_cov=config.min_flow_cov if (has_flow_cov and not none) else 0.0,
                       min_depth_cov=0.05 if none else config.min_depth_cov, use_patch_var=(has_flow_cov or depth_cov is None), rot=rot)
@@ -223,23 +223,7 @@ class HIP_MatchCovariance(ICovariance2to3):
 
     def estimate_device(self, frame, kp, depth_est, depth_cov, flow_cov, rot: torch.Tensor | None = None):
         """Same as :meth:`estimate` but the result stays on the GPU (optionally also ``R cov R^T``)."""
-        dev = torch.device(self.config.device)
-        n = kp.size(0)
-        has_flow_cov = flow_cov is not None
-        if has_flow_cov:
-            work = flow_cov if (flow_cov.is_cuda and flow_cov.dtype == torch.float32 and flow_cov.is_contiguous()) \
-                else flow_cov.to(dev, torch.float32).contiguous()
-        else:
-            work = torch.full((n, 3), float(self.config.match_cov_default), dtype=torch.float32, device=dev)
-            work[:, 2] = 0.0
-        res = ops.match_cov(depth_est.depth.to(dev), kp.to(dev), work, None if depth_cov is None else depth_cov.to(dev),
-                            frame.fx, frame.fy, frame.cx, frame.cy, kernel_size=self.config.kernel_size,
-                            min_flow_cov=self.config.min_flow_cov if has_flow_cov else 0.0,   # clamp only a GIVEN flow_cov (Project2to3.py:128-135)
-                            min_depth_cov=self.config.min_depth_cov,
-                            use_patch_var=(has_flow_cov or depth_cov is None), rot=rot)
-        if has_flow_cov and work is not flow_cov:
-            flow_cov.copy_(work)                                                   # keep the in-place side effect
-        return res
+        return _obs_cov_device("match", self.config, frame, kp, depth_est, depth_cov, flow_cov, rot)
 
     @classmethod
     def is_valid_config(cls, config: SimpleNamespace | None) -> None:
