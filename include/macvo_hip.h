@@ -278,12 +278,24 @@ size_t mv_kp_select_workspace_bytes(int H, int W);
  *   out_cand   [H*W] int32: linear indices v*W + u of the surviving pixels in row-major order
  *   out_count  [4] int32: {n_candidates, n_nms, 0, 0}
  *   out_stats  [4] fp32: {median_flow_q, thresh_flow_q, median_depth0_cov, thresh_depth0_cov}
+ *
+ * The second launch (medians, thresholds, compaction) keeps everything in registers and LDS while the NMS pixels ("records") and
+ * the 64-pixel candidate words H * ceil(W / 64) both fit mv_kp_select_finish_capacity(H, W); past either limit the same steps run
+ * against global memory — same results, several times slower.  Inputs that leave the in-register form: kernel_size 1 (every
+ * non-NaN pixel is a record) from 128 x 128 up, noisy maps with kernel_size 3 from about 360 x 480 and with 5 at 720p, and any
+ * image of more than 15 360 candidate words (taller than 768 rows at width 1280), whatever the window.
  */
 int mv_kp_select(const float* flow_cov, const float* depth0, const float* depth0_cov,
                  const float* depth1, const float* depth1_cov, const uint8_t* mask_a,
                  const uint8_t* mask_b, const mvKpSelectParams* params /* host */, void* workspace,
                  size_t workspace_bytes, int32_t* out_cand, int32_t* out_count, float* out_stats,
                  mvStream_t stream);
+
+/* Host only, launches nothing: what the in-register form of mv_kp_select's second launch holds for an H x W image in this
+ * process — *max_records NMS pixels and *max_words candidate words (H * ceil(W / 64)) — for the variant the library would launch
+ * (by the word count, and MV_KP_FINISH_SMALL_NT=512 in the environment, read once).  A call within both runs in registers, any
+ * other against global memory; the results are the same.  MV_ERR_INVALID_ARG for non-positive sizes or null pointers. */
+int mv_kp_select_finish_capacity(int H, int W, int32_t* max_records, int32_t* max_words);
 
 /* selected[perm][..., 2:].roll(1, 1)  (KeypointSelector.py:331-332,404-405):
  *   out_uv[k] = (cand[perm[k]] % W, cand[perm[k]] / W) as int64 (u, v) */

@@ -148,6 +148,7 @@ SIGNATURES = {
     "mv_kp_select_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mv_kp_select": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(mvKpSelectParams), _P, C.c_size_t,
                                _P, _P, _P, _P]),
+    "mv_kp_select_finish_capacity": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mv_kp_gather": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "mv_kp_track": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int,
                               C.c_float, _P, _P, _P, _P, _P, _P, _P]),

@@ -701,6 +701,33 @@ static int launch_finish(const mvKpSelectParams& p, const KpWs& ws, int has_flow
     return MV_OK;
 }
 
+// The three finishing variants: threads, record slots per thread, candidate-word slots per thread.  A launch takes the in-register
+// form while n_rec <= RPT * NT and H * words_per_row <= WPT * NT (mv_kp_select_finish_capacity reports the two products).
+template <int NT_, int RPT_, int WPT_>
+struct FinishShape {
+    static constexpr int NT = NT_, RPT = RPT_, WPT = WPT_;
+};
+using FinishDefault = FinishShape<1024, 16, 5>;    // 640x480-class images
+using FinishSmallNT = FinishShape<512, 16, 10>;    // MV_KP_FINISH_SMALL_NT=512: 8-wave finishing workgroup (fits beside a 3-per-CU GEMM)
+using FinishBig = FinishShape<1024, 24, 15>;       // more candidate words than the two above hold: up to 1280x768
+enum { FIN_DEFAULT = 0, FIN_SMALL_NT = 1, FIN_BIG = 2 };
+
+// the variant kp_select_impl launches for an H x W image in this process (the environment is read once)
+static int finish_variant(int H, int W) {
+    static_assert(FinishSmallNT::WPT * FinishSmallNT::NT == FinishDefault::WPT * FinishDefault::NT, "one word capacity below the big variant");
+    if ((size_t)H * mv_ceil_div(W, 64) > (size_t)FinishDefault::WPT * FinishDefault::NT) return FIN_BIG;
+    static int small_nt = -1;
+    if (small_nt < 0) { const char* e = getenv("MV_KP_FINISH_SMALL_NT"); small_nt = (e && atoi(e) == 512) ? 512 : 1024; }
+    return small_nt == 512 ? FIN_SMALL_NT : FIN_DEFAULT;
+}
+
+template <typename V>
+static int launch_finish_as(bool full, const mvKpSelectParams& p, const KpWs& ws, int has_flow, int wpr, int32_t* out_cand,
+                            int32_t* out_count, float* out_stats, int lanes, hipStream_t s) {
+    return full ? launch_finish<V::NT, V::RPT, V::WPT, true>(p, ws, has_flow, wpr, out_cand, out_count, out_stats, lanes, s)
+                : launch_finish<V::NT, V::RPT, V::WPT, false>(p, ws, has_flow, wpr, out_cand, out_count, out_stats, lanes, s);
+}
+
 // ---- MappingPointSelector: no medians, but typically 10^5 candidates.  The single finishing workgroup would emit ~150
 // indices per thread one after the other (40 us at 640x480, 115 us at 720p); instead: one workgroup scans the per-word
 // popcounts, then one WAVE per 64-pixel word emits its set bits (rank by popcount of the lower bits).
@@ -768,6 +795,19 @@ extern "C" size_t mv_kp_select_workspace_bytes(int H, int W) {
     return align_up(words * 8, 256) + 3 * align_up((size_t)H * W * 4, 256) + 256;
 }
 
+extern "C" int mv_kp_select_finish_capacity(int H, int W, int32_t* max_records, int32_t* max_words) {
+    MV_CHECK_ARG(H > 0 && W > 0 && max_records && max_words);
+    int nt, rpt, wpt;
+    switch (finish_variant(H, W)) {
+    case FIN_BIG: nt = FinishBig::NT; rpt = FinishBig::RPT; wpt = FinishBig::WPT; break;
+    case FIN_SMALL_NT: nt = FinishSmallNT::NT; rpt = FinishSmallNT::RPT; wpt = FinishSmallNT::WPT; break;
+    default: nt = FinishDefault::NT; rpt = FinishDefault::RPT; wpt = FinishDefault::WPT; break;
+    }
+    *max_records = rpt * nt;
+    *max_words = wpt * nt;
+    return MV_OK;
+}
+
 static int kp_select_impl(const float* flow_cov, const float* depth0, const float* depth0_cov, const float* depth1,
                           const float* depth1_cov, const uint8_t* mask_a, const uint8_t* mask_b, const mvKpSelectParams* params,
                           void* workspace, size_t workspace_bytes, int32_t* out_cand, int32_t* out_count, float* out_stats,
@@ -828,18 +868,14 @@ static int kp_select_impl(const float* flow_cov, const float* depth0, const floa
                            wpr, p.W, out_cand);
         return mv_launch_status();
     }
-    const bool big = (size_t)p.H * wpr > 5 * (size_t)1024;
     const bool full = p.mode == MV_KP_FULL;
+    const int has_flow = flow_cov ? 1 : 0;
     int rc;
-    static int small_nt = -1;   // MV_KP_FINISH_SMALL_NT=512: 8-wave finishing workgroup (fits beside a 3-per-CU GEMM)
-    if (small_nt < 0) { const char* e = getenv("MV_KP_FINISH_SMALL_NT"); small_nt = (e && atoi(e) == 512) ? 512 : 1024; }
-    if (big) rc = full ? launch_finish<1024, 24, 15, true>(p, ws, flow_cov ? 1 : 0, wpr, out_cand, out_count, out_stats, lanes, s)
-                       : launch_finish<1024, 24, 15, false>(p, ws, flow_cov ? 1 : 0, wpr, out_cand, out_count, out_stats, lanes, s);
-    else if (small_nt == 512)
-        rc = full ? launch_finish<512, 16, 10, true>(p, ws, flow_cov ? 1 : 0, wpr, out_cand, out_count, out_stats, lanes, s)
-                  : launch_finish<512, 16, 10, false>(p, ws, flow_cov ? 1 : 0, wpr, out_cand, out_count, out_stats, lanes, s);
-    else rc = full ? launch_finish<1024, 16, 5, true>(p, ws, flow_cov ? 1 : 0, wpr, out_cand, out_count, out_stats, lanes, s)
-                   : launch_finish<1024, 16, 5, false>(p, ws, flow_cov ? 1 : 0, wpr, out_cand, out_count, out_stats, lanes, s);
+    switch (finish_variant(p.H, p.W)) {
+    case FIN_BIG: rc = launch_finish_as<FinishBig>(full, p, ws, has_flow, wpr, out_cand, out_count, out_stats, lanes, s); break;
+    case FIN_SMALL_NT: rc = launch_finish_as<FinishSmallNT>(full, p, ws, has_flow, wpr, out_cand, out_count, out_stats, lanes, s); break;
+    default: rc = launch_finish_as<FinishDefault>(full, p, ws, has_flow, wpr, out_cand, out_count, out_stats, lanes, s); break;
+    }
     if (rc != MV_OK) return rc;
     return mv_launch_status();
 }

@@ -384,6 +384,9 @@ def check_selector(cfg: "HotPathConfig", cam: "Camera") -> None:
     if cfg.selector not in SELECTORS:
         raise ValueError(f"selector must be one of {SELECTORS}, not {cfg.selector!r}")
     if cfg.selector not in MAPLESS_SELECTORS:
+        k = cfg.kp_kernel_size
+        if not (isinstance(k, int) and k > 0 and k % 2 == 1 and k <= 15):
+            raise ValueError(f"selector {cfg.selector!r}: kp_kernel_size {k!r} must be odd and within 1..15 (the NMS kernel's halo)")
         return
     m = cfg.kp_mask_width
     if m < 0 or cam.H <= 2 * m or cam.W <= 2 * m:

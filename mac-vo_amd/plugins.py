@@ -61,7 +61,7 @@ class HIP_CovAwareSelector_NoDepth(IKeypointSelector):
         cls._enforce_config_spec(config, {
             "device": _is_device,
             "mask_width": lambda m: isinstance(m, int) and m >= 0,
-            "kernel_size": lambda k: isinstance(k, int) and k > 0 and (k % 2 == 1),
+            "kernel_size": lambda k: isinstance(k, int) and k > 0 and (k % 2 == 1) and k <= 15,   # the NMS kernel's halo
             "max_match_cov": lambda c: _num(c) and c > 0.0,
         })
 
@@ -93,7 +93,7 @@ class HIP_CovAwareSelector(IKeypointSelector):
             "device": _is_device,
             "mask_width": lambda m: isinstance(m, int) and m >= 0,
             "max_depth": lambda d: (d == "auto") or (_num(d) and d > 0.0),
-            "kernel_size": lambda k: isinstance(k, int) and k > 0 and (k % 2 == 1),
+            "kernel_size": lambda k: isinstance(k, int) and k > 0 and (k % 2 == 1) and k <= 15,   # the NMS kernel's halo
             "max_depth_cov": lambda c: _num(c) and c > 0.0,
             "max_match_cov": lambda c: _num(c) and c > 0.0,
         })

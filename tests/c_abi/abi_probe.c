@@ -20,6 +20,11 @@ int main(void) {
     printf("offsetof lm=%zu fx=%zu\n", offsetof(mvFramePipeConfig, lm), offsetof(mvFramePipeConfig, fx));
     printf("lm huber=%.3f steps=%d reject=%d\n", lm.huber_delta, lm.max_steps, lm.reject);
     printf("arena=%zu ws=%zu\n", mv_frame_pipe_arena_bytes(&c), mv_kp_select_workspace_bytes(480, 640));
+    {
+        int32_t rec = 0, words = 0;
+        const int rc = mv_kp_select_finish_capacity(480, 640, &rec, &words);
+        printf("fincap=%d/%d/%d\n", rc, (int)rec, (int)words);
+    }
     printf("err=%s\n", mv_error_string(MV_ERR_UNSUPPORTED));
     printf("MV_FB_POSE=%d MV_BF16X2=%d\n", MV_FB_POSE, MV_BF16X2);
     return 0;

@@ -181,6 +181,39 @@ def test_header_is_plain_c_and_layouts_match_ctypes(tmp_path):
     assert int(kv["offsetof lm"]) == L.mvFramePipeConfig.lm.offset and int(kv["fx"]) == L.mvFramePipeConfig.fx.offset
     assert int(kv["arena"]) > 2 * 4800 * 4800 * 4 * 2 and int(kv["MV_FB_POSE"]) == L.FB["POSE"] and int(kv["MV_BF16X2"]) == L.MV_BF16X2
     assert "steps=10" in out.stdout and "reject=16" in out.stdout and "err=unsupported" in out.stdout
+    a, b = C.c_int32(), C.c_int32()
+    assert L.load().mv_kp_select_finish_capacity(480, 640, C.byref(a), C.byref(b)) == 0
+    assert kv["fincap"] == f"0/{a.value}/{b.value}"                    # the C caller sees what the binding sees
+
+
+def test_selector_finish_capacity_is_host_only_and_checks_its_arguments():
+    """mv_kp_select_finish_capacity launches nothing: the record / candidate-word capacity of the in-register finishing form for the variant the
+    library would launch (whatever MV_KP_FINISH_SMALL_NT says; tests/test_gpu_selector_finish.py runs a child under each of its values).  The
+    variant changes where the image has more candidate words than the smaller one holds, and nowhere else."""
+    import ctypes as C
+
+    from macvo_amd import _lib as L
+
+    lib = L.load()
+
+    def cap(H, W):
+        a, b = C.c_int32(-1), C.c_int32(-1)
+        assert lib.mv_kp_select_finish_capacity(H, W, C.byref(a), C.byref(b)) == L.MV_OK
+        return a.value, b.value
+
+    small = cap(480, 640)
+    rec, words = small
+    assert rec > 0 and words >= 480 * 10                               # the 640x480 frame of the flagship workload runs in registers
+    assert cap(1, 1) == small and cap(words, 64) == small and cap(words // 2, 65) == small   # exactly `words` candidate words: still the small variant
+    big = cap(words + 1, 64)
+    assert big != small and big[0] > rec and big[1] > words and cap(720, 1280) == big and big[1] >= 720 * 20
+    assert cap(100000, 4096) == big                                    # past every capacity: the last variant, whose global-memory form takes over
+    a, b = C.c_int32(7), C.c_int32(7)
+    for H, W in ((0, 64), (64, 0), (-1, 64), (64, -5)):
+        assert lib.mv_kp_select_finish_capacity(H, W, C.byref(a), C.byref(b)) == -1          # MV_ERR_INVALID_ARG
+    assert lib.mv_kp_select_finish_capacity(48, 64, None, C.byref(b)) == -1
+    assert lib.mv_kp_select_finish_capacity(48, 64, C.byref(a), None) == -1
+    assert (a.value, b.value) == (7, 7)                                # a refused call writes nothing
 
 
 def test_bench_gpus_n_launches_itself_and_gathers(tmp_path):

@@ -5,87 +5,14 @@ window sizes of the selectors, a border mask of 0 and one that leaves a strip of
 and NaN / +-inf / very negative values in the tile, in the halo and on the image border.  The number of NMS pixels is checked against max_pool2d on the
 CPU as well, so that the pair does not merely agree with itself.  One FULL and one MAPPING case through the un-fused kernel against the oracle's selectors
 (FULL requests the two depths of its own pixels in front of the LDS phases now)."""
-import ctypes as C
-
 import pytest
 import torch
+
+from tests.selector_cases import inputs_on as _inputs_on, run as _run
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(16, 64), (33, 130), (40, 72), (20, 50), (9, 70)]      # H x W; tiles are 16 x 64
-BL_FX, BL_FX_SQ = 80.0, 6400.0
-
-
-def _inputs(H, W, lanes, cov_is_log):
-    """flow, cov [lanes, 2, 2, H, W] on the CPU.  cov is log-sigma (expf(2 x) in the kernel) or the variance itself."""
-    g = torch.Generator().manual_seed(1000 * H + W)
-    flow = torch.randn(lanes, 2, 2, H, W, generator=g) * 4
-    cov = torch.randn(lanes, 2, 2, H, W, generator=g) * 0.5
-    if not cov_is_log:
-        cov = cov.abs() + 0.01
-    flow[:, 0, 0, 0, 0] = 0.0                                      # disparity 0: depth = inf, depth_cov = NaN (0 / 0 after the squares)
-    flow[:, 0, 0, H - 1, W - 1] = -0.0
-    flow[:, 0, 0, H // 2, W // 2] = float("nan")
-    flow[:, 1, 0, 1, 1] = float("inf")
-    nan, inf = float("nan"), float("inf")
-    very_neg = -60.0 if cov_is_log else 1e-30                      # expf(-120) = 0 in fp32: a plateau of exact zeros with its neighbour
-    # (row, column, value) on the two planes the quality map is made of: image corners and edges, the seams of the 16 x 64 tiles where there are
-    # any (rows 15 | 16, columns 63 | 64: tile interior of one workgroup = halo of the next), and the interior
-    spots = [(0, 0, nan), (0, W - 1, inf), (H - 1, 0, -inf), (H - 1, W - 1, very_neg), (H - 1, W - 2, very_neg), (0, W // 2, very_neg),
-             (H // 2, 0, nan), (H // 2, W - 1, very_neg), (min(15, H - 1), min(63, W - 1), nan), (min(16, H - 1), min(64, W - 1), very_neg),
-             (min(15, H - 1), min(64, W - 1), inf), (min(16, H - 1), min(62, W - 1), -inf), (H // 3, W // 3, very_neg), (H // 3, W // 3 + 1, very_neg),
-             (2 * H // 3, 2 * W // 3, inf)]
-    for i, (y, x, v) in enumerate(spots):
-        if not cov_is_log and v == -inf:
-            v = 0.0
-        cov[:, 1, i % 2, y, x] = v
-    cov[:, 0, 0, H // 2, W // 3] = nan                              # the stereo sample: disparity variance only
-    cov[:, 0, 0, 0, W - 1] = very_neg
-    if lanes > 1:
-        cov[1, 1, :, :, W // 2:] += 0.25                            # the lanes differ
-    return flow, cov
-
-
-_cache = {}
-
-
-def _inputs_on(gpu, H, W, lanes, cov_is_log):
-    key = (H, W, lanes, cov_is_log)
-    if key not in _cache:
-        _cache[key] = tuple(t.to(gpu) for t in _inputs(H, W, lanes, cov_is_log))
-    return _cache[key]
-
-
-def _run(lib, L, gpu, H, W, lanes, fused, flow, cov, cov_is_log, ksize, mask_width):
-    """The fused launch, or mv_frontend_epilogue_lanes + mv_kp_select_lanes on the covariance planes it wrote; every output as CPU tensors."""
-    from macvo_amd import ops
-
-    mk = lambda c, dt=torch.float32: torch.full((lanes, c, H, W), 77, dtype=dt, device=gpu)  # noqa: E731
-    out = {"disparity": mk(1), "disparity_cov": mk(1), "depth": mk(1), "depth_cov": mk(1), "bad_mask": mk(1, torch.uint8),
-           "match_flow": mk(2), "match_cov": mk(3)}
-    p = L.mvKpSelectParams(H, W, L.MV_KP_NODEPTH, ksize, mask_width, 0.0, 0.0, 100.0)
-    nbytes = lib.mv_kp_select_workspace_bytes(H, W) * lanes
-    ws = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=gpu)
-    cand = torch.zeros(lanes, H * W, dtype=torch.int32, device=gpu)
-    count = torch.zeros(lanes, 4, dtype=torch.int32, device=gpu)
-    stats = torch.zeros(lanes, 4, dtype=torch.float32, device=gpu)
-    s = ops._stream()
-    o = {k: v.data_ptr() for k, v in out.items()}
-    if fused:
-        L.check(lib.mv_frontend_epilogue_select_lanes(flow.data_ptr(), cov.data_ptr(), int(cov_is_log), BL_FX, BL_FX_SQ, o["disparity"],
-                                                      o["disparity_cov"], o["depth"], o["depth_cov"], o["bad_mask"], o["match_flow"],
-                                                      o["match_cov"], None, None, C.byref(p), ws.data_ptr(), ws.numel() * 8, cand.data_ptr(),
-                                                      count.data_ptr(), stats.data_ptr(), lanes, s), "mv_frontend_epilogue_select_lanes")
-    else:
-        L.check(lib.mv_frontend_epilogue_lanes(flow.data_ptr(), cov.data_ptr(), int(cov_is_log), H, W, BL_FX, BL_FX_SQ, o["disparity"],
-                                               o["disparity_cov"], o["depth"], o["depth_cov"], o["bad_mask"], o["match_flow"], o["match_cov"],
-                                               lanes, s), "mv_frontend_epilogue_lanes")
-        L.check(lib.mv_kp_select_lanes(o["match_cov"], None, None, None, None, None, None, C.byref(p), ws.data_ptr(), ws.numel() * 8,
-                                       cand.data_ptr(), count.data_ptr(), stats.data_ptr(), lanes, s), "mv_kp_select_lanes")
-    torch.cuda.synchronize()
-    res = {k: v.cpu() for k, v in out.items()}
-    res.update(cand=cand.cpu(), count=count.cpu(), stats=stats.cpu())
-    return res
 
 
 @pytest.mark.parametrize("cov_is_log", [True, False])

@@ -35,6 +35,19 @@ def test_config_spec_exact_key_set_and_predicates():
         P.HIP_TwoFrame_PGO.is_valid_config(SimpleNamespace(device="cpu", vectorize=True, parallel=True, graph_type="bundle", autodiff=False))
 
 
+def test_selector_window_is_validated_at_configuration_time():
+    """The NMS kernel supports odd windows 1..15 and answers MV_ERR_UNSUPPORTED above: a YAML asking for more is refused when it is read, not on the
+    first frame (as the covariance plugins refuse kernel_size > 31)."""
+    nodepth = dict(device="cuda", mask_width=32, max_match_cov=100.0)
+    full = dict(device="cuda", mask_width=32, max_depth="auto", max_depth_cov=250.0, max_match_cov=100.0)
+    for cls, args in ((P.HIP_CovAwareSelector_NoDepth, nodepth), (P.HIP_CovAwareSelector, full)):
+        for k in (1, 3, 5, 7, 9, 11, 13, 15):
+            cls.is_valid_config(SimpleNamespace(kernel_size=k, **args))
+        for k in (17, 31, 0, -3, 8, 7.0):
+            with pytest.raises(ValueError):
+                cls.is_valid_config(SimpleNamespace(kernel_size=k, **args))
+
+
 def test_registry_rules():
     with pytest.raises(KeyError):
         I.IKeypointSelector.get_class("NoSuchSelector")

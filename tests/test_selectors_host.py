@@ -226,6 +226,14 @@ def test_selector_config_fields_maps_every_experiment_yaml():
         check_selector(HotPathConfig(selector="random", num_point=513), cam)
     with pytest.raises(ValueError, match="selector must be one of"):
         check_selector(HotPathConfig(selector="gradient"), cam)
+    # the NMS window of the CovAware selectors: odd, 1..15 (the kernel's halo) — refused here, not as MV_ERR_UNSUPPORTED on the first frame
+    for sel in ("nodepth", "full"):
+        for k in (1, 9, 15):
+            check_selector(HotPathConfig(selector=sel, kp_kernel_size=k), cam)
+        for k in (17, 0, 6, -1):
+            with pytest.raises(ValueError, match="kp_kernel_size"):
+                check_selector(HotPathConfig(selector=sel, kp_kernel_size=k), cam)
+    check_selector(HotPathConfig(selector="grid", kp_kernel_size=17), cam)           # ... which the map-less selectors never read
 
 
 def test_vanilla_and_covopt_blocks_instantiate_the_hip_plugins():
