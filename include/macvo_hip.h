@@ -1134,6 +1134,49 @@ int mv_eval_depth_lanes(int lanes, int H, int W, const float* est_depth /* [H,W]
                         int64_t cov_lane_stride, float max_depth, float* rows, int rows_per_lane, int row_index, uint32_t* grid /* or NULL */,
                         float* err_out /* or NULL */, float* nll_out /* or NULL */, void* workspace, size_t workspace_bytes, mvStream_t stream);
 
+/* ---- Trajectory evaluation (Evaluation/MetricsSeq.py:9-51: evaluateRTE / evaluateATE / evaluateROE / evaluateRPE, and the statistics
+ * Evaluation/EvalSeq.py:53-64 reads from their results): ATE, RTE, ROE, RPE of `lanes` finished tracks in ONE launch, one workgroup per lane, on `stream`;
+ * nothing synchronises with the host and nothing is staged.  MetricsSeq.py hands the work to evo 1.x, which is not a vendored dependency: its published
+ * definition is RESTATED here, UNPINNED (no evo run stands behind these numbers; SURVEY A21 treats PyPose the same way).  All arithmetic is fp64.
+ *   Tracks: est[l] / ref[l] are DEVICE pointers held in HOST arrays [lanes] (they travel by value in the kernel argument, so every lane may read its own
+ * allocation in place: a DeviceVisualMap's pose table, mv_body_poses' output); T[l] rows (tx ty tz qx qy qz qw) on both sides — the tracks are already
+ * time-associated, one estimate row per reference row (Trajectory.from_sandbox's align_time / interpolate_pose is not part of this) —, est_row_stride /
+ * ref_row_stride elements (>= 7) between rows, est_dtype / ref_dtype MV_TRAJ_F32 or MV_TRAJ_F64.  lanes <= MV_MAX_LANES, 0 <= T[l] <= MV_EVAL_TRAJ_MAX_POSES;
+ * MV_ERR_INVALID_ARG otherwise.
+ *   Pose -> matrix as evo's quaternion_matrix: q is normalised; q.q < 4 DBL_EPSILON gives the identity; q and -q are the same rotation.
+ *   Alignment (MetricsSeq.py passes align=True, align_origin=True to all four; in evo `align` wins and align_origin is then ignored):
+ * MV_TRAJ_ALIGN_UMEYAMA: x = estimate, y = reference positions, n = T, C = (1/n) sum (y - mu_y)(x - mu_x)^T, sigma_x = (1/n) sum |x - mu_x|^2 (both centred
+ * before they are summed), C = U diag(d) V^T by one-sided Jacobi on C itself, S = diag(1, 1, det U det V^T < 0 ? -1 : 1), R = U S V^T,
+ * c = correct_scale ? trace(diag(d) S) / sigma_x : 1, t = mu_y - c R mu_x; the estimate's translations are multiplied by c, then every pose is left-multiplied
+ * by [R | t].  Fewer than two d_k above DBL_EPSILON (absolute, as evo writes it) is DEGENERATE: evo raises there and EvalSeq.py:66-68 emits a row of None.
+ * MV_TRAJ_ALIGN_ORIGIN: the estimate is left-multiplied by Q_0 P_0^-1 (evo's align_origin branch); MV_TRAJ_ALIGN_NONE: nothing.  With correct_scale these two
+ * scale the estimate's translations by Umeyama's c first (evo's only_scale) and take over its degenerate rule; without it they never are DEGENERATE, the
+ * covariance pass and the SVD are skipped and d_1..d_3 are NaN.
+ * (evo itself skips the origin step when it corrects the scale; its fp32 round trip through Trajectory.align_origin is not reproduced either.)
+ *   ATE (ape, translation_part): e_i = |trans(P_i) - trans(Q_i)|, T values.  RTE / ROE / RPE (rpe, delta = 1 frame): E_i = (Q_i^-1 Q_i+1)^-1 (P_i^-1 P_i+1),
+ * T - 1 values: |trans E_i|; the rotation angle of E_i in degrees (atan2 of the antisymmetric part's norm and the trace: accurate at small angles);
+ * |E_i - I_4|_F.  Per metric mean, std = sqrt(mean((e - mean)^2)) (population form, two passes, as np.std) and rmse = sqrt(mean(e^2)).  Sums are taken in an
+ * order that depends on T only: a lane's row has the same bits alone, batched and at any lane index.
+ *   rows: DEVICE fp64 [lanes][MV_EVAL_TRAJ_COLS]: the 12 statistics, R (row-major), t, c, d_1..d_3, the pose count, the pair count, the status.  Any status
+ * but MV_TRAJ_OK gives NaN in the 12 statistics and in R, t, c: TOO_SHORT (T < 2: evo finds no pairs and raises), NONFINITE (a NaN / inf coordinate — this
+ * case is ours, the reference never sees it; d is NaN too), DEGENERATE (above; d holds what the rule saw; it covers T = 2).  Lanes are independent.
+ *   err_out (or NULL): DEVICE fp64 [lanes][4][err_stride], err_stride >= every T[l]: ATE_i (T values), then RTE_i, ROE_i, RPE_i (T - 1 values each) — what
+ * PlotSeq draws; NaN for a lane that is not OK; entries past a lane's counts are not written. */
+enum { MV_TRAJ_F32 = 0, MV_TRAJ_F64 = 1 };
+enum { MV_TRAJ_ALIGN_UMEYAMA = 0, MV_TRAJ_ALIGN_ORIGIN = 1, MV_TRAJ_ALIGN_NONE = 2 };
+enum { MV_TRAJ_OK = 0, MV_TRAJ_TOO_SHORT = 1, MV_TRAJ_DEGENERATE = 2, MV_TRAJ_NONFINITE = 3 };
+#define MV_EVAL_TRAJ_MAX_POSES (1 << 20)
+enum {
+    MV_EVAL_TRAJ_ATE_MEAN = 0, MV_EVAL_TRAJ_ATE_STD, MV_EVAL_TRAJ_ATE_RMSE, MV_EVAL_TRAJ_RTE_MEAN, MV_EVAL_TRAJ_RTE_STD, MV_EVAL_TRAJ_RTE_RMSE,
+    MV_EVAL_TRAJ_ROE_MEAN, MV_EVAL_TRAJ_ROE_STD, MV_EVAL_TRAJ_ROE_RMSE, MV_EVAL_TRAJ_RPE_MEAN, MV_EVAL_TRAJ_RPE_STD, MV_EVAL_TRAJ_RPE_RMSE,
+    MV_EVAL_TRAJ_R00, MV_EVAL_TRAJ_R01, MV_EVAL_TRAJ_R02, MV_EVAL_TRAJ_R10, MV_EVAL_TRAJ_R11, MV_EVAL_TRAJ_R12, MV_EVAL_TRAJ_R20, MV_EVAL_TRAJ_R21,
+    MV_EVAL_TRAJ_R22, MV_EVAL_TRAJ_TX, MV_EVAL_TRAJ_TY, MV_EVAL_TRAJ_TZ, MV_EVAL_TRAJ_SCALE, MV_EVAL_TRAJ_D1, MV_EVAL_TRAJ_D2, MV_EVAL_TRAJ_D3,
+    MV_EVAL_TRAJ_N_POSES, MV_EVAL_TRAJ_N_PAIRS, MV_EVAL_TRAJ_STATUS, MV_EVAL_TRAJ_COLS
+};
+int mv_eval_traj_lanes(int lanes, const void* const* est /* host [lanes] of device pointers */, const void* const* ref /* host [lanes] */,
+                       const int32_t* T /* host [lanes] */, int est_dtype, int ref_dtype, int64_t est_row_stride, int64_t ref_row_stride, int align,
+                       int correct_scale, double* rows, double* err_out /* or NULL */, int64_t err_stride, mvStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,16 @@ EVAL_DEPTH_COLS = ("masked_err", "err_25", "err_50", "err_75", "masked_nll", "q2
                    "n_mask", "n_mask_finite", "n_finite", "n_q25", "n_q50", "n_q75", "n_mask_nll")
 EVAL_GRID = 100          # GridRecorder((0, 25, .25), ...) / ((0, 50, .5), ...): 100 x 100 bins
 EVAL_MAX_PIXELS = 1 << 22
+# mv_eval_traj_lanes: dtypes, alignment modes, per-lane status and the row columns (enum order of the header)
+MV_TRAJ_F32, MV_TRAJ_F64 = 0, 1
+MV_TRAJ_ALIGN_UMEYAMA, MV_TRAJ_ALIGN_ORIGIN, MV_TRAJ_ALIGN_NONE = 0, 1, 2
+MV_TRAJ_OK, MV_TRAJ_TOO_SHORT, MV_TRAJ_DEGENERATE, MV_TRAJ_NONFINITE = 0, 1, 2, 3
+TRAJ_ALIGN = {"umeyama": MV_TRAJ_ALIGN_UMEYAMA, "origin": MV_TRAJ_ALIGN_ORIGIN, "none": MV_TRAJ_ALIGN_NONE}
+TRAJ_STATUS = ("OK", "TOO_SHORT", "DEGENERATE", "NONFINITE")
+EVAL_TRAJ_COLS = ("ate_mean", "ate_std", "ate_rmse", "rte_mean", "rte_std", "rte_rmse", "roe_mean", "roe_std", "roe_rmse", "rpe_mean", "rpe_std",
+                  "rpe_rmse", "r00", "r01", "r02", "r10", "r11", "r12", "r20", "r21", "r22", "tx", "ty", "tz", "scale", "d1", "d2", "d3", "n_poses",
+                  "n_pairs", "status")
+EVAL_TRAJ_MAX_POSES = 1 << 20
 
 
 class mvKpSelectParams(C.Structure):
@@ -271,6 +281,8 @@ SIGNATURES = {
                                      _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     "mv_eval_depth_lanes": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_float, _P, C.c_int, C.c_int, _P, _P, _P,
                                       _P, C.c_size_t, _P]),
+    # trajectory evaluation (MetricsSeq.py / EvalSeq.py): est / ref / T are HOST arrays [lanes] (device pointers, counts); rows fp64 [lanes][len(EVAL_TRAJ_COLS)]
+    "mv_eval_traj_lanes": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

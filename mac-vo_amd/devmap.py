@@ -376,6 +376,14 @@ class DeviceVisualMaps:
         L.check(self.lib.mv_map_set_pose_lanes(self.stores_dev(), self.lanes, int(frame_idx), pd.data_ptr(), ops._stream()), "mv_map_set_pose_lanes")
         self._keep_pose = pd
 
+    def evaluate(self, ref_tracks, align: str = "umeyama", correct_scale: bool = False, errors: bool = False):
+        """ATE / RTE / ROE / RPE of every lane's body poses (``body_poses()``: what ``poses.npy`` holds) against ``ref_tracks`` (one ``[n_frames, 7]`` GPU
+        tensor per lane, or ``[lanes, T, 7]``) in one launch: ``ops.eval_trajectory`` (MetricsSeq.py / EvalSeq.py; evo restated, parity-unpinned).  Returns
+        its device-resident result without synchronising."""
+        from . import ops
+
+        return ops.eval_trajectory([m.body_poses() for m in self.maps], ref_tracks, align, correct_scale, errors)
+
     def serialize(self) -> "list[dict[str, np.ndarray]]":
         return [m.serialize() for m in self.maps]
 

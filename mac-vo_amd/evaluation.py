@@ -1,6 +1,7 @@
-"""Frontend evaluation on the GPU: the reference's ``Evaluation/EvalFlow.py`` and ``Evaluation/EvalDepth.py``.
+"""Evaluation on the GPU: the reference's ``Evaluation/EvalFlow.py`` and ``Evaluation/EvalDepth.py`` (frontend), and ``Evaluation/MetricsSeq.py`` /
+``Evaluation/EvalSeq.py`` (sequence metrics ATE / RTE / ROE / RPE: ``evaluateATE`` ... ``EvaluateSequences`` at the end of this file).
 
-Two ways to call it:
+Two ways to call the frontend evaluation:
 
 * ``FrontendEvaluator``: push estimates and ground truth frame by frame; every push enqueues one launch group (``ops.eval_flow`` /
   ``ops.eval_depth``) that writes one row per lane into a device-resident table and accumulates the error^2-vs-variance grids.  Nothing
@@ -271,3 +272,119 @@ def evaluate_depthcov(depth, seq, max_depth: float = 80.0):
     results = [DepthCovPerformance(**{k: r[k] for k in ("masked_nll", "q25_nll", "q50_nll", "q75_nll")}) for r in recs]
     grid = np.zeros((L.EVAL_GRID, L.EVAL_GRID), np.uint32) if tables is None else tables.depth_grid[0]
     return DepthCovPerformance.mean(results), grid
+
+
+# ------------------------------------------------------------------------------------------------ sequence metrics (MetricsSeq.py, EvalSeq.py)
+# ATE / RTE / ROE / RPE of finished tracks through ``ops.eval_trajectory`` (one launch for every lane).  The reference hands these to evo 1.x; evo is
+# not a dependency here, so its published definition is RESTATED and stays parity-UNPINNED (include/macvo_hip.h).  Tracks are
+# ``[T, 7]`` rows (tx ty tz qx qy qz qw), already time-associated: ``Trajectory.from_sandbox``'s ``align_time`` (``interpolate_pose`` in fp32 PyPose
+# arithmetic), the fp32 round trip of its ``align_origin``, sandbox loading, plots and evo's ``is_so3`` exception are out of scope.
+class TrajectoryEvaluationError(RuntimeError):
+    """A lane that evo would have raised on: ``status`` is ``TOO_SHORT``, ``DEGENERATE`` or ``NONFINITE``."""
+
+    def __init__(self, status: str):
+        super().__init__(f"trajectory evaluation: {status}")
+        self.status = status
+
+
+@dataclass
+class TrajectoryMetric:
+    """What the reference reads of an ``evo`` result: ``stats["mean" | "std" | "rmse"]`` and ``np_arrays["error_array"]``."""
+    stats: dict
+    np_arrays: dict
+
+    @property
+    def error_array(self) -> np.ndarray:
+        return self.np_arrays["error_array"]
+
+
+_TRAJ_METRICS = ("ate", "rte", "roe", "rpe")
+
+
+def _track(t, device) -> torch.Tensor:
+    t = t if isinstance(t, torch.Tensor) else torch.tensor(np.asarray(t))
+    if t.dtype not in (torch.float32, torch.float64):
+        t = t.double()
+    return t.to(device)
+
+
+def _one_dtype(tracks: list) -> list:
+    """``mv_eval_traj_lanes`` takes one dtype per side: a side that mixes fp32 and fp64 is widened (exactly) to fp64."""
+    return tracks if len({t.dtype for t in tracks}) <= 1 else [t.double() for t in tracks]
+
+
+def _device_of(*tracks) -> torch.device:
+    for t in tracks:
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            return t.device
+    return torch.device("cuda:0")
+
+
+def _evaluate_metric(which: int, gt, est, correct_scale: bool) -> TrajectoryMetric:
+    dev = _device_of(est, gt)
+    res = ops.eval_trajectory([_track(est, dev)], [_track(gt, dev)], "umeyama", correct_scale, errors=True)
+    row = res.rows[0].cpu().numpy()                                   # the read-back
+    status = int(row[L.EVAL_TRAJ_COLS.index("status")])
+    if status != L.MV_TRAJ_OK:
+        raise TrajectoryEvaluationError(L.TRAJ_STATUS[status])
+    n = res.lengths[0] - (0 if which == 0 else 1)
+    stats = dict(zip(("mean", "std", "rmse"), map(float, row[3 * which:3 * which + 3])))
+    return TrajectoryMetric(stats, {"error_array": res.errors[0, which, :n].cpu().numpy()})
+
+
+def evaluateATE(gt_traj, est_traj, correct_scale: bool = False) -> TrajectoryMetric:
+    """MetricsSeq.py:18-24 (``main_ape.ape``, translation part, Umeyama alignment), metres."""
+    return _evaluate_metric(0, gt_traj, est_traj, correct_scale)
+
+
+def evaluateRTE(gt_traj, est_traj, correct_scale: bool = False) -> TrajectoryMetric:
+    """MetricsSeq.py:9-16 (``main_rpe.rpe``, translation part, delta = 1 frame), metres per frame."""
+    return _evaluate_metric(1, gt_traj, est_traj, correct_scale)
+
+
+def evaluateROE(gt_traj, est_traj, correct_scale: bool = False) -> TrajectoryMetric:
+    """MetricsSeq.py:26-41 (``main_rpe.rpe``, rotation angle, delta = 1 frame), degrees per frame."""
+    return _evaluate_metric(2, gt_traj, est_traj, correct_scale)
+
+
+def evaluateRPE(gt_traj, est_traj, correct_scale: bool = False) -> TrajectoryMetric:
+    """MetricsSeq.py:43-51 (``main_rpe.rpe``, full transformation, delta = 1 frame), unit-less."""
+    return _evaluate_metric(3, gt_traj, est_traj, correct_scale)
+
+
+def trajectory_header(correct_scale: bool = False) -> list:
+    """EvalSeq.py:77-83."""
+    dec = "[S]" if correct_scale else ""
+    return ["Trajectory"] + [x for m in ("ATE", "RTE", "ROE", "RPE") for x in (f"μ_{m}{dec}", f"σ_{m}", f"RMSE_{m}")]
+
+
+def trajectory_rows(names, rows: np.ndarray) -> list:
+    """EvalSeq.py:35-76 on read-back rows (``[n, len(EVAL_TRAJ_COLS)]``; a name with a None row had no estimate): one row per track — 12 figures, or
+    12 None where the status is not OK, which is where the reference's try / except lands — then the ``"Average"`` row over the figures present."""
+    st = L.EVAL_TRAJ_COLS.index("status")
+    out = []
+    for name, r in zip(names, rows):
+        ok = r is not None and int(r[st]) == L.MV_TRAJ_OK
+        out.append([name] + ([float(x) for x in r[:12]] if ok else [None] * 12))
+    out.append(["Average"] + [_mean([r[i] for r in out if r[i] is not None]) for i in range(1, 13)])
+    return out
+
+
+def EvaluateSequences(tracks, correct_scale: bool = False):
+    """EvalSeq.py:26-83 for tracks held in memory: ``tracks`` is a list of ``(name, gt [T,7], est [T,7] or None)``.  All tracks are scored by one launch per
+    ``MV_MAX_LANES`` of them and read back once (a side that mixes fp32 and fp64 tracks is widened to fp64 for that launch).  Returns the reference's ``(header, rows)``: a track without an estimate, or one evo would raise on,
+    gives a row of None; the last row is ``"Average"`` (it raises ``ValueError`` when no track could be scored, as the reference's ``mean`` does)."""
+    tracks = list(tracks)
+    have = [i for i, (_, _, est) in enumerate(tracks) if est is not None]
+    rows: list = [None] * len(tracks)
+    if have:
+        dev = _device_of(*[x for i in have for x in tracks[i][1:]])
+        parts = []
+        for s in range(0, len(have), L.MV_MAX_LANES):
+            idx = have[s:s + L.MV_MAX_LANES]
+            parts.append(ops.eval_trajectory(_one_dtype([_track(tracks[i][2], dev) for i in idx]), _one_dtype([_track(tracks[i][1], dev) for i in idx]),
+                                             "umeyama", correct_scale).rows)
+        host = torch.cat(parts).cpu().numpy()                         # the read-back
+        for i, r in zip(have, host):
+            rows[i] = r
+    return trajectory_header(correct_scale), trajectory_rows([t[0] for t in tracks], rows)

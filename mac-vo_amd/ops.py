@@ -1152,3 +1152,82 @@ def eval_depth(est_depth: torch.Tensor, gt_depth: torch.Tensor, est_cov: torch.T
     L.check(lib.mv_eval_depth_lanes(lanes, H, W, est.data_ptr(), n, gt.data_ptr(), n, _ptr(cov), n, float(max_depth), rows.data_ptr(), rows.shape[1],
                                     row, _ptr(grids), _ptr(err), _ptr(nll), ws.data_ptr(), ws.numel() * 8, _stream()), "mv_eval_depth_lanes")
     return EvalResult(rows[:, row], rows, grids, err, nll)
+
+
+# ------------------------------------------------------------------------------------------- trajectory evaluation (MetricsSeq.py / EvalSeq.py)
+@dataclass
+class TrajEvalResult:
+    """``rows``: fp64 ``[L, len(EVAL_TRAJ_COLS)]`` on the device (``_lib.EVAL_TRAJ_COLS`` names the columns; ``status`` is ``_lib.MV_TRAJ_*``);
+    ``errors``: fp64 ``[L, 4, T_max]`` (ATE_i, then RTE_i / ROE_i / RPE_i; NaN where a lane has no value) or None; ``lengths``: the host-side T per lane."""
+    rows: torch.Tensor
+    errors: torch.Tensor | None
+    lengths: list
+
+    def column(self, name: str) -> torch.Tensor:
+        return self.rows[:, L.EVAL_TRAJ_COLS.index(name)]
+
+
+def _traj_side(tracks, name: str):
+    """One side of ``eval_trajectory`` -> (tensors kept alive, dtype code, row stride in elements, lengths).  A track is read IN PLACE when it is a
+    GPU tensor ``[T, >= 7]`` of fp32 / fp64 with unit column stride and every lane of the side shares dtype and row stride; otherwise the side is
+    made contiguous on the device (a copy on the current stream: no synchronisation)."""
+    if isinstance(tracks, torch.Tensor):
+        if tracks.dim() == 2:
+            tracks = [tracks]
+        elif tracks.dim() == 3:
+            tracks = list(tracks.unbind(0))
+        else:
+            raise L.MacvoHipError(f"{name}: expected [T,7], [L,T,7] or a list of [T,7] tracks, got {tuple(tracks.shape)}")
+    tracks = list(tracks)
+    for t in tracks:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise L.MacvoHipError(f"{name}: expected GPU tensors (the HIP hot path has no CPU fallback)")
+        if t.dim() != 2 or t.shape[1] < 7:
+            raise L.MacvoHipError(f"{name}: a track is [T,7] rows (tx ty tz qx qy qz qw), got {tuple(t.shape)}")
+        if t.dtype not in (torch.float32, torch.float64):
+            raise L.MacvoHipError(f"{name}: fp32 or fp64 tracks, got {t.dtype}")
+    if len({t.dtype for t in tracks}) > 1:
+        raise L.MacvoHipError(f"{name}: every lane of one side in the same dtype")
+    live = [t for t in tracks if t.shape[0] > 1]
+    strides = {t.stride(0) for t in live}
+    if any(t.stride(1) != 1 for t in live) or len(strides) > 1 or any(s < 7 for s in strides):
+        tracks = [t[:, :7].contiguous() for t in tracks]
+        strides = {7}
+    return tracks, (L.MV_TRAJ_F64 if tracks and tracks[0].dtype == torch.float64 else L.MV_TRAJ_F32), (strides.pop() if strides else 7), \
+        [int(t.shape[0]) for t in tracks]
+
+
+def eval_trajectory(est, ref, align: str = "umeyama", correct_scale: bool = False, errors: bool = False) -> TrajEvalResult:
+    """ATE / RTE / ROE / RPE of every lane's track in one launch (``mv_eval_traj_lanes``; MetricsSeq.py:9-51, EvalSeq.py:53-64 — evo 1.x restated,
+    parity-unpinned: evo is not a dependency of this library).  ``est`` / ``ref``: a list of per-lane ``[T_l, 7]`` GPU tensors (fp32 or fp64 per side,
+    rows tx ty tz qx qy qz qw, read in place), or one ``[L, T, 7]`` tensor.  The tracks are time-associated: a lane whose estimate and reference
+    lengths differ is refused.  ``align``: ``"umeyama"`` (the reference's setting), ``"origin"`` or ``"none"``.  Returns device tensors on the current
+    stream; never synchronises."""
+    lib = L.load()
+    if align not in L.TRAJ_ALIGN:
+        raise L.MacvoHipError(f"eval_trajectory: align must be one of {sorted(L.TRAJ_ALIGN)}, got {align!r}")
+    e, e_dt, e_st, e_T = _traj_side(est, "est")
+    r, r_dt, r_st, r_T = _traj_side(ref, "ref")
+    lanes = len(e)
+    if not 1 <= lanes <= L.MV_MAX_LANES or len(r) != lanes:
+        raise L.MacvoHipError(f"eval_trajectory: {lanes} estimates and {len(r)} references (1 <= lanes <= {L.MV_MAX_LANES}, one reference per estimate)")
+    for l, (a, b) in enumerate(zip(e_T, r_T)):
+        if a != b:
+            raise L.MacvoHipError(f"eval_trajectory: lane {l} has {a} estimated and {b} reference poses (tracks must be time-associated: one estimate row "
+                                  "per reference row)")
+        if a > L.EVAL_TRAJ_MAX_POSES:
+            raise L.MacvoHipError(f"eval_trajectory: lane {l} has {a} poses (at most 2^20)")
+    dev = e[0].device
+    if any(t.device != dev for t in e + r):
+        raise L.MacvoHipError("eval_trajectory: every track on the same device")
+    rows = torch.empty((lanes, len(L.EVAL_TRAJ_COLS)), dtype=torch.float64, device=dev)
+    t_max = max(max(e_T), 1)
+    err = torch.full((lanes, 4, t_max), float("nan"), dtype=torch.float64, device=dev) if errors else None
+    ep = (C.c_void_p * lanes)(*[t.data_ptr() if t.shape[0] else None for t in e])
+    rp = (C.c_void_p * lanes)(*[t.data_ptr() if t.shape[0] else None for t in r])
+    Ts = (C.c_int32 * lanes)(*e_T)
+    with torch.cuda.device(dev):
+        L.check(lib.mv_eval_traj_lanes(lanes, ep, rp, Ts, e_dt, r_dt, e_st, r_st, L.TRAJ_ALIGN[align], int(bool(correct_scale)), rows.data_ptr(),
+                                       _ptr(err), t_max, _stream()), "mv_eval_traj_lanes")
+    # (the launch is enqueued; the caching allocator keeps `e` / `r` copies valid for work already on this stream)
+    return TrajEvalResult(rows, err, e_T)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Stand-alone timing of individual C-ABI kernels on the GPU box (HIP events, median of N launches).
 
-    python tools/kernel_bench.py [volume_f32 volume_f16 lookup select cov pgo eval ...] [--iters 50]
+    python tools/kernel_bench.py [volume_f32 volume_f16 lookup select cov pgo eval eval_traj ...] [--iters 50]
 
 Used for A/B tuning and as the target of `rocprofv3 --pmc ...` runs (one kernel family per process).
 """
@@ -380,6 +380,83 @@ def main():
                     h, t_ = statistics.median(res[f"eval_{kind:5s} HIP"]), statistics.median(res[f"eval_{kind:5s} torch closed form"])
                     print(f"eval_{kind}: torch / HIP = {t_ / h:.2f}x; algorithmic bytes {nb / 1e6:.2f} MB = {nb / 8e6:.2f} us at 8 TB/s; "
                           "launches per HIP call: 1 memset + 4 kernels")
+        elif w == "eval_traj":
+            # ops.eval_trajectory (csrc/traj_eval.hip: ATE / RTE / ROE / RPE, Umeyama alignment, one workgroup per lane) next to the same closed form in
+            # torch on the same device (batched torch.linalg.svd) and to the numpy restatement with its read-back (tests/traj_ref.py, once: it is a
+            # Python loop over the pairs)
+            import time
+
+            from tests import traj_ref as TR
+
+            def quat_R(q):                                          # [..., 4] (x y z w) -> [..., 3, 3], evo's quaternion_matrix
+                q = q * torch.sqrt(2.0 / (q * q).sum(-1, keepdim=True))
+                x, y, z, w_ = q.unbind(-1)
+                return torch.stack([1 - y * y - z * z, x * y - z * w_, x * z + y * w_, x * y + z * w_, 1 - x * x - z * z, y * z - x * w_,
+                                    x * z - y * w_, y * z + x * w_, 1 - x * x - y * y], -1).reshape(*q.shape[:-1], 3, 3)
+
+            def stats(e):
+                m = e.mean(-1)
+                return torch.stack([m, (e - m[:, None]).square().mean(-1).sqrt(), e.square().mean(-1).sqrt()], -1)
+
+            def torch_traj(est, ref):                               # [L, T, 7] fp64 each -> [L, 12]
+                x, y = est[..., :3], ref[..., :3]
+                mx, my = x.mean(1, keepdim=True), y.mean(1, keepdim=True)
+                cov = torch.einsum("lni,lnj->lij", y - my, x - mx) / x.shape[1]
+                U, d, Vh = torch.linalg.svd(cov)
+                s = torch.ones_like(d)
+                s[:, 2] = torch.where(torch.linalg.det(U) * torch.linalg.det(Vh) < 0, -1.0, 1.0)
+                R = (U * s[:, None, :]) @ Vh
+                t = my[:, 0] - torch.einsum("lij,lj->li", R, mx[:, 0])
+                ate = (torch.einsum("lij,lnj->lni", R, x) + t[:, None] - y).norm(dim=-1)
+                Rp, Rq = quat_R(est[..., 3:]), quat_R(ref[..., 3:])
+                dRp, dRq = Rp[:, :-1].transpose(-1, -2) @ Rp[:, 1:], Rq[:, :-1].transpose(-1, -2) @ Rq[:, 1:]
+                dtp = torch.einsum("lnji,lnj->lni", Rp[:, :-1], x[:, 1:] - x[:, :-1])
+                dtq = torch.einsum("lnji,lnj->lni", Rq[:, :-1], y[:, 1:] - y[:, :-1])
+                E = dRq.transpose(-1, -2) @ dRp
+                et = torch.einsum("lnji,lnj->lni", dRq, dtp - dtq)
+                v = 0.5 * torch.stack([E[..., 2, 1] - E[..., 1, 2], E[..., 0, 2] - E[..., 2, 0], E[..., 1, 0] - E[..., 0, 1]], -1)
+                roe = torch.rad2deg(torch.atan2(v.norm(dim=-1), 0.5 * (E.diagonal(dim1=-2, dim2=-1).sum(-1) - 1)))
+                rpe = ((E - torch.eye(3, dtype=E.dtype, device=E.device)).square().sum((-1, -2)) + et.square().sum(-1)).sqrt()
+                return torch.cat([stats(ate), stats(et.norm(dim=-1)), stats(roe), stats(rpe)], -1)
+
+            for lanes, T in ((1, 1360), (32, 4096)):
+                g = torch.Generator().manual_seed(4)
+                pos = torch.cumsum(torch.randn(lanes, T, 3, generator=g, dtype=torch.float64) * 0.3, 1)
+                quat = torch.cumsum(torch.randn(lanes, T, 4, generator=g, dtype=torch.float64) * 0.01, 1) + torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64)
+                ref = torch.cat([pos, quat / quat.norm(dim=-1, keepdim=True)], -1)
+                qe = ref[..., 3:] + torch.randn(lanes, T, 4, generator=g, dtype=torch.float64) * 1e-3
+                est = torch.cat([pos + torch.cumsum(torch.randn(lanes, T, 3, generator=g, dtype=torch.float64) * 0.004, 1), qe / qe.norm(dim=-1, keepdim=True)], -1)
+                est, ref = est.to(dev), ref.to(dev)
+                legs = [("eval_traj HIP", lambda: ops.eval_trajectory(est, ref)), ("eval_traj torch closed form", lambda: torch_traj(est, ref))]
+                h, t_ = legs[0][1]().rows[:, :12], legs[1][1]()
+                torch.cuda.synchronize()
+                print(f"lanes {lanes}: max |HIP - torch| / |torch| over the 12 statistics: {float(((h - t_).abs() / t_.abs()).max()):.3e}")
+                rounds, per = 5, max(8, (4 * a.iters) // 5)
+                res = {k: [] for k, _ in legs}
+                for k, fn in legs:
+                    for _ in range(5):
+                        fn()
+                torch.cuda.synchronize()
+                for _ in range(rounds):
+                    for k, fn in legs:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(per):
+                            fn()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        res[k].append(e0.elapsed_time(e1) * 1e3 / per)
+                for k, _ in legs:
+                    v = res[k]
+                    print(f"{k:30s} lanes {lanes:2d} x {T} poses: median {statistics.median(v):9.1f} us / call (rounds {min(v):.1f} .. {max(v):.1f}; {rounds * per} calls)")
+                t0 = time.perf_counter()
+                eh, rh = est.cpu().numpy(), ref.cpu().numpy()       # the read-back the host route needs
+                rows = [TR.stats_row(TR.evaluate(eh[l], rh[l])) for l in range(lanes)]
+                host_us = (time.perf_counter() - t0) * 1e6
+                worst = max(abs(a_ - b_) / abs(b_) for l in range(lanes) for a_, b_ in zip(h[l].tolist(), rows[l]))
+                hm, tm = statistics.median(res["eval_traj HIP"]), statistics.median(res["eval_traj torch closed form"])
+                print(f"{'eval_traj numpy restatement':30s} lanes {lanes:2d} x {T} poses: {host_us:9.0f} us (one call, read-back included); max |HIP - numpy| / |numpy| = {worst:.3e}")
+                print(f"eval_traj lanes {lanes}: torch / HIP = {tm / hm:.2f}x, numpy / HIP = {host_us / hm:.0f}x; one launch, {lanes * T * 7 * 16 / 1e6:.2f} MB of poses")
         elif w == "select":
             fc = synth.flow_cov_maps(H, W, 2).to(dev)
             d0, d0c = [t.to(dev) for t in synth.depth_maps(H, W, 3)]

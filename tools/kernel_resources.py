@@ -117,6 +117,8 @@ CHECKS = [
     (r"^eval_(pixel|select|qmean)_kernel<", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and regs(r) <= 128 and
      r.get("group_segment_fixed_size", 0) <= 60 * 1024,
      "evaluation metrics: no scratch, four waves per SIMD, the LDS-privatised recorder grids + digit histograms within the 64 KB static limit (two workgroups per CU)"),
+    (r"^traj_eval_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0,
+     "trajectory evaluation: the 3 x 3 SVD and every SE(3) product in registers (constant indices only): zero scratch, zero spills"),
 ]
 
 
