@@ -1177,6 +1177,49 @@ int mv_eval_traj_lanes(int lanes, const void* const* est /* host [lanes] of devi
                        const int32_t* T /* host [lanes] */, int est_dtype, int ref_dtype, int64_t est_row_stride, int64_t ref_row_stride, int align,
                        int correct_scale, double* rows, double* err_out /* or NULL */, int64_t err_stride, mvStream_t stream);
 
+/* ---- Trajectory time association (Utility/Trajectory.py:105-114: what Trajectory.from_sandbox does between loading poses.npy / ref_poses.npy and
+ * handing the tracks to evaluateATE / RTE / ROE / RPE, Evaluation/EvalSeq.py:36): align_origin (:188-191), the rebase of both clocks (:107-108) and
+ * align_time (:172-176 -> Utility/Math.py:96-121 interpolate_pose) of `lanes` tracks in ONE launch on `stream` — one query per thread, the lane in
+ * blockIdx.y; nothing synchronises with the host, nothing is staged and nothing passes between workgroups (every workgroup of a lane repeats the lane's
+ * checks).  PyPose's SE3 Inv / Mul / Log / Exp and evo's align_origin are RESTATED here, UNPINNED (neither is a vendored dependency).
+ *   Per lane l, read where they lie (HOST arrays [lanes] of DEVICE pointers, passed by value in the kernel argument): src[l] — T[l] rows
+ * (tx ty tz qx qy qz qw), src_dtype MV_TRAJ_F32 / MV_TRAJ_F64, src_row_stride elements (>= 7) between rows —, src_time[l] — its T[l] stamps —,
+ * query_time[l] — Q[l] stamps —, both clocks time_dtype MV_TRAJ_TIME_F64 or MV_TRAJ_TIME_I64, and origin_ref[l] (origin_ref or an entry may be NULL):
+ * the first row [7] of a reference track in origin_dtype, which turns the origin alignment on.  0 <= T[l], Q[l] <= MV_EVAL_TRAJ_MAX_POSES.
+ *   Rebase (`rebase` != 0; the reference always does it): each clock is taken relative to its own first element.  int64 stamps are subtracted as
+ * integers and only the difference becomes fp64 (EuRoC's nanoseconds, about 1.4e18, do not fit fp64: the reference's astype(float) rounds them to
+ * multiples of 256 ns); fp64 stamps are subtracted in fp64, as the reference does.
+ *   Placement (Math.py:99-121): a query <= ts[0] gets source row 0, a query >= ts[T-1] the last row, copied (widened or rounded to out_dtype), flag 1;
+ * otherwise e is the first index with ts[e] >= tq (searchsorted(right=False); a bounded binary search, <= 31 steps), s = e - 1, and the result is
+ * Exp(prop Log(P_e P_s^-1)) P_s with prop = (tq - ts[s]) / (ts[e] - ts[s]), flag 0.  A query ON an interior stamp has prop = 1 and goes through
+ * Exp(Log(.)): it is not a copy.  T = 1: every query copies row 0.  Queries may come in any order and may repeat.
+ *   Origin: with origin_ref[l] every source pose is first left-multiplied by ref_0 src_0^-1, its quaternion normalised and given w >= 0 (what evo's
+ * matrix round trip leaves) — before the placement, copies included.
+ *   Arithmetic: fp64 throughout on the exactly widened inputs, ONE rounding at the store.  The reference's chain for an fp32 estimate is mixed (fp32
+ * Inv / @ / Log, fp64 Exp, fp32 again after from_evo(...).float()) and is not reproduced bit for bit; DESIGN.md section 7 has the measured gap.
+ *   Writes: out_poses[l] — [Q[l], 7] in out_dtype (the reference's P_container takes the source's dtype) —, out_extrapolated[l] — uint8 [Q[l]], the
+ * reference's ~interp_mask —, status — DEVICE int32 [lanes]: MV_TRAJ_OK, TOO_SHORT (T = 0), UNSORTED (some ts[i] >= ts[i+1]: Math.py:97 asserts),
+ * NONFINITE (a non-finite stamp, source row or origin row; it wins over UNSORTED).  A lane that is not OK gets NaN poses and flags 0; the other lanes
+ * never see it. */
+enum { MV_TRAJ_UNSORTED = 4 };   /* extends MV_TRAJ_OK .. MV_TRAJ_NONFINITE */
+enum { MV_TRAJ_TIME_F64 = 0, MV_TRAJ_TIME_I64 = 1 };
+int mv_traj_associate_lanes(int lanes, const void* const* src /* host [lanes] of device pointers */, const void* const* src_time /* host [lanes] */,
+                            const int32_t* T /* host [lanes] */, const void* const* query_time /* host [lanes] */, const int32_t* Q /* host [lanes] */,
+                            const void* const* origin_ref /* host [lanes] or NULL */, int src_dtype, int time_dtype, int origin_dtype, int out_dtype,
+                            int64_t src_row_stride, int rebase, void* const* out_poses /* host [lanes] */,
+                            uint8_t* const* out_extrapolated /* host [lanes] */, int32_t* status /* DEVICE [lanes] */, mvStream_t stream);
+
+/* PoseInterpolate.elaborate_map (Module/MapProcessor.py:33-45) on pose [T,7] in place, one workgroup, fp64 inside, fp32 at the store:
+ * bad = need_interp with the first five and the last five rows forced to 0 — and CLEARED in need_interp itself, as the reference clears them in the
+ * stored table (AutoScalingTensor.tensor is a narrow view, TensorExtension.py:100-101) —; a bad row i becomes Exp(prop Log(P_e P_s^-1)) P_s from its
+ * nearest good rows s < i < e, prop = float(i - s) / float(e - s) (a float32 division, Utility/Math.py:114).  Good rows are never written; T < 11
+ * changes no pose.  mask: uint8 [T], 1 on the rows it rewrote (the reference's bad_idx as a mask); nothing is read back. */
+int mv_pose_interpolate(float* pose, uint8_t* need_interp, int T, uint8_t* mask, mvStream_t stream);
+/* ... of every lane's map in one launch (one workgroup per lane): pose / need_interp come from stores_dev[l], T[l] rows (HOST [lanes]; a lane whose T
+ * exceeds its store's cap_frames is left alone), mask is DEVICE uint8 [lanes][mask_stride], mask_stride >= every T[l]. */
+int mv_pose_interpolate_lanes(const mvMapStores* stores_dev /* DEVICE [lanes] */, int lanes, const int32_t* T /* host [lanes] */, uint8_t* mask,
+                              int64_t mask_stride, mvStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,8 +38,11 @@ EVAL_MAX_PIXELS = 1 << 22
 MV_TRAJ_F32, MV_TRAJ_F64 = 0, 1
 MV_TRAJ_ALIGN_UMEYAMA, MV_TRAJ_ALIGN_ORIGIN, MV_TRAJ_ALIGN_NONE = 0, 1, 2
 MV_TRAJ_OK, MV_TRAJ_TOO_SHORT, MV_TRAJ_DEGENERATE, MV_TRAJ_NONFINITE = 0, 1, 2, 3
+MV_TRAJ_UNSORTED = 4                             # mv_traj_associate_lanes only
+MV_TRAJ_TIME_F64, MV_TRAJ_TIME_I64 = 0, 1        # mv_traj_associate_lanes: the dtype of both clocks
 TRAJ_ALIGN = {"umeyama": MV_TRAJ_ALIGN_UMEYAMA, "origin": MV_TRAJ_ALIGN_ORIGIN, "none": MV_TRAJ_ALIGN_NONE}
 TRAJ_STATUS = ("OK", "TOO_SHORT", "DEGENERATE", "NONFINITE")
+TRAJ_ASSOC_STATUS = TRAJ_STATUS + ("UNSORTED",)  # mv_traj_associate_lanes' status by value (DEGENERATE never occurs there)
 EVAL_TRAJ_COLS = ("ate_mean", "ate_std", "ate_rmse", "rte_mean", "rte_std", "rte_rmse", "roe_mean", "roe_std", "roe_rmse", "rpe_mean", "rpe_std",
                   "rpe_rmse", "r00", "r01", "r02", "r10", "r11", "r12", "r20", "r21", "r22", "tx", "ty", "tz", "scale", "d1", "d2", "d3", "n_poses",
                   "n_pairs", "status")
@@ -283,6 +286,12 @@ SIGNATURES = {
                                       _P, C.c_size_t, _P]),
     # trajectory evaluation (MetricsSeq.py / EvalSeq.py): est / ref / T are HOST arrays [lanes] (device pointers, counts); rows fp64 [lanes][len(EVAL_TRAJ_COLS)]
     "mv_eval_traj_lanes": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int64, _P]),
+    # trajectory association (Trajectory.from_sandbox's align_origin / rebase / align_time): src, src_time, T, query_time, Q, origin_ref, out_poses,
+    # out_extrapolated are HOST arrays [lanes]; status int32 [lanes] on the device
+    "mv_traj_associate_lanes": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P]),
+    # PoseInterpolate (MapProcessor.py:28-49): one table, or every lane's map through the device descriptor array (T: host int32 [lanes])
+    "mv_pose_interpolate": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "mv_pose_interpolate_lanes": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

@@ -7,7 +7,8 @@
 //   `match_obs[mask]`, points.push(...[mask]), push_keyframe, the six edge updates, the lost-track flag) — the reference does
 //   all of it on the CPU after ~25 `.cpu()` copies per frame (MACVO.py:235-266);
 //   Odometry/Interface.py:47-49 (body poses T_BS @ pose @ T_BS^-1 written to poses.npy);
-//   Module/MapProcessor.py:52-76 (MotionInterpolate.elaborate_map) + Utility/Math.py:96-133 (interpolate_pose, NormalizeQuat).
+//   Module/MapProcessor.py:52-76 (MotionInterpolate.elaborate_map) and :28-49 (PoseInterpolate.elaborate_map) + Utility/Math.py:96-133
+//   (interpolate_pose, NormalizeQuat) — the se3 arithmetic of both is csrc/se3_interp.h.
 //
 // gfx950 design: all of this is a few KB per frame — one workgroup per call.  mv_map_append compacts the frame's kept rows
 // (valid mask of mv_obs_filter, order preserved: `bundle[mask]`) with a wave-ballot scan and scatters them into the stores at
@@ -15,109 +16,11 @@
 // tracks capacity UPPER bounds (rows pushed <= rows selected).
 #include "common.h"
 #include <math.h>
+#include "se3_interp.h"   // Se3d and the fp64 SE(3) arithmetic MotionInterpolate / PoseInterpolate run on (shared with traj_assoc.hip and a host twin)
 
 namespace {
 
-struct Se3d {
-    double t[3], q[4];
-};
-
-__device__ __forceinline__ void q_act(const double* q, const double* p, double* o) {   // PyPose SO3_Act
-    double u0 = q[1] * p[2] - q[2] * p[1], u1 = q[2] * p[0] - q[0] * p[2], u2 = q[0] * p[1] - q[1] * p[0];
-    u0 += u0; u1 += u1; u2 += u2;
-    o[0] = p[0] + q[3] * u0 + (q[1] * u2 - q[2] * u1);
-    o[1] = p[1] + q[3] * u1 + (q[2] * u0 - q[0] * u2);
-    o[2] = p[2] + q[3] * u2 + (q[0] * u1 - q[1] * u0);
-}
-__device__ __forceinline__ void q_mul(const double* a, const double* b, double* o) {   // PyPose SO3_Mul (x, y, z, w)
-    o[0] = a[3] * b[0] + b[3] * a[0] + (a[1] * b[2] - a[2] * b[1]);
-    o[1] = a[3] * b[1] + b[3] * a[1] + (a[2] * b[0] - a[0] * b[2]);
-    o[2] = a[3] * b[2] + b[3] * a[2] + (a[0] * b[1] - a[1] * b[0]);
-    o[3] = a[3] * b[3] - (a[0] * b[0] + a[1] * b[1] + a[2] * b[2]);
-}
-__device__ __forceinline__ Se3d se3_mul(const Se3d& a, const Se3d& b) {
-    Se3d o;
-    double r[3];
-    q_act(a.q, b.t, r);
-    o.t[0] = a.t[0] + r[0]; o.t[1] = a.t[1] + r[1]; o.t[2] = a.t[2] + r[2];
-    q_mul(a.q, b.q, o.q);
-    return o;
-}
-__device__ __forceinline__ Se3d se3_inv(const Se3d& a) {
-    Se3d o;
-    o.q[0] = -a.q[0]; o.q[1] = -a.q[1]; o.q[2] = -a.q[2]; o.q[3] = a.q[3];
-    double r[3];
-    q_act(o.q, a.t, r);
-    o.t[0] = -r[0]; o.t[1] = -r[1]; o.t[2] = -r[2];
-    return o;
-}
-__device__ __forceinline__ Se3d se3_normq(Se3d a) {   // Utility/Math.py:124-133 NormalizeQuat
-    const double n = sqrt(a.q[0] * a.q[0] + a.q[1] * a.q[1] + a.q[2] * a.q[2] + a.q[3] * a.q[3]);
-    a.q[0] /= n; a.q[1] /= n; a.q[2] /= n; a.q[3] /= n;
-    return a;
-}
-__device__ __forceinline__ void skew_sq_apply(const double* k, const double* v, double c1, double c2, double* o) {
-    // o = v + c1 * (k x v) + c2 * (k x (k x v))
-    const double a0 = k[1] * v[2] - k[2] * v[1], a1 = k[2] * v[0] - k[0] * v[2], a2 = k[0] * v[1] - k[1] * v[0];
-    const double b0 = k[1] * a2 - k[2] * a1, b1 = k[2] * a0 - k[0] * a2, b2 = k[0] * a1 - k[1] * a0;
-    o[0] = v[0] + c1 * a0 + c2 * b0;
-    o[1] = v[1] + c1 * a1 + c2 * b1;
-    o[2] = v[2] + c1 * a2 + c2 * b2;
-}
-// PyPose SE3_Log: phi = SO3_Log(q), rho = Jl^-1(phi) t   (tangent = [rho, phi])
-__device__ __forceinline__ void se3_log(const Se3d& a, double* xi) {
-    const double eps = 2.220446049250313e-16;
-    double v[3] = {a.q[0], a.q[1], a.q[2]}, w = a.q[3];
-    const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    // PyPose SO3_Log: factor = 2 atan(|v| / w) / |v| (w != 0), with the small-|v| series 2/w - 2 |v|^2 / (3 w^3)
-    double factor;
-    if (n > eps) {
-        factor = (fabs(w) > eps) ? 2.0 * atan(n / w) / n : (w >= 0 ? M_PI : -M_PI) / n;
-    } else {
-        factor = 2.0 / w - 2.0 * n * n / (3.0 * w * w * w);
-    }
-    double phi[3] = {v[0] * factor, v[1] * factor, v[2] * factor};
-    const double th = sqrt(phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]);
-    // so3_Jl_inv = I - K/2 + c K^2, c = (1 - th cos(th/2) / (2 sin(th/2))) / th^2, series 1/12 + th^2/720
-    double c;
-    if (th > eps) {
-        const double h = 0.5 * th;
-        c = (1.0 - th * cos(h) / (2.0 * sin(h))) / (th * th);
-    } else {
-        c = 1.0 / 12.0 + th * th / 720.0;
-    }
-    skew_sq_apply(phi, a.t, -0.5, c, xi);
-    xi[3] = phi[0]; xi[4] = phi[1]; xi[5] = phi[2];
-}
-// PyPose se3_Exp: t = Jl(phi) rho, q = so3_Exp(phi)
-__device__ __forceinline__ Se3d se3_exp(const double* xi) {
-    const double eps = 2.220446049250313e-16;
-    const double* phi = xi + 3;
-    const double th = sqrt(phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2]);
-    const double th2 = th * th, th4 = th2 * th2;
-    Se3d o;
-    double c1, c2, imag, real;
-    if (th > eps) {
-        c1 = (1.0 - cos(th)) / th2;
-        c2 = (th - sin(th)) / (th2 * th);
-        imag = sin(0.5 * th) / th;
-        real = cos(0.5 * th);
-    } else {
-        c1 = 0.5 - th2 / 24.0;
-        c2 = 1.0 / 6.0 - th2 / 120.0;
-        imag = 0.5 - th2 / 48.0 + th4 / 3840.0;
-        real = 1.0 - th2 / 8.0 + th4 / 384.0;
-    }
-    skew_sq_apply(phi, xi, c1, c2, o.t);
-    o.q[0] = phi[0] * imag; o.q[1] = phi[1] * imag; o.q[2] = phi[2] * imag; o.q[3] = real;
-    return o;
-}
-__device__ __forceinline__ Se3d load_pose(const float* p) {
-    Se3d o;
-    o.t[0] = p[0]; o.t[1] = p[1]; o.t[2] = p[2];
-    o.q[0] = p[3]; o.q[1] = p[4]; o.q[2] = p[5]; o.q[3] = p[6];
-    return o;
-}
+using namespace se3i;
 
 // ------------------------------------------------------------------------------------------------ registration
 // One frame into one map, by one 256-thread workgroup: the body of map_append_kernel (one frame per launch) and of map_append_lanes_kernel (one workgroup per
@@ -478,6 +381,42 @@ __global__ __launch_bounds__(256) void motion_interpolate_kernel(float* __restri
     }
 }
 
+// PoseInterpolate.elaborate_map (Module/MapProcessor.py:33-45) on one pose table, by one 256-thread workgroup, float64 inside: a flagged row outside
+// the first / last five becomes se3_interp of its nearest good rows (se3_interp.h: pose_interp_row).  A good row is never written and only good rows
+// are read as neighbours, so the rows can be rewritten in place, in any order.  The edge flags are cleared in the table as the reference clears them
+// (bad_mask is a view of the stored tensor); no flag that is read (rows 5 .. T - 6) is one that is cleared.
+__device__ __forceinline__ void pose_interpolate_table(float* __restrict__ pose, uint8_t* __restrict__ need_interp, int T, uint8_t* __restrict__ mask) {
+    for (int i = threadIdx.x; i < T; i += blockDim.x) {
+        Se3d m;
+        const bool bad = pose_interp_row(pose, need_interp, T, i, m);
+        if (bad) {
+            float* o = pose + 7 * (size_t)i;
+            o[0] = (float)m.t[0]; o[1] = (float)m.t[1]; o[2] = (float)m.t[2];
+            o[3] = (float)m.q[0]; o[4] = (float)m.q[1]; o[5] = (float)m.q[2]; o[6] = (float)m.q[3];
+        }
+        mask[i] = bad ? 1 : 0;
+        if (i < 5 || i >= T - 5) need_interp[i] = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void pose_interpolate_kernel(float* __restrict__ pose, uint8_t* __restrict__ need_interp, int T, uint8_t* __restrict__ mask) {
+    pose_interpolate_table(pose, need_interp, T, mask);
+}
+
+struct MapLaneCounts {
+    int32_t T[MV_MAX_LANES];
+};
+
+// ... of every lane: one workgroup per lane, each on its own map's pose / need_interp tables
+__global__ __launch_bounds__(256) void pose_interpolate_lanes_kernel(const mvMapStores* __restrict__ stores, MapLaneCounts n, uint8_t* __restrict__ mask,
+                                                                     int64_t mask_stride) {
+    const int l = blockIdx.x;
+    const mvMapStores st = stores[l];   // (wave-uniform loads)
+    const int T = n.T[l];
+    if (!st.pose || !st.need_interp || (int64_t)T > st.cap_frames) return;
+    pose_interpolate_table(st.pose, st.need_interp, T, mask + (int64_t)l * mask_stride);
+}
+
 }  // namespace
 
 extern "C" int mv_map_append(const mvMapFrame* frame, const mvMapStores* stores, mvStream_t stream) {
@@ -573,5 +512,24 @@ extern "C" int mv_motion_interpolate(float* pose, const uint8_t* need_interp, in
     MV_CHECK_ARG(pose && need_interp && scratch);
     hipLaunchKernelGGL(motion_interpolate_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pose, need_interp, T, scratch,
                        out_count);
+    return mv_launch_status();
+}
+
+extern "C" int mv_pose_interpolate(float* pose, uint8_t* need_interp, int T, uint8_t* mask, mvStream_t stream) {
+    MV_CHECK_ARG(T >= 0);
+    if (T == 0) return MV_OK;
+    MV_CHECK_ARG(pose && need_interp && mask);
+    hipLaunchKernelGGL(pose_interpolate_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pose, need_interp, T, mask);
+    return mv_launch_status();
+}
+
+extern "C" int mv_pose_interpolate_lanes(const mvMapStores* stores_dev, int lanes, const int32_t* T, uint8_t* mask, int64_t mask_stride, mvStream_t stream) {
+    MV_CHECK_ARG(stores_dev && lanes >= 1 && lanes <= MV_MAX_LANES && T && mask);
+    MapLaneCounts n{};
+    for (int l = 0; l < lanes; ++l) {
+        MV_CHECK_ARG(T[l] >= 0 && (int64_t)T[l] <= mask_stride);
+        n.T[l] = T[l];
+    }
+    hipLaunchKernelGGL(pose_interpolate_lanes_kernel, dim3(lanes), dim3(256), 0, (hipStream_t)stream, stores_dev, n, mask, mask_stride);
     return mv_launch_status();
 }

@@ -257,6 +257,18 @@ class DeviceVisualMap:
                                                scratch.data_ptr(), cnt.data_ptr(), ops._stream()), "mv_motion_interpolate")
         return int(cnt.item())
 
+    def pose_interpolate(self) -> torch.Tensor:
+        """``PoseInterpolate.elaborate_map`` (MapProcessor.py:28-49) on the frame poses, in place (``mv_pose_interpolate``).  As the reference does, it also
+        CLEARS ``need_interp`` on the first and last five rows of the stored table.  Returns the uint8 ``[n_frames]`` mask of the rows it rewrote (the
+        reference's ``bad_idx`` as a mask), on the device: nothing is read back."""
+        from . import ops
+
+        nf = self.n_frames
+        mask = torch.zeros((nf,), dtype=torch.uint8, device=self.dev)
+        L.check(self.lib.mv_pose_interpolate(self.frames["pose"].data_ptr(), self.frames["need_interp"].data_ptr(), nf, mask.data_ptr(), ops._stream()),
+                "mv_pose_interpolate")
+        return mask
+
     def write(self, folder: str) -> None:
         """``poses.npy`` + ``tensor_map.npz`` of ``Odometry/Interface.py:51-52``."""
         os.makedirs(folder, exist_ok=True)
@@ -376,24 +388,50 @@ class DeviceVisualMaps:
         L.check(self.lib.mv_map_set_pose_lanes(self.stores_dev(), self.lanes, int(frame_idx), pd.data_ptr(), ops._stream()), "mv_map_set_pose_lanes")
         self._keep_pose = pd
 
-    def evaluate(self, ref_tracks, align: str = "umeyama", correct_scale: bool = False, errors: bool = False):
+    def evaluate(self, ref_tracks, align: str = "umeyama", correct_scale: bool = False, errors: bool = False, ref_times=None, align_origin: bool = True):
         """ATE / RTE / ROE / RPE of every lane's body poses (``body_poses()``: what ``poses.npy`` holds) against ``ref_tracks`` (one ``[n_frames, 7]`` GPU
         tensor per lane, or ``[lanes, T, 7]``) in one launch: ``ops.eval_trajectory`` (MetricsSeq.py / EvalSeq.py; evo restated, parity-unpinned).  Returns
-        its device-resident result without synchronising."""
+        its device-resident result without synchronising.
+
+        With ``ref_times`` (one int64 nanosecond clock per lane, any length) the reference need not share the map's frames: each lane's body poses and the
+        map's own ``time_ns`` are first associated to the reference's stamps (``ops.associate_trajectory``: ``align_origin`` unless switched off, both
+        clocks rebased in integers, ``est->gt``), as ``Trajectory.from_sandbox`` does, in one more launch on the same stream."""
         from . import ops
 
-        return ops.eval_trajectory([m.body_poses() for m in self.maps], ref_tracks, align, correct_scale, errors)
+        est = [m.body_poses() for m in self.maps]
+        if ref_times is None:
+            return ops.eval_trajectory(est, ref_tracks, align, correct_scale, errors)
+        return ops.eval_trajectory(est, ref_tracks, align, correct_scale, errors, est_time=[m.frames["time_ns"][: m.n_frames] for m in self.maps],
+                                   ref_time=ref_times, align_time="est->gt", align_origin=align_origin)
+
+    def pose_interpolate(self) -> "list[torch.Tensor]":
+        """``PoseInterpolate.elaborate_map`` (MapProcessor.py:28-49) on every lane's frame poses in ONE launch (``mv_pose_interpolate_lanes``: one
+        workgroup per lane through the device descriptor array); clears the edge ``need_interp`` flags as the single-map form does.  Returns each
+        lane's uint8 ``[n_frames]`` mask of rewritten rows, on the device."""
+        from . import ops
+
+        T = [m.n_frames for m in self.maps]
+        stride = max(max(T), 1)
+        mask = torch.zeros((self.lanes, stride), dtype=torch.uint8, device=self.dev)
+        L.check(self.lib.mv_pose_interpolate_lanes(self.stores_dev(), self.lanes, (C.c_int32 * self.lanes)(*T), mask.data_ptr(), stride, ops._stream()),
+                "mv_pose_interpolate_lanes")
+        return [mask[l, :n] for l, n in enumerate(T)]
 
     def serialize(self) -> "list[dict[str, np.ndarray]]":
         return [m.serialize() for m in self.maps]
 
-    def write(self, folders, interpolate: bool = True) -> None:
-        """Finish and write every lane (once per sequence): ``MotionInterpolate`` (``Module/MapProcessor.py:52-76``) unless ``interpolate`` is off, then
-        ``poses.npy`` + ``tensor_map.npz`` (``Odometry/Interface.py:47-53``) into ``folders[l]``."""
+    def write(self, folders, interpolate: "bool | str" = True) -> None:
+        """Finish and write every lane (once per sequence): the map processor — ``True`` / ``"motion"``: ``MotionInterpolate``
+        (``Module/MapProcessor.py:52-76``), ``"pose"``: ``PoseInterpolate`` (:28-49, one launch for all lanes), ``False``: none — then ``poses.npy`` +
+        ``tensor_map.npz`` (``Odometry/Interface.py:47-53``) into ``folders[l]``."""
         folders = list(folders)
         if len(folders) != self.lanes:
             raise ValueError(f"{len(folders)} folders for {self.lanes} lanes")
+        if interpolate not in (True, False, None, "motion", "pose"):
+            raise ValueError(f"interpolate: True / \"motion\", \"pose\" or False, got {interpolate!r}")
+        if interpolate == "pose":
+            self.pose_interpolate()
         for m, folder in zip(self.maps, folders):
-            if interpolate:
+            if interpolate is True or interpolate == "motion":
                 m.motion_interpolate()
             m.write(folder)

@@ -277,8 +277,10 @@ def evaluate_depthcov(depth, seq, max_depth: float = 80.0):
 # ------------------------------------------------------------------------------------------------ sequence metrics (MetricsSeq.py, EvalSeq.py)
 # ATE / RTE / ROE / RPE of finished tracks through ``ops.eval_trajectory`` (one launch for every lane).  The reference hands these to evo 1.x; evo is
 # not a dependency here, so its published definition is RESTATED and stays parity-UNPINNED (include/macvo_hip.h).  Tracks are
-# ``[T, 7]`` rows (tx ty tz qx qy qz qw), already time-associated: ``Trajectory.from_sandbox``'s ``align_time`` (``interpolate_pose`` in fp32 PyPose
-# arithmetic), the fp32 round trip of its ``align_origin``, sandbox loading, plots and evo's ``is_so3`` exception are out of scope.
+# ``[T, 7]`` rows (tx ty tz qx qy qz qw), already time-associated, or — what ``poses.npy`` holds — ``[T, 8]`` timed rows / :class:`Trajectory` objects,
+# which first go through ``Trajectory.from_sandbox``'s steps on the GPU (``ops.associate_trajectory``: ``align_origin``, the clock rebase,
+# ``align_time`` / ``interpolate_pose``, in fp64 with one rounding — the reference's mixed fp32 / fp64 PyPose chain is not reproduced bit for bit).
+# ``align_scale``, ``align_SE3``, ``as_motion`` / ``MotionSequence``, plots, ``Sandbox`` config parsing and evo's ``is_so3`` exception are out of scope.
 class TrajectoryEvaluationError(RuntimeError):
     """A lane that evo would have raised on: ``status`` is ``TOO_SHORT``, ``DEGENERATE`` or ``NONFINITE``."""
 
@@ -308,6 +310,138 @@ def _track(t, device) -> torch.Tensor:
     return t.to(device)
 
 
+class Trajectory:
+    """``Utility/Trajectory.py:33-206`` on device tensors: ``poses`` ``[T, 7]`` (fp32 or fp64), ``time`` ``[T]`` (fp64 or int64), ``frame_status``
+    ``[T]`` bool.  ``align_time`` / ``align_origin`` run ``ops.associate_trajectory`` (one launch, no synchronisation)."""
+
+    def __init__(self, poses: torch.Tensor, time: torch.Tensor, frame_status: torch.Tensor | None = None):
+        self.poses, self.time = poses, time.to(poses.device)
+        self.frame_status = torch.zeros((poses.shape[0],), dtype=torch.bool, device=poses.device) if frame_status is None else frame_status.to(poses.device)
+
+    def __getitem__(self, index) -> "Trajectory":
+        return Trajectory(self.poses[index], self.time[index], self.frame_status[index])
+
+    @classmethod
+    def _untimed(cls, data, timestamp, frame_status, device) -> "Trajectory":
+        poses = torch.tensor(np.asarray(data, dtype=float)).to(device)
+        if timestamp is None:
+            timestamp = torch.arange(0, poses.shape[0], step=1)
+        assert frame_status is None or frame_status.dtype == torch.bool
+        return cls(poses, timestamp, frame_status)
+
+    @classmethod
+    def _timed(cls, data, frame_status, device) -> "Trajectory":
+        data = np.asarray(data, dtype=float)
+        assert frame_status is None or frame_status.dtype == torch.bool
+        return cls(torch.tensor(data[:, 1:]).to(device), torch.tensor(data[:, 0]), frame_status)
+
+    @classmethod
+    def from_SE3_txt(cls, file, timestamp=None, frame_status=None, device="cuda") -> "Trajectory":
+        return cls._untimed(np.loadtxt(file), timestamp, frame_status, device)
+
+    @classmethod
+    def from_SE3_numpy(cls, file, timestamp=None, frame_status=None, device="cuda") -> "Trajectory":
+        return cls._untimed(np.load(file).astype(float), timestamp, frame_status, device)
+
+    @classmethod
+    def from_timed_SE3_txt(cls, file, frame_status=None, device="cuda") -> "Trajectory":
+        return cls._timed(np.loadtxt(file, dtype=float), frame_status, device)
+
+    @classmethod
+    def from_timed_SE3_numpy(cls, file, frame_status=None, device="cuda") -> "Trajectory":
+        return cls._timed(np.load(file).astype(float), frame_status, device)
+
+    @classmethod
+    def from_pair(cls, est_rows8, gt_rows8, align_time: str | None = "est->gt", frame_status=None, device="cuda"):
+        """The arithmetic of ``from_sandbox`` (Trajectory.py:103-116) on ``[T, 8]`` timed rows -> ``(gt, est)``: the estimate moved onto the reference's
+        first pose, both clocks rebased, then ``align_time``."""
+        est, gt = cls._timed(est_rows8, frame_status, device), cls._timed(gt_rows8, None, device)
+        est = est.align_origin(gt)
+        gt.time = gt.time - gt.time[0]
+        est.time = est.time - est.time[0]
+        if align_time == "est->gt":
+            est = est.align_time(gt.time)
+        elif align_time == "gt->est":
+            gt = gt.align_time(est.time)
+        else:
+            assert align_time is None, align_time
+        return gt, est
+
+    @classmethod
+    def from_sandbox(cls, folder, align_time: str | None = "est->gt", device="cuda"):
+        """``Trajectory.from_sandbox`` for a result folder: ``poses.npy``, ``ref_poses.npy`` and the optional ``frame_status.pth`` -> ``(gt, est)``."""
+        import os
+
+        for f in ("poses.npy", "ref_poses.npy"):
+            assert os.path.exists(os.path.join(folder, f)), f"Unable to load {f} from {folder}"
+        flag = os.path.join(folder, "frame_status.pth")
+        frame_status = torch.load(flag, weights_only=True) if os.path.exists(flag) else None
+        return cls.from_pair(np.load(os.path.join(folder, "poses.npy")), np.load(os.path.join(folder, "ref_poses.npy")), align_time, frame_status, device)
+
+    @property
+    def length(self) -> int:
+        return int(self.poses.shape[0])
+
+    @property
+    def translation(self) -> torch.Tensor:
+        return self.poses[:, :3]
+
+    @property
+    def rotation(self) -> torch.Tensor:
+        return self.poses[:, 3:7]
+
+    def align_time(self, new_time: torch.Tensor) -> "Trajectory":
+        """Trajectory.py:172-176: the poses interpolated at ``new_time`` (no rebase: the clocks are used as they are); ``frame_status`` becomes the
+        ``extrapolated`` flag."""
+        r = ops.associate_trajectory([self.poses], [self.time], [new_time], rebase=False)
+        return Trajectory(r.poses[0], new_time, r.extrapolated[0].bool())
+
+    def align_origin(self, ref: "Trajectory") -> "Trajectory":
+        """Trajectory.py:188-191: every pose left-multiplied by ``ref_0 self_0^-1``, quaternions normalised with ``w >= 0``, cast to fp32 as
+        ``from_evo`` does.  Runs as an association at the track's own stamps, all flagged as placements of the aligned rows."""
+        if self.length == 0:
+            return Trajectory(self.poses.float(), self.time, self.frame_status)
+        # the track queried at its own row indices: the end rows are copies of the aligned rows, an interior row is Exp(Log(P_i P_i-1^-1)) P_i-1 — the
+        # aligned row itself to fp64 rounding, far below the fp32 store
+        idx = torch.arange(self.length, dtype=torch.float64, device=self.poses.device)
+        r = ops.associate_trajectory([self.poses], [idx], [idx], origin_ref=[ref.poses[:1]], rebase=False, out_dtype=torch.float32)
+        return Trajectory(r.poses[0], self.time, self.frame_status)
+
+    def crop(self, from_idx: int | None = None, to_idx: int | None = None) -> "Trajectory":
+        return Trajectory(self.poses[from_idx:to_idx], self.time[from_idx:to_idx], self.frame_status[from_idx:to_idx])
+
+    def scale(self, s: float) -> "Trajectory":
+        """Trajectory.py:200-203 (evo's ``scale``: the translation columns multiplied)."""
+        poses = self.poses.clone()
+        poses[:, :3] *= s
+        return Trajectory(poses, self.time, self.frame_status)
+
+    def __repr__(self) -> str:
+        return f"Trajectory(length={self.length})"
+
+
+def _timed_side(t, device):
+    """-> (poses [T, 7], stamps [T] or None): a :class:`Trajectory`, ``[T, 8]`` timed rows (the stamp first, as ``poses.npy``) or an untimed ``[T, 7]`` track."""
+    if isinstance(t, Trajectory):
+        return t.poses.to(device), t.time.to(device)
+    t = _track(t, device)
+    if t.dim() == 2 and t.shape[1] == 8:
+        return t[:, 1:], t[:, 0].contiguous()
+    return t, None
+
+
+def _timed_pairs(ests, gts, device):
+    """Both sides of a launch -> (est, gt, est_time, gt_time); the stamps are None unless EVERY track of the launch carries some (then the launch does
+    what EvalSeq.py:36 does first: origin, rebase, est->gt)."""
+    e, g = [_timed_side(t, device) for t in ests], [_timed_side(t, device) for t in gts]
+    timed = [a[1] is not None for a in e + g]
+    if any(timed) and not all(timed):
+        raise ValueError("trajectory evaluation: timed ([T, 8] rows / Trajectory) and untimed ([T, 7]) tracks cannot be mixed in one call")
+    if not any(timed):
+        return [a[0] for a in e], [a[0] for a in g], None, None
+    return [a[0] for a in e], [a[0] for a in g], [a[1] for a in e], [a[1] for a in g]
+
+
 def _one_dtype(tracks: list) -> list:
     """``mv_eval_traj_lanes`` takes one dtype per side: a side that mixes fp32 and fp64 is widened (exactly) to fp64."""
     return tracks if len({t.dtype for t in tracks}) <= 1 else [t.double() for t in tracks]
@@ -321,8 +455,9 @@ def _device_of(*tracks) -> torch.device:
 
 
 def _evaluate_metric(which: int, gt, est, correct_scale: bool) -> TrajectoryMetric:
-    dev = _device_of(est, gt)
-    res = ops.eval_trajectory([_track(est, dev)], [_track(gt, dev)], "umeyama", correct_scale, errors=True)
+    dev = _device_of(*[x.poses if isinstance(x, Trajectory) else x for x in (est, gt)])
+    e, g, te, tg = _timed_pairs([est], [gt], dev)
+    res = ops.eval_trajectory(e, g, "umeyama", correct_scale, errors=True, est_time=te, ref_time=tg, align_origin=te is not None)
     row = res.rows[0].cpu().numpy()                                   # the read-back
     status = int(row[L.EVAL_TRAJ_COLS.index("status")])
     if status != L.MV_TRAJ_OK:
@@ -371,19 +506,22 @@ def trajectory_rows(names, rows: np.ndarray) -> list:
 
 
 def EvaluateSequences(tracks, correct_scale: bool = False):
-    """EvalSeq.py:26-83 for tracks held in memory: ``tracks`` is a list of ``(name, gt [T,7], est [T,7] or None)``.  All tracks are scored by one launch per
+    """EvalSeq.py:26-83 for tracks held in memory: ``tracks`` is a list of ``(name, gt [T,7], est [T,7] or None)``; either side may instead be ``[T, 8]``
+    timed rows (what ``poses.npy`` holds) or a :class:`Trajectory` — then every track of the call must be timed, and each launch first does what
+    ``Trajectory.from_sandbox(..., align_time="est->gt")`` does (EvalSeq.py:36), still with one read-back per ``MV_MAX_LANES`` tracks.  All tracks are scored by one launch per
     ``MV_MAX_LANES`` of them and read back once (a side that mixes fp32 and fp64 tracks is widened to fp64 for that launch).  Returns the reference's ``(header, rows)``: a track without an estimate, or one evo would raise on,
     gives a row of None; the last row is ``"Average"`` (it raises ``ValueError`` when no track could be scored, as the reference's ``mean`` does)."""
     tracks = list(tracks)
     have = [i for i, (_, _, est) in enumerate(tracks) if est is not None]
     rows: list = [None] * len(tracks)
     if have:
-        dev = _device_of(*[x for i in have for x in tracks[i][1:]])
+        dev = _device_of(*[x.poses if isinstance(x, Trajectory) else x for i in have for x in tracks[i][1:]])
         parts = []
         for s in range(0, len(have), L.MV_MAX_LANES):
             idx = have[s:s + L.MV_MAX_LANES]
-            parts.append(ops.eval_trajectory(_one_dtype([_track(tracks[i][2], dev) for i in idx]), _one_dtype([_track(tracks[i][1], dev) for i in idx]),
-                                             "umeyama", correct_scale).rows)
+            e, g, te, tg = _timed_pairs([tracks[i][2] for i in idx], [tracks[i][1] for i in idx], dev)
+            parts.append(ops.eval_trajectory(_one_dtype(e), _one_dtype(g), "umeyama", correct_scale, est_time=te, ref_time=tg,
+                                             align_origin=te is not None).rows)
         host = torch.cat(parts).cpu().numpy()                         # the read-back
         for i, r in zip(have, host):
             rows[i] = r

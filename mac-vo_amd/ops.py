@@ -1162,6 +1162,7 @@ class TrajEvalResult:
     rows: torch.Tensor
     errors: torch.Tensor | None
     lengths: list
+    assoc_status: torch.Tensor | None = None      # int32 [L] of the association launch (``eval_trajectory`` with stamps), else None
 
     def column(self, name: str) -> torch.Tensor:
         return self.rows[:, L.EVAL_TRAJ_COLS.index(name)]
@@ -1197,15 +1198,39 @@ def _traj_side(tracks, name: str):
         [int(t.shape[0]) for t in tracks]
 
 
-def eval_trajectory(est, ref, align: str = "umeyama", correct_scale: bool = False, errors: bool = False) -> TrajEvalResult:
+def eval_trajectory(est, ref, align: str = "umeyama", correct_scale: bool = False, errors: bool = False, est_time=None, ref_time=None,
+                    align_time: str | None = None, align_origin: bool = False) -> TrajEvalResult:
     """ATE / RTE / ROE / RPE of every lane's track in one launch (``mv_eval_traj_lanes``; MetricsSeq.py:9-51, EvalSeq.py:53-64 — evo 1.x restated,
     parity-unpinned: evo is not a dependency of this library).  ``est`` / ``ref``: a list of per-lane ``[T_l, 7]`` GPU tensors (fp32 or fp64 per side,
     rows tx ty tz qx qy qz qw, read in place), or one ``[L, T, 7]`` tensor.  The tracks are time-associated: a lane whose estimate and reference
     lengths differ is refused.  ``align``: ``"umeyama"`` (the reference's setting), ``"origin"`` or ``"none"``.  Returns device tensors on the current
-    stream; never synchronises."""
+    stream; never synchronises.
+
+    With ``est_time`` and ``ref_time`` (per-lane stamps, fp64 or int64) the tracks need not be associated: ``associate_trajectory`` runs first on the same
+    stream — what ``Trajectory.from_sandbox`` does before EvalSeq.py:36 scores a track: both clocks rebased, ``align_time`` ``"est->gt"`` (the default
+    with stamps; the estimate interpolated at the reference's stamps) or ``"gt->est"``, and with ``align_origin`` the estimate moved onto the
+    reference's first pose first (``"est->gt"`` only).  The associated track is handed on in fp64 (the store is exact: no rounding between the two
+    launches, where the reference rounds to fp32).  ``assoc_status`` then holds that launch's per-lane status; a lane that is not OK there reaches
+    the evaluation as NaN rows and comes out ``NONFINITE``."""
     lib = L.load()
     if align not in L.TRAJ_ALIGN:
         raise L.MacvoHipError(f"eval_trajectory: align must be one of {sorted(L.TRAJ_ALIGN)}, got {align!r}")
+    assoc_status = None
+    if est_time is not None or ref_time is not None:
+        if est_time is None or ref_time is None:
+            raise L.MacvoHipError("eval_trajectory: est_time and ref_time come together")
+        align_time = "est->gt" if align_time is None else align_time
+        if align_time == "est->gt":
+            a = associate_trajectory(est, est_time, ref_time, origin_ref=ref if align_origin else None, out_dtype=torch.float64)
+            est = a.poses
+        elif align_time == "gt->est" and not align_origin:
+            a = associate_trajectory(ref, ref_time, est_time, out_dtype=torch.float64)
+            ref = a.poses
+        else:
+            raise L.MacvoHipError(f"eval_trajectory: align_time {align_time!r} with align_origin={align_origin} (\"est->gt\", or \"gt->est\" without align_origin)")
+        assoc_status = a.status
+    elif align_time is not None or align_origin:
+        raise L.MacvoHipError("eval_trajectory: align_time / align_origin need est_time and ref_time")
     e, e_dt, e_st, e_T = _traj_side(est, "est")
     r, r_dt, r_st, r_T = _traj_side(ref, "ref")
     lanes = len(e)
@@ -1230,4 +1255,82 @@ def eval_trajectory(est, ref, align: str = "umeyama", correct_scale: bool = Fals
         L.check(lib.mv_eval_traj_lanes(lanes, ep, rp, Ts, e_dt, r_dt, e_st, r_st, L.TRAJ_ALIGN[align], int(bool(correct_scale)), rows.data_ptr(),
                                        _ptr(err), t_max, _stream()), "mv_eval_traj_lanes")
     # (the launch is enqueued; the caching allocator keeps `e` / `r` copies valid for work already on this stream)
-    return TrajEvalResult(rows, err, e_T)
+    return TrajEvalResult(rows, err, e_T, assoc_status)
+
+
+# ------------------------------------------------------------------------------------------- trajectory association (Trajectory.from_sandbox)
+@dataclass
+class TrajAssocResult:
+    """Per lane: ``poses`` ``[Q_l, 7]`` (the requested dtype), ``extrapolated`` uint8 ``[Q_l]`` (the reference's ``~interp_mask``); ``status``: int32
+    ``[L]`` (``_lib.MV_TRAJ_*``).  Device tensors on the current stream."""
+    poses: list
+    extrapolated: list
+    status: torch.Tensor
+
+
+def _traj_clock(times, name: str, lanes: int, dev):
+    """One clock side of ``associate_trajectory`` -> per-lane contiguous 1-D device tensors (fp64 or int64; anything else is widened to fp64)."""
+    if isinstance(times, torch.Tensor):
+        times = [times] if times.dim() == 1 else list(times.unbind(0))
+    times = list(times)
+    if len(times) != lanes:
+        raise L.MacvoHipError(f"{name}: {len(times)} clocks for {lanes} lanes")
+    out = []
+    for t in times:
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise L.MacvoHipError(f"{name}: one 1-D tensor of stamps per lane")
+        if t.dtype not in (torch.float64, torch.int64):
+            t = t.to(torch.int64) if not t.dtype.is_floating_point else t.to(torch.float64)
+        out.append(t.to(dev).contiguous())
+    return out
+
+
+def associate_trajectory(src, src_time, query_time, origin_ref=None, rebase: bool = True, out_dtype=None) -> TrajAssocResult:
+    """``Trajectory.from_sandbox``'s association step (Utility/Trajectory.py:105-114) for every lane in one launch (``mv_traj_associate_lanes``):
+    the optional origin alignment onto ``origin_ref`` (a reference track or its first row per lane), the rebase of both clocks to their own first stamp,
+    and ``interpolate_pose`` (Utility/Math.py:96-121) of ``src`` at ``query_time``.  ``src``: per-lane ``[T_l, >= 7]`` GPU tensors or one stacked tensor,
+    handled as ``eval_trajectory`` handles a side; the clocks: per-lane 1-D fp64 or int64 tensors (one dtype per launch: a mixed call is widened to fp64
+    unless every clock is int64).  ``out_dtype``: fp32 or fp64, default the source's (as the reference's ``P_container``).  fp64 arithmetic, one
+    rounding at the store; PyPose / evo restated, parity-unpinned.  Never synchronises."""
+    lib = L.load()
+    s, s_dt, s_st, s_T = _traj_side(src, "src")
+    lanes = len(s)
+    if not 1 <= lanes <= L.MV_MAX_LANES:
+        raise L.MacvoHipError(f"associate_trajectory: {lanes} lanes (1 <= lanes <= {L.MV_MAX_LANES})")
+    dev = s[0].device
+    ts = _traj_clock(src_time, "src_time", lanes, dev)
+    tq = _traj_clock(query_time, "query_time", lanes, dev)
+    if len({t.dtype for t in ts + tq}) > 1:
+        ts, tq = [t.double() for t in ts], [t.double() for t in tq]
+    t_dt = L.MV_TRAJ_TIME_I64 if ts[0].dtype == torch.int64 else L.MV_TRAJ_TIME_F64
+    Q = [int(t.shape[0]) for t in tq]
+    for l in range(lanes):
+        if ts[l].shape[0] != s_T[l]:
+            raise L.MacvoHipError(f"associate_trajectory: lane {l} has {s_T[l]} poses and {ts[l].shape[0]} stamps")
+        if max(s_T[l], Q[l]) > L.EVAL_TRAJ_MAX_POSES:
+            raise L.MacvoHipError(f"associate_trajectory: lane {l} has {s_T[l]} poses and {Q[l]} queries (at most 2^20 each)")
+    o_dt, org = L.MV_TRAJ_F64, None
+    if origin_ref is not None:
+        if isinstance(origin_ref, torch.Tensor):                  # one lane's track or first row, or the stacked [L, T, 7] / [L, 7]
+            origin_ref = [origin_ref] if origin_ref.dim() == 1 or (origin_ref.dim() == 2 and lanes == 1) else list(origin_ref.unbind(0))
+        o, o_dt, _, o_T = _traj_side([r.reshape(1, -1) if isinstance(r, torch.Tensor) and r.dim() == 1 else r for r in origin_ref], "origin_ref")
+        if len(o) != lanes or any(n < 1 for n in o_T):
+            raise L.MacvoHipError("associate_trajectory: origin_ref needs one reference track (or first row) per lane")
+        org = [t[0, :7].contiguous() for t in o]
+    if out_dtype is None:
+        out_dtype = s[0].dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise L.MacvoHipError(f"associate_trajectory: out_dtype fp32 or fp64, got {out_dtype}")
+    poses = [torch.empty((q, 7), dtype=out_dtype, device=dev) for q in Q]
+    flags = [torch.empty((q,), dtype=torch.uint8, device=dev) for q in Q]
+    status = torch.empty((lanes,), dtype=torch.int32, device=dev)
+
+    def arr(ts_):
+        return (C.c_void_p * lanes)(*[t.data_ptr() if t.numel() else None for t in ts_])
+
+    with torch.cuda.device(dev):
+        L.check(lib.mv_traj_associate_lanes(lanes, arr(s), arr(ts), (C.c_int32 * lanes)(*s_T), arr(tq), (C.c_int32 * lanes)(*Q),
+                                            None if org is None else arr(org), s_dt, t_dt, o_dt, L.MV_TRAJ_F64 if out_dtype == torch.float64 else L.MV_TRAJ_F32,
+                                            s_st, int(bool(rebase)), arr(poses), arr(flags), status.data_ptr(), _stream()), "mv_traj_associate_lanes")
+    # (the launch is enqueued; the caching allocator keeps the copies made above valid for work already on this stream)
+    return TrajAssocResult(poses, flags, status)

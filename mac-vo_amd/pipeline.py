@@ -163,6 +163,18 @@ def keyframe_config_fields(block) -> dict:
     return {"keyframe_freq": k}
 
 
+_POSTPROCESS_TYPES = {"MotionInterpolate": "motion", "PoseInterpolate": "pose"}
+
+
+def postprocess_config_fields(block) -> dict:
+    """A reference ``Odometry.postprocess`` block (``{type, args}``; Module/MapProcessor.py) -> ``{"interpolate"}``: the choice
+    ``DeviceVisualMaps.write(..., interpolate=)`` takes — ``MotionInterpolate`` -> ``"motion"``, ``PoseInterpolate`` -> ``"pose"``."""
+    t = _ns_get(block, "type")
+    if t not in _POSTPROCESS_TYPES:
+        raise ValueError(f"map processor {t!r} has no HIP form (one of {sorted(_POSTPROCESS_TYPES)})")
+    return {"interpolate": _POSTPROCESS_TYPES[t]}
+
+
 def check_keyframes(cfg: "HotPathConfig") -> None:
     if cfg.solve_frame not in SOLVE_FRAMES:
         raise ValueError(f"solve_frame must be one of {SOLVE_FRAMES}, not {cfg.solve_frame!r}")

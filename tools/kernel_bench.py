@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Stand-alone timing of individual C-ABI kernels on the GPU box (HIP events, median of N launches).
 
-    python tools/kernel_bench.py [volume_f32 volume_f16 lookup select cov pgo eval eval_traj ...] [--iters 50]
+    python tools/kernel_bench.py [volume_f32 volume_f16 lookup select cov pgo eval eval_traj traj_assoc ...] [--iters 50]
 
 Used for A/B tuning and as the target of `rocprofv3 --pmc ...` runs (one kernel family per process).
 """
@@ -457,6 +457,60 @@ def main():
                 hm, tm = statistics.median(res["eval_traj HIP"]), statistics.median(res["eval_traj torch closed form"])
                 print(f"{'eval_traj numpy restatement':30s} lanes {lanes:2d} x {T} poses: {host_us:9.0f} us (one call, read-back included); max |HIP - numpy| / |numpy| = {worst:.3e}")
                 print(f"eval_traj lanes {lanes}: torch / HIP = {tm / hm:.2f}x, numpy / HIP = {host_us / hm:.0f}x; one launch, {lanes * T * 7 * 16 / 1e6:.2f} MB of poses")
+        elif w == "traj_assoc":
+            # ops.associate_trajectory (csrc/traj_assoc.hip: interpolate_pose, one query per thread, the lane in blockIdx.y) next to the same placement in
+            # torch on the same device: searchsorted + the batched quaternion / se3 operations of oracle/se3.py, one lane after the other (the lanes'
+            # lengths differ in general).  Sources are 10 x denser than the queries; same method as the eval_traj leg.
+            from oracle import se3
+
+            def torch_assoc(src, ts, tq):                           # per lane [T, 7], [T], [Q] fp64 -> [Q, 7]
+                out = []
+                for P, t, q in zip(src, ts, tq):
+                    t, q = t - t[0], q - q[0]
+                    e = torch.searchsorted(t, q, right=False).clamp(1, t.shape[0] - 1)
+                    s = e - 1
+                    prop = ((q - t[s]) / (t[e] - t[s])).unsqueeze(-1)
+                    Ps, Pe = P[s], P[e]
+                    r = se3.se3_mul(se3.se3_exp(prop * se3.se3_log(se3.se3_mul(Pe, se3.se3_inv(Ps)))), Ps)
+                    r = torch.where((q <= t[0]).unsqueeze(-1), P[0], torch.where((q >= t[-1]).unsqueeze(-1), P[-1], r))
+                    out.append(r)
+                return out
+
+            for lanes, Q in ((1, 1360), (32, 4096)):
+                T = 10 * Q
+                g = torch.Generator().manual_seed(5)
+                pos = torch.cumsum(torch.randn(lanes, T, 3, generator=g, dtype=torch.float64) * 0.03, 1)
+                quat = torch.cumsum(torch.randn(lanes, T, 4, generator=g, dtype=torch.float64) * 0.001, 1) + torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64)
+                src = list(torch.cat([pos, quat / quat.norm(dim=-1, keepdim=True)], -1).to(dev).unbind(0))
+                ts = list((torch.cumsum(torch.rand(lanes, T, generator=g, dtype=torch.float64) * 0.01 + 0.005, 1) + 50.0).to(dev).unbind(0))
+                tq = [t[0] - 0.02 + (t[-1] - t[0] + 0.04) * torch.rand(Q, generator=g, dtype=torch.float64).to(dev) for t in ts]
+                legs = [("traj_assoc HIP", lambda: ops.associate_trajectory(src, ts, tq).poses), ("traj_assoc torch searchsorted", lambda: torch_assoc(src, ts, tq))]
+                h, t_ = legs[0][1](), legs[1][1]()
+                torch.cuda.synchronize()
+                worst = max(float((a_ - b_).abs().max()) for a_, b_ in zip(h, t_))
+                print(f"lanes {lanes}: max |HIP - torch| over the poses: {worst:.3e}")
+                rounds, per = 5, max(8, (4 * a.iters) // 5)
+                res = {k: [] for k, _ in legs}
+                for k, fn in legs:
+                    for _ in range(5):
+                        fn()
+                torch.cuda.synchronize()
+                for _ in range(rounds):
+                    for k, fn in legs:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(per):
+                            fn()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        res[k].append(e0.elapsed_time(e1) * 1e3 / per)
+                for k, _ in legs:
+                    v = res[k]
+                    print(f"{k:30s} lanes {lanes:2d} x {Q} queries over {T} poses: median {statistics.median(v):9.1f} us / call (rounds {min(v):.1f} .. {max(v):.1f}; "
+                          f"{rounds * per} calls)")
+                hm, tm = statistics.median(res["traj_assoc HIP"]), statistics.median(res["traj_assoc torch searchsorted"])
+                print(f"traj_assoc lanes {lanes}: torch / HIP = {tm / hm:.2f}x; one launch, every workgroup of a lane repeats the lane's checks "
+                      f"({lanes * T * 64 / 1e6:.2f} MB of source rows and stamps)")
         elif w == "select":
             fc = synth.flow_cov_maps(H, W, 2).to(dev)
             d0, d0c = [t.to(dev) for t in synth.depth_maps(H, W, 3)]

@@ -119,6 +119,9 @@ CHECKS = [
      "evaluation metrics: no scratch, four waves per SIMD, the LDS-privatised recorder grids + digit histograms within the 64 KB static limit (two workgroups per CU)"),
     (r"^traj_eval_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0,
      "trajectory evaluation: the 3 x 3 SVD and every SE(3) product in registers (constant indices only): zero scratch, zero spills"),
+    (r"^traj_assoc_kernel|^pose_interpolate(_lanes)?_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and
+     r["sgpr_spill_count"] == 0,
+     "trajectory association / PoseInterpolate: the se3 Log / Exp chain of se3_interp.h in registers (constant indices only): zero scratch, zero spills"),
 ]
 
 
