@@ -13,8 +13,8 @@
 //   back   pose-independent half of frame t's backend: gather, tracking, back-projection, covariances (one launch)
 //   side   filters + rotation into the world frame + LM solve (one launch; the GPU analogue of the reference's optimizer child process,
 //          Optimization/Interface.py:80-96)
-// Round-5 layout (one- and two-lane pipes; `layout_alt` below): vol | main = even frames' decoder side | a second decoder-side stream = odd frames' |
-//   side = backend + solve of every frame, in order; the GEMM leaves 32 CUs without a workgroup (see mv_frame_pipe_create).
+// Round-5 layout (one- and two-lane pipes; `Knobs::alt` below): vol | main = even frames' decoder side | a second decoder-side stream = odd frames' |
+//   side = backend + solve of every frame, in order; the GEMM leaves 32 CUs without a workgroup (Knobs::free_cus).
 // Frame t+1's frontend is enqueued before frame t's `finish`, so the selector's host round trip (candidate count ->
 // torch.randperm on the CPU, kept for bit-exact indices -> permutation back) never idles the GPU.
 // Stream layouts measured on the bench (ms / frame): this one 0.3235; even / odd frames each entirely on their own
@@ -203,17 +203,63 @@ struct EvRing {   // one edge per running frame / finish number: generation g li
     Ev& operator[](long g) { return slot[g % N]; }
 };
 
+// Stream of a frame's selector segment (MV_PIPE_SELECTOR_ON; classic layout only).  `vol`, `late`, `own`: lower latency, lower throughput.
+enum class SelOn {
+    Decoder,   // main: in order behind the frame's lookups
+    Back,      // the backend stream, behind an event on the last lookup: one lane 5.38 k vs 4.94 k frames/s, 32 lanes 7.43 k vs 7.64 k
+    Own,       // a fifth stream
+    Vol,       // the GEMM's stream, deferred until the next frame's GEMM has been queued
+    Late       // the backend stream, handed to the next finish when two unfinished frames are in front (3-deep pipeline; profiles/r04_latency_ab.log)
+};
+// Stream of frame f + 1's operand pack (MV_PIPE_PACK_ON).  One lane, frames/s: in front of the GEMM on its stream 4.28 k, backend stream 4.09 k,
+// decoder-side stream 3.11 k.
+enum class PackOn { Vol, Back, Main, Side };
+enum { SYNC_STREAM = 0, SYNC_HOST = 1, SYNC_NEWEST = 2 };   // mv_frame_pipe_sync's block_host
+
+// Everything the environment, the lane count and the configuration decide about schedule and layout, resolved in ONE place (resolve_knobs) when a pipe is
+// created, sized (mv_frame_pipe_arena_bytes) or asked for its depth (mv_frame_pipe_default_depth).  DESIGN appendix: the variables.
+struct Knobs {
+    // The round-5 layout, default for one- and two-lane pipes without mapping: two decoder-side streams (frame f's lookups on stream f % 2), backend +
+    // solve in order on ONE stream — still four queues; a fifth costs a third of the frame rate (profiles/r05_pipe_ab.log run 15).  MV_PIPE_LAYOUT=classic,
+    // or a placement that exists in the classic layout only (MV_PIPE_SELECTOR_ON, MV_PIPE_LOOKUPS_ON=vol), selects the classic one.
+    bool alt;
+    int n_lk;            // decoder-side streams: 2 (alt) or 1
+    int n_volbuf;        // 3: the GEMM one frame ahead rewrites a buffer read two frames ago (272 vs 245 us per frame with 2); alt: three tracked frames in
+                         // flight + that GEMM = 4 (6.95 k vs 6.74 k frames/s at 300 steps; 5: no gain)
+    int default_depth;   // tracked frames the host should keep in flight: 3 (alt and batched pipes), the classic one-lane pipe 2
+    SelOn sel_on;        // alt: Decoder; classic: MV_PIPE_SELECTOR_ON, else Back for one and two lanes
+    PackOn pack_on;
+    bool lookups_on_main;   // MV_PIPE_LOOKUPS_ON=vol: the lookups stay behind the GEMM on its stream (0.3256 vs 0.3197 ms per frame)
+    int free_cus;        // CUs the GEMM leaves without a persistent workgroup, for the solve's: alt 32 (0 / 8 / 16 / 32 / 48 / 64 = 6.26 / 6.34 / 6.68 / 6.84 /
+                         // 6.87 / 6.82 k frames/s, profiles/r05_pipe_ab.log), classic 0 (no gain); MV_PIPE_FREE_CUS
+    bool alt_indep;      // alt: consecutive frames' selector segments may overlap (ordered segments: -6 %, profiles/r05_pipe_ab.log run 18)
+    // MV_PIPE_LEAN (alt only): a device-driven frame's chain carries fewer packets.  A marker costs the queue ~6 us, a cross-queue barrier ~10
+    // (profiles/r06_chain_gaps.log).  Two decisions:
+    bool no_segment_markers;     // e_cand / e_seg behind a selector segment are recorded on demand only: the front launch follows in stream order
+    bool front_frees_volume;     // a frame's front launch, not a marker behind its lookups, releases its volume buffer
+    bool front_on_decoder;       // alt: a device-driven frame's front launch runs behind its selector segment on the decoder-side stream, the backend stream
+                                 // carries the solves only (300 steps 6.83-6.95 k vs 6.60-6.64 k frames/s, profiles/r06_device_draw_ab.log); MV_PIPE_FRONT_ON=side
+    bool fuse_backend;           // backend = front launch + posed solve; MV_PIPE_FUSE_BACKEND=0: the five-launch form
+    int tiled_wish;              // MV_PIPE_TILED: 1 / 0, -1 unset = on for fp16 cells (32 lanes 11.8 k -> 13.3 k frames/s), off for fp32 cells (7.44 k vs 7.95 k)
+    bool async_wish;             // backend launch thread: the configuration, else MV_PIPE_ASYNC_BACKEND, else on (one lane 6.01 k vs 5.26 k frames/s)
+    bool async_explicit;         // ... and whether either of them chose (a device-driven pipe on a small host otherwise drops the thread: mv_frame_pipe_seed_lanes)
+    double spin_us;              // how long the launch thread spins for a job before it sleeps (MV_PIPE_LAUNCH_SPIN_US; 250 where the process has >= 3 cores)
+    int host_stats;              // MV_PIPE_HOST_STATS=1: mean host latencies, printed by destroy
+    bool device_draw_wish;       // MV_PIPE_DEVICE_DRAW=0: host-drawn frames also where the device draw applies
+};
+
 }  // namespace
 
 struct mvFramePipe {
     mvFramePipeConfig c;
+    Knobs k;     // schedule and layout as resolved at create
     int plane, h8, w8, n8, KK;
     int lanes;   // independent sequences batched through every launch (= pairs / 2)
+    size_t fb_count[MV_FB_PRIOR + 1];   // element count of each buffer mv_frame_pipe_buffer reports, recorded where it is carved
     char* arena;
     size_t arena_bytes;
     // device buffers
-    float* vol[MAX_VOL];
-    int n_volbuf;   // 3 (classic layout) or 4 (round-5 layout): volbufs_for
+    float* vol[MAX_VOL];   // k.n_volbuf of them
     float* tok[2 * MAX_LK];   // two alternating token buffers per decoder-side stream
     void* planes[2];   // bf16x3 split planes of fmap1 / fmap2 (volume_split3)
     // volume_split = MV_PACK_BF16X3: packed three-piece operands of the streaming split GEMM, two sets (the pack of frame f + 1 may
@@ -226,8 +272,6 @@ struct mvFramePipe {
     bool vol16;        // volume_split = MV_VOL_ENC16 on a shape the out16 kernel covers: 2-byte cells (Fast mode as the reference computes it)
     bool tiled;        // MV_PIPE_TILED=1 && packed: operand 2 packed in 4 x 4-tile order -> the volume is tiled for mv_corr_lookup_tiled
                        // (the driver owns both the producer and the consumer of the volume; MV_FB_VOLUME then shows that layout)
-    int pack_on;       // 0 = on the GEMM's stream (in front of it), 1 = backend stream, 2 = decoder-side stream
-    int sel_on_back;   // 1: upsampling / epilogue / selector / count copy of a frame run on the backend stream behind its lookups
     Ev e_lk[N_CAND];   // a frame's last lookup (decoder-side stream)
     Ev e_packed[2];
     float *up_flow, *up_cov;
@@ -242,25 +286,15 @@ struct mvFramePipe {
     float* pose[3];   // [lanes, 7]
     float *intr, *bl;   // [lanes, 4], [lanes]
     int32_t* offs;    // [lanes + 1]: lane l owns rows [l * cap, (l + 1) * cap) of the backend tables
-    int fuse_backend; // 1 (default): backend = mv_backend_front_lanes + mv_pgo_solve_posed, two launches; MV_PIPE_FUSE_BACKEND=0: the five-launch form
     // host
     int32_t* h_count[N_CAND];      // pinned
     int64_t* h_perm[N_PERM];  // pinned
     // streams / events
     hipStream_t s_vol, s_main, s_back, s_side;
-    hipStream_t s_lk[MAX_LK];   // decoder-side streams: frame f's lookups run on s_lk[f % n_lk]; s_lk[0] = s_main
-    int n_lk;
-    int alt;                     // the two-decoder-stream layout: see mv_frame_pipe_create
-    int free_cus;                // CUs the volume GEMM leaves without a persistent workgroup (mv_corr_volume_packed_shared)
+    hipStream_t s_lk[MAX_LK];   // decoder-side streams: frame f's lookups run on s_lk[f % k.n_lk]; s_lk[0] = s_main
     EvRing<N_INEV> e_seg;        // alt: end of frame f's selector segment (the next frame's segment runs on the other decoder-side stream)
-    int alt_indep;               // alt: consecutive frames' segments may overlap (own selector workspace each; NODEPTH selector, no upsampling)
-    void* kp_ws2;                // ... the odd frames' workspace
-    int lean_chain;              // device-driven frames with the front launch on the decoder side: fewer packets on the frame's chain — no e_cand / e_seg markers behind
-                                 // the selector (nobody waits for them: the front launch follows in order), the volume buffer is released by the front launch's event
-                                 // instead of a marker behind the lookups.  A marker costs the queue ~6 us, a cross-queue barrier ~10 (rocprofv3 trace, r06_chain_gaps.log)
+    void* kp_ws2;                // alt_indep: the odd frames' selector workspace
     Ev* vol_free_ev[MAX_VOL];    // what the GEMM that rewrites volume buffer k waits for (e_vol_free[k], or the ring event of the frame's front launch; null: nothing)
-    int front_on_decoder;        // device-driven alt layout: a frame's front launch (draw + gathers + covariances) runs on the frame's decoder-side stream right
-                                 // behind its selector segment (no cross-queue barrier in front of it); the backend stream carries the solves only
 
     hipStream_t s_sel;   // MV_PIPE_SELECTOR_ON=own: a fifth stream for the selector segment (nullptr otherwise)
     SelSeg deferred;     // MV_PIPE_SELECTOR_ON=vol: the newest frame's selector segment, not issued yet
@@ -279,7 +313,6 @@ struct mvFramePipe {
     long n_enq, n_fin;
     long n_vol;            // volume GEMMs issued (n_enq <= n_vol <= n_enq + 1: at most one GEMM ahead of its frame's decoder side)
     Ev* e_in_of[MAX_VOL];  // per volume buffer: the input-ready event its GEMM waited for (the decoder side re-uses it)
-    int lookups_on_main;   // default 1; MV_PIPE_LOOKUPS_ON=vol is the measured alternative
     int pose_cur;
     int prior_slot;        // pose slot the newest finished frame started from (its motion-model prior)
     int solve_frame = MV_SOLVE_WORLD;   // mv_frame_pipe_set_solve_frame
@@ -317,8 +350,8 @@ struct mvFramePipe {
     long last_backend_frame = -1;   // frame index of the newest backend issued with keypoints (launch-thread / inline issuer only)
     // optional timing of the dominant kernel (bench.py roofline): event pairs around each volume GEMM on its stream
     int vol_timed[MAX_VOL];      // timing slot of the GEMM that filled each volume buffer (-1: not timed)
-    std::vector<Ev> tv0, tv1, tv2, tv3;   // GEMM start / end, last lookup done, selector done (timeline hook)
-    std::vector<Ev> tv4, tv5, tv6, tv7;   // backend start / end (backend stream), pose_apply start / solve end (solve stream)
+    std::vector<Ev> tv[8];       // per timing slot: GEMM start / end, last lookup done, selector done; backend start / end (backend stream), pose_apply
+                                 // start / solve end (solve stream)
     int n_timed, timed_cap;
     int time_detail;   // 1 (default): a timed frame also records the six timeline events tv2..tv7 on three streams; 0: only the pair around its GEMM
     // Backend launch thread (round 3).  A one-lane stream is bound by the HOST: ~38 launches per frame at ~4 us each on one thread
@@ -330,8 +363,7 @@ struct mvFramePipe {
     //   launch thread:   Backend tables, e_solved / e_posed / e_pgo / e_perm / e_backend, pinned permutation slots, rng
     // Cross-thread event edges: e_cand and e_release are recorded by the caller BEFORE the job is queued; e_backend is consumed by
     // the caller's enqueue only after `issued` says the launch thread has recorded it.
-    int async_backend;
-    int async_explicit;     // the caller / MV_PIPE_ASYNC_BACKEND chose (the device-driven pipe otherwise drops the launch thread: see mv_frame_pipe_seed_lanes)
+    int async_backend;      // k.async_wish, until something takes the thread away (no device, mv_frame_pipe_seed_lanes)
     int device;
     std::thread worker;
     std::mutex mu;
@@ -340,8 +372,6 @@ struct mvFramePipe {
     long issued;            // finishes whose launches have all been issued (guarded by mu)
     std::atomic<long> n_submitted{0};   // jobs ever queued: what the launch thread spins on
     std::atomic<bool> stop_flag{false};
-    double spin_us;         // how long the launch thread spins for the next job before it sleeps (MV_PIPE_LAUNCH_SPIN_US, default 250)
-    int host_stats;         // MV_PIPE_HOST_STATS=1: mean host latencies of the selector-count -> backend-launch chain, printed by destroy
     double st_n = 0, st_count_to_submit = 0, st_submit_to_pick = 0, st_pick_to_issued = 0, st_wait = 0;
     double st_enq = 0, st_enq_lookups = 0, st_enq_seg = 0, st_vol = 0, st_fin = 0, st_calls = 0;   // us inside enqueue (its lookups / its selector segment), enqueue_volume, finish_device
     bool stop;
@@ -373,41 +403,63 @@ static inline double now_us() {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-#define MV_ASYNC_DEFAULT(p) (1)   // measured (640x480, f16x2 volume): one lane 6.01 k vs 5.26 k frames/s, 32 lanes 7.56 k vs 7.54 k
 static int wait_issued(mvFramePipe* p, long n);
 static int flush_deferred(mvFramePipe* p);
 static int issue_selector_segment(mvFramePipe* p, const SelSeg& d);
 static int flush_jobs(mvFramePipe* p);
 static void launch_thread_main(mvFramePipe* p);
 
-// 1 = the round-5 layout for one- and two-lane pipes (two decoder-side streams; see mv_frame_pipe_create).  MV_PIPE_LAYOUT=classic | alt; an explicit
-// placement knob of the classic layout (MV_PIPE_SELECTOR_ON, MV_PIPE_LOOKUPS_ON=vol) selects the classic layout
-static int layout_alt(int lanes, int mapping) {
-    const char* e = getenv("MV_PIPE_LAYOUT");
-    if (e && strcmp(e, "classic") == 0) return 0;
-    const char* lk = getenv("MV_PIPE_LOOKUPS_ON");
-    if (lanes > 2 || mapping || (lk && strcmp(lk, "vol") == 0) || getenv("MV_PIPE_SELECTOR_ON")) return 0;
-    return 1;
+// THE reader of the environment.  `async_backend`: the configuration's (1 on, -1 off, 0 = not said).
+static Knobs resolve_knobs(int lanes, int mapping, int async_backend) {
+    struct Var {
+        const char* v;
+        bool is(const char* s) const { return v && strcmp(v, s) == 0; }
+        bool off() const { return v && atoi(v) == 0; }
+        int num(int unset) const { return v ? atoi(v) : unset; }
+    };
+    const auto var = [](const char* name) { return Var{getenv(name)}; };
+    const Var sel = var("MV_PIPE_SELECTOR_ON"), pack = var("MV_PIPE_PACK_ON"), lookups = var("MV_PIPE_LOOKUPS_ON"), async = var("MV_PIPE_ASYNC_BACKEND");
+    Knobs k{};
+    k.alt = !var("MV_PIPE_LAYOUT").is("classic") && lanes <= 2 && !mapping && !lookups.is("vol") && !sel.v;
+    k.n_lk = k.alt ? 2 : 1;
+    k.n_volbuf = k.alt ? 4 : 3;
+    k.default_depth = (lanes > 2 || k.alt) ? 3 : 2;
+    k.sel_on = k.alt ? SelOn::Decoder
+             : sel.v ? (sel.is("back") ? SelOn::Back : sel.is("own") ? SelOn::Own : sel.is("vol") ? SelOn::Vol : sel.is("late") ? SelOn::Late : SelOn::Decoder)
+                     : (lanes <= 2 ? SelOn::Back : SelOn::Decoder);
+    k.pack_on = pack.is("back") ? PackOn::Back : pack.is("main") ? PackOn::Main : pack.is("side") ? PackOn::Side : PackOn::Vol;
+    k.lookups_on_main = !lookups.is("vol");
+    k.free_cus = var("MV_PIPE_FREE_CUS").num(k.alt ? 32 : 0);   // (multiples of 8: per XCD)
+    k.alt_indep = k.alt;
+    const bool lean = k.alt && !var("MV_PIPE_LEAN").off();
+    k.front_on_decoder = k.alt && !var("MV_PIPE_FRONT_ON").is("side");
+    k.no_segment_markers = lean && k.front_on_decoder;       // (alt: the segment is on the decoder-side stream, and there is no mapping tail)
+    k.front_frees_volume = lean && k.n_volbuf > MAX_PENDING;  // (the GEMM that rewrites the buffer is issued after the frame's finish: enqueue)
+    k.fuse_backend = !var("MV_PIPE_FUSE_BACKEND").off();
+    k.tiled_wish = var("MV_PIPE_TILED").v ? var("MV_PIPE_TILED").num(0) != 0 : -1;
+    k.async_wish = (async_backend ? async_backend : async.v ? (async.num(0) ? 1 : -1) : 1) > 0;
+    k.async_explicit = async_backend || async.v;
+    // a spinning launch thread needs a core of its own beside the caller's (and Python's): with fewer than three it sleeps on the condition variable instead
+    const Var spin = var("MV_PIPE_LAUNCH_SPIN_US");
+    k.spin_us = spin.v ? atof(spin.v) : (affinity_cores() >= 3 ? 250.0 : 0.0);
+    k.host_stats = var("MV_PIPE_HOST_STATS").num(0);
+    k.device_draw_wish = !var("MV_PIPE_DEVICE_DRAW").off();
+    return k;
 }
 
-// tracked frames the host should keep in flight (pipeline.NativeHotPath.run): the alt layout and batched pipes want 3, the classic one-lane pipe 2
-extern "C" int mv_frame_pipe_default_depth(int lanes, int mapping) { return (lanes > 2 || layout_alt(lanes, mapping)) ? 3 : 2; }
-
-static int volbufs_for(int lanes, int mapping) {
-    // 3: with a GEMM issued one frame ahead (mv_frame_pipe_enqueue_volume) the buffer it rewrites was last read by the lookups of frame t - 1, long
-    // finished; with 2 (rounds 1-2; an A/B knob until round 5) it waited for frame t's lookups, which run beside the previous GEMM at a third of their
-    // isolated speed (measured 272 vs 245 us per frame)
-    // alt layout: three tracked frames in flight + the GEMM one ahead = 4 (measured 6.95 k vs 6.74 k frames/s at 300 steps with 3, the same at 20; 5: no gain)
-    return layout_alt(lanes, mapping) ? 4 : 3;
-}
+extern "C" int mv_frame_pipe_default_depth(int lanes, int mapping) { return resolve_knobs(lanes, mapping, 0).default_depth; }
 
 static size_t carve(mvFramePipe* p, char* base) {
     const mvFramePipeConfig& c = p->c;
     Carver a{base};
     const size_t L = p->lanes;
     const size_t plane = p->plane, n8 = p->n8, B = c.pairs, N = (size_t)cap_of(c);
-    for (int k = 0; k < p->n_volbuf; ++k) p->vol[k] = a.take<float>(B * n8 * n8);
-    for (int k = 0; k < 2 * (L <= 2 ? MAX_LK : 1); ++k) p->tok[k] = a.take<float>(B * p->KK * n8);
+    // Every buffer mv_frame_pipe_buffer reports has a leading [lanes] dimension (VALS: [11, lanes, cap]; N = capacity rows, a lane's live rows: its n_sel).
+    // `n` notes its element count, here and nowhere else, and hands it on to `take`.
+    size_t* const n = p->fb_count;
+    for (int k = 0; k < p->k.n_volbuf; ++k) p->vol[k] = a.take<float>(B * n8 * n8);
+    n[MV_FB_VOLUME] = B * n8 * p->n2t;   // in cells, n2t per slice: 2-byte cells of a tiled slice padded to whole tiles still fit the buffer's n8 * n8 * 4 bytes
+    for (int k = 0; k < 2 * (L <= 2 ? MAX_LK : 1); ++k) p->tok[k] = a.take<float>(n[MV_FB_TOKENS] = B * p->KK * n8);
     for (int k = 0; k < 2; ++k)
         p->planes[k] = (c.volume_split == 2 || c.volume_split == 3) ? (void*)a.take<uint16_t>(3 * B * n8 * c.C) : nullptr;
     // (ceil(n8 / 32) + 1 row blocks per pair: the rounded-up last block and the replica block the GEMM's ragged last sub-tile reads — n8 % 64 != 0, 376 x 784 and
@@ -423,12 +475,12 @@ static size_t carve(mvFramePipe* p, char* base) {
     p->up_cov = (no_d && no_m) ? nullptr : a.take<float>(B * 2 * plane);
     for (int k = 0; k < N_MAPS; ++k) {   // every map is [lanes, ch, H, W]
         Maps& m = p->maps[k];
-        m.disparity = a.take<float>(L * plane);
-        m.disparity_cov = no_d ? nullptr : a.take<float>(L * plane);
-        m.depth = a.take<float>(L * plane);
-        m.depth_cov = no_d ? nullptr : a.take<float>(L * plane);
-        m.match_flow = a.take<float>(L * 2 * plane);
-        m.match_cov = no_m ? nullptr : a.take<float>(L * 3 * plane);
+        m.disparity = a.take<float>(n[MV_FB_DISPARITY] = L * plane);
+        m.disparity_cov = no_d ? nullptr : a.take<float>(n[MV_FB_DISPARITY_COV] = L * plane);
+        m.depth = a.take<float>(n[MV_FB_DEPTH] = L * plane);
+        m.depth_cov = no_d ? nullptr : a.take<float>(n[MV_FB_DEPTH_COV] = L * plane);
+        m.match_flow = a.take<float>(n[MV_FB_MATCH_FLOW] = L * 2 * plane);
+        m.match_cov = no_m ? nullptr : a.take<float>(n[MV_FB_MATCH_COV] = L * 3 * plane);
         m.bad_mask = a.take<uint8_t>(L * plane);
     }
     p->kp_ws_bytes = L * mv_kp_select_workspace_bytes(c.H, c.W);
@@ -436,31 +488,31 @@ static size_t carve(mvFramePipe* p, char* base) {
     p->kp_ws2 = L <= 2 ? a.take<char>(p->kp_ws_bytes) : nullptr;
 
     for (int k = 0; k < N_CAND; ++k) {
-        p->cand[k] = a.take<int32_t>(L * plane);
-        p->count[k] = a.take<int32_t>(L * 4);
-        p->stats[k] = a.take<float>(L * 4);
+        p->cand[k] = a.take<int32_t>(n[MV_FB_CAND] = L * plane);
+        p->count[k] = a.take<int32_t>(n[MV_FB_COUNT] = L * 4);
+        p->stats[k] = a.take<float>(n[MV_FB_STATS] = L * 4);
     }
     for (int k = 0; k < 2; ++k) {
         Backend& b = p->be[k];
-        b.perm = a.take<int64_t>(L * N);
-        b.kp0 = a.take<int64_t>(L * 2 * N);
-        b.kp0f = a.take<float>(L * 2 * N);
-        b.kp1 = a.take<float>(L * 2 * N);
-        b.vals = a.take<float>(L * 11 * N);
-        b.sigma0 = a.take<float>(L * 3 * N);
-        b.sigma1 = a.take<float>(L * 3 * N);
-        b.pos_Tc = a.take<float>(L * 3 * N);
-        b.pos_Tw = a.take<float>(L * 3 * N);
-        b.inbound = a.take<uint8_t>(L * N);
-        b.valid = a.take<uint8_t>(L * N);
-        b.rot = a.take<double>(L * 9);
-        b.cov0 = a.take<double>(L * 9 * N);
-        b.cov0w = a.take<double>(L * 9 * N);
-        b.cov1 = a.take<double>(L * 9 * N);
-        b.pose64 = a.take<double>(L * 7);
-        b.info = a.take<double>(L * 4);
-        b.n_valid = a.take<int32_t>(L);
-        b.live_dev = a.take<int32_t>(2 * L);
+        b.perm = a.take<int64_t>(n[MV_FB_PERM] = L * N);
+        b.kp0 = a.take<int64_t>(n[MV_FB_KP0] = L * 2 * N);
+        b.kp0f = a.take<float>(n[MV_FB_KP0F] = L * 2 * N);
+        b.kp1 = a.take<float>(n[MV_FB_KP1] = L * 2 * N);
+        b.vals = a.take<float>(n[MV_FB_VALS] = L * 11 * N);
+        b.sigma0 = a.take<float>(n[MV_FB_SIGMA0] = L * 3 * N);
+        b.sigma1 = a.take<float>(n[MV_FB_SIGMA1] = L * 3 * N);
+        b.pos_Tc = a.take<float>(n[MV_FB_POS_TC] = L * 3 * N);
+        b.pos_Tw = a.take<float>(n[MV_FB_POS_TW] = L * 3 * N);
+        b.inbound = a.take<uint8_t>(n[MV_FB_INBOUND] = L * N);
+        b.valid = a.take<uint8_t>(n[MV_FB_VALID] = L * N);
+        b.rot = a.take<double>(n[MV_FB_ROT] = L * 9);
+        b.cov0 = a.take<double>(n[MV_FB_COV0] = L * 9 * N);
+        b.cov0w = a.take<double>(n[MV_FB_COV0W] = L * 9 * N);
+        b.cov1 = a.take<double>(n[MV_FB_COV1] = L * 9 * N);
+        b.pose64 = a.take<double>(n[MV_FB_POSE64] = L * 7);
+        b.info = a.take<double>(n[MV_FB_INFO] = L * 4);
+        b.n_valid = a.take<int32_t>(n[MV_FB_NVALID] = L);
+        b.live_dev = a.take<int32_t>(n[MV_FB_LIVE] = 2 * L);
     }
     for (int k = 0; k < 2; ++k) p->rp_state[k] = a.take<uint32_t>(L * (size_t)mv_randperm_state_words());
     if (c.mapping) {
@@ -470,23 +522,24 @@ static size_t carve(mvFramePipe* p, char* base) {
             p->count_m[k] = a.take<int32_t>(4);
             p->stats_m[k] = a.take<float>(4);
         }
+        // (the dense-mapping tail's buffers are reported with the rows of the newest tail: `n` notes the elements per ROW)
         p->mp_perm = a.take<int64_t>(MP);
         p->mp_uv = a.take<int64_t>(2 * MP);
-        p->mp_uvf = a.take<float>(2 * MP);
-        p->mp_d = a.take<float>(MP);
-        p->mp_sdd = a.take<float>(MP);
+        p->mp_uvf = a.take<float>((n[MV_FB_MAP_UV] = 2) * MP);
+        p->mp_d = a.take<float>((n[MV_FB_MAP_D] = 1) * MP);
+        p->mp_sdd = a.take<float>((n[MV_FB_MAP_SDD] = 1) * MP);
         p->mp_sigma = a.take<float>(3 * MP);
-        p->mp_Tc = a.take<float>(3 * MP);
-        p->mp_Tw = a.take<float>(3 * MP);
-        p->mp_cov = a.take<double>(9 * MP);
-        p->mp_color = a.take<uint8_t>(3 * MP);
+        p->mp_Tc = a.take<float>((n[MV_FB_MAP_TC] = 3) * MP);
+        p->mp_Tw = a.take<float>((n[MV_FB_MAP_TW] = 3) * MP);
+        p->mp_cov = a.take<double>((n[MV_FB_MAP_COV] = 9) * MP);
+        p->mp_color = a.take<uint8_t>((n[MV_FB_MAP_COLOR] = 3) * MP);
     }
-    for (int k = 0; k < 3; ++k) p->pose[k] = a.take<float>(L * 7);
+    for (int k = 0; k < 3; ++k) p->pose[k] = a.take<float>(n[MV_FB_POSE] = L * 7);
     if (c.motion_model == MV_MOTION_TARTAN) {
-        for (int k = 0; k < N_MAPS; ++k) p->motion_in[k] = a.take<float>(L * (size_t)motion::OUT_C * motion::OUT_H * motion::OUT_W);
+        for (int k = 0; k < N_MAPS; ++k) p->motion_in[k] = a.take<float>(n[MV_FB_MOTION_IN] = L * (size_t)motion::OUT_C * motion::OUT_H * motion::OUT_W);
         for (int k = 0; k < N_MOT; ++k) {
             p->motion_raw[k] = a.take<float>(L * 6);
-            p->prior[k] = a.take<float>(L * 7);
+            p->prior[k] = a.take<float>(n[MV_FB_PRIOR] = L * 7);
         }
         p->pose_norm = a.take<float>(6);
     }
@@ -580,23 +633,51 @@ static int check_config(const mvFramePipeConfig* c) {
     return MV_OK;
 }
 
+// Everything that follows from the configuration, the lane count and the environment alone: the shapes, the knobs, which volume kernels cover the shape.
+// What mv_frame_pipe_arena_bytes sizes and what mv_frame_pipe_create carves are the same because both start here.
+static void derive_shape(mvFramePipe* p, const mvFramePipeConfig* cfg) {
+    p->c = *cfg;
+    p->plane = cfg->H * cfg->W;
+    p->h8 = eighth_dims(cfg->H, cfg->W).h8;
+    p->w8 = eighth_dims(cfg->H, cfg->W).w8;
+    p->n8 = p->h8 * p->w8;
+    p->KK = (2 * cfg->radius + 1) * (2 * cfg->radius + 1);
+    p->lanes = cfg->pairs / 2;
+    p->k = resolve_knobs(p->lanes, cfg->mapping, cfg->async_backend);
+    p->packed = (cfg->volume_split == MV_PACK_BF16X3 || cfg->volume_split == MV_PACK_F16X2) &&
+                mv_corr_volume_packed_supported(cfg->pairs, cfg->C, p->n8, p->n8, cfg->volume_split);
+    // shapes outside the out16 kernel's domain keep the fp32-stored volume of the same 16-bit GEMM
+    p->vol16 = cfg->volume_split == MV_VOL_ENC16 && mv_corr_volume_out16_supported(cfg->pairs, cfg->C, p->n8, p->n8, cfg->feat_dtype, cfg->layout);
+    // Tiled volume + tiled lookup (Knobs::tiled_wish).  Fast mode's 2-byte cells: a tile is one 32-byte sector (mv_corr_lookup_tiled_vol16: B = 64 alone 115 -> 79 us)
+    const bool want = p->k.tiled_wish < 0 ? p->vol16 : p->k.tiled_wish != 0;
+    p->tiled = want && cfg->radius == 4 && (p->w8 % 4) == 0 &&
+               (p->vol16 ? mv_corr_volume_out16_supported(cfg->pairs, cfg->C, p->n8, mv_tiled_slice_cells(p->h8, p->w8), cfg->feat_dtype, cfg->layout) != 0
+                         : (p->packed && (p->h8 % 4) == 0));
+    p->n2t = (p->tiled && p->vol16) ? mv_tiled_slice_cells(p->h8, p->w8) : p->n8;
+}
+
 extern "C" size_t mv_frame_pipe_arena_bytes(const mvFramePipeConfig* cfg) {
     if (check_config(cfg) != MV_OK) return 0;
     mvFramePipe tmp{};
-    tmp.c = *cfg;
-    tmp.plane = cfg->H * cfg->W;
-    tmp.h8 = eighth_dims(cfg->H, cfg->W).h8;
-    tmp.w8 = eighth_dims(cfg->H, cfg->W).w8;
-    tmp.n8 = tmp.h8 * tmp.w8;
-    tmp.KK = (2 * cfg->radius + 1) * (2 * cfg->radius + 1);
-    tmp.lanes = cfg->pairs / 2;
-    tmp.n_volbuf = volbufs_for(tmp.lanes, cfg->mapping);
-    tmp.packed = (cfg->volume_split == MV_PACK_BF16X3 || cfg->volume_split == MV_PACK_F16X2) &&
-                 mv_corr_volume_packed_supported(cfg->pairs, cfg->C, tmp.n8, tmp.n8, cfg->volume_split);
+    derive_shape(&tmp, cfg);
     return carve(&tmp, nullptr);
 }
 
 extern "C" int mv_frame_pipe_max_pending(void) { return MAX_PENDING; }
+
+// THE list of the pipe's streams, in creation order, by role: `f` runs on every stream that exists and has one of the roles `which`.  Where backend and
+// solve share a stream (alt) it is listed under both roles, so whoever synchronises "backend, then solve" does so twice, as it always has.
+enum : unsigned { ST_VOL = 1, ST_DECODER = 2, ST_BACK = 4, ST_SIDE = 8, ST_SEL = 16, ST_ALL = 31 };
+template <class F>
+static int each_stream(const mvFramePipe* p, unsigned which, F f) {
+    const struct { unsigned role; hipStream_t s; } all[] = {{ST_VOL, p->s_vol},   {ST_DECODER, p->s_lk[0]}, {ST_DECODER, p->s_lk[1]},
+                                                            {ST_BACK, p->s_back}, {ST_SIDE, p->s_side},     {ST_SEL, p->s_sel}};
+    static_assert(MAX_LK == 2, "the decoder-side streams are listed one by one");
+    for (const auto& e : all)
+        if ((which & e.role) && e.s && f(e.s) != hipSuccess) return MV_ERR_LAUNCH;
+    return MV_OK;
+}
+static int sync_streams(const mvFramePipe* p, unsigned which) { return each_stream(p, which, hipStreamSynchronize); }
 
 extern "C" void mv_frame_pipe_destroy(mvFramePipe* p) {
     if (!p) return;
@@ -609,29 +690,21 @@ extern "C" void mv_frame_pipe_destroy(mvFramePipe* p) {
         p->cv_job.notify_all();
         p->worker.join();   // (drains the queue first)
     }
-    if (p->host_stats && p->st_calls > 0)
+    if (p->k.host_stats && p->st_calls > 0)
         fprintf(stderr, "[mv_frame_pipe host stats] per frame over %.0f device-driven frames: enqueue %.1f us (lookups %.1f, selector segment %.1f), enqueue_volume %.1f us, "
                         "finish_device %.1f us\n", p->st_calls, p->st_enq / p->st_calls, p->st_enq_lookups / p->st_calls, p->st_enq_seg / p->st_calls,
                 p->st_vol / p->st_calls, p->st_fin / p->st_calls);
-    if (p->host_stats && p->st_n > 0)
+    if (p->k.host_stats && p->st_n > 0)
         fprintf(stderr, "[mv_frame_pipe host stats] finishes %.0f: wait for the candidate count %.1f us, count seen -> job queued %.1f us, queued -> picked up by the "
                         "launch thread %.1f us, picked up -> every launch issued %.1f us (means per frame)\n",
                 p->st_n, p->st_wait / p->st_n, p->st_count_to_submit / p->st_n, p->st_submit_to_pick / p->st_n, p->st_pick_to_issued / p->st_n);
-    (void)hipStreamSynchronize(p->s_vol);
-    for (int k = 0; k < MAX_LK; ++k) if (p->s_lk[k]) (void)hipStreamSynchronize(p->s_lk[k]);
-    (void)hipStreamSynchronize(p->s_back);
-    (void)hipStreamSynchronize(p->s_side);
-    if (p->s_sel) (void)hipStreamSynchronize(p->s_sel);
+    (void)sync_streams(p, ST_ALL);
     for (int k = 0; k < 2; ++k) if (p->h_nvalid[k]) (void)hipHostFree(p->h_nvalid[k]);
     for (int k = 0; k < N_CAND; ++k) if (p->h_count_m[k]) (void)hipHostFree(p->h_count_m[k]);
     if (p->h_perm_m) (void)hipHostFree(p->h_perm_m);
     for (int k = 0; k < N_CAND; ++k) if (p->h_count[k]) (void)hipHostFree(p->h_count[k]);
     for (auto h : p->h_perm) if (h) (void)hipHostFree(h);
-    if (p->s_vol) (void)hipStreamDestroy(p->s_vol);
-    for (int k = 0; k < MAX_LK; ++k) if (p->s_lk[k]) (void)hipStreamDestroy(p->s_lk[k]);   // (s_lk[0] = s_main)
-    if (p->s_back && p->s_back != p->s_side) (void)hipStreamDestroy(p->s_back);
-    if (p->s_side) (void)hipStreamDestroy(p->s_side);
-    if (p->s_sel) (void)hipStreamDestroy(p->s_sel);
+    (void)each_stream(p, p->s_back == p->s_side ? ST_ALL & ~ST_BACK : ST_ALL, hipStreamDestroy);
     delete p;   // (every Ev destroys its event: the streams were synchronised above)
 }
 
@@ -646,12 +719,12 @@ static int create_impl(mvFramePipe* p) {
     MV_HIP(hipStreamCreateWithPriority(&p->s_vol, hipStreamNonBlocking, 0));
     MV_HIP(hipStreamCreateWithPriority(&p->s_main, hipStreamNonBlocking, 0));
     p->s_lk[0] = p->s_main;
-    for (int k = 1; k < p->n_lk; ++k) MV_HIP(hipStreamCreateWithPriority(&p->s_lk[k], hipStreamNonBlocking, 0));
+    for (int k = 1; k < p->k.n_lk; ++k) MV_HIP(hipStreamCreateWithPriority(&p->s_lk[k], hipStreamNonBlocking, 0));
     // (creation order matters on this stack: with `side` created before `back` the same schedule ran 15 % slower, profiles/r05_pipe_ab.log)
-    if (!p->alt) MV_HIP(hipStreamCreateWithPriority(&p->s_back, hipStreamNonBlocking, hi));
+    if (!p->k.alt) MV_HIP(hipStreamCreateWithPriority(&p->s_back, hipStreamNonBlocking, hi));
     MV_HIP(hipStreamCreateWithPriority(&p->s_side, hipStreamNonBlocking, hi));
-    if (p->alt) p->s_back = p->s_side;   // backend + solve of a frame in order on ONE stream: the fourth queue belongs to the odd frames' decoder side
-    if (p->sel_on_back == 2) MV_HIP(hipStreamCreateWithPriority(&p->s_sel, hipStreamNonBlocking, hi));
+    if (p->k.alt) p->s_back = p->s_side;   // backend + solve of a frame in order on ONE stream: the fourth queue belongs to the odd frames' decoder side
+    if (p->k.sel_on == SelOn::Own) MV_HIP(hipStreamCreateWithPriority(&p->s_sel, hipStreamNonBlocking, hi));
     MV_TRY(create_all(p->e_in.slot));
     MV_TRY(create_all(p->e_rest.slot));
     MV_TRY(create_all(p->e_vol_done));
@@ -701,7 +774,6 @@ static int create_impl(mvFramePipe* p) {
     MV_HIP(hipMemcpyAsync(p->offs, offs.data(), offs.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->s_main));
     static const float pose_norm[6] = {0.13f, 0.13f, 0.13f, 0.013f, 0.013f, 0.013f};   // TartanStereoVONetInterface.pose_norm (StereoVO_Interface.py:51-53)
     if (p->pose_norm) MV_HIP(hipMemcpyAsync(p->pose_norm, pose_norm, sizeof(pose_norm), hipMemcpyHostToDevice, p->s_main));
-    { const char* e = getenv("MV_PIPE_FUSE_BACKEND"); p->fuse_backend = (e && atoi(e) == 0) ? 0 : 1; }
     p->time_detail = 1;
     MV_HIP(hipStreamSynchronize(p->s_main));   // the host vectors die here
     return MV_OK;
@@ -712,53 +784,7 @@ extern "C" int mv_frame_pipe_create(const mvFramePipeConfig* cfg, void* arena, s
     MV_TRY(check_config(cfg));
     mvFramePipe* p = new (std::nothrow) mvFramePipe{};
     if (!p) return MV_ERR_WORKSPACE;
-    p->c = *cfg;
-    p->plane = cfg->H * cfg->W;
-    p->h8 = eighth_dims(cfg->H, cfg->W).h8;
-    p->w8 = eighth_dims(cfg->H, cfg->W).w8;
-    p->n8 = p->h8 * p->w8;
-    p->KK = (2 * cfg->radius + 1) * (2 * cfg->radius + 1);
-    p->lanes = cfg->pairs / 2;
-    p->n_volbuf = volbufs_for(p->lanes, cfg->mapping);
-    p->packed = (cfg->volume_split == MV_PACK_BF16X3 || cfg->volume_split == MV_PACK_F16X2) &&
-                mv_corr_volume_packed_supported(cfg->pairs, cfg->C, p->n8, p->n8, cfg->volume_split);
-    // shapes outside the out16 kernel's domain keep the fp32-stored volume of the same 16-bit GEMM
-    p->vol16 = cfg->volume_split == MV_VOL_ENC16 && mv_corr_volume_out16_supported(cfg->pairs, cfg->C, p->n8, p->n8, cfg->feat_dtype, cfg->layout);
-    {
-        // Tiled volume for the batched lookups, MV_PIPE_TILED=1.  Measured (640x480, 32 lanes, f16x2): the tiled lookup
-        // alone is 15 % faster (B = 64: 114 -> 97 us: the same bytes in half as many, aligned 64-byte requests), the 32-lane step
-        // 6 % SLOWER (7.44 k vs 7.95 k frames/s; beside the GEMM's write stream the row-major form's 32-byte sector gathers do better)
-        // -> off by default.
-        // [r6] ... and ON by default for Fast-mode pipes: measured 32 lanes 11.8 k -> 13.3 k frames/s, 8 lanes 12.0 k -> 13.3 k, one lane 8.3 k -> 8.4-8.6 k
-        const char* e = getenv("MV_PIPE_TILED");
-        const bool want = e ? atoi(e) != 0 : p->vol16;
-        // [r6] Fast mode's 2-byte cells: a tile is one 32-byte sector (mv_corr_lookup_tiled_vol16: B = 64 alone 115 -> 79 us)
-        p->tiled = want && cfg->radius == 4 && (p->w8 % 4) == 0 &&
-                   (p->vol16 ? mv_corr_volume_out16_supported(cfg->pairs, cfg->C, p->n8, mv_tiled_slice_cells(p->h8, p->w8), cfg->feat_dtype, cfg->layout) != 0
-                             : (p->packed && (p->h8 % 4) == 0));
-        p->n2t = (p->tiled && p->vol16) ? mv_tiled_slice_cells(p->h8, p->w8) : p->n8;    // (2-byte cells: a padded slice still fits the buffer's n8 * n8 * 4 bytes)
-    }
-    {
-        // MV_PIPE_SELECTOR_ON=back: the selector segment of a frame (epilogue, NMS, finishing workgroup, count copy: ~60 us beside the
-        // GEMM) moves from the decoder-side stream — which a one-lane stream saturates: 12 dependent lookups + that segment = one
-        // period — to the backend stream, behind an event on the frame's last lookup; the next frame's lookups start meanwhile.
-        // Measured (640x480, f16x2 volume): one lane 5.38 k vs 4.94 k frames/s (period 183 vs 198 us), 32 lanes 7.43 k vs 7.64 k: the
-        // default follows the lane count; MV_PIPE_SELECTOR_ON=main|back forces it.
-        // [r4] `late` needs two unfinished frames in front of the new one, i.e. a 3-deep pipeline; the default depth for <= 2 lanes is now 2
-        // (pipeline.py; profiles/r04_latency_ab.log: the same frame rate within the box's +-3 %, GEMM start -> pose 1.18 -> 0.82 ms), where
-        // `late` and `back` are the same schedule.
-        const char* e = getenv("MV_PIPE_SELECTOR_ON");
-        p->sel_on_back = e ? (strcmp(e, "back") == 0 ? 1 : strcmp(e, "own") == 0 ? 2 : strcmp(e, "vol") == 0 ? 3 : strcmp(e, "late") == 0 ? 4 : 0)
-                           : (p->lanes <= 2 ? 1 : 0);
-    }
-    {
-        // Where the operand pack of frame f + 1 runs.  It needs only the feature maps, so it can run beside GEMM(f) on another of
-        // the pipe's streams (a fifth stream measured 2.50 k vs 3.41 k frames/s in round 2: four is the ceiling on this stack).
-        const char* e = getenv("MV_PIPE_PACK_ON");
-        // Measured (640x480, one lane, frames/s): in front of the GEMM on its own stream 4.28 k, backend stream 4.09 k, decoder-side
-        // stream 3.11 k: beside a one-wave-per-SIMD GEMM every co-running kernel costs the GEMM more than the 8 us the pack takes.
-        p->pack_on = (e && strcmp(e, "back") == 0) ? 1 : (e && strcmp(e, "main") == 0) ? 2 : (e && strcmp(e, "side") == 0) ? 3 : 0;
-    }
+    derive_shape(p, cfg);
     p->arena = (char*)arena;
     p->arena_bytes = arena_bytes;
     if (((uintptr_t)arena & 255) != 0 || carve(p, p->arena) > arena_bytes) {
@@ -767,60 +793,14 @@ extern "C" int mv_frame_pipe_create(const mvFramePipeConfig* cfg, void* arena, s
     }
     describe_backend(p);
     p->newest_maps = -1;
-    {
-        const char* e = getenv("MV_PIPE_LOOKUPS_ON");
-        p->lookups_on_main = (e && strcmp(e, "vol") == 0) ? 0 : 1;
-    }
-    {
-        // Decoder-side streams (round 5).  The 12 dependent lookups of a frame are latency-bound (5.8 us each alone, 13-15 us per launch beside the GEMM): on
-        // ONE stream they are 160-175 us per frame, and that stream — busy all the time — was the period of a one-lane pipe.  Consecutive frames' decoder
-        // sides are independent (own volume buffer, coordinates, token buffers, maps slot, candidate slot), so frame f's lookups run on stream f % n_lk.
-        //   * A FIFTH queue is not an option on this stack: with one more stream every configuration ran at 3.4-3.8 k frames/s instead of 5.9 k (GEMM 89 ->
-        //     132 us; also with GPU_MAX_HW_QUEUES=8; profiles/r05_pipe_ab.log run 15, and the same finding in round 2; the A/B knob is gone).
-        //   * The alt layout keeps FOUR:   vol: pack + GEMM | main: even frames' lookups + selector segment | a second decoder-side stream: the odd
-        //     frames' | side: backend + solve of every frame, in order (the chain solve -> solve is sequential anyway; the backend no longer overlaps it).
-        //     Consecutive selector segments may overlap (own selector workspace per parity); the backend waits for the previous frame's segment by event.
-        p->alt = layout_alt(p->lanes, cfg->mapping);
-        p->n_lk = p->alt ? 2 : 1;
-        if (p->alt) p->sel_on_back = 0;
-        // ... and in that layout the GEMM leaves 32 CUs (4 per XCD) without a persistent workgroup: backend + solve share ONE stream there, and the solve's
-        // workgroup (496 registers + 77 KB of LDS) cannot sit beside a GEMM wave (300 registers, the LDS ring) — with no CU free it waited for the gap between two GEMMs (73 of its 127 us).  Measured
-        // (profiles/r05_pipe_ab.log): 0 / 8 / 16 / 32 / 48 / 64 free = 6.26 / 6.34 / 6.68 / 6.84 / 6.87 / 6.82 k frames/s; in the classic layout no gain (r3, r5).
-        p->free_cus = p->alt ? 32 : 0;
-        if (const char* e = getenv("MV_PIPE_FREE_CUS")) p->free_cus = atoi(e);   // A/B knob (multiples of 8: per XCD)
-        p->alt_indep = p->alt;   // (ordered segments for every selector: -6 % on the 20-step line, profiles/r05_pipe_ab.log run 18)
-        // Device-driven frames: the front launch (permutation draw + gathers + both covariance models) rides behind the frame's own selector segment on its
-        // decoder-side stream — no cross-queue barrier in front of it — and the fourth stream carries the solves only.  With front + solve in order on one
-        // stream that stream was the bound of a device-driven pipe (a frame's backend started 250 us after its selector had finished: a backlog of front /
-        // solve pairs, each with a pending barrier in front).  Measured (profiles/r06_device_draw_ab.log): 20 steps 5.97 / 5.63 / 6.18 k vs 5.75 / 5.65 / 5.61 k
-        // frames/s, 300 steps 6.83-6.95 k vs 6.60-6.64 k; bit-identical.  MV_PIPE_FRONT_ON=side: the old placement.  (Also measured and dropped: the selector's
-        // FINISHING workgroup moved in front of the backend on the backend's stream — 5.62 k at 300 steps.)
-        // (Also measured and dropped, same log: THREE decoder-side streams — the fourth stream as the third, a frame's whole chain incl. its solve in order on one
-        // stream, solves chained across streams by event: bit-identical, 5.3 k instead of 6.7 k frames/s at 300 steps.  More concurrency is not what this pipe lacks.)
-        { const char* e = getenv("MV_PIPE_LEAN"); p->lean_chain = (p->alt && !(e && atoi(e) == 0)) ? 1 : 0; }
-        { const char* e = getenv("MV_PIPE_FRONT_ON"); p->front_on_decoder = (p->alt && !(e && strcmp(e, "side") == 0)) ? 1 : 0; }
-    }
     const int rc = create_impl(p);
     if (rc != MV_OK) {
         mv_frame_pipe_destroy(p);
         return rc;
     }
-    {
-        // config.async_backend: 1 on, -1 off, 0 = MV_PIPE_ASYNC_BACKEND if set, else the measured default (see mvFramePipe)
-        const char* e = getenv("MV_PIPE_ASYNC_BACKEND");
-        const int want = cfg->async_backend ? cfg->async_backend : (e ? (atoi(e) ? 1 : -1) : MV_ASYNC_DEFAULT(p));
-        p->async_backend = want > 0 ? 1 : 0;
-        p->async_explicit = (cfg->async_backend || e) ? 1 : 0;
-        if (hipGetDevice(&p->device) != hipSuccess) p->async_backend = 0;
-        {
-            // a spinning launch thread needs a core of its own beside the caller's (and Python's): with fewer than three in the process' affinity mask it
-            // sleeps on the condition variable instead (per-rank core slices of bench --gpus N, 1-2 core hosts)
-            const char* e3 = getenv("MV_PIPE_LAUNCH_SPIN_US");
-            p->spin_us = e3 ? atof(e3) : (affinity_cores() >= 3 ? 250.0 : 0.0);
-        }
-        { const char* e4 = getenv("MV_PIPE_HOST_STATS"); p->host_stats = e4 ? atoi(e4) : 0; }
-        if (p->async_backend) p->worker = std::thread(launch_thread_main, p);
-    }
+    const bool have_device = hipGetDevice(&p->device) == hipSuccess;   // (the launch thread binds itself to it)
+    p->async_backend = p->k.async_wish && have_device;
+    if (p->async_backend) p->worker = std::thread(launch_thread_main, p);
     *out = p;
     return MV_OK;
 }
@@ -838,7 +818,7 @@ extern "C" int mv_frame_pipe_set_pose(mvFramePipe* p, const float* pose7_host) {
 static int issue_volume(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_stream) {
     const mvFramePipeConfig& c = p->c;
     const long f = p->n_vol;
-    const int k = (int)(f % p->n_volbuf);
+    const int k = (int)(f % p->k.n_volbuf);
     const int B = c.pairs;
     // inputs were produced on the caller's stream
     Ev& e_in = p->e_in[f];
@@ -847,14 +827,15 @@ static int issue_volume(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_s
     MV_TRY(e_in.wait_if_pending(p->s_vol));
     if (p->vol_free_ev[k]) MV_TRY(p->vol_free_ev[k]->wait_if_pending(p->s_vol));
     const bool timed = p->n_timed < p->timed_cap;
-    if (timed && !p->packed) MV_TRY(p->tv0[p->n_timed].record(p->s_vol));
+    if (timed && !p->packed) MV_TRY(p->tv[0][p->n_timed].record(p->s_vol));
     if (p->packed) {
         void** pk = p->pk[f & 1];
-        hipStream_t sp = p->pack_on == 0 ? p->s_vol : p->pack_on == 1 ? p->s_back : p->pack_on == 2 ? p->s_main : p->s_side;
+        const PackOn on = p->k.pack_on;
+        hipStream_t sp = on == PackOn::Vol ? p->s_vol : on == PackOn::Back ? p->s_back : on == PackOn::Main ? p->s_main : p->s_side;
         if (sp != p->s_vol) {
             MV_TRY(e_in.wait_if_pending(sp));
             // this operand set was last read by the GEMM of frame f - 2 (same stream order as the volume buffers' events)
-            if (f >= 2) MV_TRY(p->e_vol_done[(f - 2) % p->n_volbuf].wait_if_pending(sp));
+            if (f >= 2) MV_TRY(p->e_vol_done[(f - 2) % p->k.n_volbuf].wait_if_pending(sp));
         }
         if (p->tiled)
             MV_TRY(mv_volume_pack_tiled((const float*)in->fmap1, (const float*)in->fmap2, pk[0], pk[1], B, c.C, p->n8, p->h8, p->w8,
@@ -867,8 +848,8 @@ static int issue_volume(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_s
             MV_TRY(p->e_packed[f & 1].wait(p->s_vol));
         }
         // (round-4 A/B, removed: the GEMM waiting for the previous frame's lookups — each then has the chip to itself — cost 21 % of the frame rate)
-        if (timed) MV_TRY(p->tv0[p->n_timed].record(p->s_vol));   // the GEMM alone: behind the pack, wherever that ran
-        MV_TRY(mv_corr_volume_packed_shared(pk[0], pk[1], p->vol[k], B, c.C, p->n8, p->n8, c.volume_split, p->free_cus, p->s_vol));
+        if (timed) MV_TRY(p->tv[0][p->n_timed].record(p->s_vol));   // the GEMM alone: behind the pack, wherever that ran
+        MV_TRY(mv_corr_volume_packed_shared(pk[0], pk[1], p->vol[k], B, c.C, p->n8, p->n8, c.volume_split, p->k.free_cus, p->s_vol));
     } else if (c.volume_split == 2 || c.volume_split == 3) {
         const size_t nel = (size_t)B * p->n8 * c.C;
         MV_TRY(mv_split_bf16x3((const float*)in->fmap1, p->planes[0], nel, p->s_vol));
@@ -886,7 +867,7 @@ static int issue_volume(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_s
         MV_TRY(mv_corr_volume(in->fmap1, in->fmap2, p->vol[k], B, c.C, p->n8, p->n8, c.feat_dtype, c.layout, p->s_vol));
     }
     p->vol_timed[k] = timed ? p->n_timed : -1;
-    if (timed) MV_TRY(p->tv1[p->n_timed++].record(p->s_vol));
+    if (timed) MV_TRY(p->tv[1][p->n_timed++].record(p->s_vol));
     MV_TRY(p->e_vol_done[k].record(p->s_vol));
     p->n_vol = f + 1;
     return MV_OK;
@@ -898,21 +879,21 @@ static int issue_volume(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_s
 extern "C" int mv_frame_pipe_enqueue_volume(mvFramePipe* p, const mvFrameInputs* in, mvStream_t in_stream) {
     MV_CHECK_ARG(p && in && in->fmap1 && in->fmap2);
     MV_CHECK_ARG(p->n_vol == p->n_enq);                 // at most one GEMM ahead of its frame
-    MV_CHECK_ARG(p->lookups_on_main);                   // the alternative layout keeps the lookups behind the GEMM on its stream
+    MV_CHECK_ARG(p->k.lookups_on_main);                   // the alternative layout keeps the lookups behind the GEMM on its stream
     // the volume buffer of frame n_vol was last read by the lookups of frame n_vol - 2: their event exists (frame enqueued)
-    const double t_hs = p->host_stats ? now_us() : 0.0;
+    const double t_hs = p->k.host_stats ? now_us() : 0.0;
     MV_TRY(issue_volume(p, in, in_stream));
-    if (p->host_stats) p->st_vol += now_us() - t_hs;
+    if (p->k.host_stats) p->st_vol += now_us() - t_hs;
     // MV_PIPE_SELECTOR_ON=vol: the newest enqueued frame's selector segment goes behind this GEMM on the GEMM's stream — it needs that
     // frame's lookups, which finish about when this GEMM does, and then runs in the gap the GEMM stream idles in anyway, alone on the chip
-    return p->sel_on_back == 3 ? flush_deferred(p) : MV_OK;
+    return p->k.sel_on == SelOn::Vol ? flush_deferred(p) : MV_OK;
 }
 
 // lean chain: the markers behind frame f's selector segment were not recorded; whoever needs them (a host-permuted finish, mv_frame_pipe_wait_candidates, a
 // selector segment that depends on the previous one) records them now, on the frame's decoder-side stream — a later point of the same in-order stream
 static int ensure_chain_events(mvFramePipe* p, long f, int cand_slot) {
-    if (cand_slot >= 0 && !p->e_cand[cand_slot].recorded()) MV_TRY(p->e_cand[cand_slot].record(p->s_lk[f % p->n_lk]));
-    if (p->alt && f >= 0 && !p->e_seg[f].recorded()) MV_TRY(p->e_seg[f].record(p->s_lk[f % p->n_lk]));
+    if (cand_slot >= 0 && !p->e_cand[cand_slot].recorded()) MV_TRY(p->e_cand[cand_slot].record(p->s_lk[f % p->k.n_lk]));
+    if (p->k.alt && f >= 0 && !p->e_seg[f].recorded()) MV_TRY(p->e_seg[f].record(p->s_lk[f % p->k.n_lk]));
     return MV_OK;
 }
 
@@ -932,9 +913,9 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
     const mvFrameInputs* in = &d.in;
     const int k = d.k, m = d.m, ti = d.ti, B = c.pairs;
     const bool timed = d.timed, with_selector = d.with_selector, up = d.up;
-    hipStream_t s = p->s_lk[d.f % p->n_lk];   // (same stream as the frame's lookups: in order behind them)
-    if (p->sel_on_back) {   // everything behind the lookups continues on another stream (in order with the backends it must follow)
-        s = p->sel_on_back == 2 ? p->s_sel : p->sel_on_back == 3 ? p->s_vol : p->s_back;   // (1 and 4: the backend stream)
+    hipStream_t s = p->s_lk[d.f % p->k.n_lk];   // (same stream as the frame's lookups: in order behind them)
+    if (p->k.sel_on != SelOn::Decoder) {   // everything behind the lookups continues on another stream (in order with the backends it must follow)
+        s = p->k.sel_on == SelOn::Own ? p->s_sel : p->k.sel_on == SelOn::Vol ? p->s_vol : p->s_back;   // (Back and Late: the backend stream)
         MV_TRY(p->e_lk[k].wait(s));
     }
     // maps slot m and candidate slot k were last read by the backend of frame f - 2 (f - 3 for the maps) on `back`
@@ -965,15 +946,17 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
     // behind e_cand) and shares the selector workspace / upsampling buffers with it
     // (alt_indep: NODEPTH selector without upsampling reads nothing of the previous frame and has its own workspace — the segments may overlap and
     // the BACKEND waits for the previous frame's segment instead, finish_issue)
-    const bool indep = p->alt_indep && !up && (c.selector_mode == MV_KP_NODEPTH || kp_new_mode(c.selector_mode));
-    if (p->alt && !indep && d.f > 0) {
+    const bool indep = p->k.alt_indep && !up && (c.selector_mode == MV_KP_NODEPTH || kp_new_mode(c.selector_mode));
+    if (p->k.alt && !indep && d.f > 0) {
         MV_TRY(ensure_chain_events(p, d.f - 1, -1));
         MV_TRY(p->e_seg[d.f - 1].wait_if_pending(s));
     }
     void* const kp_ws = (indep && (d.f & 1)) ? p->kp_ws2 : p->kp_ws;
     Maps& mp = p->maps[m];
-    constexpr bool fuse_epi = true;   // epilogue + the selector's first kernel in one launch (the separate form was an A/B knob of rounds 2-4)
     const int nocov = c.frontend_nocov;
+    // epilogue + the selector's first kernel in ONE launch (one launch and one pass over the maps less on the chain that bounds a single-sequence stream):
+    // the NODEPTH selector on full-resolution inputs with both covariances
+    const bool fused_select = with_selector && !up && !nocov && c.selector_mode == MV_KP_NODEPTH;
     if (up) {
         MV_TRY(upsample_frame(p, in->flow8, in->up_mask, p->up_flow, B, 0.25f, 0, s));
         if (!nocov) {
@@ -989,22 +972,20 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
         MV_TRY(mv_frontend_epilogue_lanes(p->up_flow, p->up_cov, 0, c.H, c.W, c.bl_fx, c.bl_fx_sq, mp.disparity,
                                           mp.disparity_cov, mp.depth, mp.depth_cov, nullptr, mp.match_flow, mp.match_cov,
                                           p->lanes, s));
-    } else if (nocov || !(fuse_epi && with_selector && c.selector_mode == MV_KP_NODEPTH)) {   // (no fused epilogue + selector launch without depth covariance)
+    } else if (!fused_select) {
         MV_TRY(mv_frontend_epilogue_lanes(in->flow, in->logcov, 1, c.H, c.W, c.bl_fx, c.bl_fx_sq, mp.disparity,
                                           mp.disparity_cov, mp.depth, mp.depth_cov, nullptr, mp.match_flow, mp.match_cov,
                                           p->lanes, s));
     }
     const Pending pd{m, d.maps_prev, k, with_selector, ti};
-    if (with_selector && c.motion_model == MV_MOTION_TARTAN && !(c.selector_mode == MV_KP_NODEPTH && fuse_epi && !up && !nocov)) MV_TRY(issue_motion_input(p, m, s));
+    if (with_selector && c.motion_model == MV_MOTION_TARTAN && !fused_select) MV_TRY(issue_motion_input(p, m, s));
     if (with_selector) {
         mvKpSelectParams sp{c.H, c.W, c.selector_mode, c.kp_kernel_size, c.kp_mask_width, c.max_depth, c.max_depth_cov,
                             c.max_match_cov};
         const bool sel_kernels = !kp_new_mode(c.selector_mode);   // (Random / Grid / explicit keypoints: the segment ends with the epilogue)
         if (!sel_kernels) {
             // (nothing: the maps are written, the keypoints come with the finish)
-        } else if (c.selector_mode == MV_KP_NODEPTH && fuse_epi && !up && !nocov) {
-            // epilogue + selector's first kernel in one launch (one launch and one pass over the maps less on the chain that
-            // bounds a single-sequence stream)
+        } else if (fused_select) {
             MV_TRY(mv_frontend_epilogue_select_lanes(in->flow, in->logcov, 1, c.bl_fx, c.bl_fx_sq, mp.disparity, mp.disparity_cov,
                                                      mp.depth, mp.depth_cov, nullptr, mp.match_flow, mp.match_cov, nullptr,
                                                      nullptr, &sp, kp_ws, p->kp_ws_bytes, p->cand[k], p->count[k],
@@ -1031,16 +1012,16 @@ static int issue_selector_segment(mvFramePipe* p, const SelSeg& d) {
             MV_HIP(hipMemcpyAsync(p->h_count_m[k], p->count_m[k], 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         }
         // lean chain (device-driven, front launch in order behind this segment, segments independent): no marker here — e_cand is recorded on demand
-        // (ensure_cand_event) and nothing waits for e_seg
-        const bool lean = p->lean_chain && p->dev_draw && p->front_on_decoder && indep && !p->sel_on_back && !c.mapping;
-        if (lean) p->e_cand[k].skip();
+        // (ensure_chain_events) and nothing waits for e_seg
+        const bool no_markers = p->k.no_segment_markers && p->dev_draw && indep;
+        if (no_markers) p->e_cand[k].skip();
         else MV_TRY(p->e_cand[k].record(s));
-        if (timed) MV_TRY(p->tv3[ti].record(s));
-        if (p->alt) {
-            if (lean) p->e_seg[d.f].skip();
+        if (timed) MV_TRY(p->tv[3][ti].record(s));
+        if (p->k.alt) {
+            if (no_markers) p->e_seg[d.f].skip();
             else MV_TRY(p->e_seg[d.f].record(s));
         }
-    } else if (p->alt) {
+    } else if (p->k.alt) {
         MV_TRY(p->e_seg[d.f].record(s));
     }
     return MV_OK;
@@ -1055,7 +1036,7 @@ static int flush_deferred(mvFramePipe* p) {
 // the newest frame's segment for the finish that is about to happen, unless that newest frame IS the oldest pending one; a segment that
 // travelled with an earlier finish has been issued once the launch thread is through with that job.
 static int selector_of_front_issued(mvFramePipe* p) {
-    if (p->sel_on_back != 4 || p->pending.size() <= 1) MV_TRY(flush_deferred(p));
+    if (p->k.sel_on != SelOn::Late || p->pending.size() <= 1) MV_TRY(flush_deferred(p));
     const long sj = p->pending.empty() ? -1 : p->pending.front().sel_job;
     return sj >= 0 ? wait_issued(p, sj + 1) : MV_OK;
 }
@@ -1072,13 +1053,13 @@ extern "C" int mv_frame_pipe_enqueue(mvFramePipe* p, const mvFrameInputs* in, mv
     MV_CHECK_ARG(!with_selector || p->newest_maps >= 0);   // a tracked frame needs the previous frame's maps
     MV_CHECK_ARG(!with_selector || (int)p->pending.size() < MAX_PENDING);  // slot rotation covers MAX_PENDING tracked frames in flight
     const int B = c.pairs;
-    const double t_hs0 = p->host_stats ? now_us() : 0.0;
+    const double t_hs0 = p->k.host_stats ? now_us() : 0.0;
     MV_TRY(flush_deferred(p));   // (the previous frame's selector segment, had nobody asked for it yet: frames stay in order)
 
     // ---- volume GEMM (own stream) unless mv_frame_pipe_enqueue_volume already issued it
     const bool ahead = p->n_vol != f;
     if (!ahead) MV_TRY(issue_volume(p, in, in_stream));
-    const int kv = (int)(f % p->n_volbuf);   // volume buffer of this frame (k = its candidate / backend slot)
+    const int kv = (int)(f % p->k.n_volbuf);   // volume buffer of this frame (k = its candidate / backend slot)
     const int ti = p->time_detail ? p->vol_timed[kv] : -1;   // timeline slot (the GEMM's own event pair was recorded by issue_volume)
     const bool timed = ti >= 0;
 
@@ -1086,27 +1067,27 @@ extern "C" int mv_frame_pipe_enqueue(mvFramePipe* p, const mvFrameInputs* in, mv
     // GEMM's stream instead — no cross-stream event in front of the first lookup, GEMM undisturbed at 215 us — measured
     // 0.3256 vs 0.3197 ms per frame: behind a 215-us kernel each of the 12 launch boundaries costs ~9 us.)
     const size_t coord_stride = (size_t)B * 2 * p->n8;
-    const int lk = (int)(f % p->n_lk);
+    const int lk = (int)(f % p->k.n_lk);
     hipStream_t s = p->s_lk[lk];
     float* const* tok = p->tok + 2 * lk;
     if (ahead) {   // the GEMM's input event predates this call: order the decoder side after the caller's stream as of NOW
         MV_TRY(p->e_rest[f].record((hipStream_t)in_stream));
         MV_TRY(p->e_rest[f].wait_if_pending(s));
     }
-    if (p->lookups_on_main) {
+    if (p->k.lookups_on_main) {
         MV_TRY(p->e_vol_done[kv].wait(s));   // also orders `s` after e_in (the GEMM stream waited for it)
         for (int it = 0; it < c.iters; ++it)
             MV_TRY(mv_lookup(p->vol[kv], p->vol16, p->tiled, in->coords + it * coord_stride, tok[it & 1], B, p->h8, p->w8, p->h8, p->w8, c.radius, s));
         // lean chain: this frame's front launch (same stream, behind the lookups) releases the buffer — its ring event exists before the GEMM that rewrites the
         // buffer is issued (that GEMM belongs to frame f + n_volbuf, enqueued only after this frame has been finished: MAX_PENDING < n_volbuf)
-        const bool lean = p->lean_chain && p->dev_draw && with_selector && c.num_point > 0 && p->n_volbuf > MAX_PENDING;
-        if (lean) {
+        const bool freed_by_front = p->k.front_frees_volume && p->dev_draw && with_selector && c.num_point > 0;
+        if (freed_by_front) {
             p->vol_free_ev[kv] = &p->e_backend[p->n_fin + (long)p->pending.size()];
         } else {
             MV_TRY(p->e_vol_free[kv].record(s));
             p->vol_free_ev[kv] = &p->e_vol_free[kv];
         }
-        if (timed) MV_TRY(p->tv2[ti].record(s));
+        if (timed) MV_TRY(p->tv[2][ti].record(s));
     } else {
         for (int it = 0; it < c.iters; ++it)
             MV_TRY(mv_lookup(p->vol[kv], p->vol16, p->tiled, in->coords + it * coord_stride, tok[it & 1], B, p->h8, p->w8, p->h8, p->w8, c.radius, p->s_vol));
@@ -1115,16 +1096,16 @@ extern "C" int mv_frame_pipe_enqueue(mvFramePipe* p, const mvFrameInputs* in, mv
         p->vol_free_ev[kv] = nullptr;                 // vol[k] / tok are only touched on s_vol: stream order suffices
     }
 
-    const double t_hs1 = p->host_stats ? now_us() : 0.0;
+    const double t_hs1 = p->k.host_stats ? now_us() : 0.0;
     SelSeg d{*in, f, k, m, ti, p->newest_maps, timed, with_selector != 0, up,
              p->n_fin - MAX_PENDING + (long)p->pending.size()};
-    if (p->sel_on_back) MV_TRY(p->e_lk[k].record(s));   // the segment continues on another stream behind the last lookup
+    if (p->k.sel_on != SelOn::Decoder) MV_TRY(p->e_lk[k].record(s));   // the segment continues on another stream behind the last lookup
     // MV_PIPE_SELECTOR_ON=late: with two unfinished frames in front of it (the steady state of a 3-deep pipeline) the segment is
     // handed to the NEXT finish, which issues it right behind that frame's backend: the backend stream then holds
     // backend(f - 2), selector(f), backend(f - 1), selector(f + 1) ... — a backend waits behind ONE queued selector segment (whose
     // lookups are done by then) instead of two that still wait for their lookups (frame latency: see DESIGN, backend timeline)
-    const bool late = p->sel_on_back == 4 && with_selector && p->pending.size() >= 2;
-    if ((p->sel_on_back == 3 && with_selector) || late) {
+    const bool late = p->k.sel_on == SelOn::Late && with_selector && p->pending.size() >= 2;
+    if ((p->k.sel_on == SelOn::Vol && with_selector) || late) {
         p->deferred = d;            // issued behind the next frame's GEMM (mv_frame_pipe_enqueue_volume) / the next backend, or by whoever needs it first
         p->deferred_valid = true;
     } else {
@@ -1133,7 +1114,7 @@ extern "C" int mv_frame_pipe_enqueue(mvFramePipe* p, const mvFrameInputs* in, mv
     if (with_selector) p->pending.push_back(Pending{m, p->newest_maps, k, true, ti, -1, f});
     p->newest_maps = m;
     p->n_enq = f + 1;
-    if (p->host_stats) {
+    if (p->k.host_stats) {
         const double t_hs2 = now_us();
         p->st_enq += t_hs2 - t_hs0;
         p->st_enq_lookups += t_hs1 - t_hs0;
@@ -1204,13 +1185,11 @@ extern "C" int mv_frame_pipe_seed_lanes(mvFramePipe* p, const uint64_t* seeds) {
     p->perm_host.assign((size_t)p->lanes * cap * (p->c.selector_mode == MV_KP_RANDOM ? 2 : 1), 0);
     p->nsel_host.assign((size_t)p->lanes, 0);
     {
-        // ... and the same generators in device memory: the device-driven frame (default wherever it applies; MV_PIPE_DEVICE_DRAW=0: the host draw above).
+        // ... and the same generators in device memory: the device-driven frame (default wherever it applies; Knobs::device_draw_wish).
         // Needs the two-launch backend, a head the device draw covers, and no dense-mapping tail (its second permutation is drawn by the Python side).
-        const char* e = getenv("MV_PIPE_DEVICE_DRAW");
-        const bool want = e ? atoi(e) != 0 : true;
-        p->dev_draw = want && p->fuse_backend && !p->c.mapping && p->c.num_point >= 1 && p->c.num_point <= mv_randperm_max_head() && p->pending.empty() &&
+        p->dev_draw = p->k.device_draw_wish && p->k.fuse_backend && !p->c.mapping && p->c.num_point >= 1 && p->c.num_point <= mv_randperm_max_head() && p->pending.empty() &&
                       p->c.selector_mode != MV_KP_GRID && p->c.selector_mode != MV_KP_EXPLICIT;   // (nothing to draw)
-        if (p->dev_draw && p->async_backend && !p->async_explicit && affinity_cores() < 3) {
+        if (p->dev_draw && p->async_backend && !p->k.async_explicit && affinity_cores() < 3) {
             // One host thread on small hosts.  The launch thread existed to overlap the host draw + the backend launches with the caller's next enqueue while the caller
             // waited for candidate counts; a device-driven frame has no wait and no draw, and one thread issues it in ~105-140 us — about the frame period.  With the lean
             // chain (below) that is the edge: measured (profiles/r06_chain_gaps.log) one thread 6.99 / 6.85 / 6.64 k frames/s at 300 steps with issue times of 115 / 134 /
@@ -1230,8 +1209,8 @@ extern "C" int mv_frame_pipe_seed_lanes(mvFramePipe* p, const uint64_t* seeds) {
             const size_t W = (size_t)mv_randperm_state_words();
             std::vector<uint32_t> st((size_t)p->lanes * W);
             for (int l = 0; l < p->lanes; ++l) MV_TRY(mv_mt19937_seed(seeds[l], st.data() + (size_t)l * W));
-            MV_HIP(hipStreamSynchronize(p->s_back));   // (no front launch may be reading a generator: they run on the backend stream or on the
-            for (int k = 0; k < p->n_lk; ++k) MV_HIP(hipStreamSynchronize(p->s_lk[k]));   //  decoder-side streams)
+            MV_TRY(sync_streams(p, ST_BACK));      // (no front launch may be reading a generator: they run on the backend stream or on the
+            MV_TRY(sync_streams(p, ST_DECODER));   //  decoder-side streams)
             MV_HIP(hipMemcpy(p->rp_state[p->n_fin & 1], st.data(), st.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
     }
@@ -1274,7 +1253,7 @@ static int finish_host(mvFramePipe* p, const int32_t* n_sel, float* pose_sink, F
     p->pending.pop_front();
     j.g = p->n_fin;
     j.has_sel = false;
-    if (p->sel_on_back == 4 && p->deferred_valid && !p->pending.empty()) {   // (never the frame being finished: flush_deferred ran first)
+    if (p->k.sel_on == SelOn::Late && p->deferred_valid && !p->pending.empty()) {   // (never the frame being finished: flush_deferred ran first)
         j.sel = p->deferred;
         j.has_sel = true;
         p->deferred_valid = false;
@@ -1341,8 +1320,8 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     // front_on_decoder (device-driven frames of the alt layout): the pose-independent launch goes behind the frame's own selector segment on its decoder-side
     // stream — in order, so no barrier for the selector; consecutive frames' front launches (other decoder-side stream each) are chained by the ring event of the
     // previous finish, which also orders the generator's state buffers and covers the previous frame's segment
-    const bool on_dec = j.device && p->front_on_decoder && p->alt && !p->sel_on_back;
-    hipStream_t s = on_dec ? p->s_lk[j.pd.f % p->n_lk] : p->s_back;
+    const bool on_dec = j.device && p->k.front_on_decoder;
+    hipStream_t s = on_dec ? p->s_lk[j.pd.f % p->k.n_lk] : p->s_back;
     // a finish that draws nothing on the device, in a device-driven pipe: the generators move on to the buffer the NEXT finish reads, unchanged
     const auto pass_generators = [&] {
         return hipMemcpyAsync(p->rp_state[(g + 1) & 1], p->rp_state[g & 1], (size_t)L * (size_t)mv_randperm_state_words() * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
@@ -1400,11 +1379,11 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     // ... unless the previous frame's backend ran on THIS stream and waited for that segment itself (its e_cand is recorded at the same point): stream order
     // then covers it, and a pending cross-queue barrier less sits in front of the backend (device-driven frames are issued long before their selector is done;
     // every unsatisfied barrier at the head of a queue costs the other queues dispatch latency, profiles/r06_device_draw_ab.log)
-    const bool prev_here = p->alt && p->last_backend_frame == pd.f - 1;   // (on_dec: the previous front launch's event, waited for above, covers it too)
-    if (p->alt && pd.f > 0 && !prev_here) MV_TRY(p->e_seg[pd.f - 1].wait_if_pending(s));
+    const bool prev_here = p->k.alt && p->last_backend_frame == pd.f - 1;   // (on_dec: the previous front launch's event, waited for above, covers it too)
+    if (p->k.alt && pd.f > 0 && !prev_here) MV_TRY(p->e_seg[pd.f - 1].wait_if_pending(s));
     p->last_backend_frame = pd.f;
     const int ti = pd.ti;
-    if (ti >= 0) MV_TRY(p->tv4[ti].record(s));
+    if (ti >= 0) MV_TRY(p->tv[4][ti].record(s));
     const bool perm_in_args = j.kp == KPJ_PERM && L == 1 && n_max <= 256;   // one lane: the permutation rides in the kernel arguments (no pinned staging copy, no H2D node)
     if (!perm_in_args && host_rows) {   // (keypoint rows go straight into the frame's kp0 table, which the front launch then reads in place)
         const size_t perm_bytes = ((size_t)(L - 1) * cap + n_sel[L - 1]) * rw * sizeof(int64_t);
@@ -1417,7 +1396,7 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     // ~290 us).  Only the rotation into the world frame needs the previous pose (MACVO.py:273-281): it runs as one tiny kernel on
     // the SOLVE's stream right behind the previous solve, so the critical chain is solve -> mv_pose_apply_lanes -> solve on one
     // in-order stream.
-    const bool fused = p->fuse_backend != 0;
+    const bool fused = p->k.fuse_backend != 0;
     const mvKpSource src = kp_source_of(p, j, b, ps, perm_in_args);
     const auto obs_filter = [&] {
         return mv_obs_filter_lanes(t.inbound, t.cov0, t.cov1, t.vals, c.filters, c.filter_min_depth, c.max_depth, L, n_sel, cap, b.valid, b.n_valid, s);
@@ -1452,14 +1431,14 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
         MV_TRY(p->e_nvalid[k].record(s));
     }
     MV_TRY(p->e_backend[g].record(s));
-    if (ti >= 0) MV_TRY(p->tv5[ti].record(s));
+    if (ti >= 0) MV_TRY(p->tv[5][ti].record(s));
 
     // ---- side stream: world-frame tables from the previous solve's pose (same stream: no event), then the LM solves of all
     // lanes in ONE launch (problem l = rows [l * cap, (l + 1) * cap), dead rows masked by `valid`); the optimised poses become
     // the next frame's priors (StaticMotionModel)
     hipStream_t ss = p->s_side;
     if (ss != s) MV_TRY(p->e_backend[g].wait(ss));   // (alt layout: backend + solve share one in-order stream)
-    if (ti >= 0) MV_TRY(p->tv6[ti].record(ss));
+    if (ti >= 0) MV_TRY(p->tv[6][ti].record(ss));
     mvPosedSolve sv = b.solve;
     sv.init_pose = p->pose[j.pose_from];
     sv.out_pose_f32 = p->pose[j.pose_to];
@@ -1490,7 +1469,7 @@ static int finish_issue(mvFramePipe* p, const FinishJob& j, const int64_t* perm_
     }
     MV_TRY(p->e_solved[k].record(ss));   // (two adjacent records on one in-order stream, nothing between them: both fire behind the solve, in either order)
     MV_TRY(p->e_pgo.record(ss));
-    if (ti >= 0) MV_TRY(p->tv7[ti].record(ss));
+    if (ti >= 0) MV_TRY(p->tv[7][ti].record(ss));
     return MV_OK;
 }
 
@@ -1518,8 +1497,8 @@ static void launch_thread_main(mvFramePipe* p) {
         // A job arrives once per frame period (~150 us) and sits on the frame's critical chain (selector count -> backend): waking a thread that
         // sleeps on a condition variable costs 30-60 us of it.  Spin on the submission counter for up to MV spin_us first (one period and a half),
         // sleep only when the stream has really gone quiet.
-        if (p->spin_us > 0) {
-            const double t_end = now_us() + p->spin_us;
+        if (p->k.spin_us > 0) {
+            const double t_end = now_us() + p->k.spin_us;
             int it = 0;
             while (p->n_submitted.load(std::memory_order_acquire) == taken && !p->stop_flag.load(std::memory_order_relaxed)) {
 #if defined(__x86_64__) || defined(__i386__)
@@ -1539,9 +1518,9 @@ static void launch_thread_main(mvFramePipe* p) {
         }
         ++taken;
         const double t_pick = now_us();
-        if (p->host_stats) { p->st_n += 1; p->st_submit_to_pick += t_pick - j.t_submit; p->st_count_to_submit += j.t_submit - j.t_count; }
+        if (p->k.host_stats) { p->st_n += 1; p->st_submit_to_pick += t_pick - j.t_submit; p->st_count_to_submit += j.t_submit - j.t_count; }
         int rc = finish_issue(p, j, j.seeded ? draw_perms(p, j) : j.perm.data());
-        if (p->host_stats) p->st_pick_to_issued += now_us() - t_pick;
+        if (p->k.host_stats) p->st_pick_to_issued += now_us() - t_pick;
         if (rc == MV_OK && j.has_sel) rc = issue_selector_segment(p, j.sel);
         {
             std::lock_guard<std::mutex> lk(p->mu);
@@ -1598,7 +1577,7 @@ static int finish_prologue(mvFramePipe* p, bool markers, bool map_count) {
 static FinishJob new_job(const mvFramePipe* p, int kp, bool seeded, bool device) {
     FinishJob j{};
     j.kp = kp; j.seeded = seeded; j.device = device;
-    j.t_count = j.t_submit = p->host_stats ? now_us() : 0.0;
+    j.t_count = j.t_submit = p->k.host_stats ? now_us() : 0.0;
     return j;
 }
 // ... and last, for a frame whose every lane tracks `rows` rows (an upper bound where the live count exists on the device only: rows beyond are masked by `valid`)
@@ -1631,10 +1610,10 @@ extern "C" int mv_frame_pipe_finish_seeded(mvFramePipe* p, float* pose_sink, int
     if (p->c.selector_mode == MV_KP_RANDOM) return finish_rows(p, KPJ_HOST, pose_sink, n_cand_out, n_sel_out);
     MV_TRY(finish_prologue(p, false, false));
     const Pending& pd = p->pending.front();
-    const double t_w0 = p->host_stats ? now_us() : 0.0;
+    const double t_w0 = p->k.host_stats ? now_us() : 0.0;
     MV_TRY(p->e_cand[pd.cand].sync());
     FinishJob j = new_job(p, KPJ_PERM, true, false);
-    if (p->host_stats) p->st_wait += j.t_count - t_w0;
+    if (p->k.host_stats) p->st_wait += j.t_count - t_w0;
     int32_t nsel[MV_MAX_LANES];
     for (int l = 0; l < p->lanes; ++l) {
         const int64_t n = p->h_count[pd.cand][4 * l];
@@ -1658,7 +1637,7 @@ extern "C" int mv_frame_pipe_finish_device(mvFramePipe* p, float* pose_sink) {
     MV_TRY(finish_prologue(p, false, false));
     FinishJob j = new_job(p, KPJ_PERM, false, true);
     const int rc = finish_uniform(p, j, p->c.num_point, pose_sink);
-    if (p->host_stats) { p->st_fin += now_us() - j.t_count; p->st_calls += 1; }
+    if (p->k.host_stats) { p->st_fin += now_us() - j.t_count; p->st_calls += 1; }
     return rc;
 }
 
@@ -1741,7 +1720,7 @@ extern "C" int mv_frame_pipe_finish_keypoints(mvFramePipe* p, const int64_t* kp_
 }
 
 extern "C" int mv_frame_pipe_finish_keypoints_dev(mvFramePipe* p, const int64_t* kp_uv_dev, const int32_t* n_sel_dev, mvStream_t stream, float* pose_sink) {
-    MV_CHECK_ARG(p && kp_uv_dev && n_sel_dev && !p->pending.empty() && p->fuse_backend && !p->c.mapping && table_rows(p->c) >= 1);
+    MV_CHECK_ARG(p && kp_uv_dev && n_sel_dev && !p->pending.empty() && p->k.fuse_backend && !p->c.mapping && table_rows(p->c) >= 1);
     MV_TRY(finish_prologue(p, true, true));
     FinishJob j = new_job(p, KPJ_DEV, false, false);
     j.kp_dev = kp_uv_dev;
@@ -1769,12 +1748,12 @@ static int map_append_finished(mvFramePipe* p, Frame& f, int prev_frame, const f
     f.K = K_dev; f.T_BS = T_BS_dev;
     f.prior_pose = c.motion_model == MV_MOTION_TARTAN ? p->prior[g % N_MOT] : p->pose[p->prior_slot];   // push_keyframe(frame1, est_pose) (MACVO.py:282)
     f.baseline = baseline;
-    MV_TRY((p->fuse_backend ? p->e_solved[k] : p->e_posed[k]).wait(p->s_back));   // pos_Tw / cov0_world come from the side stream
+    MV_TRY((p->k.fuse_backend ? p->e_solved[k] : p->e_posed[k]).wait(p->s_back));   // pos_Tw / cov0_world come from the side stream
     MV_TRY(launch(b));
     MV_TRY(p->e_map.record(p->s_back));
     // The backend tables must outlive the append.  A front launch that runs on this stream is behind it in order; one on a decoder-side stream — the default of
     // the one-lane device-driven pipe — waits for e_mapl[k] before finish g + 2 rewrites the slot (finish_issue).  No packet for a pipe that has no such launch.
-    if (p->front_on_decoder) MV_TRY(p->e_mapl[k].record(p->s_back));
+    if (p->k.front_on_decoder) MV_TRY(p->e_mapl[k].record(p->s_back));
     // the optimised pose goes in after the append wrote the prior
     MV_TRY(p->e_map.wait(p->s_side));
     MV_TRY(set_pose(p->pose[p->pose_cur]));
@@ -1845,7 +1824,7 @@ static int map_skip_row(mvFramePipe* p, Launch launch) {
     // map_append_finished made this stream wait for when it registered finish g lies behind that write, so stream order already covers it and the wait
     // below adds nothing to the stream; it only keeps a caller that registers no keyframes correct.  (Not e_pgo: that is re-recorded behind the append's pose
     // copy and would put the backend stream behind work it does not depend on.)
-    if (g >= 0) MV_TRY((p->fuse_backend ? p->e_solved[g & 1] : p->e_posed[g & 1]).wait(p->s_back));
+    if (g >= 0) MV_TRY((p->k.fuse_backend ? p->e_solved[g & 1] : p->e_posed[g & 1]).wait(p->s_back));
     MV_TRY(launch(prior));
     return p->e_map.record(p->s_back);
 }
@@ -1917,38 +1896,30 @@ extern "C" int mv_frame_pipe_sync(mvFramePipe* p, mvStream_t stream, int block_h
     MV_CHECK_ARG(p);
     MV_TRY(flush_deferred(p));
     MV_TRY(flush_jobs(p));   // everything finished so far has been issued
-    if (block_host == 2) {   // results of the newest FINISHED frame only: its solve (which ran behind its backend kernels)
+    if (block_host == SYNC_NEWEST)   // results of the newest FINISHED frame only: its solve (which ran behind its backend kernels)
         return p->e_pgo.wait((hipStream_t)stream);
-    }
-    if (block_host) {
-        MV_HIP(hipStreamSynchronize(p->s_vol));
-        for (int k = 0; k < p->n_lk; ++k) MV_HIP(hipStreamSynchronize(p->s_lk[k]));
-        MV_HIP(hipStreamSynchronize(p->s_back));
-        MV_HIP(hipStreamSynchronize(p->s_side));
-        if (p->s_sel) MV_HIP(hipStreamSynchronize(p->s_sel));
-        return MV_OK;
-    }
-    // make `stream` wait for everything enqueued so far
+    if (block_host != SYNC_STREAM) return sync_streams(p, ST_ALL);   // SYNC_HOST (and, as ever, any other value)
+    // make `stream` wait for everything enqueued so far (every stream is visited even after a failure)
     Ev e;
     MV_TRY(e.create());
-    hipStream_t all[4 + MAX_LK] = {p->s_vol, p->s_back, p->s_side, p->s_sel};
-    for (int k = 0; k < p->n_lk; ++k) all[4 + k] = p->s_lk[k];
     int rc = MV_OK;
-    for (hipStream_t q : all) {
-        if (!q) continue;
+    const auto join = [&](hipStream_t q) {
         if (e.record(q) != MV_OK || e.wait((hipStream_t)stream) != MV_OK) rc = MV_ERR_LAUNCH;
-    }
+        return hipSuccess;
+    };
+    (void)each_stream(p, ST_ALL & ~ST_DECODER, join);
+    (void)each_stream(p, ST_DECODER, join);
     return rc;
 }
 
 extern "C" int mv_frame_pipe_time_volume(mvFramePipe* p, int max_launches) {
     MV_CHECK_ARG(p && max_launches >= 0 && max_launches <= (1 << 20));
     MV_TRY(flush_jobs(p));   // finish_issue on the launch thread records into tv3..tv7 (which may reallocate below)
-    for (auto* v : {&p->tv0, &p->tv1, &p->tv2, &p->tv3, &p->tv4, &p->tv5, &p->tv6, &p->tv7})
-        while ((int)v->size() < max_launches) {
+    for (std::vector<Ev>& v : p->tv)
+        while ((int)v.size() < max_launches) {
             Ev e;
             MV_TRY(e.create(hipEventDefault));   // (timing enabled)
-            v->push_back(std::move(e));
+            v.push_back(std::move(e));
         }
     p->n_timed = 0;
     p->timed_cap = max_launches;
@@ -1962,71 +1933,50 @@ extern "C" int mv_frame_pipe_time_detail(mvFramePipe* p, int on) {
     return MV_OK;
 }
 
-extern "C" int mv_frame_pipe_volume_times(mvFramePipe* p, float* ms, int cap, int* n) {
+// The one reader of the timing events: for each timed frame i and each column c of `cols` (indices into mvFramePipe::tv), ms[i * |cols| + c] = time from the
+// first timed GEMM start — `per_frame`: from frame i's own GEMM start — to that event.  Blocks until the streams `sync_a`, then `sync_b`, have drained.
+// `detail`: columns that exist only under mv_frame_pipe_time_detail (no frames without it); a pair that cannot be read is -1 there, an error otherwise.
+static int read_times(mvFramePipe* p, float* ms, int cap, int* n, std::initializer_list<int> cols, bool per_frame, bool detail, unsigned sync_a,
+                      unsigned sync_b) {
     MV_CHECK_ARG(p && n && cap >= 0 && (cap == 0 || ms));
-    MV_TRY(flush_jobs(p));
-    MV_HIP(hipStreamSynchronize(p->s_vol));
+    MV_TRY(flush_jobs(p));   // (the launch thread records tv[3] .. tv[7])
+    if (detail && !p->time_detail) { *n = 0; return MV_OK; }
+    MV_TRY(sync_streams(p, sync_a));
+    MV_TRY(sync_streams(p, sync_b));
     const int m = p->n_timed < cap ? p->n_timed : cap;
-    for (int i = 0; i < m; ++i) MV_HIP(hipEventElapsedTime(&ms[i], p->tv0[i].e, p->tv1[i].e));
+    float* out = ms;
+    for (int i = 0; i < m; ++i)
+        for (const int c : cols)
+            if (hipEventElapsedTime(out++, p->tv[0][per_frame ? i : 0].e, p->tv[c][i].e) != hipSuccess) {
+                if (!detail) return MV_ERR_LAUNCH;
+                out[-1] = -1.f;
+            }
     *n = m;
     return MV_OK;
 }
 
-// ... and when each timed GEMM STARTED, ms since the first one (the steady-state period of the very pass whose wall time is the bench line's `value`:
-// only the event pairs around the GEMM are recorded in that pass)
-extern "C" int mv_frame_pipe_volume_starts(mvFramePipe* p, float* ms, int cap, int* n) {
-    MV_CHECK_ARG(p && n && cap >= 0 && (cap == 0 || ms));
-    MV_TRY(flush_jobs(p));
-    MV_HIP(hipStreamSynchronize(p->s_vol));
-    const int m = p->n_timed < cap ? p->n_timed : cap;
-    for (int i = 0; i < m; ++i) MV_HIP(hipEventElapsedTime(&ms[i], p->tv0[0].e, p->tv0[i].e));
-    *n = m;
-    return MV_OK;
-}
+// how long each timed GEMM took ...
+extern "C" int mv_frame_pipe_volume_times(mvFramePipe* p, float* ms, int cap, int* n) { return read_times(p, ms, cap, n, {1}, true, false, ST_VOL, 0); }
 
-// timeline of the timed frames: for frame i, ms[4*i + {0,1,2,3}] = GEMM start, GEMM end, last lookup done, selector done,
-// all relative to the first timed GEMM start (blocks until everything enqueued so far has finished)
+// ... and when each STARTED, ms since the first one (the steady-state period of the very pass whose wall time is the bench line's `value`: only the event
+// pairs around the GEMM are recorded in that pass)
+extern "C" int mv_frame_pipe_volume_starts(mvFramePipe* p, float* ms, int cap, int* n) { return read_times(p, ms, cap, n, {0}, false, false, ST_VOL, 0); }
+
+// timeline of the timed frames: for frame i, ms[4*i + {0,1,2,3}] = GEMM start, GEMM end, last lookup done, selector done, all relative to the first timed
+// GEMM start (blocks until everything enqueued so far has finished)
 extern "C" int mv_frame_pipe_timeline(mvFramePipe* p, float* ms, int cap_frames, int* n) {
-    MV_CHECK_ARG(p && n && cap_frames >= 0 && (cap_frames == 0 || ms));
-    MV_TRY(flush_jobs(p));   // in the 'late' selector placement tv3 is recorded on the launch thread
-    if (!p->time_detail) { *n = 0; return MV_OK; }   // only the GEMM pairs were recorded
-    MV_HIP(hipStreamSynchronize(p->s_vol));
-    for (int k = 0; k < p->n_lk; ++k) MV_HIP(hipStreamSynchronize(p->s_lk[k]));
-    MV_HIP(hipStreamSynchronize(p->s_back));
-    if (p->s_sel) MV_HIP(hipStreamSynchronize(p->s_sel));
-    const int m = p->n_timed < cap_frames ? p->n_timed : cap_frames;
-    for (int i = 0; i < m; ++i) {
-        hipEvent_t evs[4] = {p->tv0[i].e, p->tv1[i].e, p->tv2[i].e, p->tv3[i].e};
-        for (int j = 0; j < 4; ++j)
-            if (hipEventElapsedTime(&ms[4 * i + j], p->tv0[0].e, evs[j]) != hipSuccess) ms[4 * i + j] = -1.f;
-    }
-    *n = m;
-    return MV_OK;
+    return read_times(p, ms, cap_frames, n, {0, 1, 2, 3}, false, true, ST_VOL | ST_DECODER | ST_BACK | ST_SEL, 0);
 }
 
-// ... and the backend side of the same frames: ms[4*i + {0,1,2,3}] = backend start, backend end (backend stream), pose_apply start,
-// solve end (solve stream); -1 where a frame was not finished (or had no keypoints)
+// ... and the backend side of the same frames: ms[4*i + {0,1,2,3}] = backend start, backend end (backend stream), pose_apply start, solve end (solve
+// stream); -1 where a frame was not finished (or had no keypoints).  (Device-driven frames run the front launch on the decoder side.)
 extern "C" int mv_frame_pipe_timeline_backend(mvFramePipe* p, float* ms, int cap_frames, int* n) {
-    MV_CHECK_ARG(p && n && cap_frames >= 0 && (cap_frames == 0 || ms));
-    MV_TRY(flush_jobs(p));
-    if (!p->time_detail) { *n = 0; return MV_OK; }
-    MV_HIP(hipStreamSynchronize(p->s_back));
-    MV_HIP(hipStreamSynchronize(p->s_side));
-    for (int k = 0; k < p->n_lk; ++k) MV_HIP(hipStreamSynchronize(p->s_lk[k]));   // (device-driven frames run the front launch on the decoder side)
-    const int m = p->n_timed < cap_frames ? p->n_timed : cap_frames;
-    for (int i = 0; i < m; ++i) {
-        hipEvent_t evs[4] = {p->tv4[i].e, p->tv5[i].e, p->tv6[i].e, p->tv7[i].e};
-        for (int j = 0; j < 4; ++j)
-            if (hipEventElapsedTime(&ms[4 * i + j], p->tv0[0].e, evs[j]) != hipSuccess) ms[4 * i + j] = -1.f;
-    }
-    *n = m;
-    return MV_OK;
+    return read_times(p, ms, cap_frames, n, {4, 5, 6, 7}, false, true, ST_BACK | ST_SIDE, ST_DECODER);
 }
 
 extern "C" int mv_frame_pipe_buffer(mvFramePipe* p, int which, int age, void** ptr, size_t* count) {
     MV_CHECK_ARG(p && ptr && count && age >= 0);
     const mvFramePipeConfig& c = p->c;
-    const size_t L = p->lanes, plane = L * p->plane;   // every buffer has a leading [lanes] dimension (VALS: [11, lanes, cap])
     *ptr = nullptr;
     *count = 0;
     // frontend-side buffers: age 0 = the newest enqueued frame; backend-side: age 0 = the newest finished frame
@@ -2034,53 +1984,55 @@ extern "C" int mv_frame_pipe_buffer(mvFramePipe* p, int which, int age, void** p
     auto front = [&](int depth) { return f >= 0 && age < depth; };
     auto back = [&]() { return g >= 0 && age < 2; };
     const Backend* b = back() ? &p->be[g & 1] : nullptr;
-    const size_t N = L * (size_t)cap_of(c);   // capacity rows (a lane's live rows: its n_sel)
+    const Maps* m = front(N_MAPS) ? &p->maps[f % N_MAPS] : nullptr;
+    const bool motion = c.motion_model == MV_MOTION_TARTAN, tail = c.mapping && age == 0;
+    void* at = nullptr;   // where the buffer of that age is (null: no such age, or no such buffer in this pipe); its count is what `carve` noted
     switch (which) {
-        case MV_FB_VOLUME:
-            // age limit: with a GEMM issued ahead (n_vol > n_enq) the buffer of frame f - 1 is being rewritten
-            if (!front(p->n_vol > p->n_enq ? 1 : 2)) break;
-            *ptr = p->vol[f % p->n_volbuf]; *count = (size_t)c.pairs * p->n8 * p->n2t; return MV_OK;   // (n2t cells per slice: padded for a tiled fp16 volume with h8 % 4 != 0)
-        case MV_FB_TOKENS: if (!front(1) || c.iters == 0) break; *ptr = p->tok[2 * (f % p->n_lk) + ((c.iters - 1) & 1)]; *count = (size_t)c.pairs * p->KK * p->n8; return MV_OK;
-        case MV_FB_DISPARITY: if (!front(N_MAPS)) break; *ptr = p->maps[f % N_MAPS].disparity; *count = plane; return MV_OK;
-        case MV_FB_DISPARITY_COV: if (!front(N_MAPS) || !p->maps[0].disparity_cov) break; *ptr = p->maps[f % N_MAPS].disparity_cov; *count = plane; return MV_OK;
-        case MV_FB_DEPTH: if (!front(N_MAPS)) break; *ptr = p->maps[f % N_MAPS].depth; *count = plane; return MV_OK;
-        case MV_FB_DEPTH_COV: if (!front(N_MAPS) || !p->maps[0].depth_cov) break; *ptr = p->maps[f % N_MAPS].depth_cov; *count = plane; return MV_OK;
-        case MV_FB_MATCH_FLOW: if (!front(N_MAPS)) break; *ptr = p->maps[f % N_MAPS].match_flow; *count = 2 * plane; return MV_OK;
-        case MV_FB_MATCH_COV: if (!front(N_MAPS) || !p->maps[0].match_cov) break; *ptr = p->maps[f % N_MAPS].match_cov; *count = 3 * plane; return MV_OK;
-        case MV_FB_CAND: if (!front(N_CAND)) break; *ptr = p->cand[f % N_CAND]; *count = plane; return MV_OK;
-        case MV_FB_COUNT: if (!front(N_CAND)) break; *ptr = p->count[f % N_CAND]; *count = 4 * L; return MV_OK;
-        case MV_FB_STATS: if (!front(N_CAND)) break; *ptr = p->stats[f % N_CAND]; *count = 4 * L; return MV_OK;
-        case MV_FB_KP0: if (!b) break; *ptr = b->kp0; *count = 2 * N; return MV_OK;
-        case MV_FB_KP0F: if (!b) break; *ptr = b->kp0f; *count = 2 * N; return MV_OK;
-        case MV_FB_KP1: if (!b) break; *ptr = b->kp1; *count = 2 * N; return MV_OK;
-        case MV_FB_INBOUND: if (!b) break; *ptr = b->inbound; *count = N; return MV_OK;
-        case MV_FB_VALS: if (!b) break; *ptr = b->vals; *count = 11 * N; return MV_OK;
-        case MV_FB_SIGMA0: if (!b) break; *ptr = b->sigma0; *count = 3 * N; return MV_OK;
-        case MV_FB_SIGMA1: if (!b) break; *ptr = b->sigma1; *count = 3 * N; return MV_OK;
-        case MV_FB_POS_TC: if (!b) break; *ptr = b->pos_Tc; *count = 3 * N; return MV_OK;
-        case MV_FB_POS_TW: if (!b) break; *ptr = b->pos_Tw; *count = 3 * N; return MV_OK;
-        case MV_FB_ROT: if (!b) break; *ptr = b->rot; *count = 9 * L; return MV_OK;
-        case MV_FB_COV0: if (!b) break; *ptr = b->cov0; *count = 9 * N; return MV_OK;
-        case MV_FB_COV0W: if (!b) break; *ptr = b->cov0w; *count = 9 * N; return MV_OK;
-        case MV_FB_COV1: if (!b) break; *ptr = b->cov1; *count = 9 * N; return MV_OK;
-        case MV_FB_VALID: if (!b) break; *ptr = b->valid; *count = N; return MV_OK;
-        case MV_FB_NVALID: if (!b) break; *ptr = b->n_valid; *count = L; return MV_OK;
-        case MV_FB_POSE64: if (!b) break; *ptr = b->pose64; *count = 7 * L; return MV_OK;
-        case MV_FB_INFO: if (!b) break; *ptr = b->info; *count = 4 * L; return MV_OK;
-        case MV_FB_POSE: if (age > 1) break; *ptr = p->pose[(p->pose_cur + 3 - age) % 3]; *count = 7 * L; return MV_OK;
-        case MV_FB_PERM: if (!b) break; *ptr = b->perm; *count = N; return MV_OK;
-        case MV_FB_LIVE: if (!b || !p->dev_draw) break; *ptr = b->live_dev; *count = 2 * L; return MV_OK;
-        case MV_FB_MOTION_IN: if (c.motion_model != MV_MOTION_TARTAN || !front(N_MAPS)) break; *ptr = p->motion_in[f % N_MAPS];
-            *count = L * (size_t)motion::OUT_C * motion::OUT_H * motion::OUT_W; return MV_OK;
-        case MV_FB_PRIOR: if (c.motion_model != MV_MOTION_TARTAN || !back()) break; *ptr = p->prior[g % N_MOT]; *count = 7 * L; return MV_OK;
-        case MV_FB_MAP_UV: if (!c.mapping || age) break; *ptr = p->mp_uvf; *count = 2 * (size_t)p->mp_rows; return MV_OK;
-        case MV_FB_MAP_D: if (!c.mapping || age) break; *ptr = p->mp_d; *count = (size_t)p->mp_rows; return MV_OK;
-        case MV_FB_MAP_SDD: if (!c.mapping || age) break; *ptr = p->mp_sdd; *count = (size_t)p->mp_rows; return MV_OK;
-        case MV_FB_MAP_TC: if (!c.mapping || age) break; *ptr = p->mp_Tc; *count = 3 * (size_t)p->mp_rows; return MV_OK;
-        case MV_FB_MAP_TW: if (!c.mapping || age) break; *ptr = p->mp_Tw; *count = 3 * (size_t)p->mp_rows; return MV_OK;
-        case MV_FB_MAP_COV: if (!c.mapping || age) break; *ptr = p->mp_cov; *count = 9 * (size_t)p->mp_rows; return MV_OK;
-        case MV_FB_MAP_COLOR: if (!c.mapping || age) break; *ptr = p->mp_color; *count = 3 * (size_t)p->mp_rows; return MV_OK;
+        // age limit: with a GEMM issued ahead (n_vol > n_enq) the buffer of frame f - 1 is being rewritten
+        case MV_FB_VOLUME: if (front(p->n_vol > p->n_enq ? 1 : 2)) at = p->vol[f % p->k.n_volbuf]; break;
+        case MV_FB_TOKENS: if (front(1) && c.iters > 0) at = p->tok[2 * (f % p->k.n_lk) + ((c.iters - 1) & 1)]; break;
+        case MV_FB_DISPARITY: if (m) at = m->disparity; break;
+        case MV_FB_DISPARITY_COV: if (m) at = m->disparity_cov; break;
+        case MV_FB_DEPTH: if (m) at = m->depth; break;
+        case MV_FB_DEPTH_COV: if (m) at = m->depth_cov; break;
+        case MV_FB_MATCH_FLOW: if (m) at = m->match_flow; break;
+        case MV_FB_MATCH_COV: if (m) at = m->match_cov; break;
+        case MV_FB_CAND: if (front(N_CAND)) at = p->cand[f % N_CAND]; break;
+        case MV_FB_COUNT: if (front(N_CAND)) at = p->count[f % N_CAND]; break;
+        case MV_FB_STATS: if (front(N_CAND)) at = p->stats[f % N_CAND]; break;
+        case MV_FB_KP0: if (b) at = b->kp0; break;
+        case MV_FB_KP0F: if (b) at = b->kp0f; break;
+        case MV_FB_KP1: if (b) at = b->kp1; break;
+        case MV_FB_INBOUND: if (b) at = b->inbound; break;
+        case MV_FB_VALS: if (b) at = b->vals; break;
+        case MV_FB_SIGMA0: if (b) at = b->sigma0; break;
+        case MV_FB_SIGMA1: if (b) at = b->sigma1; break;
+        case MV_FB_POS_TC: if (b) at = b->pos_Tc; break;
+        case MV_FB_POS_TW: if (b) at = b->pos_Tw; break;
+        case MV_FB_ROT: if (b) at = b->rot; break;
+        case MV_FB_COV0: if (b) at = b->cov0; break;
+        case MV_FB_COV0W: if (b) at = b->cov0w; break;
+        case MV_FB_COV1: if (b) at = b->cov1; break;
+        case MV_FB_VALID: if (b) at = b->valid; break;
+        case MV_FB_NVALID: if (b) at = b->n_valid; break;
+        case MV_FB_POSE64: if (b) at = b->pose64; break;
+        case MV_FB_INFO: if (b) at = b->info; break;
+        case MV_FB_POSE: if (age <= 1) at = p->pose[(p->pose_cur + 3 - age) % 3]; break;
+        case MV_FB_PERM: if (b) at = b->perm; break;
+        case MV_FB_LIVE: if (b && p->dev_draw) at = b->live_dev; break;
+        case MV_FB_MOTION_IN: if (motion && m) at = p->motion_in[f % N_MAPS]; break;
+        case MV_FB_PRIOR: if (motion && back()) at = p->prior[g % N_MOT]; break;
+        case MV_FB_MAP_UV: if (tail) at = p->mp_uvf; break;
+        case MV_FB_MAP_D: if (tail) at = p->mp_d; break;
+        case MV_FB_MAP_SDD: if (tail) at = p->mp_sdd; break;
+        case MV_FB_MAP_TC: if (tail) at = p->mp_Tc; break;
+        case MV_FB_MAP_TW: if (tail) at = p->mp_Tw; break;
+        case MV_FB_MAP_COV: if (tail) at = p->mp_cov; break;
+        case MV_FB_MAP_COLOR: if (tail) at = p->mp_color; break;
         default: break;
     }
-    return MV_ERR_INVALID_ARG;
+    if (!at) return MV_ERR_INVALID_ARG;
+    *ptr = at;
+    *count = p->fb_count[which] * (which >= MV_FB_MAP_UV && which <= MV_FB_MAP_COLOR ? (size_t)p->mp_rows : 1);   // (the tail's buffers: per row)
+    return MV_OK;
 }
