@@ -1220,6 +1220,69 @@ int mv_pose_interpolate(float* pose, uint8_t* need_interp, int T, uint8_t* mask,
 int mv_pose_interpolate_lanes(const mvMapStores* stores_dev /* DEVICE [lanes] */, int lanes, const int32_t* T /* host [lanes] */, uint8_t* mask,
                               int64_t mask_stride, mvStream_t stream);
 
+/* ---- Frame preprocessing (DataLoader/Transform.py:41-209: ScaleFrame, CenterCropFrame, SmartResizeFrame, CastDataType — the `Preprocess` block of
+ * Config/Experiment/Common/Preprocess.yaml that every KITTI / Zed / VBR run starts with, DataLoader/SequenceBase.py:120-141): a host-only plan and ONE launch
+ * per frame that resamples, crops or pads and converts every plane of every lane.  torchvision's tensor path (resize -> F.interpolate, center_crop) is
+ * RESTATED, UNPINNED: torchvision is no dependency and the reference does not pin it (requirements.txt:17).
+ *
+ * mvPreprocessPlan: any foldable list of the four transforms as three steps per axis —
+ *   window   the source after the crops / pads in FRONT of the resize: window(y, x) = src(y + win_y0, x + win_x0) for win_vy0 <= y < win_vy1 and
+ *            win_vx0 <= x < win_vx1, 0 elsewhere (center_crop zero-pads a frame smaller than the crop; False for the mask);
+ *   resized  window resampled to rs_h x rs_w: MV_PP_NEAREST = InterpolationMode.NEAREST_EXACT (src = min(floorf((dst + 0.5f) * (float(in) / float(out))),
+ *            in - 1) in fp32) or MV_PP_BILINEAR = bilinear, align_corners False, antialias True (per axis scale = in / out, support = max(scale, 1),
+ *            center = scale (i + 0.5), taps [max(0, int(center - support + 0.5)), min(in, int(center + support + 0.5))), weights
+ *            max(0, 1 - |(j - center + 0.5) / max(scale, 1)|) normalised to sum 1; width pass first, then height; a weight-0 tap is still multiplied in, so
+ *            a NaN under it spreads as in torch; an axis of unchanged size is not resampled).  scaled = 0: no resize, rs = window;
+ *   out      the crops / pads BEHIND the resize: out(y, x) = resized(y + out_y0, x + out_x0) inside [out_vy0, out_vy1) x [out_vx0, out_vx1), 0 elsewhere.
+ *            For SmartResizeFrame: crop origin = (max(out_y0, 0), max(out_x0, 0)), pads = out_vy0 / out_h - out_vy1 rows, out_vx0 / out_w - out_vx1 columns.
+ *   round_scale_u / _v: W / target_w and H / target_h of the resize as fp32 (Transform.py:65-66): gt_flow's planes are divided by them AFTER the resize (:79-80),
+ *   a true fp32 division.  K: the intrinsics after the list, row-major 3 x 3: rows 0 / 1 divided by round_scale_u / _v (:71-72), K[0][2] / K[1][2] lowered by the
+ *   UN-rounded half difference of a crop (:124-125) while the crop itself starts at Python's round((size - crop) / 2.0), half to EVEN — 376 x 1241 -> 376 x 780
+ *   cuts at column 230 and lowers cx by 230.5: the half-pixel disagreement is the reference's and is reproduced.
+ *   mid_dtype / out_dtype (-1 = none): CastDataType in front of the resize (taps and the resized plane are rounded to it) / anywhere (the type of every plane at
+ *   the store, the mask included).  16-bit planes are resampled in fp32 and rounded once, as torchvision does.
+ *
+ * mv_preprocess_plan (host only; the reference's Python double arithmetic, int() truncation and half-to-even rounding in C, as mv_input_pad does for the padder):
+ *   prev == NULL: the plan of ONE transform of a src_h x src_w frame with intrinsics K (host float[9], NULL = identity); prev != NULL: `prev` followed by the
+ *   transform (src_h, src_w, K are ignored; plan may be prev) — a `Preprocess` list still costs one launch.  kind MV_PP_SCALE: a0 = scale_u, a1 = scale_v,
+ *   mode = MV_PP_NEAREST / MV_PP_BILINEAR: target = int(size / scale); a target equal to the size is a copy.  MV_PP_CENTER_CROP: a0 = height, a1 = width.
+ *   MV_PP_SMART_RESIZE: a0 = height, a1 = width, mode = interpolation: s = min(H / a0, W / a1), scale by (s, s), then the centre crop — after int() the resized
+ *   frame is often one pixel short of the target (379 x 1250 -> 375 x 1240 for 376 x 780) and the crop pads a zero row / column.  MV_PP_CAST: mode = MV_F32 /
+ *   MV_F16 / MV_BF16.  MV_ERR_UNSUPPORTED: the transform does not fold into `prev` (a second real resize, a second cast to another type): start a new plan
+ *   from prev's output; MV_ERR_INVALID_ARG: a size outside [1, 32768], a scale that is not positive, a target of 0 rows or columns.
+ *
+ * mv_preprocess_lanes: the launch.  groups: HOST array of n_groups <= MV_PP_MAX_GROUPS plane groups, each `planes` planes per lane: src [lanes][planes][src_h]
+ *   [src_w] with src_lane_stride ELEMENTS between lanes, dst [lanes][planes][out_h][out_w] likewise; kind MV_PP_IMAGE (src fp32 / fp16 / bf16 or MV_PP_U8,
+ *   widened as float(u8) / 255.0f — what the reference's loaders do in front of the transform, a quarter of the upload), MV_PP_FLOW (2 planes: u, v; divided by
+ *   their round_scale), MV_PP_MASK (src MV_PP_U8 = bool: a gather under MV_PP_NEAREST, resampled != 0 under MV_PP_BILINEAR — torchvision filters it as fp32 and
+ *   casts back without rounding —; dst MV_PP_U8 or a float type), MV_PP_DEPTH.  dst_dtype: the store type, rounded once.  Nearest plans and plans without a
+ *   resize are gathers: bit-exact.  Pointers need their element's alignment only (vector loads / stores are used where an address allows them).
+ *   MV_PP_BILINEAR with a downscale above 8 on an axis: MV_ERR_UNSUPPORTED, nothing is launched (the reference's resolution sweep goes to 4). */
+enum { MV_PP_SCALE = 0, MV_PP_CENTER_CROP = 1, MV_PP_SMART_RESIZE = 2, MV_PP_CAST = 3 };
+enum { MV_PP_NEAREST = 0, MV_PP_BILINEAR = 1 };
+enum { MV_PP_IMAGE = 0, MV_PP_FLOW = 1, MV_PP_MASK = 2, MV_PP_DEPTH = 3 };
+enum { MV_PP_U8 = 7 };           /* extends MV_F32 / MV_F16 / MV_BF16 for mvPreprocessGroup.src_dtype / dst_dtype */
+#define MV_PP_MAX_GROUPS 8
+typedef struct mvPreprocessPlan {
+    int32_t src_h, src_w;
+    int32_t win_h, win_w, win_y0, win_x0, win_vy0, win_vy1, win_vx0, win_vx1;
+    int32_t rs_h, rs_w;
+    int32_t out_h, out_w, out_y0, out_x0, out_vy0, out_vy1, out_vx0, out_vx1;
+    int32_t scaled, interp, mid_dtype, out_dtype;
+    float round_scale_u, round_scale_v;
+    float K[9];
+} mvPreprocessPlan;
+typedef struct mvPreprocessGroup {
+    const void* src;
+    void* dst;
+    int64_t src_lane_stride, dst_lane_stride;
+    int32_t planes, kind, src_dtype, dst_dtype;
+} mvPreprocessGroup;
+int mv_preprocess_plan(mvPreprocessPlan* plan /* host */, const mvPreprocessPlan* prev /* host or NULL */, int src_h, int src_w,
+                       const float* K /* host [9] or NULL */, int kind, double a0, double a1, int mode);
+int mv_preprocess_lanes(const mvPreprocessPlan* plan /* host */, const mvPreprocessGroup* groups /* host [n_groups] */, int n_groups, int lanes,
+                        mvStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

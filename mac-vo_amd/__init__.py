@@ -9,6 +9,8 @@ Layout
   plugins.py       drop-in plugin classes (HIP_CovAwareSelector(_NoDepth), HIP_MappingPointSelector,
                    HIP_MatchCovariance, HIP_GaussianMixtureCovariance, HIP_NoCovariance,
                    HIP_Modifier_Diagonalize / _Normalize, HIP_TwoFrame_PGO, ...)
+  transforms.py    the resampling data transforms (HIP_ScaleFrame, HIP_CenterCropFrame, HIP_SmartResizeFrame,
+                   HIP_CastDataType, smart_transform): the `Preprocess` block as one launch per frame
   pipeline.py      the per-frame hot path in the reference's call order (Odometry/MACVO.py:173-311)
   distributed.py   one process per GPU, sequence sharding, RCCL pose gather
 

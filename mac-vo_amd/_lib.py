@@ -47,6 +47,13 @@ EVAL_TRAJ_COLS = ("ate_mean", "ate_std", "ate_rmse", "rte_mean", "rte_std", "rte
                   "rpe_rmse", "r00", "r01", "r02", "r10", "r11", "r12", "r20", "r21", "r22", "tx", "ty", "tz", "scale", "d1", "d2", "d3", "n_poses",
                   "n_pairs", "status")
 EVAL_TRAJ_MAX_POSES = 1 << 20
+# mv_preprocess_plan / mv_preprocess_lanes: transform kinds, interpolation modes, plane-group kinds, the uint8 / bool element type
+MV_PP_SCALE, MV_PP_CENTER_CROP, MV_PP_SMART_RESIZE, MV_PP_CAST = 0, 1, 2, 3
+MV_PP_NEAREST, MV_PP_BILINEAR = 0, 1
+MV_PP_IMAGE, MV_PP_FLOW, MV_PP_MASK, MV_PP_DEPTH = 0, 1, 2, 3
+MV_PP_U8 = 7
+MV_PP_MAX_GROUPS = 8
+PP_INTERP = {"nearest": MV_PP_NEAREST, "bilinear": MV_PP_BILINEAR}
 
 
 class mvKpSelectParams(C.Structure):
@@ -108,6 +115,18 @@ class mvMapFrameLanes(C.Structure):
     _fields_ = [("lanes", C.c_int32), ("cap", C.c_int32), ("prev_frame", C.c_int32), ("min_num_point", C.c_int32)] + \
         [(n, C.c_void_p) for n in ("n_rows", "time_ns", "valid", "kp0", "kp1", "vals", "sigma0", "sigma1", "cov0", "cov1", "pos_Tw", "cov0_world",
                                    "color", "K", "T_BS", "prior_pose")] + [("baseline", C.c_float)]
+
+
+class mvPreprocessPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "src_h", "src_w", "win_h", "win_w", "win_y0", "win_x0", "win_vy0", "win_vy1", "win_vx0", "win_vx1", "rs_h", "rs_w",
+        "out_h", "out_w", "out_y0", "out_x0", "out_vy0", "out_vy1", "out_vx0", "out_vx1", "scaled", "interp", "mid_dtype", "out_dtype")] + \
+        [("round_scale_u", C.c_float), ("round_scale_v", C.c_float), ("K", C.c_float * 9)]
+
+
+class mvPreprocessGroup(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_lane_stride", C.c_int64), ("dst_lane_stride", C.c_int64)] + \
+        [(n, C.c_int32) for n in ("planes", "kind", "src_dtype", "dst_dtype")]
 
 
 class mvFrameInputs(C.Structure):
@@ -292,6 +311,10 @@ SIGNATURES = {
     # PoseInterpolate (MapProcessor.py:28-49): one table, or every lane's map through the device descriptor array (T: host int32 [lanes])
     "mv_pose_interpolate": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "mv_pose_interpolate_lanes": (C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P]),
+    # frame preprocessing (DataLoader/Transform.py): the host-only plan (plan, prev or NULL, src_h, src_w, K host [9] or NULL, kind, a0, a1, mode) and the launch
+    "mv_preprocess_plan": (C.c_int, [C.POINTER(mvPreprocessPlan), C.POINTER(mvPreprocessPlan), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_double,
+                                     C.c_double, C.c_int]),
+    "mv_preprocess_lanes": (C.c_int, [C.POINTER(mvPreprocessPlan), C.POINTER(mvPreprocessGroup), C.c_int, C.c_int, _P]),
 }
 
 _lib = None

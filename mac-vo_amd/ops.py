@@ -1334,3 +1334,179 @@ def associate_trajectory(src, src_time, query_time, origin_ref=None, rebase: boo
                                             s_st, int(bool(rebase)), arr(poses), arr(flags), status.data_ptr(), _stream()), "mv_traj_associate_lanes")
     # (the launch is enqueued; the caching allocator keeps the copies made above valid for work already on this stream)
     return TrajAssocResult(poses, flags, status)
+
+
+# ------------------------------------------------------------------------------------------- frame preprocessing (DataLoader/Transform.py)
+class PlanDoesNotFold(L.MacvoHipError):
+    """The transform cannot be folded into the plan it was appended to (a second real resize, a second cast to another type): start a new plan."""
+
+
+_PP_KINDS = {"scale": L.MV_PP_SCALE, "crop": L.MV_PP_CENTER_CROP, "smart": L.MV_PP_SMART_RESIZE, "cast": L.MV_PP_CAST}
+_PP_CAST = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
+_PP_SRC = {torch.float32: L.MV_F32, torch.float16: L.MV_F16, torch.bfloat16: L.MV_BF16, torch.uint8: L.MV_PP_U8, torch.bool: L.MV_PP_U8}
+_PP_TORCH = {L.MV_F32: torch.float32, L.MV_F16: torch.float16, L.MV_BF16: torch.bfloat16}
+
+
+@dataclass
+class PreprocessPlan:
+    """What ``mv_preprocess_plan`` made of one transform or of a folded list: ``c`` is the C record the launch takes, ``K`` the intrinsics after the
+    list (CPU fp32, ``[3, 3]`` or ``[B, 3, 3]`` as they were given)."""
+    c: L.mvPreprocessPlan
+    K: torch.Tensor
+
+    @property
+    def src_shape(self) -> tuple:
+        return self.c.src_h, self.c.src_w
+
+    @property
+    def resized(self) -> tuple:
+        """The frame the last crop sees: the resized frame, or the source when no resize is folded in (a unit scale is a copy)."""
+        return (self.c.rs_h, self.c.rs_w) if self.c.scaled else (self.c.src_h, self.c.src_w)
+
+    @property
+    def height(self) -> int:
+        return self.c.out_h
+
+    @property
+    def width(self) -> int:
+        return self.c.out_w
+
+    def _crop(self) -> tuple:
+        c = self.c                 # the crops behind the resize — without a resize every crop has moved the window instead
+        return (c.out_y0, c.out_x0, c.out_vy0, c.out_vy1, c.out_vx0, c.out_vx1) if c.scaled else (c.win_y0, c.win_x0, c.win_vy0, c.win_vy1, c.win_vx0, c.win_vx1)
+
+    @property
+    def origin(self) -> tuple:
+        """``(top, left)`` of the crop (0 on an axis that is padded instead)."""
+        y0, x0 = self._crop()[:2]
+        return max(y0, 0), max(x0, 0)
+
+    @property
+    def pads(self) -> tuple:
+        """``(top, bottom, left, right)`` zero rows / columns of the output."""
+        _, _, vy0, vy1, vx0, vx1 = self._crop()
+        return vy0, self.c.out_h - vy1, vx0, self.c.out_w - vx1
+
+    @property
+    def round_scale(self) -> tuple:
+        """``(round_scale_u, round_scale_v)`` as fp32 values (``gt_flow``'s divisors)."""
+        return self.c.round_scale_u, self.c.round_scale_v
+
+    @property
+    def out_dtype(self):
+        return _PP_TORCH.get(self.c.out_dtype)
+
+    def then(self, kind: str, **args) -> "PreprocessPlan":
+        return preprocess_plan(0, 0, kind, prev=self, **args)
+
+
+def preprocess_plan(H: int, W: int, kind: str, K: torch.Tensor | None = None, prev: "PreprocessPlan | None" = None, *, scale_u=None, scale_v=None,
+                    height=None, width=None, interp: str = "nearest", dtype=None) -> PreprocessPlan:
+    """``mv_preprocess_plan``: the host arithmetic of one transform of DataLoader/Transform.py on an ``H x W`` frame with intrinsics ``K`` — or, with
+    ``prev``, of that transform appended to a plan (``H``, ``W``, ``K`` are then ignored).  ``kind``: ``"scale"`` (``scale_u``, ``scale_v``, ``interp``) =
+    ScaleFrame, ``"crop"`` (``height``, ``width``) = CenterCropFrame, ``"smart"`` (``height``, ``width``, ``interp``) = SmartResizeFrame, ``"cast"``
+    (``dtype``: "fp32" / "fp16" / "bf16" or the torch type) = CastDataType.  :class:`PlanDoesNotFold` when the transform does not fold into ``prev``."""
+    lib = L.load()
+    if kind not in _PP_KINDS:
+        raise ValueError(f"preprocess_plan: kind {kind!r} is not one of {sorted(_PP_KINDS)}")
+    if kind == "scale":
+        a0, a1, mode = float(scale_u), float(scale_v), L.PP_INTERP[interp]
+    elif kind == "cast":
+        dt = _PP_CAST.get(dtype, dtype)
+        if dt not in _DT:
+            raise ValueError(f"preprocess_plan: cast to {dtype!r} (fp32, fp16 or bf16)")
+        a0, a1, mode = 0.0, 0.0, _DT[dt]
+    else:
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in (height, width)):
+            raise ValueError(f"preprocess_plan: {kind} needs integer height and width, not {height!r}, {width!r}")
+        a0, a1, mode = float(height), float(width), L.PP_INTERP[interp]
+    if prev is not None:
+        Kin = prev.K
+    else:
+        Kin = torch.eye(3) if K is None else K.detach().to("cpu", torch.float32)
+    if Kin.shape[-2:] != (3, 3) or Kin.dim() not in (2, 3):
+        raise ValueError(f"preprocess_plan: K must be [3, 3] or [B, 3, 3], not {tuple(Kin.shape)}")
+    rows = Kin.reshape(-1, 9).contiguous()
+    out_rows, rec = [], None
+    for b in range(rows.shape[0]):                     # K goes through the same chain of fp32 operations for every matrix of a batch
+        c = L.mvPreprocessPlan()
+        kb = (C.c_float * 9)(*rows[b].tolist())
+        if prev is not None:
+            p = L.mvPreprocessPlan.from_buffer_copy(prev.c)
+            p.K = kb
+            code = lib.mv_preprocess_plan(C.byref(c), C.byref(p), 0, 0, None, _PP_KINDS[kind], a0, a1, mode)
+        else:
+            code = lib.mv_preprocess_plan(C.byref(c), None, int(H), int(W), kb, _PP_KINDS[kind], a0, a1, mode)
+        if code == -2:
+            raise PlanDoesNotFold(f"preprocess_plan: {kind} does not fold into the plan in front of it")
+        L.check(code, "mv_preprocess_plan")
+        out_rows.append(torch.tensor(list(c.K), dtype=torch.float32))
+        rec = rec or c
+    return PreprocessPlan(rec, torch.stack(out_rows).reshape(Kin.shape))
+
+
+@dataclass
+class PreprocessedFrame:
+    """The planes ``preprocess`` wrote (device tensors ``[B, C, out_h, out_w]`` on the current stream; None where the input was None)."""
+    imageL: torch.Tensor
+    imageR: torch.Tensor | None = None
+    gt_flow: torch.Tensor | None = None
+    flow_mask: torch.Tensor | None = None
+    gt_depth: torch.Tensor | None = None
+
+
+def preprocess(plan: PreprocessPlan, imageL: torch.Tensor, imageR: torch.Tensor | None = None, gt_flow: torch.Tensor | None = None,
+               flow_mask: torch.Tensor | None = None, gt_depth: torch.Tensor | None = None, out_dtype=None, out: "dict | None" = None) -> PreprocessedFrame:
+    """``mv_preprocess_lanes``: every plane of a frame through ``plan`` in ONE launch on the current stream; never synchronises.  Planes are ``[B, C, H, W]``
+    GPU tensors of the plan's source size (B = lanes, at most ``MV_MAX_LANES``): images fp32 / fp16 / bf16 or uint8 (widened as ``u8.float() / 255``), ``gt_flow``
+    ``[B, 2, H, W]``, ``flow_mask`` ``[B, 1, H, W]`` bool, ``gt_depth`` ``[B, 1, H, W]``; any but ``imageL`` may be None.  ``out_dtype`` (or the plan's
+    CastDataType): the type of every plane at the store, rounded once; otherwise a plane keeps its type (uint8 images become fp32, the mask stays bool).
+    ``out``: optional ``{name: tensor}`` of contiguous outputs to write (any element-aligned address)."""
+    lib = L.load()
+    od = _PP_CAST.get(out_dtype, out_dtype) if out_dtype is not None else plan.out_dtype
+    if od is not None and od not in _DT:
+        raise ValueError(f"preprocess: out_dtype {out_dtype!r} (fp32, fp16 or bf16)")
+    H, W = plan.src_shape
+    B = imageL.shape[0]
+    if not 1 <= B <= L.MV_MAX_LANES:
+        raise L.MacvoHipError(f"preprocess: {B} lanes (1 <= lanes <= {L.MV_MAX_LANES})")
+    kinds = {"imageL": L.MV_PP_IMAGE, "imageR": L.MV_PP_IMAGE, "gt_flow": L.MV_PP_FLOW, "flow_mask": L.MV_PP_MASK, "gt_depth": L.MV_PP_DEPTH}
+    planes = {"imageL": imageL, "imageR": imageR, "gt_flow": gt_flow, "flow_mask": flow_mask, "gt_depth": gt_depth}
+    groups, res, keep = [], {}, []
+    for name, t in planes.items():
+        if t is None:
+            res[name] = None
+            continue
+        if not t.is_cuda:
+            raise L.MacvoHipError(f"{name}: expected a GPU tensor (the HIP hot path has no CPU fallback)")
+        if t.dim() != 4 or t.shape[0] != B or tuple(t.shape[-2:]) != (H, W) or t.dtype not in _PP_SRC:
+            raise L.MacvoHipError(f"preprocess: {name} {tuple(t.shape)} {t.dtype}: expected [{B}, C, {H}, {W}] in fp32, fp16, bf16, uint8 or bool")
+        kind, Cn = kinds[name], int(t.shape[1])
+        if (kind == L.MV_PP_FLOW and Cn != 2) or (kind in (L.MV_PP_MASK, L.MV_PP_DEPTH) and Cn != 1) or not 1 <= Cn <= 16:
+            raise L.MacvoHipError(f"preprocess: {name} has {Cn} planes")
+        is_u8 = t.dtype in (torch.uint8, torch.bool)
+        if is_u8 and kind not in (L.MV_PP_IMAGE, L.MV_PP_MASK):
+            raise L.MacvoHipError(f"preprocess: {name} must be a floating-point plane")
+        t = t.contiguous()
+        if od is not None:
+            dt = od
+        elif kind == L.MV_PP_MASK and is_u8:
+            dt = torch.bool
+        else:
+            dt = torch.float32 if is_u8 else t.dtype
+        o = None if out is None else out.get(name)
+        if o is None:
+            o = torch.empty((B, Cn, plan.height, plan.width), dtype=dt, device=t.device)
+        elif o.shape != (B, Cn, plan.height, plan.width) or o.dtype != dt or not o.is_contiguous() or o.device != t.device:
+            raise ValueError(f"preprocess: out[{name!r}] must be a contiguous {dt} [{B}, {Cn}, {plan.height}, {plan.width}] tensor on the inputs' device")
+        g = L.mvPreprocessGroup()
+        g.src, g.dst = t.data_ptr(), o.data_ptr()
+        g.src_lane_stride, g.dst_lane_stride = Cn * H * W, Cn * plan.height * plan.width
+        g.planes, g.kind, g.src_dtype, g.dst_dtype = Cn, kind, _PP_SRC[t.dtype], _PP_SRC[dt]
+        groups.append(g)
+        keep.append(t)                 # (a contiguous copy made above must outlive the enqueue)
+        res[name] = o
+    arr = (L.mvPreprocessGroup * len(groups))(*groups)
+    with torch.cuda.device(imageL.device):
+        L.check(lib.mv_preprocess_lanes(C.byref(plan.c), arr, len(groups), B, _stream()), "mv_preprocess_lanes")
+    return PreprocessedFrame(**res)

@@ -250,6 +250,34 @@ def cov_config_fields(obs) -> dict:
     return out
 
 
+def preprocess_config_fields(block, seq_type: str, camera: "Camera") -> dict:
+    """A reference ``Preprocess`` block (Config/Experiment/Common/Preprocess.yaml: a mapping from sequence type to a list of ``{type, args}``, or such a list;
+    dicts or SimpleNamespaces) for a ``seq_type`` sequence whose frames arrive as ``camera`` -> ``{"plans", "camera"}``: the folded
+    :class:`ops.PreprocessPlan` list (one plan = one launch per frame; empty when the block does not name ``seq_type``) and the :class:`Camera` the backend
+    must use — size and intrinsics after the transforms, K through the reference's own fp32 steps.  KITTI's block turns a 376 x 1241 camera into 376 x 780."""
+    from .transforms import _FOLDABLE, _cfg_ns, plan_steps
+
+    if isinstance(block, (list, tuple)):
+        cfgs = list(block)
+    else:
+        table = vars(block) if not isinstance(block, dict) else block
+        cfgs = list(table.get(seq_type, ()))
+    steps = []
+    for c in cfgs:
+        c = _cfg_ns(c)
+        if c.type not in _FOLDABLE:
+            raise ValueError(f"data transform {c.type!r} has no HIP form (one of {sorted(_FOLDABLE)})")
+        _FOLDABLE[c.type].is_valid_config(c.args)
+        steps += _FOLDABLE[c.type](c.args).steps()
+    if not steps:
+        return {"plans": [], "camera": camera}
+    K = torch.tensor([[camera.fx, 0.0, camera.cx], [0.0, camera.fy, camera.cy], [0.0, 0.0, 1.0]], dtype=torch.float32)
+    plans = plan_steps(steps, camera.H, camera.W, K)
+    Ko = plans[-1].K
+    cam = replace(camera, fx=float(Ko[0, 0]), fy=float(Ko[1, 1]), cx=float(Ko[0, 2]), cy=float(Ko[1, 2]), H=plans[-1].height, W=plans[-1].width)
+    return {"plans": plans, "camera": cam}
+
+
 _MOTION_TYPES = {"StaticMotionModel": "static", "TartanMotionNet": "tartan", "HIP_TartanMotionNet": "tartan"}
 
 

@@ -122,6 +122,10 @@ CHECKS = [
     (r"^traj_assoc_kernel|^pose_interpolate(_lanes)?_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and
      r["sgpr_spill_count"] == 0,
      "trajectory association / PoseInterpolate: the se3 Log / Exp chain of se3_interp.h in registers (constant indices only): zero scratch, zero spills"),
+    (r"^preprocess_(gather|aa)_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and
+     regs(r) <= 128 and r.get("group_segment_fixed_size", 0) <= 48 * 1024,
+     "frame preprocessing: the plane table is read from the kernel argument with constant indices (no scratch, no spills), four waves per SIMD, the antialias "
+     "kernel's row-footprint tile + weight tables in 40.4 KB of LDS (three workgroups per CU)"),
 ]
 
 
