@@ -1283,6 +1283,72 @@ int mv_preprocess_plan(mvPreprocessPlan* plan /* host */, const mvPreprocessPlan
 int mv_preprocess_lanes(const mvPreprocessPlan* plan /* host */, const mvPreprocessGroup* groups /* host [n_groups] */, int n_groups, int lanes,
                         mvStream_t stream);
 
+/* ---- Stereo rectification (DataLoader/Dataset/EuRoC.py:143-174, 231-236 and VBR.py:60-64, 155-180: cv2.stereoRectify(flags = CALIB_ZERO_DISPARITY,
+ * alpha = -1) once per sequence, cv2.initUndistortRectifyMap(CV_32FC1) once per camera, cv2.remap(INTER_LINEAR) on every image, then float32 / 255): a
+ * host-only plan in double arithmetic, one launch that builds both cameras' maps, one launch per frame that remaps every plane of every lane.  OpenCV is
+ * RESTATED, PARITY-UNPINNED: it is no dependency here.  Known difference: OpenCV keeps the four undistorted image corners in float32, the plan keeps them in
+ * double, so the rectified principal point agrees with OpenCV's to about 1e-4 px.  Fed EuRoC's public calibration the plan gives the baseline the reference
+ * hard-codes (EuRoC.py:76, 0.1100778422).
+ *
+ * mv_stereo_rectify_plan (host only, no GPU; replaces cv2.stereoRectify, EuRoC.py:165-167 / VBR.py:175-177): K1, K2 row-major 3 x 3 doubles; D1, D2 n_d1 /
+ *   n_d2 = 4, 5 or 8 coefficients k1 k2 p1 p2 [k3 [k4 k5 k6]] (missing ones are 0; another count: MV_ERR_UNSUPPORTED); image size (nx, ny) = (width,
+ *   height); R (3 x 3), T (3): camera 1 to camera 2.  Bouguet's method:
+ *     om = Rodrigues^-1(R); r_r = Rodrigues(-om / 2); t = r_r T; idx = |t.x| > |t.y| ? 0 : 1 (0 a horizontal rig, 1 a vertical one);
+ *     c = t[idx]; uu = e_idx sign(c); ww = t x uu; if |ww| > 0: ww *= acos(|c| / |t|) / |ww|; wR = Rodrigues(ww);
+ *     R1 = wR r_r^T, R2 = wR r_r, t_new = R2 T;
+ *     per camera f = K[idx ^ 1][idx ^ 1], f *= 1 + k1 (nx^2 + ny^2) / (4 f^2) if k1 < 0; fc = the smaller of the two;
+ *     per camera the corners (0 | nx - 1, 0 | ny - 1) are undistorted (five fixed-point iterations of the inverse model), rotated by R_k and projected with
+ *     focal fc and a zero principal point; cc_k = ((nx - 1) / 2, (ny - 1) / 2) - their mean; both cameras get the average of cc_1 and cc_2;
+ *     P1 = [fc 0 ccx 0; 0 fc ccy 0; 0 0 1 0], P2 = P1 with P2[idx][3] = t_new[idx] fc.
+ *   The plan holds R1, R2, P1, P2 (row-major 3 x 4), per camera what the map builder needs (iR = (P[:3,:3] R_k)^-1, fx fy cx cy of the ORIGINAL camera, the
+ *   eight coefficients), K = P1[:3,:3] as fp32 (the K of every later stage) and baseline = |P2[idx][3] / fc|.  MV_ERR_INVALID_ARG: |T| = 0, a non-finite
+ *   input, a size outside [1, 32768].  alpha >= 0, the valid ROIs, Q and fisheye models are not built.
+ *
+ * mv_rectify_maps (one launch; replaces cv2.initUndistortRectifyMap, EuRoC.py:169-170 / VBR.py:179-180): for each of n_cams <= MV_RM_MAX_GROUPS cameras (HOST
+ *   array) and each pixel (u, v) of an out_h x out_w grid: [x y w] = iR [u v 1]; x' = x / w, y' = y / w; r2 = x'^2 + y'^2;
+ *   kr = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3); xd = x' kr + 2 p1 x' y' + p2 (r2 + 2 x'^2); yd = y' kr + p1 (r2 + 2 y'^2) +
+ *   2 p2 x' y'; map_x = fx xd + cx, map_y = fy yd + cy — in fp64 on the device, rounded once to fp32.  map_x, map_y: DEVICE fp32 [n_cams][out_h][out_w]
+ *   (cv2's CV_32FC1 pair: a map made elsewhere serves mv_remap_lanes as well).
+ *
+ * mv_remap_lanes (one launch per frame; replaces cv2.remap and the loaders' float32 / 255, EuRoC.py:224-236 / VBR.py:50-65): groups: HOST array of n_groups <=
+ *   MV_RM_MAX_GROUPS groups (the left and the right images are two groups with their own maps), each with `channels` = 1, 3 or 4: src uint8 (src_dtype
+ *   MV_PP_U8), layout MV_RM_HWC [lanes][src_h][src_w][channels] (what cv2.imread returns) or MV_RM_PLANAR [lanes][channels][src_h][src_w]; dst always planar
+ *   [lanes][channels][out_h][out_w] of dst_dtype MV_PP_U8 / MV_F32 / MV_F16 / MV_BF16; map_x, map_y fp32 [out_h][out_w] with map_lane_stride ELEMENTS between
+ *   lanes (0: one map for every lane, the usual case); lane strides in ELEMENTS; reverse_channels: destination channels 0 and 2 read source channels 2 and 0
+ *   (VBR's BGR -> RGB; EuRoC keeps BGR).  Arithmetic (csrc/remap_math.h): cv2's fixed-point INTER_LINEAR for 8-bit images, BORDER_CONSTANT 0, in integers:
+ *   s = rndne(map * 32) in fp32 (half to even); i = s >> 5 (floor), f = s & 31; taps outside the source count 0, each on its own; out = ((32 - fx)(32 - fy)
+ *   p00 + fx (32 - fy) p01 + (32 - fx) fy p10 + fx fy p11 + 512) >> 10 — OpenCV's 15-bit weight table exactly.  Defined where OpenCV's result depends on the
+ *   platform: a NaN entry, or one whose * 32 leaves [-2^30, 2^30], yields 0.  Float destinations store float(out) / 255.0f (a true division), rounded once
+ *   more for fp16 / bf16.  MV_ERR_UNSUPPORTED (nothing is launched): channels other than 1, 3, 4; a source that is not uint8; MV_ERR_INVALID_ARG: more than
+ *   MV_RM_MAX_GROUPS groups, sizes outside [1, 32768], strides smaller than a lane, misaligned maps or destinations.  INTER_CUBIC and float sources are not
+ *   built. */
+#define MV_RM_MAX_GROUPS 4
+enum { MV_RM_PLANAR = 0, MV_RM_HWC = 1 };
+typedef struct mvRectifyCam {
+    double iR[9];              /* (P[:3,:3] R_k)^-1, row-major */
+    double fx, fy, cx, cy;     /* the original camera */
+    double k[8];               /* k1 k2 p1 p2 k3 k4 k5 k6 */
+} mvRectifyCam;
+typedef struct mvRectifyPlan {
+    double R1[9], R2[9], P1[12], P2[12];
+    mvRectifyCam cam[2];
+    double fc, baseline;
+    float K[9];                /* P1[:3,:3] */
+    int32_t width, height, idx;
+} mvRectifyPlan;
+typedef struct mvRemapGroup {
+    const void* src;
+    void* dst;
+    const float* map_x;
+    const float* map_y;
+    int64_t src_lane_stride, dst_lane_stride, map_lane_stride;
+    int32_t channels, layout, reverse_channels, src_dtype, dst_dtype, reserved;
+} mvRemapGroup;
+int mv_stereo_rectify_plan(mvRectifyPlan* plan /* host */, const double* K1, const double* D1, int n_d1, const double* K2, const double* D2, int n_d2, int nx,
+                           int ny, const double* R, const double* T);
+int mv_rectify_maps(const mvRectifyCam* cams /* host [n_cams] */, int n_cams, int out_h, int out_w, float* map_x, float* map_y, mvStream_t stream);
+int mv_remap_lanes(const mvRemapGroup* groups /* host [n_groups] */, int n_groups, int lanes, int src_h, int src_w, int out_h, int out_w, mvStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

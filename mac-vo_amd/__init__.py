@@ -11,6 +11,8 @@ Layout
                    HIP_Modifier_Diagonalize / _Normalize, HIP_TwoFrame_PGO, ...)
   transforms.py    the resampling data transforms (HIP_ScaleFrame, HIP_CenterCropFrame, HIP_SmartResizeFrame,
                    HIP_CastDataType, smart_transform): the `Preprocess` block as one launch per frame
+  rectify.py       StereoRectifier: stereo rectification of EuRoC / VBR frames (plan and maps once, one remap launch per
+                   frame) in front of the `Preprocess` block
   pipeline.py      the per-frame hot path in the reference's call order (Odometry/MACVO.py:173-311)
   distributed.py   one process per GPU, sequence sharding, RCCL pose gather
 

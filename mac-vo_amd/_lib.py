@@ -54,6 +54,9 @@ MV_PP_IMAGE, MV_PP_FLOW, MV_PP_MASK, MV_PP_DEPTH = 0, 1, 2, 3
 MV_PP_U8 = 7
 MV_PP_MAX_GROUPS = 8
 PP_INTERP = {"nearest": MV_PP_NEAREST, "bilinear": MV_PP_BILINEAR}
+# mv_rectify_maps / mv_remap_lanes: cameras or groups per launch, source layouts
+MV_RM_MAX_GROUPS = 4
+MV_RM_PLANAR, MV_RM_HWC = 0, 1
 
 
 class mvKpSelectParams(C.Structure):
@@ -129,6 +132,21 @@ class mvPreprocessGroup(C.Structure):
         [(n, C.c_int32) for n in ("planes", "kind", "src_dtype", "dst_dtype")]
 
 
+class mvRectifyCam(C.Structure):
+    _fields_ = [("iR", C.c_double * 9), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("k", C.c_double * 8)]
+
+
+class mvRectifyPlan(C.Structure):
+    _fields_ = [("R1", C.c_double * 9), ("R2", C.c_double * 9), ("P1", C.c_double * 12), ("P2", C.c_double * 12), ("cam", mvRectifyCam * 2),
+                ("fc", C.c_double), ("baseline", C.c_double), ("K", C.c_float * 9), ("width", C.c_int32), ("height", C.c_int32), ("idx", C.c_int32)]
+
+
+class mvRemapGroup(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("map_x", C.c_void_p), ("map_y", C.c_void_p)] + \
+        [(n, C.c_int64) for n in ("src_lane_stride", "dst_lane_stride", "map_lane_stride")] + \
+        [(n, C.c_int32) for n in ("channels", "layout", "reverse_channels", "src_dtype", "dst_dtype", "reserved")]
+
+
 class mvFrameInputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("fmap1", "fmap2", "coords", "flow", "logcov", "flow8", "cov8", "up_mask",
                                           "cov_mask")]
@@ -142,6 +160,7 @@ FB_NAMES = ("VOLUME", "TOKENS", "DISPARITY", "DISPARITY_COV", "DEPTH", "DEPTH_CO
 FB = {n: i for i, n in enumerate(FB_NAMES)}
 
 _P = C.c_void_p
+_PD = C.POINTER(C.c_double)
 # the four window lookups: vol, coords, out, B, H1, W1, H2, W2, radius, stream
 _LOOKUP = [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]
 # the six posed solves: (nprob, offsets, n_live, cap, graph_type) or (nprob, offsets, n_live_dev, n_live_stride, cap, graph_type), then the poses and tables
@@ -315,6 +334,12 @@ SIGNATURES = {
     "mv_preprocess_plan": (C.c_int, [C.POINTER(mvPreprocessPlan), C.POINTER(mvPreprocessPlan), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_double,
                                      C.c_double, C.c_int]),
     "mv_preprocess_lanes": (C.c_int, [C.POINTER(mvPreprocessPlan), C.POINTER(mvPreprocessGroup), C.c_int, C.c_int, _P]),
+    # stereo rectification (DataLoader/Dataset/EuRoC.py:143-174, 231-236; VBR.py:60-64, 155-180): the host-only plan (plan, K1, D1, n_d1, K2, D2, n_d2, nx, ny,
+    # R, T: host doubles), the map builder (cams host [n_cams], n_cams, out_h, out_w, map_x, map_y, stream) and the per-frame remap (groups host [n_groups],
+    # n_groups, lanes, src_h, src_w, out_h, out_w, stream)
+    "mv_stereo_rectify_plan": (C.c_int, [C.POINTER(mvRectifyPlan), _PD, _PD, C.c_int, _PD, _PD, C.c_int, C.c_int, C.c_int, _PD, _PD]),
+    "mv_rectify_maps": (C.c_int, [C.POINTER(mvRectifyCam), C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "mv_remap_lanes": (C.c_int, [C.POINTER(mvRemapGroup), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
 }
 
 _lib = None

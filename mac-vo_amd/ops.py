@@ -1510,3 +1510,143 @@ def preprocess(plan: PreprocessPlan, imageL: torch.Tensor, imageR: torch.Tensor 
     with torch.cuda.device(imageL.device):
         L.check(lib.mv_preprocess_lanes(C.byref(plan.c), arr, len(groups), B, _stream()), "mv_preprocess_lanes")
     return PreprocessedFrame(**res)
+
+
+# ------------------------------------------------------------------------------------------- stereo rectification (DataLoader/Dataset/EuRoC.py, VBR.py)
+@dataclass
+class RectifyPlan:
+    """What ``mv_stereo_rectify_plan`` made of a stereo calibration: ``c`` is the C record (its ``cam`` pair feeds ``rectify_maps``); ``R1``, ``R2`` ``[3, 3]``
+    and ``P1``, ``P2`` ``[3, 4]`` are CPU fp64 tensors, ``K`` = ``P1[:3, :3]`` CPU fp32 ``[3, 3]``."""
+    c: L.mvRectifyPlan
+    R1: torch.Tensor
+    R2: torch.Tensor
+    P1: torch.Tensor
+    P2: torch.Tensor
+    K: torch.Tensor
+
+    @property
+    def baseline(self) -> float:
+        return self.c.baseline
+
+    @property
+    def focal(self) -> float:
+        return self.c.fc
+
+    @property
+    def idx(self) -> int:
+        """0: a horizontal rig, 1: a vertical one."""
+        return self.c.idx
+
+    @property
+    def size(self) -> tuple:
+        """``(width, height)``."""
+        return self.c.width, self.c.height
+
+
+def _f64_host(a, n: int, name: str):
+    t = torch.as_tensor(a, dtype=torch.float64).detach().to("cpu").reshape(-1)
+    if n >= 0 and t.numel() != n:
+        raise ValueError(f"stereo_rectify_plan: {name} has {t.numel()} values, expected {n}")
+    return (C.c_double * t.numel())(*t.tolist()), t.numel()
+
+
+def stereo_rectify_plan(K1, D1, K2, D2, size, R, T) -> RectifyPlan:
+    """``mv_stereo_rectify_plan``: ``cv2.stereoRectify(K1, D1, K2, D2, size, R, T, flags=CALIB_ZERO_DISPARITY, alpha=-1)`` restated in C doubles on the host
+    (EuRoC.py:165-167, VBR.py:175-177); no GPU is touched.  ``K`` ``[3, 3]``, ``D`` 4, 5 or 8 coefficients, ``size`` = ``(width, height)``, ``R`` ``[3, 3]`` and
+    ``T`` ``[3]`` from camera 1 to camera 2."""
+    lib = L.load()
+    k1, _ = _f64_host(K1, 9, "K1")
+    k2, _ = _f64_host(K2, 9, "K2")
+    d1, n1 = _f64_host(D1, -1, "D1")
+    d2, n2 = _f64_host(D2, -1, "D2")
+    r, _ = _f64_host(R, 9, "R")
+    t, _ = _f64_host(T, 3, "T")
+    c = L.mvRectifyPlan()
+    L.check(lib.mv_stereo_rectify_plan(C.byref(c), k1, d1, n1, k2, d2, n2, int(size[0]), int(size[1]), r, t), "mv_stereo_rectify_plan")
+    f64 = lambda a, shape: torch.tensor(list(a), dtype=torch.float64).reshape(shape)          # noqa: E731
+    return RectifyPlan(c, f64(c.R1, (3, 3)), f64(c.R2, (3, 3)), f64(c.P1, (3, 4)), f64(c.P2, (3, 4)), torch.tensor(list(c.K), dtype=torch.float32).reshape(3, 3))
+
+
+def rectify_maps(plan: "RectifyPlan | list", out_h: int | None = None, out_w: int | None = None, device=None) -> tuple:
+    """``mv_rectify_maps``: the ``cv2.initUndistortRectifyMap(..., CV_32FC1)`` pair of every camera of ``plan`` (or of a list of ``mvRectifyCam`` records) in ONE
+    launch on the current stream -> ``(map_x, map_y)``, fp32 ``[n_cams, out_h, out_w]`` (default: the plan's image size).  fp64 on the device, rounded once."""
+    lib = L.load()
+    cams = list(plan.c.cam) if isinstance(plan, RectifyPlan) else list(plan)
+    if isinstance(plan, RectifyPlan):
+        out_h, out_w = plan.c.height if out_h is None else out_h, plan.c.width if out_w is None else out_w
+    if not 1 <= len(cams) <= L.MV_RM_MAX_GROUPS:
+        raise L.MacvoHipError(f"rectify_maps: {len(cams)} cameras (1 <= cameras <= {L.MV_RM_MAX_GROUPS})")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise L.MacvoHipError("rectify_maps: expected a GPU device (the HIP hot path has no CPU fallback)")
+    mx = torch.empty((len(cams), int(out_h), int(out_w)), dtype=torch.float32, device=dev)
+    my = torch.empty_like(mx)
+    arr = (L.mvRectifyCam * len(cams))(*cams)
+    with torch.cuda.device(dev):
+        L.check(lib.mv_rectify_maps(arr, len(cams), int(out_h), int(out_w), mx.data_ptr(), my.data_ptr(), _stream()), "mv_rectify_maps")
+    return mx, my
+
+
+_RM_DST = {torch.uint8: L.MV_PP_U8, torch.float32: L.MV_F32, torch.float16: L.MV_F16, torch.bfloat16: L.MV_BF16}
+
+
+def remap(images, maps, dtype=torch.float32, layout: str = "hwc", reverse_channels=False, out: "list | None" = None) -> list:
+    """``mv_remap_lanes``: ``cv2.remap(image, map_x, map_y, INTER_LINEAR)`` (8-bit fixed point, constant border 0) of every image of every group in ONE launch
+    on the current stream, and the loaders' ``float32 / 255`` (EuRoC.py:224-236, VBR.py:50-65); never synchronises.
+
+    ``images``: a list of up to ``MV_RM_MAX_GROUPS`` uint8 GPU tensors (a single tensor is one group) of one source size and lane count — ``[lanes, H, W, C]``
+    under ``layout="hwc"`` (what ``cv2.imread`` returns; ``[lanes, H, W]`` is C = 1) or ``[lanes, C, H, W]`` under ``"planar"``, C in 1, 3, 4.  ``maps``: one
+    ``(map_x, map_y)`` pair per group, fp32 ``[h, w]`` (shared by the lanes) or ``[lanes, h, w]``.  ``dtype``: ``torch.float32`` / ``float16`` / ``bfloat16``
+    (``out / 255``, a true division, rounded once more for the 16-bit types) or ``torch.uint8`` (the remapped bytes, planar).  ``reverse_channels`` (a bool, or
+    one per group): BGR -> RGB.  Returns one ``[lanes, C, h, w]`` tensor per group."""
+    lib = L.load()
+    if isinstance(images, torch.Tensor):
+        images, maps = [images], ([maps] if isinstance(maps[0], torch.Tensor) else maps)
+    if layout not in ("hwc", "planar"):
+        raise ValueError(f"remap: layout {layout!r} (hwc or planar)")
+    if dtype not in _RM_DST:
+        raise ValueError(f"remap: dtype {dtype!r} (uint8, float32, float16 or bfloat16)")
+    if len(images) != len(maps) or (out is not None and len(out) != len(images)):
+        raise ValueError("remap: one map pair (and one output) per group")
+    rev = list(reverse_channels) if isinstance(reverse_channels, (list, tuple)) else [bool(reverse_channels)] * len(images)
+    groups, res, keep = [], [], []
+    lanes = src_hw = out_hw = None
+    for i, (t, (mx, my)) in enumerate(zip(images, maps)):
+        if not (t.is_cuda and mx.is_cuda and my.is_cuda):
+            raise L.MacvoHipError("remap: expected GPU tensors (the HIP hot path has no CPU fallback)")
+        if layout == "hwc" and t.dim() == 3:
+            t = t.unsqueeze(-1)
+        if t.dim() != 4:
+            raise L.MacvoHipError(f"remap: image {tuple(t.shape)}: expected [lanes, H, W, C] (hwc) or [lanes, C, H, W] (planar)")
+        B = int(t.shape[0])
+        Cn, hw = (int(t.shape[3]), tuple(t.shape[1:3])) if layout == "hwc" else (int(t.shape[1]), tuple(t.shape[2:4]))
+        if mx.dtype != torch.float32 or my.dtype != torch.float32 or mx.shape != my.shape or mx.dim() not in (2, 3) or (mx.dim() == 3 and mx.shape[0] != B):
+            raise L.MacvoHipError(f"remap: maps must be an fp32 pair of one shape, [h, w] or [{B}, h, w], not {tuple(mx.shape)} / {tuple(my.shape)}")
+        ohw = tuple(mx.shape[-2:])
+        if lanes is None:
+            lanes, src_hw, out_hw = B, hw, ohw
+        if (B, hw, ohw) != (lanes, src_hw, out_hw):
+            raise L.MacvoHipError("remap: every group of a launch has the same lane count, source size and map size")
+        t, mx, my = t.contiguous(), mx.contiguous(), my.contiguous()
+        o = None if out is None else out[i]
+        if o is None:
+            o = torch.empty((B, Cn, ohw[0], ohw[1]), dtype=dtype, device=t.device)
+        elif o.shape != (B, Cn, ohw[0], ohw[1]) or o.dtype != dtype or not o.is_contiguous() or o.device != t.device:
+            raise ValueError(f"remap: out[{i}] must be a contiguous {dtype} [{B}, {Cn}, {ohw[0]}, {ohw[1]}] tensor on the inputs' device")
+        g = L.mvRemapGroup()
+        g.src, g.dst, g.map_x, g.map_y = t.data_ptr(), o.data_ptr(), mx.data_ptr(), my.data_ptr()
+        g.src_lane_stride, g.dst_lane_stride = Cn * hw[0] * hw[1], Cn * ohw[0] * ohw[1]
+        g.map_lane_stride = ohw[0] * ohw[1] if mx.dim() == 3 else 0
+        g.channels, g.layout, g.reverse_channels = Cn, L.MV_RM_HWC if layout == "hwc" else L.MV_RM_PLANAR, int(rev[i])
+        g.src_dtype = L.MV_PP_U8 if t.dtype == torch.uint8 else _DT.get(t.dtype, -1)           # (anything but uint8 is refused by the library)
+        g.dst_dtype = _RM_DST[dtype]
+        groups.append(g)
+        keep += [t, mx, my]                # (contiguous copies made above must outlive the enqueue)
+        res.append(o)
+    if not groups:
+        raise ValueError("remap: no images")
+    # (the group count, the lane count, the channel count and the source type are checked by the library: one place decides, its code is raised)
+    arr = (L.mvRemapGroup * len(groups))(*groups)
+    with torch.cuda.device(res[0].device):
+        L.check(lib.mv_remap_lanes(arr, len(groups), lanes, src_hw[0], src_hw[1], out_hw[0], out_hw[1], _stream()), "mv_remap_lanes")
+    return res

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Stand-alone timing of individual C-ABI kernels on the GPU box (HIP events, median of N launches).
 
-    python tools/kernel_bench.py [volume_f32 volume_f16 lookup select cov pgo eval eval_traj traj_assoc ...] [--iters 50]
+    python tools/kernel_bench.py [volume_f32 volume_f16 lookup select cov pgo eval eval_traj traj_assoc remap rectify_maps ...] [--iters 50]
 
 Used for A/B tuning and as the target of `rocprofv3 --pmc ...` runs (one kernel family per process).
 """
@@ -511,6 +511,83 @@ def main():
                 hm, tm = statistics.median(res["traj_assoc HIP"]), statistics.median(res["traj_assoc torch searchsorted"])
                 print(f"traj_assoc lanes {lanes}: torch / HIP = {tm / hm:.2f}x; one launch, every workgroup of a lane repeats the lane's checks "
                       f"({lanes * T * 64 / 1e6:.2f} MB of source rows and stamps)")
+        elif w in ("remap", "rectify_maps"):
+            # stereo rectification at EuRoC size (csrc/remap.hip): two cameras, 480 x 752 x 3.  `remap`: uint8 HWC -> fp32 planar, 1 lane and 32 lanes, next to
+            # torch's grid_sample on the same frames (bilinear, zeros padding, align_corners: float arithmetic on float images, so a yardstick only — it also
+            # needs the uint8 -> float conversion and the HWC -> planar permute the kernel does on the fly, timed with it).  `rectify_maps`: both cameras' maps.
+            # Back-to-back launches in alternating rounds (the spread over the rounds is the run-to-run spread).  Algorithmic bytes: the maps at 8 B per output
+            # pixel, the source at C B, the destination at C (uint8) or 4 C (fp32) B.
+            import torch.nn.functional as F
+
+            from tests import rectify_ref as RR
+
+            eh, ew, ec = 480, 752, 3
+            plan = ops.stereo_rectify_plan(*RR.euroc_rig())
+            mx, my = ops.rectify_maps(plan, device=dev)
+            if w == "rectify_maps":
+                rounds, per, res = 5, max(8, (4 * a.iters) // 5), []
+                for _ in range(5):
+                    ops.rectify_maps(plan, device=dev)
+                torch.cuda.synchronize()
+                for _ in range(rounds):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(per):
+                        ops.rectify_maps(plan, device=dev)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    res.append(e0.elapsed_time(e1) * 1e3 / per)
+                nb = 2 * eh * ew * 8
+                med = statistics.median(res)
+                print(f"rectify_maps 2 x {eh}x{ew}: median {med:8.2f} us / call, allocation of the two maps included (rounds {min(res):.2f} .. {max(res):.2f}; "
+                      f"{rounds * per} calls); {nb / 1e6:.2f} MB written = {nb / med / 1e3:.0f} GB/s = {nb / med / 1e3 / 8000 * 100:.2f}% of HBM peak (fp64 arithmetic, once per sequence)")
+                continue
+            maps = [(mx[0], my[0]), (mx[1], my[1])]
+            # grid_sample's grid: align_corners=True maps [-1, 1] onto pixel centres 0 .. size - 1
+            grids = [torch.stack([m[0] * (2.0 / (ew - 1)) - 1.0, m[1] * (2.0 / (eh - 1)) - 1.0], -1) for m in maps]
+            for lanes in (1, 32):
+                imgs = [torch.randint(0, 256, (lanes, eh, ew, ec), dtype=torch.uint8, generator=g).to(dev) for _ in range(2)]
+                outs = [torch.empty((lanes, ec, eh, ew), dtype=torch.float32, device=dev) for _ in range(2)]
+                gexp = [gr[None].expand(lanes, eh, ew, 2) for gr in grids]
+
+                def torch_leg():
+                    return [F.grid_sample(im.permute(0, 3, 1, 2).float() / 255, gr, mode="bilinear", padding_mode="zeros", align_corners=True)
+                            for im, gr in zip(imgs, gexp)]
+
+                legs = [("remap HIP u8 -> fp32", lambda: ops.remap(imgs, maps, dtype=torch.float32, out=outs)),
+                        ("remap HIP u8 -> u8", lambda: ops.remap(imgs, maps, dtype=torch.uint8)),
+                        ("torch grid_sample (float)", torch_leg)]
+                hh, tt = legs[0][1](), legs[2][1]()
+                torch.cuda.synchronize()
+                print(f"lanes {lanes}: max |HIP - grid_sample| = {max(float((x - y).abs().max()) for x, y in zip(hh, tt)):.3e} (1/32-pixel fixed point against float weights)")
+                rounds, per = 5, max(8, (4 * a.iters) // 5)
+                res = {k: [] for k, _ in legs}
+                for k, fn in legs:
+                    for _ in range(5):
+                        fn()
+                torch.cuda.synchronize()
+                for _ in range(rounds):
+                    for k, fn in legs:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(per):
+                            fn()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        res[k].append(e0.elapsed_time(e1) * 1e3 / per)
+                px = 2 * eh * ew
+                # per output pixel of every lane: 8 B of maps, C B of source, C or 4 C B of destination; `once`: the shared map counted once per launch instead
+                nbytes = {"remap HIP u8 -> fp32": lanes * px * (8 + ec * (1 + 4)), "remap HIP u8 -> u8": lanes * px * (8 + ec * (1 + 1))}
+                for k, _ in legs:
+                    v = res[k]
+                    med = statistics.median(v)
+                    tail = ""
+                    if k in nbytes:
+                        once = nbytes[k] - (lanes - 1) * px * 8
+                        tail = (f"; {nbytes[k] / 1e6:.1f} MB algorithmic = {nbytes[k] / med / 1e3:.0f} GB/s = {nbytes[k] / med / 1e3 / 8000 * 100:.1f}% of HBM peak "
+                                f"(shared maps counted once: {once / 1e6:.1f} MB = {once / med / 1e3 / 8000 * 100:.1f}%)")
+                    print(f"{k:28s} 2 x {eh}x{ew}x{ec} lanes {lanes:2d}: median {med:9.2f} us / call (rounds {min(v):.2f} .. {max(v):.2f}; {rounds * per} calls){tail}")
+                print(f"remap lanes {lanes}: grid_sample / HIP = {statistics.median(res['torch grid_sample (float)']) / statistics.median(res['remap HIP u8 -> fp32']):.2f}x; one launch")
         elif w == "select":
             fc = synth.flow_cov_maps(H, W, 2).to(dev)
             d0, d0c = [t.to(dev) for t in synth.depth_maps(H, W, 3)]

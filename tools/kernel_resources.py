@@ -126,6 +126,10 @@ CHECKS = [
      regs(r) <= 128 and r.get("group_segment_fixed_size", 0) <= 48 * 1024,
      "frame preprocessing: the plane table is read from the kernel argument with constant indices (no scratch, no spills), four waves per SIMD, the antialias "
      "kernel's row-footprint tile + weight tables in 40.4 KB of LDS (three workgroups per CU)"),
+    (r"^remap_lanes_kernel|^rectify_maps_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and
+     regs(r) <= 64 and r.get("group_segment_fixed_size", 0) == 0,
+     "stereo rectification: a gather through the caches — no LDS, no scratch, no spills (the group table is read from the kernel argument at a wave-uniform "
+     "offset, every register array is indexed by unrolled constants), eight waves per SIMD to hide the taps' latency"),
 ]
 
 
