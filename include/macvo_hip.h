@@ -1001,6 +1001,39 @@ int mv_kp_random_then_randperm_emulated(uint64_t seed, int calls, int num_point,
 int mv_kp_random_heads(uint64_t seed, int calls, int num_point, int H, int W, int mask_width, int64_t* out);
 int mv_kp_grid_count(int H, int W, int mask_width, int num_point);
 int mv_kp_grid(int H, int W, int mask_width, int num_point, int64_t* out_uv, mvStream_t stream);
+/* ---- GradientSelector and SparseGradienSelector: the image-gradient selectors (Module/KeypointSelector.py:121-158, :161-213) ---------------------------
+ *   grad = |conv2d(imageL[0] [3, H, W], Laplacian [[0,1,0],[1,-4,1],[0,1,0]] over the three channels, padding = 1)|   (:129-135 — the zero padding makes the
+ *          border pixels large; that is the reference and is kept)
+ *   thr  = grad.mean() + grad_std * grad.std()  (unbiased), candidates = grad > thr (strict) inside the border mask [m:-m, m:-m] (:136-147) and — nms_size
+ *          given — where grad == max_pool2d(grad, nms_size, stride 1, padding nms_size / 2): -inf padding, every tied maximum survives (:192-199)
+ *   in torch.nonzero's row-major order (:147, :201).  mask_width = 0 is the empty slice 0:-0 and 2 * mask_width >= H or W an empty mask: zero candidates,
+ *   no error.  A NaN pixel makes thr NaN: zero candidates.
+ * Arithmetic (csrc/kp_grad_math.h, replayed on the host by tests/c_abi/kp_grad_twin.cpp): per channel ((up + down) + (left + right)) - 4 c in fp32, channels
+ * added in order, fabsf; mean and std from fp64 sums of g and g^2 in a fixed order (per 64 x 16 tile, then the tiles in ascending index — no floating-point
+ * atomics), var = (S2 - n mean^2) / (n - 1) in fp64, mean and sqrt(var) rounded to fp32 once, thr = mean + (float)grad_std * std in fp32.  A lane's bits are
+ * the same from run to run, alone or batched.  On images whose values are multiples of 1 / 256 every step is exact and the candidates are those of torch.
+ *   image      [lanes, 3, H, W] fp32 planar
+ *   params     nms_size 0: GradientSelector; odd 1 .. 15: SparseGradienSelector (1 = the window is the pixel itself); an even or negative one, grad_std <= 0,
+ *              non-positive sizes, null pointers: MV_ERR_INVALID_ARG; an odd one above 15: MV_ERR_UNSUPPORTED; all checked before anything is launched
+ *   workspace  lanes * mv_kp_gradient_workspace_bytes(H, W) bytes, 8-byte aligned, no initial content required (MV_ERR_WORKSPACE when smaller)
+ *   out_cand   [lanes, H * W] int32 v * W + u, out_count [lanes, 4] int32 {n_candidates, n_above_threshold (inside the border, before the NMS), 0, 0}:
+ *              the layout of mv_kp_select_lanes, so mv_kp_gather(_lanes) applies;  out_stats [lanes, 4] fp32 {mean, std, thr, 0}
+ * mv_kp_finish_device_lanes: `selected[torch.randperm(n)[:k]]` rolled to (u, v) (:150-151, :204-205) without the host.  One workgroup per lane reads
+ * n = count_dev[l * count_stride], draws the permutation head from the lane's device-resident generator (mv_mt19937_seed representation, advanced in place
+ * by max(n - 1, 0) draws, as mv_randperm_head_lanes does), gathers the rows from cand + l * cand_lane_stride and writes out_uv int64 [lanes, cap, 2] — rows at
+ * or past min(n, k) are zero — and out_n_sel[l] = min(n, k).  k <= cap; k > mv_randperm_max_head(): MV_ERR_UNSUPPORTED.  Works on any candidate list of the
+ * mv_kp_select layout. */
+typedef struct {
+    int32_t H, W;
+    int32_t mask_width;    /* border exclusion in pixels; 0 selects nothing (the reference's empty slice) */
+    int32_t nms_size;      /* 0: GradientSelector; odd 1 .. 15: SparseGradienSelector */
+    float grad_std;        /* > 0 */
+} mvKpGradParams;
+size_t mv_kp_gradient_workspace_bytes(int H, int W);
+int mv_kp_gradient_lanes(const float* image, const mvKpGradParams* params /* host */, void* workspace, size_t workspace_bytes, int32_t* out_cand,
+                         int32_t* out_count, float* out_stats, int lanes, mvStream_t stream);
+int mv_kp_finish_device_lanes(uint32_t* state, const int32_t* cand, size_t cand_lane_stride, const int32_t* count_dev, int count_stride, int lanes, int k,
+                              int cap, int W, int64_t* out_uv, int32_t* out_n_sel, mvStream_t stream);
 /* Frame pipe.  Rows of capacity per lane of every per-keypoint table (0: invalid configuration): max(num_point, grid count) for MV_KP_GRID, num_point otherwise.
  * A configuration is rejected when H <= 2 * kp_mask_width or W <= 2 * kp_mask_width (new modes), when the grid has a step of 0, when the capacity exceeds
  * MV_KP_TABLE_MAX (the observation filter and the solve walk a lane's rows with one 256-thread workgroup: "a few thousand" is what they are built and tested
@@ -1016,7 +1049,8 @@ int mv_kp_grid(int H, int W, int mask_width, int num_point, int64_t* out_uv, mvS
  * mv_frame_pipe_finish_keypoints_dev: the same from device memory (kp_uv_dev as above, n_sel_dev int32 [lanes], clamped to [0, cap]), read on the pipe's
  * streams behind everything enqueued on `stream` so far; never waits for the host.  PRECONDITION (not checked): rows as above.  A row outside the image is
  * marked out of bounds and a patch that leaves the image is clamped — nothing is read outside the maps — but such a frame no longer follows the reference.
- * Needs the two-launch backend (the default) and no dense-mapping tail.  The caller may reuse both arrays once `stream` has passed mv_frame_pipe_sync(p, stream, 2). */
+ * Needs the two-launch backend (the default) and no dense-mapping tail.  The caller may reuse both arrays once `stream` has passed mv_frame_pipe_sync(p, stream, 2).
+ * The host learns such a frame's live-row counts only if it asks: mv_frame_pipe_finished_counts reads them back (n_cand = n_sel = the clamped count), on any pipe. */
 #define MV_KP_TABLE_MAX 4096
 int mv_frame_pipe_table_rows(const mvFramePipeConfig* cfg);
 int mv_frame_pipe_finish_keypoints(mvFramePipe* p, const int64_t* kp_uv_host, const int32_t* n_sel, float* pose_sink);

@@ -67,6 +67,10 @@ class mvKpSelectParams(C.Structure):
     ]
 
 
+class mvKpGradParams(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("mask_width", C.c_int32), ("nms_size", C.c_int32), ("grad_std", C.c_float)]
+
+
 class mvMatchCovParams(C.Structure):
     _fields_ = [
         ("H", C.c_int32), ("W", C.c_int32), ("kernel_size", C.c_int32), ("use_patch_var", C.c_int32),
@@ -304,6 +308,11 @@ SIGNATURES = {
     "mv_kp_random_heads": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mv_kp_grid_count": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mv_kp_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    # the image-gradient selectors: (image, params, workspace, workspace_bytes, out_cand, out_count, out_stats, lanes, stream) and the device finish
+    # (state, cand, cand_lane_stride, count_dev, count_stride, lanes, k, cap, W, out_uv, out_n_sel, stream)
+    "mv_kp_gradient_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mv_kp_gradient_lanes": (C.c_int, [_P, C.POINTER(mvKpGradParams), _P, C.c_size_t, _P, _P, _P, C.c_int, _P]),
+    "mv_kp_finish_device_lanes": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "mv_frame_pipe_table_rows": (C.c_int, [_P]),
     "mv_frame_pipe_finish_keypoints": (C.c_int, [_P, _P, _P, _P]),
     "mv_frame_pipe_finish_keypoints_dev": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -100,6 +100,7 @@ struct Backend {   // every table is [lanes, cap = num_point, ...]; rows beyond 
     int32_t* n_valid;
     int32_t* live_dev;   // [lanes, 2] device-driven frame: selected keypoints = live rows, candidate count (written by the front launch's draw)
     int32_t n_sel[MV_MAX_LANES];
+    bool rows_dev;       // the slot's frame took its rows and live-row counts from device memory (mv_frame_pipe_finish_keypoints_dev): the counts are in live_dev only
     // the slot's tables as the two backend launches take them, laid out once (describe_backend) and read-only afterwards
     mvFrontTables front;
     mvPosedSolve solve;   // ... with everything of the solve that does not change per finish (finish_issue fills in the poses and the live rows)
@@ -1263,6 +1264,7 @@ static int finish_host(mvFramePipe* p, const int32_t* n_sel, float* pose_sink, F
     j.pose_sink = pose_sink;
     Backend& b = p->be[j.g & 1];
     for (int l = 0; l < L; ++l) b.n_sel[l] = j.n_sel[l] = n_sel[l];
+    b.rows_dev = j.kp == KPJ_DEV;
     p->n_fin = j.g + 1;
     j.skipped = p->skipped;
     p->skipped = false;
@@ -1644,9 +1646,11 @@ extern "C" int mv_frame_pipe_finish_device(mvFramePipe* p, float* pose_sink) {
 // candidate / selected-keypoint counts of the `age`-th newest FINISHED frame (age 0 or 1), read back from the frame's backend slot: blocks until that
 // frame's front launch has run.  Off the hot path (result views, tests).
 extern "C" int mv_frame_pipe_finished_counts(mvFramePipe* p, int age, int32_t* n_cand, int32_t* n_sel) {
-    MV_CHECK_ARG(p && p->dev_draw && age >= 0 && age <= 1 && p->n_fin - 1 - age >= 0);
+    MV_CHECK_ARG(p && age >= 0 && age <= 1 && p->n_fin - 1 - age >= 0);
+    const bool rows_dev = p->be[(p->n_fin - 1 - age) & 1].rows_dev;   // device rows with device counts: published by the front launch, on any pipe
+    MV_CHECK_ARG(p->dev_draw || rows_dev);
     MV_TRY(flush_jobs(p));
-    if (kp_new_mode(p->c.selector_mode)) {   // (no candidate list: the row count is the configuration's)
+    if (kp_new_mode(p->c.selector_mode) && !rows_dev) {   // (no candidate list: the row count is the configuration's)
         for (int l = 0; l < p->lanes; ++l) {
             if (n_sel) n_sel[l] = p->be[(p->n_fin - 1 - age) & 1].n_sel[l];
             if (n_cand) n_cand[l] = frame_rows(p->c);

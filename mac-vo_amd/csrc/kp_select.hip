@@ -40,6 +40,7 @@
 //   MAPPING mode (no medians, ~10^5 candidates): kernel 1, a one-workgroup popcount scan, and a wave-per-word emit.
 // No host synchronisation inside; the caller reads back out_count when it needs n for randperm.
 #include "common.h"
+#include "kp_scan_dev.h"
 #include <math.h>
 
 namespace {
@@ -343,31 +344,6 @@ __device__ __forceinline__ float key_float(unsigned k) {
 
 constexpr int RANK_CAP = 256;                        // bucket size at which selection switches to direct ranking
 constexpr unsigned NAN_KEY = 0xFFFFFFFFu;
-
-// workgroup exclusive scan of one int per thread; returns the exclusive prefix and the total
-template <int NT>
-__device__ __forceinline__ int block_exclusive_scan(int v, int* wave_tot /*[NT/64] LDS*/, int& total) {
-    constexpr int NW = NT / 64;
-    const int tid = threadIdx.x;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if ((tid & 63) >= o) incl += t;
-    }
-    __syncthreads();  // protect wave_tot reuse
-    if ((tid & 63) == 63) wave_tot[tid >> 6] = incl;
-    __syncthreads();
-    int off = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const int t = wave_tot[w];
-        if (w < (tid >> 6)) off += t;
-        total += t;
-    }
-    return off + incl - v;
-}
 
 template <int NT, bool CACHED, int RPT, typename F>
 __device__ __forceinline__ void for_each_key(const float* __restrict__ vals, int n, const unsigned (&keys)[RPT], F&& f) {

@@ -455,14 +455,28 @@ def cost_patch_embed(cost_maps: torch.Tensor, weights: PatchEmbedWeights, tokens
 
 # ------------------------------------------------------------------------------------------- A10 / A11
 class KeypointCandidates:
-    """Device-side result of the dense selector stage; ``finish`` applies the reference's CPU randperm."""
+    """Device-side result of the dense selector stage; ``finish`` applies the reference's CPU randperm, ``finish_device`` the same draw from a
+    device-resident generator.  One frame: ``cand`` [H*W], ``count`` / ``stats`` [4].  A lane batch (``kp_gradient`` of ``[lanes, 3, H, W]``): ``cand``
+    [lanes, H*W], ``count`` / ``stats`` [lanes, 4]; ``lane(l)`` is the one-frame view that ``n`` / ``candidates_vu`` / ``finish`` work on."""
 
     def __init__(self, cand: torch.Tensor, count: torch.Tensor, stats: torch.Tensor, W: int):
         self.cand, self.count, self.stats, self.W = cand, count, stats, W
         self._n = None
 
     @property
+    def lanes(self) -> int:
+        return 1 if self.cand.dim() == 1 else self.cand.shape[0]
+
+    def lane(self, l: int) -> "KeypointCandidates":
+        return self if self.cand.dim() == 1 else KeypointCandidates(self.cand[l], self.count[l], self.stats[l], self.W)
+
+    def _one(self, what: str) -> None:
+        if self.cand.dim() != 1:
+            raise ValueError(f"KeypointCandidates.{what}: a lane batch; take one lane with lane(l) (or use finish_device)")
+
+    @property
     def n(self) -> int:
+        self._one("n")
         if self._n is None:
             self._n = int(self.count[0].item())  # the one host sync of the selector (reference has two)
         return self._n
@@ -489,6 +503,25 @@ class KeypointCandidates:
             L.check(lib.mv_kp_gather(self.cand.data_ptr(), perm_d.data_ptr(), n_sel, self.W, out.data_ptr(), _stream()),
                     "mv_kp_gather")
         return out
+
+    def finish_device(self, numPoint: int, state: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor]":
+        """The same draw and gather without the host (``mv_kp_finish_device_lanes``): ``(rows int64 [lanes, numPoint, 2], n_sel int32 [lanes])`` on the
+        device, ``n_sel = min(n, numPoint)`` live rows per lane and zeros behind them.  ``state`` (``mt19937_state``, one generator per lane) is
+        advanced in place as ``torch.randperm(n, generator=g)`` advances ``g``; the candidate count is read from device memory: no host sync."""
+        lib = L.load()
+        lanes = self.lanes
+        if (state.dim() != 2 or state.shape != (lanes, lib.mv_randperm_state_words()) or state.dtype != torch.int32 or not state.is_contiguous()
+                or state.device != self.cand.device):
+            raise ValueError(f"finish_device: state must be the contiguous int32 [{lanes}, state_words] tensor of mt19937_state on the candidates' device")
+        if numPoint < 0 or numPoint > lib.mv_randperm_max_head():
+            raise ValueError(f"finish_device: numPoint {numPoint} outside 0 .. {lib.mv_randperm_max_head()} (the device draw's permutation head)")
+        cap = max(numPoint, 1)      # (numPoint 0 still advances the generators, as torch.randperm(n)[:0] does)
+        rows = torch.empty((lanes, cap, 2), dtype=torch.int64, device=self.cand.device)
+        n_sel = torch.empty((lanes,), dtype=torch.int32, device=self.cand.device)
+        stride = self.cand.shape[-1]
+        L.check(lib.mv_kp_finish_device_lanes(state.data_ptr(), self.cand.data_ptr(), stride, self.count.data_ptr(), 4, lanes, numPoint, cap, self.W,
+                                              rows.data_ptr(), n_sel.data_ptr(), _stream()), "mv_kp_finish_device_lanes")
+        return rows[:, :numPoint], n_sel
 
 
 # ------------------------------------------------------------------------------------------- RandomSelector / GridSelector
@@ -590,6 +623,39 @@ def kp_select(mode: str, H: int, W: int, flow_cov: torch.Tensor | None = None, d
                              ws.data_ptr(), ws.numel() * 8, cand.data_ptr(), count.data_ptr(), stats.data_ptr(),
                              _stream()), "mv_kp_select")
     return KeypointCandidates(cand, count, stats, W)
+
+
+_grad_ws_cache: dict = {}
+
+
+def kp_gradient(image: torch.Tensor, mask_width: int, grad_std: float, nms_size: "int | None" = None) -> KeypointCandidates:
+    """Dense part of ``GradientSelector`` (``nms_size=None``) / ``SparseGradienSelector`` (KeypointSelector.py:121-158, :161-213) on ``imageL[0]``:
+    ``image`` fp32 planar ``[3, H, W]`` (one frame) or ``[lanes, 3, H, W]`` (independent frames of one launch).  ``nms_size`` odd 1 .. 15."""
+    lib = L.load()
+    if image.dim() not in (3, 4) or image.shape[-3] != 3:
+        raise ValueError(f"kp_gradient: image must be [3, H, W] or [lanes, 3, H, W], got {tuple(image.shape)}")
+    if not isinstance(mask_width, int) or mask_width < 0 or not grad_std > 0:
+        raise ValueError(f"kp_gradient: need an int mask_width >= 0 and grad_std > 0 (mask_width={mask_width!r}, grad_std={grad_std!r})")
+    if nms_size is not None and (not isinstance(nms_size, int) or nms_size < 1 or nms_size % 2 == 0 or nms_size > 15):
+        raise ValueError(f"kp_gradient: nms_size must be odd, 1 .. 15 (the NMS tile's halo), got {nms_size!r}")
+    image = _req(image, torch.float32, "image")
+    batched = image.dim() == 4
+    lanes = image.shape[0] if batched else 1
+    if lanes < 1 or lanes > L.MV_MAX_LANES:
+        raise ValueError(f"kp_gradient: {lanes} lanes outside 1 .. {L.MV_MAX_LANES}")
+    H, W = image.shape[-2:]
+    dev = image.device
+    key = (H, W, lanes, str(dev), _stream())     # (its content is rewritten by every call: one workspace per stream is enough)
+    ws = _grad_ws_cache.get(key)
+    if ws is None:
+        ws = _grad_ws_cache[key] = torch.empty((lib.mv_kp_gradient_workspace_bytes(H, W) * lanes + 7) // 8, dtype=torch.int64, device=dev)
+    p = L.mvKpGradParams(H, W, mask_width, nms_size or 0, float(grad_std))
+    cand = torch.empty((lanes, H * W), dtype=torch.int32, device=dev)
+    count = torch.empty((lanes, 4), dtype=torch.int32, device=dev)
+    stats = torch.empty((lanes, 4), dtype=torch.float32, device=dev)
+    L.check(lib.mv_kp_gradient_lanes(image.data_ptr(), C.byref(p), ws.data_ptr(), ws.numel() * 8, cand.data_ptr(), count.data_ptr(), stats.data_ptr(),
+                                     lanes, _stream()), "mv_kp_gradient_lanes")
+    return KeypointCandidates(cand, count, stats, W) if batched else KeypointCandidates(cand[0], count[0], stats[0], W)
 
 
 def pose_apply(pose: torch.Tensor, pos_Tc: torch.Tensor, cov_Tc: torch.Tensor):

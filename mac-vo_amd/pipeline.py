@@ -24,6 +24,7 @@ from __future__ import annotations
 import os
 import time
 from dataclasses import dataclass, field, replace
+from types import SimpleNamespace
 
 import torch
 
@@ -300,12 +301,14 @@ MAPLESS_SELECTORS = ("random", "grid", "explicit")     # look at no map: no sele
 def selector_config_fields(block) -> dict:
     """A reference ``keypoint`` block (``{type, args}`` as a dict or SimpleNamespace) -> ``{"selector", "kp_mask_width", ...}`` for
     :class:`HotPathConfig`: ``mask_width`` for every selector, and ``kernel_size`` / ``max_depth`` / ``max_depth_cov`` / ``max_match_cov`` for the
-    CovAware ones.  ``GradientSelector``, ``SparseGradienSelector`` and ``SelectorCompose`` have no HIP form: run them from torch and hand their
-    pixels to the pipe as explicit keypoints (``selector="explicit"``)."""
+    CovAware ones.  ``GradientSelector``, ``SparseGradienSelector`` and ``SelectorCompose`` have no HIP form inside the pipe (they look at the image,
+    which the pipe never sees): their HIP kernels run in front of it — :func:`image_selector` for the two gradient selectors, the ``HIP_*`` plugins for
+    all three — and hand their pixels to the pipe as explicit keypoints (``selector="explicit"``), device rows and device counts included."""
     t = _ns_get(block, "type")
     if t not in _SELECTOR_TYPES:
-        raise ValueError(f"keypoint selector {t!r} has no HIP form (one of {sorted(set(_SELECTOR_TYPES))}); "
-                         "its pixels can be fed through selector='explicit'")
+        hint = ("pipeline.image_selector(block, device) computes its rows on the GPU; feed them through selector='explicit'"
+                if t in _IMAGE_SELECTOR_TYPES else "its pixels can be fed through selector='explicit'")
+        raise ValueError(f"keypoint selector {t!r} has no HIP form as a pipe selector (one of {sorted(set(_SELECTOR_TYPES))}); {hint}")
     out = {"selector": _SELECTOR_TYPES[t]}
     args = _ns_get(block, "args")
     names = [("mask_width", "kp_mask_width")]
@@ -317,6 +320,51 @@ def selector_config_fields(block) -> dict:
         except (KeyError, AttributeError, TypeError):
             pass
     return out
+
+
+_IMAGE_SELECTOR_TYPES = {"GradientSelector": False, "SparseGradienSelector": True, "HIP_GradientSelector": False, "HIP_SparseGradienSelector": True}
+
+
+def image_selector(block, device, seeds=None):
+    """A reference ``keypoint`` block of type ``GradientSelector`` / ``SparseGradienSelector`` (or their ``HIP_`` names; ``{type, args}`` as a dict or
+    SimpleNamespace, the reference's keys ``mask_width``, ``grad_std``, ``nms_size``) -> a callable ``(imageL [lanes, 3, H, W] fp32, num_point) ->
+    (rows int64 [lanes, num_point, 2], counts int32 [lanes])``, both on ``device``, the rows zero-padded behind each lane's count: what
+    ``FrameInputs.keypoints`` / ``keypoint_counts`` of a ``selector="explicit"`` pipe take.  ``seeds`` (one per lane): device-resident generators with
+    the bits of ``torch.Generator().manual_seed(seed)``, advanced call by call — nothing reaches the host.  Without: ``torch.randperm`` of torch's
+    global CPU generator per lane, in lane order, as the reference draws (one host read of the counts per call)."""
+    from .plugins import HIP_GradientSelector, HIP_SparseGradienSelector
+
+    t = _ns_get(block, "type")
+    if t not in _IMAGE_SELECTOR_TYPES:
+        raise ValueError(f"image_selector: {t!r} is not an image selector (one of {sorted(_IMAGE_SELECTOR_TYPES)})")
+    args = _ns_get(block, "args")
+    args = SimpleNamespace(**args) if isinstance(args, dict) else args
+    sparse = _IMAGE_SELECTOR_TYPES[t]
+    (HIP_SparseGradienSelector if sparse else HIP_GradientSelector).is_valid_config(args)
+    if getattr(args, "seed", None) is not None and seeds is None:
+        seeds = [args.seed]
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"image_selector: {device!r} is not a GPU device (the HIP selectors have no CPU fallback)")
+    mask_width, grad_std, nms = args.mask_width, float(args.grad_std), (args.nms_size if sparse else None)
+    state = None if seeds is None else ops.mt19937_state(list(seeds), dev)
+
+    def select(imageL: torch.Tensor, num_point: int):
+        if imageL.dim() != 4:
+            raise ValueError(f"image_selector: imageL must be [lanes, 3, H, W], got {tuple(imageL.shape)}")
+        lanes = imageL.shape[0]
+        cands = ops.kp_gradient(imageL.to(dev), mask_width, grad_std, nms)
+        if state is not None:
+            if state.shape[0] != lanes:
+                raise ValueError(f"image_selector: {state.shape[0]} seeds for {lanes} lanes")
+            return cands.finish_device(num_point, state)
+        rows = torch.zeros((lanes, num_point, 2), dtype=torch.int64, device=dev)
+        live = [cands.lane(l).finish(num_point) for l in range(lanes)]
+        for l, r in enumerate(live):
+            rows[l, : r.shape[0]] = r
+        return rows, torch.tensor([r.shape[0] for r in live], dtype=torch.int32).to(dev)
+
+    return select
 
 
 _DEPTH_TYPES = {"FlowFormerCovDepth": True, "HIP_FlowFormerCovDepth": True, "FlowFormerDepth": False, "HIP_FlowFormerDepth": False}
@@ -512,9 +560,10 @@ class FrameInputs:
     lane_time_ns: "list | None" = None
     # caller-supplied keypoints of this frame: int64 (u, v) rows [n, 2] ([lanes, n, 2] for a batched step), on the host (checked) or on the device
     # (used as given: the caller keeps them cov_kernel_size // 2 inside the image).  Required by selector "explicit"; on any other selector they
-    # replace the frame's own selection.  keypoint_counts: live rows per lane (default: all n).
+    # replace the frame's own selection.  keypoint_counts: live rows per lane (default: all n) — a list, or with device keypoints a device int32 [lanes]
+    # tensor (image_selector's), which the native driver hands to the pipe as it is: no host read.
     keypoints: torch.Tensor | None = None
-    keypoint_counts: "list | None" = None
+    keypoint_counts: "list | torch.Tensor | None" = None
     # promise that every tensor above lives at a fixed address for the lifetime of the HotPath (e.g. the static output
     # buffers of a graph-captured network, as in the reference's CUDAGraph frontend): allows hipGraph replay
     static: bool = False
@@ -1512,6 +1561,8 @@ class NativeHotPath:
             raise ValueError("selector 'explicit': the frame carries no keypoints (FrameInputs.keypoints / step(..., keypoints=))")
         kp = kp.reshape(self.lanes, -1, 2)
         n = kp.shape[1]
+        if isinstance(counts, torch.Tensor) and counts.is_cuda:
+            return self._finish_keypoints_dev_counts(kp, counts, sink)
         counts = [n] * self.lanes if counts is None else [int(k) for k in counts]
         if len(counts) != self.lanes or any(k < 0 or k > n for k in counts) or max(counts) > self._cap:
             raise ValueError(f"keypoints: {counts} live rows of {n} given, table capacity {self._cap}")
@@ -1537,6 +1588,27 @@ class NativeHotPath:
                     self._kp[l, : counts[l]] = r
             L.check(lib.mv_frame_pipe_finish_keypoints(self._pipe, self._kp.data_ptr(), self._nsel, sink), "mv_frame_pipe_finish_keypoints")
         return self._finished(host_counts=True)
+
+    def _finish_keypoints_dev_counts(self, kp, counts, sink):
+        """Device rows with device counts (``image_selector``): both go to mv_frame_pipe_finish_keypoints_dev as they are — the pipe clamps each count to
+        the table capacity — and the frame's counts come back lazily (mv_frame_pipe_finished_counts) for whoever reads ``n_sel``."""
+        L, lib = ops.L, self._lib
+        n = kp.shape[1]
+        if not kp.is_cuda or counts.dtype != torch.int32 or counts.shape != (self.lanes,) or n > self._cap:
+            raise ValueError(f"keypoints with device counts: need device int64 rows [{self.lanes}, n <= {self._cap}, 2] and int32 counts [{self.lanes}]")
+        if self.cfg.mapping:
+            raise L.MacvoHipError("device keypoints do not combine with mapping=True (the mapping decision needs the host anyway): pass a host tensor")
+        L.check(lib.mv_frame_pipe_release(self._pipe, ops._stream()), "mv_frame_pipe_release")
+        if n == self._cap and kp.dtype == torch.int64 and kp.is_contiguous():
+            tab = kp
+        else:
+            tab = torch.zeros((self.lanes, self._cap, 2), dtype=torch.int64, device=self.dev)
+            tab[:, :n] = kp.to(torch.int64)
+        cnt = counts.contiguous() if n == self._cap else counts.clamp(max=n)     # (rows behind n do not exist; on the device)
+        self._kp_keep = self._kp_keep[-6:] + [(tab, cnt)]     # alive until the pipe has read them (two more finishes at most)
+        L.check(lib.mv_frame_pipe_finish_keypoints_dev(self._pipe, tab.data_ptr(), cnt.data_ptr(), ops._stream(), sink),
+                "mv_frame_pipe_finish_keypoints_dev")
+        return self._finished(lazy_counts=True)
 
     def _map_tail(self, mps):
         """Dense-mapping tail of the frame just finished (Odometry/MACVO.py:303-337): the reference maps only when tracking
@@ -1564,14 +1636,14 @@ class NativeHotPath:
         return ops.MapPoints(v("MAP_UV", f32, (2,)), v("MAP_D", f32, ()), v("MAP_SDD", f32, ()), v("MAP_TC", f32, (3,)), v("MAP_TW", f32, (3,)),
                              v("MAP_COV", torch.float64, (3, 3)), None if img is None else v("MAP_COLOR", torch.uint8, (3,)))
 
-    def _finished(self, host_counts: bool = False):
+    def _finished(self, host_counts: bool = False, lazy_counts: bool = False):
         """Bookkeeping behind a finish call: map registration, result views.  host_counts: the frame's row counts are known on the host
-        (self._nsel / self._ncand) although the pipe is device-driven."""
+        (self._nsel / self._ncand) although the pipe is device-driven; lazy_counts: they exist on the device only although it is not."""
         L, lib = ops.L, self._lib
         self._n_fin += 1
         if self._kps:
             self._kps.pop(0)
-        dd = self.device_driven and not host_counts
+        dd = (self.device_driven and not host_counts) or lazy_counts
         mps = getattr(self, "_maps", None)
         if mps is not None:   # every lane into its own map: one launch for all lanes, then the optimised poses by one more (mv_frame_pipe_map_append_lanes)
             n_rows = [self._cap if dd else int(self._nsel[l]) for l in range(self.lanes)]   # (device-driven: an upper bound; the append compacts by the `valid` mask)

@@ -7,6 +7,8 @@ replace, every hot arithmetic step in the HIP kernels (``include/macvo_hip.h``).
     CovAwareSelector                          HIP_CovAwareSelector
     MappingPointSelector                      HIP_MappingPointSelector
     RandomSelector / GridSelector             HIP_RandomSelector / HIP_GridSelector
+    GradientSelector / SparseGradienSelector  HIP_GradientSelector / HIP_SparseGradienSelector
+    SelectorCompose                           HIP_SelectorCompose  (sub-selectors through the registry, HIP_* or not)
     MatchCovariance                           HIP_MatchCovariance
     GaussianMixtureCovariance / NoCovariance  HIP_GaussianMixtureCovariance / HIP_NoCovariance
     Modifier_Diagonalize / Modifier_Normalize HIP_Modifier_Diagonalize / HIP_Modifier_Normalize  (fused into the kernel over a HIP model)
@@ -175,6 +177,86 @@ class HIP_GridSelector(IKeypointSelector):
             "mask_width": lambda m: isinstance(m, int) and m >= 0,
             "device": lambda d: _is_device(d) and d != "cpu",
         })
+
+
+class HIP_GradientSelector(IKeypointSelector):
+    """``GradientSelector`` (Module/KeypointSelector.py:121-158) on ``frame.imageL[0]`` (fp32 ``[3, H, W]``; a CPU image is moved to the GPU): the
+    Laplacian magnitude, its mean / std threshold, the border mask and ``torch.nonzero``'s order in HIP (``ops.kp_gradient``).  The reference's YAML keys
+    (no ``device``: the rows live where the kernels ran).  Without a ``seed`` the permutation is ``torch.randperm`` of torch's global CPU generator — the
+    reference's word stream, at the cost of one host read of the candidate count.  An optional ``seed: <int>`` switches to a device-resident generator with
+    the bits of ``torch.Generator().manual_seed(seed)`` and ``KeypointCandidates.finish_device`` (``numPoint <= mv_randperm_max_head()``)."""
+    _NMS = False
+
+    def __init__(self, config: SimpleNamespace):
+        super().__init__(config)
+        self._state = None
+
+    def select_point(self, frame, numPoint: int, depth0_est, depth1_est, match_est) -> torch.Tensor:
+        image = frame.imageL[0]
+        if not image.is_cuda:
+            image = image.cuda()
+        cands = ops.kp_gradient(image, self.config.mask_width, float(self.config.grad_std), self.config.nms_size if self._NMS else None)
+        seed = getattr(self.config, "seed", None)
+        if seed is None:
+            return cands.finish(numPoint)
+        if self._state is None:
+            self._state = ops.mt19937_state([seed], image.device)
+        rows, n_sel = cands.finish_device(numPoint, self._state)
+        return rows[0, : int(n_sel[0].item())]       # (the interface returns the live rows only: pipeline.image_selector keeps the count on the device)
+
+    @classmethod
+    def _spec(cls) -> dict:
+        return {"mask_width": lambda m: isinstance(m, int) and m >= 0,
+                "grad_std": lambda g: _num(g) and g > 0.0}
+
+    @classmethod
+    def is_valid_config(cls, config: SimpleNamespace | None) -> None:
+        assert config is not None
+        spec = cls._spec()
+        seed = getattr(config, "seed", None)
+        if seed is not None:   # (the exact-key-set rule: the optional key is part of the specification only where it is given)
+            spec["seed"] = lambda s: isinstance(s, int) and not isinstance(s, bool) and s >= 0
+        cls._enforce_config_spec(config, spec)
+
+
+class HIP_SparseGradienSelector(HIP_GradientSelector):
+    """``SparseGradienSelector`` (Module/KeypointSelector.py:161-213): ``HIP_GradientSelector`` plus ``grad == max_pool2d(grad, nms_size, 1, nms_size // 2)``
+    (every tied maximum survives).  ``nms_size`` odd, 1 .. 15 (the NMS tile's halo)."""
+    _NMS = True
+
+    @classmethod
+    def _spec(cls) -> dict:
+        spec = super()._spec()
+        spec["nms_size"] = lambda k: isinstance(k, int) and k >= 0 and (k % 2 == 1) and k <= 15
+        return spec
+
+
+class HIP_SelectorCompose(IKeypointSelector):
+    """``SelectorCompose`` (Module/KeypointSelector.py:51-75): sub-selector i is asked for ``int(numPoint * weight[i])`` keypoints — fp32 weights normalised
+    in fp32, an fp32 product, truncated ([1, 1, 1] with 200: 66 each) — and the rows are concatenated in order.  Sub-selectors are instantiated through the
+    registry, ``HIP_*`` or not; rows of a sub-selector that lives on another device are moved to the first one's."""
+
+    def __init__(self, config: SimpleNamespace):
+        super().__init__(config)
+        self.selectors = [IKeypointSelector.instantiate(arg.type, arg.args) for arg in self.config.selector_args]
+        self.weight = torch.tensor(self.config.weight)
+        self.weight = self.weight / self.weight.sum()
+
+    def split(self, numPoint: int) -> list:
+        return [int(numPoint * w) for w in self.weight]
+
+    def select_point(self, frame, numPoint: int, depth0_est, depth1_est, match_est) -> torch.Tensor:
+        keypoints = [sel.select_point(frame, k, depth0_est, depth1_est, match_est) for sel, k in zip(self.selectors, self.split(numPoint))]
+        return torch.cat([kp.to(keypoints[0].device) for kp in keypoints], dim=0)
+
+    @classmethod
+    def is_valid_config(cls, config: SimpleNamespace | None) -> None:
+        assert config is not None
+        for arg in config.selector_args:
+            IKeypointSelector.is_valid_config(arg)
+        assert isinstance(config.weight, list)
+        for val in config.weight:
+            assert isinstance(val, (int, float))
 
 
 def _grid_select(frame, numPoint: int, mask_width: int, dev) -> torch.Tensor:

@@ -588,6 +588,67 @@ def main():
                                 f"(shared maps counted once: {once / 1e6:.1f} MB = {once / med / 1e3 / 8000 * 100:.1f}%)")
                     print(f"{k:28s} 2 x {eh}x{ew}x{ec} lanes {lanes:2d}: median {med:9.2f} us / call (rounds {min(v):.2f} .. {max(v):.2f}; {rounds * per} calls){tail}")
                 print(f"remap lanes {lanes}: grid_sample / HIP = {statistics.median(res['torch grid_sample (float)']) / statistics.median(res['remap HIP u8 -> fp32']):.2f}x; one launch")
+        elif w == "grad_select":
+            # GradientSelector / SparseGradienSelector (csrc/kp_gradient.hip) at 480 x 640, 1 lane and 32 lanes, 200 keypoints per lane: the dense part alone,
+            # dense part + device finish (device-resident generators: nothing reaches the host inside the timed loop), and the same restatement run eagerly by
+            # torch on the same GPU, lane by lane, with `randperm` on the CPU as the reference has it (one host read of the count per lane).  Back-to-back calls
+            # in alternating rounds (the spread over the rounds is the run-to-run spread).  Algorithmic bytes per lane: three planes in, `grad` out and back.
+            import torch.nn.functional as F
+
+            from tests import grad_selectors_ref as GR
+
+            gh, gw, k_pts, m_w, g_std = 480, 640, 200, 32, 1.0
+            lap = torch.tensor(GR.LAPLACIAN).float().expand((1, 3, 3, 3)).to(dev)
+
+            def torch_select(images, nms):
+                out = []
+                for l in range(images.shape[0]):
+                    grad = F.conv2d(images[l:l + 1], lap, padding=1)[0].abs()
+                    points = grad > (grad.mean(dim=(1, 2), keepdim=True) + g_std * grad.std(dim=(1, 2), keepdim=True))
+                    border = torch.zeros_like(points)
+                    border[..., m_w:-m_w, m_w:-m_w] = 1.0
+                    points = points * border
+                    if nms:
+                        points = points * (grad == F.max_pool2d(grad, kernel_size=nms, stride=1, padding=nms // 2))
+                    sel = torch.nonzero(points, as_tuple=False)
+                    perm = torch.randperm(sel.shape[0])[:k_pts]
+                    out.append(sel[perm.to(dev)][..., 1:].roll(shifts=1, dims=1))
+                return out
+
+            for lanes in (1, 32):
+                images = torch.stack([GR.quantised_image(gh, gw, 40 + l) for l in range(lanes)]).to(dev)
+                state = ops.mt19937_state(list(range(lanes)), dev)
+                for name, nms in (("GradientSelector", None), ("SparseGradienSelector nms 7", 7)):
+                    legs = [("HIP dense part", lambda: ops.kp_gradient(images, m_w, g_std, nms)),
+                            ("HIP dense + device finish", lambda: ops.kp_gradient(images, m_w, g_std, nms).finish_device(k_pts, state)),
+                            ("torch eager + CPU randperm", lambda: torch_select(images, nms))]
+                    cand = legs[0][1]()
+                    n_hip = cand.count[:, 0].tolist()
+                    n_torch = [int(GR.candidates(images[l].cpu(), m_w, g_std, nms).numel()) for l in range(min(lanes, 2))]
+                    print(f"{name}, lanes {lanes}: candidates of lane 0 {n_hip[0]} (torch on the CPU: {n_torch[0]}; images are 1/256-valued: equal counts expected)")
+                    rounds, per = 5, max(8, (4 * a.iters) // 5)
+                    res = {kk: [] for kk, _ in legs}
+                    for kk, fn in legs:
+                        for _ in range(5):
+                            fn()
+                    torch.cuda.synchronize()
+                    for _ in range(rounds):
+                        for kk, fn in legs:
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record()
+                            for _ in range(per):
+                                fn()
+                            e1.record()
+                            torch.cuda.synchronize()
+                            res[kk].append(e0.elapsed_time(e1) * 1e3 / per)
+                    nbytes = lanes * gh * gw * 4 * 5
+                    for kk, _ in legs:
+                        v = res[kk]
+                        med = statistics.median(v)
+                        tail = "" if kk.startswith("torch") else f"; {nbytes / 1e6:.1f} MB algorithmic = {nbytes / med / 1e3:.0f} GB/s = {nbytes / med / 1e3 / 8000 * 100:.1f}% of HBM peak"
+                        print(f"{kk:28s} {name:28s} {gh}x{gw} lanes {lanes:2d}: median {med:9.2f} us / call (rounds {min(v):.2f} .. {max(v):.2f}; {rounds * per} calls){tail}")
+                    print(f"grad_select {name}, lanes {lanes}: torch eager / HIP with finish = "
+                          f"{statistics.median(res['torch eager + CPU randperm']) / statistics.median(res['HIP dense + device finish']):.2f}x")
         elif w == "select":
             fc = synth.flow_cov_maps(H, W, 2).to(dev)
             d0, d0c = [t.to(dev) for t in synth.depth_maps(H, W, 3)]
