@@ -1383,6 +1383,30 @@ int mv_stereo_rectify_plan(mvRectifyPlan* plan /* host */, const double* K1, con
 int mv_rectify_maps(const mvRectifyCam* cams /* host [n_cams] */, int n_cams, int out_h, int out_w, float* map_x, float* map_y, mvStream_t stream);
 int mv_remap_lanes(const mvRemapGroup* groups /* host [n_groups] */, int n_groups, int lanes, int src_h, int src_w, int out_h, int out_w, mvStream_t stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The PoseNet of TartanMotionNet (Module/Network/TartanVOStereo/FlowPoseNet.py:45-166 as StereoVO.py:21 constructs it: VOFlowRes(config = 1,
+ * stereo, down_scale, intrinsic, autoDistTarget = 0, no out_feature), called with scale_disp = 1): 51 convolutions and 6 linear layers,
+ * 15 135 430 fp32 parameters in 120 tensors.  Forward only; fp32 weights, activations and accumulation (csrc/posenet.hip, csrc/posenet_math.h).
+ *
+ * mv_posenet_tensor_count / mv_posenet_tensor_info: the 120 tensors in the order of the module's state_dict(), with the reference's key names
+ *   ("firstconv.0.0.weight", "layer3.0.downsample.bias", "voflow_rot.2.weight", ...); name_buf holds at least 64 bytes, shape[ndim..3] = 0.
+ * mv_posenet_pack: host.  tensors_host[i] = tensor i, contiguous fp32; packed_host = mv_posenet_packed_bytes() bytes in the layout the kernels read
+ *   (per launch: 16-channel tiles of K steps in MFMA operand order, a downsample's rows behind its block's second convolution, the summed bias).
+ *   Pack once per network, upload once.
+ * mv_posenet_forward_lanes: x [lanes, 5, 112, 160] fp32 (what mv_motion_input_lanes writes) -> out [lanes, 6] fp32 = cat(trans, rot), before the
+ *   pose_norm scaling.  1 <= lanes <= MV_MAX_LANES.  50 launches on `stream`, no host synchronisation, allocation or copy.  workspace:
+ *   mv_posenet_workspace_bytes(lanes) bytes (0 for an unsupported lane count), 16-byte aligned, contents irrelevant.  stage_out: NULL, or six device
+ *   pointers (NULL entries are skipped) that receive the NCHW outputs of firstconv [32,56,80], layer1 [64,28,40], layer2 [128,14,20], layer3
+ *   [128,7,10], layer4 [256,4,5] and layer5 [256,2,3] per lane.  A lane's output bits depend on neither `lanes` nor its place in the batch; two
+ *   runs give the same bits; NaN propagates as in torch (ReLU keeps it). */
+int mv_posenet_tensor_count(void);
+int mv_posenet_tensor_info(int i, char* name_buf, int32_t* shape /* [4] */, int32_t* ndim);
+size_t mv_posenet_packed_bytes(void);
+size_t mv_posenet_workspace_bytes(int lanes);
+int mv_posenet_pack(const float* const* tensors_host /* [120] */, void* packed_host);
+int mv_posenet_forward_lanes(const void* packed_dev, const float* x, int lanes, float* out, void* workspace, float* const* stage_out /* host [6] or NULL */,
+                             mvStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

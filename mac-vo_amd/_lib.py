@@ -349,6 +349,13 @@ SIGNATURES = {
     "mv_stereo_rectify_plan": (C.c_int, [C.POINTER(mvRectifyPlan), _PD, _PD, C.c_int, _PD, _PD, C.c_int, C.c_int, C.c_int, _PD, _PD]),
     "mv_rectify_maps": (C.c_int, [C.POINTER(mvRectifyCam), C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "mv_remap_lanes": (C.c_int, [C.POINTER(mvRemapGroup), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    # the PoseNet of TartanMotionNet: tensor table, host packer, forward (packed, x, lanes, out, workspace, stage_out [6] or NULL, stream)
+    "mv_posenet_tensor_count": (C.c_int, []),
+    "mv_posenet_tensor_info": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mv_posenet_packed_bytes": (C.c_size_t, []),
+    "mv_posenet_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "mv_posenet_pack": (C.c_int, [C.POINTER(_P), _P]),
+    "mv_posenet_forward_lanes": (C.c_int, [_P, _P, C.c_int, _P, _P, C.POINTER(_P), _P]),
 }
 
 _lib = None

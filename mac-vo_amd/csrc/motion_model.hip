@@ -2,7 +2,7 @@
 //
 // The reference runs ~15 small torch launches per frame on full-resolution maps around the learned PoseNet: an H x W intrinsic
 // layer, three crop + bilinear passes, reciprocal / nan_to_num / clamp / two scalar divisions, a cat and a PyPose compose.
-// Only the PoseNet stays PyTorch (like FlowFormer); the rest is two launches here:
+// The PoseNet itself is the caller's (eager PyTorch, or posenet.hip); the rest is two launches here:
 //
 //   mv_motion_input_lanes   one thread per output pixel of a lane: the four bilinear taps of the cropped flow (2 planes), depth and
 //                           intrinsic layer (computed at the tap from its row / column, never materialised), then the depth transform;

@@ -1101,6 +1101,88 @@ def pose_exp_compose(prev: torch.Tensor, raw: torch.Tensor, norm: torch.Tensor |
     return out.reshape(7) if single else out
 
 
+# ---------------------------------------------------------------------------------------------- the PoseNet of TartanMotionNet
+POSENET_STAGES = ("firstconv", "layer1", "layer2", "layer3", "layer4", "layer5")
+POSENET_STAGE_SHAPES = ((32, 56, 80), (64, 28, 40), (128, 14, 20), (128, 7, 10), (256, 4, 5), (256, 2, 3))     # per lane, NCHW
+_POSENET_PREFIXES = ("module.flowPoseNet.", "flowPoseNet.")       # the release checkpoint (a DataParallel StereoVONet), or its bare module
+
+
+def posenet_tensor_table() -> "list[tuple[str, tuple[int, ...]]]":
+    """(state-dict key, shape) of the PoseNet's 120 tensors in canonical order, as the library lists them."""
+    lib = L.load()
+    table = []
+    name, shape, ndim = C.create_string_buffer(64), (C.c_int32 * 4)(), C.c_int32()
+    for i in range(lib.mv_posenet_tensor_count()):
+        L.check(lib.mv_posenet_tensor_info(i, name, shape, C.byref(ndim)), "mv_posenet_tensor_info")
+        table.append((name.value.decode(), tuple(shape[d] for d in range(ndim.value))))
+    return table
+
+
+class PoseNet:
+    """TartanVO's PoseNet (``VOFlowRes`` config 1, stereo, as ``StereoVONet.flowPoseNet``) forward in HIP: a callable
+    ``[lanes,5,112,160] fp32 -> [lanes,6]`` raw motion (before ``pose_norm``) on the current torch stream — what ``HotPath``,
+    ``NativeHotPath`` and ``HIP_TartanMotionNet`` take as ``pose_net``.  The weights are packed on the host and uploaded once at
+    construction; a call allocates only its output and its workspace (torch's caching allocator), copies nothing from the host and
+    does not synchronise.  ``net(x, return_stages=True)`` also returns the six stage outputs (firstconv, layer1..5), NCHW."""
+
+    def __init__(self, state_dict, device="cuda"):
+        lib = L.load()
+        self.device = torch.device(device)
+        tensors = []
+        for key, shape in posenet_tensor_table():
+            if key not in state_dict:
+                raise L.MacvoHipError(f"PoseNet: the state dict has no tensor '{key}'")
+            t = state_dict[key]
+            if tuple(t.shape) != shape:
+                raise L.MacvoHipError(f"PoseNet: tensor '{key}' has shape {tuple(t.shape)}, expected {shape}")
+            tensors.append(t.detach().to("cpu", torch.float32).contiguous())
+        ptrs = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        nbytes = lib.mv_posenet_packed_bytes()
+        packed = torch.empty((nbytes // 4,), dtype=torch.float32)
+        L.check(lib.mv_posenet_pack(ptrs, packed.data_ptr()), "mv_posenet_pack")
+        self.packed = packed.to(self.device)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, device="cuda") -> "PoseNet":
+        """Bare keys (``firstconv.0.0.weight`` ...) or the release checkpoint's (``module.flowPoseNet.`` / ``flowPoseNet.`` prefixes; the
+        ``flowNet`` / ``stereoNet`` tensors beside them are ignored)."""
+        for prefix in _POSENET_PREFIXES:
+            if any(k.startswith(prefix) for k in state_dict):
+                state_dict = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+                break
+        return cls(state_dict, device)
+
+    @classmethod
+    def from_file(cls, path: str, device="cuda") -> "PoseNet":
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        if isinstance(sd, dict) and "state_dict" in sd and not any(torch.is_tensor(v) for v in sd.values()):
+            sd = sd["state_dict"]
+        return cls.from_state_dict(sd, device)
+
+    @classmethod
+    def from_module(cls, module: "torch.nn.Module", device="cuda") -> "PoseNet":
+        return cls.from_state_dict(module.state_dict(), device)
+
+    def __call__(self, x: torch.Tensor, return_stages: bool = False):
+        lib = L.load()
+        x = _req(x, torch.float32, "x")
+        if x.dim() != 4 or tuple(x.shape[1:]) != MOTION_IN_SHAPE or x.device != self.packed.device:
+            raise L.MacvoHipError(f"PoseNet: x must be [lanes,5,112,160] fp32 on {self.packed.device} (got {tuple(x.shape)} on {x.device})")
+        lanes = x.shape[0]
+        nws = lib.mv_posenet_workspace_bytes(lanes)
+        if nws == 0:
+            raise L.MacvoHipError(f"PoseNet: {lanes} lanes are not supported (1 <= lanes <= {L.MV_MAX_LANES})")
+        ws = torch.empty((nws // 4,), dtype=torch.float32, device=x.device)
+        out = torch.empty((lanes, 6), dtype=torch.float32, device=x.device)
+        stages, sp = None, None
+        if return_stages:
+            stages = [torch.empty((lanes,) + s, dtype=torch.float32, device=x.device) for s in POSENET_STAGE_SHAPES]
+            sp = (C.c_void_p * 6)(*[s.data_ptr() for s in stages])
+        L.check(lib.mv_posenet_forward_lanes(self.packed.data_ptr(), x.data_ptr(), lanes, out.data_ptr(), ws.data_ptr(), sp, _stream()),
+                "mv_posenet_forward_lanes")
+        return (out, stages) if return_stages else out
+
+
 # ------------------------------------------------------------------------------------------- frontend evaluation
 @dataclass
 class EvalResult:

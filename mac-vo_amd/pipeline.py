@@ -279,7 +279,18 @@ def preprocess_config_fields(block, seq_type: str, camera: "Camera") -> dict:
     return {"plans": plans, "camera": cam}
 
 
-_MOTION_TYPES = {"StaticMotionModel": "static", "TartanMotionNet": "tartan", "HIP_TartanMotionNet": "tartan"}
+_MOTION_TYPES = {"StaticMotionModel": "static", "TartanMotionNet": "tartan", "HIP_TartanMotionNet": "tartan",
+                 "HIP_TartanMotionNet_HIPPoseNet": "tartan"}
+
+
+def hip_pose_net(weight_or_state_dict, device="cuda") -> "ops.PoseNet":
+    """The ``pose_net`` of :class:`HotPath` / :class:`NativeHotPath` (motion_model "tartan") in HIP: a checkpoint path (the ``weight`` of a
+    ``TartanMotionNet`` block) or a state dict -> the ``[lanes,5,112,160] -> [lanes,6]`` callable :class:`ops.PoseNet`."""
+    if isinstance(weight_or_state_dict, (str, os.PathLike)):
+        if not str(weight_or_state_dict):
+            raise ops.L.MacvoHipError("hip_pose_net needs a checkpoint path or a state dict (an empty `weight` names no network)")
+        return ops.PoseNet.from_file(str(weight_or_state_dict), device)
+    return ops.PoseNet.from_state_dict(weight_or_state_dict, device)
 
 
 def motion_config_fields(block) -> dict:

@@ -1206,6 +1206,21 @@ class HIP_TartanMotionNet(IMotionModel):
         cls._enforce_config_spec(config, {"weight": lambda s: isinstance(s, str), "device": _is_device})
 
 
+class HIP_TartanMotionNet_HIPPoseNet(HIP_TartanMotionNet):
+    """``HIP_TartanMotionNet`` whose PoseNet runs in HIP as well (``ops.PoseNet``: 50 launches, fp32 throughout): same YAML ``args``
+    (weight, device), same predict / update.  The network is built from the checkpoint alone (``ops.PoseNet.from_file``: the release
+    file's ``module.flowPoseNet.*`` tensors), so no MAC-VO checkout has to be importable.  ``weight: ""`` is refused: a network without
+    weights has no random initialisation worth keeping."""
+
+    def __init__(self, config: SimpleNamespace, pose_net=None):
+        if pose_net is None and type(self).pose_net is None:
+            if not getattr(config, "weight", ""):
+                raise ops.L.MacvoHipError("HIP_TartanMotionNet_HIPPoseNet needs `weight`: the PoseNet checkpoint (e.g. ./Model/MACVO_posenet.pkl); "
+                                          "the HIP forward keeps no random initialisation")
+            pose_net = ops.PoseNet.from_file(config.weight, config.device)
+        super().__init__(config, pose_net=pose_net)
+
+
 def _raw_pose(p) -> torch.Tensor:
     return p.tensor() if hasattr(p, "tensor") and callable(p.tensor) else torch.as_tensor(p)
 

@@ -130,6 +130,10 @@ CHECKS = [
      regs(r) <= 64 and r.get("group_segment_fixed_size", 0) == 0,
      "stereo rectification: a gather through the caches — no LDS, no scratch, no spills (the group table is read from the kernel argument at a wave-uniform "
      "offset, every register array is indexed by unrolled constants), eight waves per SIMD to hide the taps' latency"),
+    (r"^posenet_conv_kernel|^posenet_head_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and
+     regs(r) <= 128 and r.get("group_segment_fixed_size", 0) <= 32 * 1024,
+     "PoseNet forward: the per-round operand arrays and the MT x NT accumulators are indexed by unrolled constants (no scratch, no spills); the K-split's "
+     "partial sums take at most 32 KB of LDS"),
     (r"^kg_(grad|select|compact)_kernel|^kp_finish_device_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and
      r["sgpr_spill_count"] == 0 and regs(r) <= 64 and r.get("group_segment_fixed_size", 0) <= 20 * 1024,
      "image-gradient selectors and the device finish: the staged loads of a thread sit in registers indexed by unrolled constants (no scratch, no spills), "
