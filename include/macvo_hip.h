@@ -1407,6 +1407,33 @@ int mv_posenet_pack(const float* const* tensors_host /* [120] */, void* packed_h
 int mv_posenet_forward_lanes(const void* packed_dev, const float* x, int lanes, float* out, void* workspace, float* const* stage_out /* host [6] or NULL */,
                              mvStream_t stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The decoder's recurrent update blocks in 16-bit operands, one call per decoder iteration (csrc/update_block.hip, csrc/update_block_math.h).
+ *   MV_UPDATE_COV   CovUpdateBlock.forward (Module/Network/FlowFormerCov/covhead.py:24-43): SepConvGRU (hidden 128, input 384; 1x5 then 5x1),
+ *                   CovHead 128 -> 256 -> 128 -> 64 -> 2 (covhead.py:8-21), mask 128 -> 256 -> 576 scaled by 0.25 (covhead.py:42)
+ *   MV_UPDATE_FLOW  covhead.py:112-114: the gru, flow_head (128 -> 256 -> 2) and mask (128 -> 256 -> 576, unscaled: the caller applies 0.25 at
+ *                   covhead.py:122) members of FlowFormer's GMAUpdateBlock
+ * operand: MV_F16 or MV_BF16 — the type of net, inp, the three outputs and the MFMA operands; accumulation and pointwise maths are fp32, a value is
+ * rounded once where it is stored.  Not bit-equal to the eager 16-bit module, which rounds after every operator.
+ *
+ * mv_update_block_tensor_count / _tensor_info: the block's tensors in state_dict() order ("gru.convz1.weight", ..., "mask.2.bias"; COV 24, FLOW 20 =
+ *   the gru.*, flow_head.* and mask.* entries of the GMAUpdateBlock); name_buf holds at least 64 bytes, shape[ndim..3] = 0.
+ * mv_update_block_pack: device.  tensors[i] (host array of DEVICE pointers) = tensor i, contiguous fp32; packed = mv_update_block_packed_bytes(kind,
+ *   operand) bytes, 16-byte aligned: per launch the weights in MFMA fragment order, rounded to the operand type, and the fp32 biases.  Pack once.
+ * mv_update_block_forward: net [B,128,H,W], inp [B,384,H,W] (NCHW-contiguous, or channels-last memory when channels_last = 1) ->
+ *   net_out [B,128,H,W], delta [B,2,H,W], mask [B,576,H,W], NCHW-contiguous.  net_out may be net.  B, H, W >= 1, B * H * W <= 2^20.  workspace:
+ *   mv_update_block_workspace_bytes(kind, B, H, W) bytes (0 for sizes out of range), 16-byte aligned, contents irrelevant.  9 (FLOW) or 11 (COV)
+ *   launches on `stream`; no atomics, host synchronisation or allocation; two calls give the same bits; NaN propagates as in torch (ReLU keeps it).
+ * Arguments are checked before anything touches the device: MV_ERR_INVALID_ARG for a null pointer, an unknown kind or operand, a size out of range. */
+enum { MV_UPDATE_COV = 0, MV_UPDATE_FLOW = 1 };
+int mv_update_block_tensor_count(int kind);
+int mv_update_block_tensor_info(int kind, int i, char* name_buf, int32_t* shape /* [4] */, int32_t* ndim);
+size_t mv_update_block_packed_bytes(int kind, int operand);
+int mv_update_block_pack(int kind, int operand, const float* const* tensors /* host [count] of device pointers */, void* packed, mvStream_t stream);
+size_t mv_update_block_workspace_bytes(int kind, int B, int H, int W);
+int mv_update_block_forward(int kind, int operand, const void* packed, const void* net, const void* inp, int B, int H, int W, int channels_last,
+                            void* net_out, void* delta, void* mask, void* workspace, mvStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

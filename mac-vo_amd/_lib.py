@@ -25,6 +25,7 @@ MV_COVMOD_DIAG, MV_COVMOD_NORMALIZE = 1, 2
 MV_MOTION_STATIC, MV_MOTION_TARTAN = 0, 1
 MV_SOLVE_WORLD, MV_SOLVE_LOCAL = 0, 1
 MV_NOCOV_DEPTH, MV_NOCOV_MATCH = 1, 2
+MV_UPDATE_COV, MV_UPDATE_FLOW = 0, 1
 ABI_VERSION = 8
 MV_MAX_LANES = 64        # include/macvo_hip.h
 # row columns of mv_eval_flow_lanes / mv_eval_depth_lanes (enum order of the header)
@@ -356,6 +357,14 @@ SIGNATURES = {
     "mv_posenet_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mv_posenet_pack": (C.c_int, [C.POINTER(_P), _P]),
     "mv_posenet_forward_lanes": (C.c_int, [_P, _P, C.c_int, _P, _P, C.POINTER(_P), _P]),
+    # the decoder's update blocks (kind MV_UPDATE_COV / MV_UPDATE_FLOW, operand MV_F16 / MV_BF16): tensor table, device packer (kind, operand, tensors, packed,
+    # stream), forward (kind, operand, packed, net, inp, B, H, W, channels_last, net_out, delta, mask, workspace, stream)
+    "mv_update_block_tensor_count": (C.c_int, [C.c_int]),
+    "mv_update_block_tensor_info": (C.c_int, [C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mv_update_block_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mv_update_block_pack": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P), _P, _P]),
+    "mv_update_block_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mv_update_block_forward": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1183,6 +1183,103 @@ class PoseNet:
         return (out, stages) if return_stages else out
 
 
+# ---------------------------------------------------------------------------------- the decoder's recurrent update blocks
+UPDATE_KINDS = {"cov": L.MV_UPDATE_COV, "flow": L.MV_UPDATE_FLOW}
+_UPDATE_OPERANDS = {"f16": (L.MV_F16, torch.float16), "bf16": (L.MV_BF16, torch.bfloat16)}
+
+
+def _update_kind(kind) -> int:
+    k = UPDATE_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+    if k not in (L.MV_UPDATE_COV, L.MV_UPDATE_FLOW):
+        raise L.MacvoHipError(f"update block: kind must be 'cov' or 'flow', got {kind!r}")
+    return int(k)
+
+
+def update_block_tensor_table(kind) -> "list[tuple[str, tuple[int, ...]]]":
+    """(state-dict key, shape) of the block's tensors in the module's order, as the library lists them: ``"cov"`` = ``CovUpdateBlock`` (24 tensors),
+    ``"flow"`` = the ``gru`` / ``flow_head`` / ``mask`` members of FlowFormer's ``GMAUpdateBlock`` (20)."""
+    lib, k = L.load(), _update_kind(kind)
+    table = []
+    name, shape, ndim = C.create_string_buffer(64), (C.c_int32 * 4)(), C.c_int32()
+    for i in range(lib.mv_update_block_tensor_count(k)):
+        L.check(lib.mv_update_block_tensor_info(k, i, name, shape, C.byref(ndim)), "mv_update_block_tensor_info")
+        table.append((name.value.decode(), tuple(shape[d] for d in range(ndim.value))))
+    return table
+
+
+class UpdateBlockWeights:
+    """The weights of one recurrent update block of the FlowFormerCov decoder, packed once into the fragment order of ``mv_update_block_forward``
+    (16-bit weights in ``operand``, fp32 biases holding 16-bit values).  ``operand``: ``"bf16"`` / ``"f16"``; None: bf16 for bf16 tensors, f16 for fp16
+    and fp32 ones.  A missing or mis-shaped tensor is named in the error, before anything touches the device."""
+
+    def __init__(self, state_dict, kind, operand: str | None = None, device=None):
+        lib = L.load()
+        self.kind = _update_kind(kind)
+        table = update_block_tensor_table(self.kind)
+        tensors = []
+        for key, shape in table:
+            if key not in state_dict:
+                raise L.MacvoHipError(f"UpdateBlockWeights: the state dict has no tensor '{key}'")
+            t = state_dict[key]
+            if tuple(t.shape) != shape:
+                raise L.MacvoHipError(f"UpdateBlockWeights: tensor '{key}' has shape {tuple(t.shape)}, expected {shape}")
+            tensors.append(t)
+        if operand is None:
+            operand = "bf16" if tensors[0].dtype == torch.bfloat16 else "f16"
+        if operand not in _UPDATE_OPERANDS:
+            raise L.MacvoHipError(f"UpdateBlockWeights: operand must be 'f16' or 'bf16', got {operand!r}")
+        self.operand = operand
+        self.operand_type, self.dtype = _UPDATE_OPERANDS[operand]
+        device = torch.device(device) if device is not None else tensors[0].device
+        ts = [_req(t.detach().to(device, torch.float32), torch.float32, "update-block weight") for t in tensors]
+        with torch.cuda.device(device):
+            self.packed = torch.empty(int(lib.mv_update_block_packed_bytes(self.kind, self.operand_type)), dtype=torch.uint8, device=device)
+            ptrs = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+            L.check(lib.mv_update_block_pack(self.kind, self.operand_type, ptrs, self.packed.data_ptr(), _stream()), "mv_update_block_pack")
+        self._keep = ts          # (the pack kernels read them on the stream)
+
+    @classmethod
+    def from_module(cls, block, kind, operand: str | None = None, device=None) -> "UpdateBlockWeights":
+        """``block``: a ``CovUpdateBlock`` (kind "cov"), a ``GMAUpdateBlock`` or any module / state dict that holds its ``gru.*``, ``flow_head.*`` and
+        ``mask.*`` tensors (kind "flow"); other entries (``encoder.*``, ``aggregator.*``) are ignored."""
+        sd = block if isinstance(block, dict) else block.state_dict()
+        return cls(sd, kind, operand, device)
+
+
+def update_block(net: torch.Tensor, inp: torch.Tensor, weights: UpdateBlockWeights, workspace: torch.Tensor | None = None):
+    """One iteration of a recurrent update block: ``net [B,128,H,W]``, ``inp [B,384,H,W]`` in ``weights.dtype`` (NCHW, or both channels-last) ->
+    ``(net, delta [B,2,H,W], mask [B,576,H,W])``, NCHW-contiguous, in that dtype.  Kind "cov" is ``CovUpdateBlock.forward`` (covhead.py:39-43, mask
+    already scaled by 0.25); kind "flow" is covhead.py:112-114 (mask unscaled).  fp32 accumulation, one rounding per stored tensor; allocates the
+    outputs and — unless ``workspace`` (uint8, at least ``mv_update_block_workspace_bytes``; its contents do not matter) is handed in — a workspace from
+    torch's caching allocator, copies nothing from the host, does not synchronise."""
+    lib = L.load()
+    for t, c, name in ((net, 128, "net"), (inp, 384, "inp")):
+        if not t.is_cuda or t.dtype != weights.dtype or t.dim() != 4 or t.shape[1] != c:
+            raise L.MacvoHipError(f"update_block: {name} must be a [B,{c},H,W] {weights.dtype} GPU tensor (got {tuple(t.shape)} {t.dtype} on {t.device})")
+    if net.shape[0] != inp.shape[0] or net.shape[2:] != inp.shape[2:] or net.device != weights.packed.device or inp.device != net.device:
+        raise L.MacvoHipError(f"update_block: net {tuple(net.shape)} on {net.device} and inp {tuple(inp.shape)} on {inp.device} do not belong together")
+    B, _, H, W = net.shape
+    nws = lib.mv_update_block_workspace_bytes(weights.kind, B, H, W)
+    if nws == 0:
+        raise L.MacvoHipError(f"update_block: B x H x W = {B} x {H} x {W} is out of range (1 <= B * H * W <= 2^20)")
+    cl = torch.channels_last
+    channels_last = all(t.is_contiguous(memory_format=cl) and not t.is_contiguous() for t in (net, inp))
+    if not channels_last:
+        net, inp = net.contiguous(), inp.contiguous()
+    if workspace is None:
+        workspace = torch.empty((nws,), dtype=torch.uint8, device=net.device)
+    elif workspace.dtype != torch.uint8 or workspace.device != net.device or not workspace.is_contiguous() or workspace.numel() < nws or workspace.data_ptr() % 16:
+        raise L.MacvoHipError(f"update_block: workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {nws} bytes on {net.device}")
+    ws = workspace
+    net_out = torch.empty((B, 128, H, W), dtype=weights.dtype, device=net.device)
+    delta = torch.empty((B, 2, H, W), dtype=weights.dtype, device=net.device)
+    mask = torch.empty((B, 576, H, W), dtype=weights.dtype, device=net.device)
+    L.check(lib.mv_update_block_forward(weights.kind, weights.operand_type, weights.packed.data_ptr(), net.data_ptr(), inp.data_ptr(), B, H, W,
+                                        int(channels_last), net_out.data_ptr(), delta.data_ptr(), mask.data_ptr(), ws.data_ptr(), _stream()),
+            "mv_update_block_forward")
+    return net_out, delta, mask
+
+
 # ------------------------------------------------------------------------------------------- frontend evaluation
 @dataclass
 class EvalResult:

@@ -980,7 +980,96 @@ class _FusedProjForward:
         return out
 
 
-def install_flowformer_hooks(model, volume_precision: str | None = None, fuse_patch_embed: bool | None = None) -> list[str]:
+class _FusedUpdateBlock:
+    """One recurrent update block of the decoder through ``ops.update_block`` (``mv_update_block_forward``): ``CovUpdateBlock.forward`` (kind "cov",
+    covhead.py:39-43) or the ``gru`` / ``flow_head`` / ``mask`` calls of covhead.py:112-114 (kind "flow").
+
+    * The modules stay in place (only ``forward`` attributes are rebound): ``state_dict`` keys, ``.to()`` and ``load_state_dict`` keep working, and the
+      packed weights are rebuilt whenever a parameter's storage, dtype or version counter changes.
+    * Numerics policy: the kernels run in the decoder's own 16-bit type (bf16 in ``MACVO_Fast.yaml:73-74``, or fp16) with fp32 accumulation, and round once
+      per stored tensor where the eager layers round after every operator.  An fp32 decoder, inputs whose dtype is not the parameters', CPU tensors,
+      unexpected shapes and anything that could require a gradient fall through to the original layers.
+    * kind "flow": ``gru.forward`` runs the whole block and keeps ``delta`` and ``mask`` for the ``flow_head`` / ``mask`` calls that follow on the very
+      tensor it returned; called on any other tensor, those two run their own layers."""
+
+    def __init__(self, kind: str, holder):
+        self.kind, self.holder = kind, holder          # holder: the CovUpdateBlock, or the GMAUpdateBlock that owns gru / flow_head / mask
+        self.members = (holder,) if kind == "cov" else (holder.gru, holder.flow_head, holder.mask)
+        self._packed: dict = {}                        # operand -> (key, UpdateBlockWeights)
+        self._last = None                              # kind "flow": (net_out, delta, mask) of the last fused gru call
+        self.fused_calls = 0
+
+    def _params(self):
+        return [p for m in self.members for p in m.parameters()]
+
+    def state_dict(self) -> dict:
+        if self.kind == "cov":
+            return self.holder.state_dict()
+        return {f"{n}.{k}": v for n, m in zip(("gru", "flow_head", "mask"), self.members) for k, v in m.state_dict().items()}
+
+    def shapes_ok(self) -> bool:
+        sd = self.state_dict()
+        return all(k in sd and tuple(sd[k].shape) == s for k, s in ops.update_block_tensor_table(self.kind))
+
+    def repack(self, operand: str):
+        def version(p):
+            try:
+                return p._version
+            except RuntimeError:        # inference tensors carry no version counter (and cannot be updated in place)
+                return -1
+        key = tuple((p.data_ptr(), version(p), p.dtype) for p in self._params())
+        hit = self._packed.get(operand)
+        if hit is None or hit[0] != key:
+            hit = (key, ops.UpdateBlockWeights(self.state_dict(), self.kind, operand))
+            self._packed[operand] = hit
+        return hit[1]
+
+    def fused(self, net, inp):
+        """(net, delta, mask) from the kernels, or None when the call has to run the original layers."""
+        operand = {torch.bfloat16: "bf16", torch.float16: "f16"}.get(net.dtype)
+        if operand is None or not (net.is_cuda and inp.is_cuda) or inp.dtype != net.dtype or net.dim() != 4 or inp.dim() != 4:
+            return None
+        if net.shape[1] != 128 or inp.shape[1] != 384 or net.shape[0] != inp.shape[0] or net.shape[2:] != inp.shape[2:]:
+            return None
+        params = self._params()
+        if any(p.dtype != net.dtype or p.device != net.device for p in params):
+            return None
+        if torch.is_grad_enabled() and (net.requires_grad or inp.requires_grad or any(p.requires_grad for p in params)):
+            return None
+        try:
+            out = ops.update_block(net, inp, self.repack(operand))
+        except ops.L.MacvoHipError:                      # anything the kernels refuse falls through to the layers
+            return None
+        self.fused_calls += 1
+        return out
+
+    # -- kind "cov": CovUpdateBlock.forward ---------------------------------------------------------------------------------------------------
+    def cov_forward(self, covs_net, inp_cat):
+        out = self.fused(covs_net, inp_cat)
+        return out if out is not None else type(self.holder).forward(self.holder, covs_net, inp_cat)
+
+    # -- kind "flow": gru, then flow_head and mask on the tensor gru returned -----------------------------------------------------------------------
+    def gru_forward(self, net, inp_cat):
+        out = self.fused(net, inp_cat)
+        if out is None:
+            self._last = None
+            return type(self.holder.gru).forward(self.holder.gru, net, inp_cat)
+        self._last = out
+        return out[0]
+
+    def flow_head_forward(self, x):
+        if self._last is not None and x is self._last[0]:
+            return self._last[1]
+        return type(self.holder.flow_head).forward(self.holder.flow_head, x)
+
+    def mask_forward(self, x):
+        if self._last is not None and x is self._last[0]:
+            return self._last[2]
+        return type(self.holder.mask).forward(self.holder.mask, x)
+
+
+def install_flowformer_hooks(model, volume_precision: str | None = None, fuse_patch_embed: bool | None = None,
+                             fuse_update_blocks: bool | None = None) -> list[str]:
     """Route the three frontend kernels of ``FlowFormerCov`` through the HIP library by rebinding bound methods on the model
     instance — signatures and result layouts are those of the methods they replace, the network's own code is untouched:
 
@@ -999,6 +1088,11 @@ def install_flowformer_hooks(model, volume_precision: str | None = None, fuse_pa
     * ``memory_encoder...patch_embed.proj`` — the cost patch embedding's three convolutions (row (f)2) -> ``ops.cost_patch_embed``
       (``_FusedProjForward``).  ``fuse_patch_embed``: None = for 16-bit slices only (the encoder's own precision is kept; fp32 slices stay on the
       PyTorch layers), True = also for fp32 slices (IEEE-half operands), False = never; ``MACVO_HIP_PATCH_EMBED=1|0`` sets the default.
+
+    * ``memory_decoder.cov_update`` and the ``gru`` / ``flow_head`` / ``mask`` members of ``memory_decoder.update_block`` — the two recurrent update
+      blocks, once each per decoder iteration (covhead.py:112-117) -> ``ops.update_block`` (``_FusedUpdateBlock``).  Opt-in: ``fuse_update_blocks``
+      None = the environment variable ``MACVO_HIP_UPDATE_BLOCK`` (``1`` / ``on`` / ``true``; default off), True / False decide here.  Only 16-bit
+      decoders take the kernels (an fp32 decoder keeps its layers, bit for bit); a block whose tensors do not have the published shapes is left alone.
 
     Every attribute that exists is rebound (the FlowFormer submodule is absent from some checkouts, and a stand-in model may
     carry only part of them); the names of the rebound methods are returned so that a caller can insist on all three."""
@@ -1058,6 +1152,21 @@ def install_flowformer_hooks(model, volume_precision: str | None = None, fuse_pa
             # an instance attribute shadows nn.Sequential.forward: the module, its parameters and its state_dict keys stay where they were
             pe.proj.forward = fused
             done.append(f"memory_encoder.{pe_name}.proj")
+    if fuse_update_blocks is None:
+        fuse_update_blocks = os.environ.get("MACVO_HIP_UPDATE_BLOCK", "0").lower() in ("1", "on", "true")
+    if fuse_update_blocks and dec is not None:
+        cov = getattr(dec, "cov_update", None)
+        if isinstance(cov, torch.nn.Module):
+            fused = _FusedUpdateBlock("cov", cov)
+            if fused.shapes_ok():
+                cov.forward = fused.cov_forward        # an instance attribute shadows the class's forward: the module and its keys stay where they were
+                done.append("memory_decoder.cov_update.forward")
+        ub = getattr(dec, "update_block", None)
+        if ub is not None and all(isinstance(getattr(ub, n, None), torch.nn.Module) for n in ("gru", "flow_head", "mask")):
+            fused = _FusedUpdateBlock("flow", ub)
+            if fused.shapes_ok():
+                ub.gru.forward, ub.flow_head.forward, ub.mask.forward = fused.gru_forward, fused.flow_head_forward, fused.mask_forward
+                done += [f"memory_decoder.update_block.{n}" for n in ("gru", "flow_head", "mask")]
     if not done:
         raise ops.L.MacvoHipError("install_flowformer_hooks: the model has none of memory_decoder.encode_flow_token / "
                                   "upsample_flow / memory_encoder.corr")

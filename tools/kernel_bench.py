@@ -37,6 +37,65 @@ def synth_coords(B, h8, w8, dev):
     base = torch.stack([torch.arange(w8).float()[None].expand(h8, w8), torch.arange(h8).float()[:, None].expand(h8, w8)])[None]
     return (base + (torch.rand(B, 2, h8, w8, generator=g) * 2 - 1) * 8).to(dev)
 
+# one call of a recurrent update block (csrc/update_block_math.h): (launch, kh * kw, cin, rows executed, rows that are real outputs)
+UPDATE_LAUNCHES = {
+    "cov": [("zr1 1x5", 5, 512, 256, 256), ("q1 1x5", 5, 512, 128, 128), ("zr2 5x1", 5, 512, 256, 256), ("q2 5x1", 5, 512, 128, 128),
+            ("conv1|mask.0 3x3", 9, 128, 512, 512), ("conv2 3x3", 9, 256, 128, 128), ("conv3 3x3", 9, 128, 64, 64), ("conv4 3x3", 9, 64, 64, 2),
+            ("mask.2 1x1", 1, 256, 576, 576)],
+    "flow": [("zr1 1x5", 5, 512, 256, 256), ("q1 1x5", 5, 512, 128, 128), ("zr2 5x1", 5, 512, 256, 256), ("q2 5x1", 5, 512, 128, 128),
+             ("flow_head.0|mask.0 3x3", 9, 128, 512, 512), ("flow_head.2 3x3", 9, 256, 64, 2), ("mask.2 1x1", 1, 256, 576, 576)],
+}
+MFMA16_PEAK_TFLOPS = 2500.0     # dense bf16 / fp16 MFMA rate of an MI355X
+
+
+def update_block_case(a, dev, B, h8, w8):
+    """The HIP update block against the eager PyTorch-ROCm module with the same bf16 weights and inputs, in this process: median, min and the 10th-90th
+    percentile spread of each, the useful FLOP of every launch, and — with --launch-trace FILE, a rocprofv3 --kernel-trace CSV of THIS case — the
+    measured time and achieved fraction of the 16-bit MFMA rate per launch."""
+    from tests import update_block_twin as T
+
+    M = B * h8 * w8
+    for kind in a.update_kinds.split(","):
+        block = T.make_block(T.COV if kind == "cov" else T.FLOW, 0).to(dev, torch.bfloat16)
+        net, inp = (t.to(dev, torch.bfloat16) for t in T.make_inputs((B, h8, w8), 0))
+        wts = ops.UpdateBlockWeights.from_module(block, kind, "bf16")
+        launches = UPDATE_LAUNCHES[kind]
+        useful = sum(2.0 * M * t * cin * real for _, t, cin, _, real in launches)
+
+        def spread(fn):
+            for _ in range(10):
+                fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(max(a.iters, 20)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                ts.append(e0.elapsed_time(e1) * 1e3)
+            ts.sort()
+            return statistics.median(ts), ts[0], ts[len(ts) // 10], ts[len(ts) * 9 // 10]
+        with torch.inference_mode():
+            hip = spread(lambda: ops.update_block(net, inp, wts))
+            eager = spread(lambda: block(net, inp))
+        print(f"update_block {kind} bf16 B={B} {h8}x{w8} (M = {M}, {useful / 1e9:.2f} GFLOP): HIP {hip[0]:.1f} us (min {hip[1]:.1f}, p10-p90 {hip[2]:.1f}-{hip[3]:.1f}) = "
+              f"{useful / hip[0] / 1e6 / MFMA16_PEAK_TFLOPS * 100:.1f}% of the 16-bit MFMA rate; eager {eager[0]:.1f} us (min {eager[1]:.1f}, p10-p90 "
+              f"{eager[2]:.1f}-{eager[3]:.1f}); eager / HIP = {eager[0] / hip[0]:.2f}")
+        if a.launch_trace:
+            import csv
+            rows = [r for r in csv.DictReader(open(a.launch_trace)) if "update_conv_kernel" in r["Kernel_Name"] or "update_to_nhwc" in r["Kernel_Name"]]
+            rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+            per = len(launches) + 1
+            first = next(i for i, r in enumerate(rows) if "update_to_nhwc" in r["Kernel_Name"])
+            calls = [rows[i:i + per] for i in range(first, len(rows) - per + 1, per)]
+            calls = [c for c in calls if "update_to_nhwc" in c[0]["Kernel_Name"] and all("update_conv" in r["Kernel_Name"] for r in c[1:])][len(calls) // 2:]
+            print(f"per launch, mean of {len(calls)} traced calls: us, executed GFLOP, % of the 16-bit MFMA rate")
+            for j, name in enumerate(["to_nhwc"] + [n for n, *_ in launches]):
+                us = statistics.mean((int(c[j]["End_Timestamp"]) - int(c[j]["Start_Timestamp"])) / 1e3 for c in calls)
+                fl = 0.0 if j == 0 else 2.0 * M * launches[j - 1][1] * launches[j - 1][2] * launches[j - 1][3]
+                print(f"  {name:24s} {us:8.1f} us {fl / 1e9:7.2f} GFLOP {fl / us / 1e6 / MFMA16_PEAK_TFLOPS * 100:6.1f}%")
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -46,6 +105,8 @@ def main():
     ap.add_argument("--W", type=int, default=640)
     ap.add_argument("--B", type=int, default=2)
     ap.add_argument("--zeros", action="store_true", help="volume_split: all-zero operands (DVFS probe: same instruction stream, less switching power)")
+    ap.add_argument("--launch-trace", default="", help="update_block: a rocprofv3 --kernel-trace CSV of this case, for the per-launch table")
+    ap.add_argument("--update-kinds", default="cov,flow", help="update_block: the kinds to time (a trace for --launch-trace holds one kind only)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     H, W, B, C = a.H, a.W, a.B, 256
@@ -77,6 +138,8 @@ def main():
                 med, mn = timeit(lambda: ops.corr_volume_packed(pk[0], pk[1], B, C, n, n, out=vol, mode=mode), a.iters, warm=20)
                 print(f"volume_split {mode} B={B} {med:8.1f} us (min {mn:.1f})  {flops / med / 1e6:7.1f} TFLOP/s algorithmic = {nprod * flops / med / 1e6 / 2500 * 100:.1f}% of the "
                       f"16-bit MFMA peak executed ({'zero' if a.zeros else 'random'} operands)")
+        elif w == "update_block":
+            update_block_case(a, dev, B, h8, w8)
         elif w == "patch_embed":
             # (f)2: both volumes of a frame (S = B n slices) through the fused conv stack; 2 x (36 + 16*36*... ) MAC per output, see DESIGN
             from tools.synth import patch_embed_weights

@@ -134,6 +134,12 @@ CHECKS = [
      regs(r) <= 128 and r.get("group_segment_fixed_size", 0) <= 32 * 1024,
      "PoseNet forward: the per-round operand arrays and the MT x NT accumulators are indexed by unrolled constants (no scratch, no spills); the K-split's "
      "partial sums take at most 32 KB of LDS"),
+    (r"^update_conv_kernel<|^update_to_nhwc_kernel|^update_pack_kernel<", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and
+     r["sgpr_spill_count"] == 0 and regs(r) <= 256 and r.get("group_segment_fixed_size", 0) <= 46080,
+     "recurrent update blocks: the accumulator, the four k-steps of operand fragments per tap and the next chunk's prefetched staging pieces (10 x 16 B per "
+     "thread) in registers indexed by unrolled constants: no scratch, no spills, at most 256 registers (two waves per SIMD; LDS "
+     "bounds the 64-pixel tile at three workgroups = three waves per SIMD, which its 140 registers allow); LDS = the staged strips, 5 x 64 pixels x 144 B = 46 080 B for the 64-pixel tile (three workgroups per CU), 23 040 B for "
+     "the 32-pixel tiles, 8 448 B for the layout transpose"),
     (r"^kg_(grad|select|compact)_kernel|^kp_finish_device_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and
      r["sgpr_spill_count"] == 0 and regs(r) <= 64 and r.get("group_segment_fixed_size", 0) <= 20 * 1024,
      "image-gradient selectors and the device finish: the staged loads of a thread sit in registers indexed by unrolled constants (no scratch, no spills), "
