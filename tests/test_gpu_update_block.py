@@ -93,15 +93,24 @@ def _selection_weights(sd, scrambled: str, seed: int):
     return out
 
 
-@pytest.mark.parametrize("kind,conv", [(T.COV, n) for n in _COV_CONVS] + [(T.FLOW, n) for n in _FLOW_CONVS])
-def test_layers_one_by_one(gpu, kind, conv):
+_ALL_CONVS = [(T.COV, n) for n in _COV_CONVS] + [(T.FLOW, n) for n in _FLOW_CONVS]
+_THREE_IMAGES = (3, 5, 7)     # three images inside one 64-pixel tile: what the 1x5 and 5x1 taps of the GRU launches must not read across
+# (kind, conv, operand, shape); the bf16 cases at (2, 9, 18) keep the ids they have always had
+_LAYER_CASES = ([pytest.param(k, n, "bf16", T.SHAPES[1], id=f"{k}-{n}") for k, n in _ALL_CONVS]
+                + [pytest.param(k, n, "f16", T.SHAPES[1], id=f"{k}-{n}-f16") for k, n in _ALL_CONVS]
+                + [pytest.param(T.COV, n, d, _THREE_IMAGES, id=f"{T.COV}-{n}-{d}-3x5x7") for d in T.DTYPES for n in _COV_CONVS if n.startswith("gru.")])
+
+
+@pytest.mark.parametrize("kind,conv,dtname,shape", _LAYER_CASES)
+def test_layers_one_by_one(gpu, kind, conv, dtname, shape):
     """Tap order, 1x5 against 5x1, the channel order across the [h, x] / [r h, x] concatenation, the z / r row split, the conv1 | mask.0 pairing and the
-    2-of-64-row conv4 / flow_head.2 launches: one convolution at a time gets scrambled one-hot weights, the others pass their centre tap through."""
+    2-of-64-row conv4 / flow_head.2 launches: one convolution at a time gets scrambled one-hot weights, the others pass their centre tap through.  Both
+    operand types at (2, 9, 18); the GRU convolutions also at (3, 5, 7), where a tile holds three images."""
     from macvo_amd import ops
 
-    c = T.case(kind, "bf16", T.SHAPES[1])
+    c = T.case(kind, dtname, shape)
     sd = _selection_weights(c.sd, conv, 3)
-    w = ops.UpdateBlockWeights.from_module({k: v.to(gpu) for k, v in sd.items()}, KINDS[kind], "bf16")
+    w = ops.UpdateBlockWeights.from_module({k: v.to(gpu) for k, v in sd.items()}, KINDS[kind], dtname)
     with torch.no_grad():
         twin = T.forward(sd, kind, c.net, c.inp, c.dt)
     scale = [float(t.abs().max()) for t in twin]
@@ -109,24 +118,34 @@ def test_layers_one_by_one(gpu, kind, conv):
     _check_twin(c, _run(gpu, w, c.net, c.inp), twin, scale, what=conv + " ")
 
 
-@pytest.mark.parametrize("shape", [T.SHAPES[0], T.SHAPES[1]])
-def test_border_only_input(gpu, weights, shape):
+@pytest.mark.parametrize("kind,shape", [pytest.param(k, s, id=("flow-" if k == T.FLOW else "") + f"shape{i}")
+                                        for k in (T.COV, T.FLOW) for i, s in enumerate(T.SHAPES[:2])])
+def test_border_only_input(gpu, weights, kind, shape):
     """Only the border pixels of net and inp are non-zero: a wrong zero pad, or a tap read across the row, image or tile edge, moves interior outputs."""
-    c = T.case(T.COV, "bf16", shape)
+    c = T.case(kind, "bf16", shape)
     B, H, W = shape
     keep = torch.zeros(1, 1, H, W, dtype=torch.bool)
     keep[..., 0, :] = keep[..., -1, :] = keep[..., :, 0] = keep[..., :, -1] = True
     net, inp = c.net * keep, c.inp * keep
     with torch.no_grad():
-        twin = T.forward(c.sd, T.COV, net, inp, c.dt)
+        twin = T.forward(c.sd, kind, net, inp, c.dt)
     _check_twin(c, _run(gpu, weights(c), net, inp), twin, [float(t.abs().max()) for t in twin])
 
 
 def test_layout_determinism_and_dirty_workspace(gpu, weights):
     """Channels-last and NCHW inputs, a second call, and a workspace filled with NaN bit patterns beforehand all give the same bits."""
+    _layout_determinism_and_dirty_workspace(gpu, weights, T.COV)
+
+
+def test_layout_determinism_and_dirty_workspace_flow(gpu, weights):
+    """The same for the FLOW members: their two-row flow_head.2 launch and the unscaled mask."""
+    _layout_determinism_and_dirty_workspace(gpu, weights, T.FLOW)
+
+
+def _layout_determinism_and_dirty_workspace(gpu, weights, kind):
     from macvo_amd import _lib as L
 
-    c = T.case(T.COV, "f16", T.SHAPES[1])
+    c = T.case(kind, "f16", T.SHAPES[1])
     w = weights(c)
     ref = _run(gpu, w, c.net, c.inp)
     again = _run(gpu, w, c.net, c.inp)
@@ -135,22 +154,22 @@ def test_layout_determinism_and_dirty_workspace(gpu, weights):
     assert not net_cl.is_contiguous() and net_cl.is_contiguous(memory_format=cl)
     last = _run(gpu, w, net_cl, inp_cl)
     B, H, W = c.shape
-    ws = torch.full((L.load().mv_update_block_workspace_bytes(L.MV_UPDATE_COV, B, H, W),), 0xFF, dtype=torch.uint8, device=gpu)   # 0xFFFF: NaN in both types
+    ws = torch.full((L.load().mv_update_block_workspace_bytes(w.kind, B, H, W),), 0xFF, dtype=torch.uint8, device=gpu)   # 0xFFFF: NaN in both types
     dirty = _run(gpu, w, c.net, c.inp, workspace=ws)
     for a, b, d, r in zip(again, last, dirty, ref):
         assert torch.equal(a, r) and torch.equal(b, r) and torch.equal(d, r)
 
 
-@pytest.mark.parametrize("dtname", list(T.DTYPES))
-def test_recurrence_of_twelve_iterations(gpu, weights, dtname):
+@pytest.mark.parametrize("kind,dtname", [pytest.param(k, d, id=("flow-" if k == T.FLOW else "") + d) for k in (T.COV, T.FLOW) for d in T.DTYPES])
+def test_recurrence_of_twelve_iterations(gpu, weights, kind, dtname):
     """Twelve calls feeding net back, against the twin's twelve.  Bar: the per-call 2 ulp(scale) times the drift the twin itself shows between fp32 and
-    fp64 accumulation over twelve iterations relative to one (update_block_twin.recurrence; measured on the CPU at (2, 9, 18): factors 1.0-1.9 for bf16,
-    1.0-1.8 for fp16 — the GRU is contractive).  Measured on MI355X after twelve calls: 0.58 / 0.44 / 0.68 ulp(scale) for net / delta / mask in both
-    operand types, no more than after one call."""
+    fp64 accumulation over twelve iterations relative to one (update_block_twin.recurrence of the same kind; measured on the CPU at (2, 9, 18): factors
+    1.0-1.9 for bf16 and 1.0-1.8 for fp16 (COV), 1.9-2.1 and 1.0 (FLOW) — the GRU is contractive).  Measured on MI355X after twelve calls (COV): 0.58 / 0.44 / 0.68 ulp(scale) for net /
+    delta / mask in both operand types, no more than after one call."""
     from macvo_amd import ops
 
-    c = T.case(T.COV, dtname, T.SHAPES[1])
-    twin12, scale12, factor, d = T.recurrence(T.COV, dtname, T.SHAPES[1], 12)
+    c = T.case(kind, dtname, T.SHAPES[1])
+    twin12, scale12, factor, d = T.recurrence(kind, dtname, T.SHAPES[1], 12)
     print("twin fp32 against fp64 accumulation, / scale: one call", ["%.2e" % v for v in d[0]], "twelve", ["%.2e" % v for v in d[1]], "factor", factor)
     w, net, inp = weights(c), c.net.to(gpu), c.inp.to(gpu)
     for _ in range(12):

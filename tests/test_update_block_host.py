@@ -62,6 +62,37 @@ def test_twin_is_no_worse_than_the_eager_module(kind, dtname, shape):
         assert moved > 0.1                                             # ... and such a change is visible at that bar's scale
 
 
+@pytest.mark.parametrize("kind,dtname,shape", [(k, d, s) for d in T.DTYPES for k in (T.COV, T.FLOW) for s in T.EDGE_SHAPES])
+def test_edge_shapes_leave_the_gpu_bar_its_meaning(kind, dtname, shape):
+    """What tests/test_gpu_update_block_edges.py relies on at update_block_twin.EDGE_SHAPES: every output has a scale to measure against (> 0), and the
+    twin's own summation order is worth at most 1.0 ulp(scale) of the 2 ulp(scale) bar — fp32 against fp64 accumulation, measured here at most 0.91
+    ((3, 5, 7) COV f16 delta).  A case that misses gets another seed in update_block_twin.SEEDS; the bar is not widened."""
+    c = T.case(kind, dtname, shape)
+    for i, name in enumerate(T.OUTPUTS):
+        assert c.scale[i] > 0 and all(torch.isfinite(t).all() for t in (c.twin[i], c.twin64[i])), name
+        d64 = float((c.twin[i].double() - c.twin64[i]).abs().max()) / (T.ULP[dtname] * c.scale[i])
+        print(f"{name}: fp32 -> fp64 accumulation {d64:.2f} ulp(scale), scale {c.scale[i]:.3e}")
+        assert d64 <= 1.0, (name, d64)
+
+
+@pytest.mark.parametrize("dtname", list(T.DTYPES))
+@pytest.mark.parametrize("kind", [T.COV, T.FLOW])
+def test_one_nan_stays_inside_its_image_in_the_twin(kind, dtname):
+    """The NaN case of the GPU test (update_block_twin.NAN_CASE: one NaN in net at the last pixel of image 0) asks something: in every output the twin's
+    non-finite pixels of image 0 are a non-empty proper subset of its pixels (the receptive field: 5 x 5, 9 x 9 (COV; FLOW 7 x 7) and 6 x 6 pixels
+    clipped at the corner: 25 / 81 / 36 of 162 for COV), whole pixels (every channel or none), and image 1 is wholly finite."""
+    (B, H, W), _ = T.NAN_CASE
+    _, out, scale = T.nan_case(kind, dtname)
+    for name, t, s in zip(T.OUTPUTS, out, scale):
+        bad = ~torch.isfinite(t)
+        px = bad.any(dim=1)
+        print(f"{name}: {int(px[0].sum())} of {H * W} pixels of image 0 are not finite")
+        assert 0 < int(px[0].sum()) < H * W and not px[1].any() and s > 0, name
+        assert torch.equal(bad.all(dim=1), px), name
+        side = {"net": 5, "delta": 9 if kind == T.COV else 7, "mask": 6}[name]
+        assert int(px[0].sum()) == side * side and px[0, H - side:, W - side:].all(), name
+
+
 def test_tensor_tables_are_the_modules_state_dicts():
     cov = ops.update_block_tensor_table("cov")
     assert cov == [(k, tuple(v.shape)) for k, v in FH.CovUpdateBlock().state_dict().items()]

@@ -19,6 +19,17 @@ DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16}
 ULP = {"bf16": 2.0 ** -7, "f16": 2.0 ** -10}          # ulp(scale) / scale of the issue's bar
 SHAPES = ((1, 5, 7), (2, 9, 18), (1, 47, 98))         # (B, H8, W8)
 OUTPUTS = ("net", "delta", "mask")
+# Degenerate geometry for the edge tests (the kernel's tiles are 32 or 64 consecutive pixels of M = B * H * W, its halos 1x5, 5x1 and 3x3):
+EDGE_SHAPES = (
+    (1, 1, 1),       # M = 1
+    (1, 1, 37),      # one row, wider than a 32-pixel block: every vertical tap is outside the image
+    (1, 37, 1),      # one column: vertical neighbours are linearly adjacent, every horizontal tap is outside
+    (1, 2, 3),       # M = 6
+    (3, 5, 7),       # M = 105: image boundaries at 35 and 70 inside tiles, three images in one 64-pixel tile
+    (2, 4, 16),      # M = 128: the image boundary falls exactly on a tile edge for both tile configurations
+    (1, 3, 33),      # row starts drift by one against the 32-pixel block
+)
+NAN_CASE = ((2, 9, 18), (0, 5, 8, 17))                # shape and the net element set to NaN: the last pixel of image 0
 # The seed of each (kind, operand, shape): the smallest in 0..7 for which the twin's error against the fp64 module stays within 0.95 x the eager 16-bit
 # module's on the CPU for all three outputs (seed 0 everywhere but two of the 35-pixel cases, where one output sat at 1.00-1.09 x).
 SEEDS = {(COV, "bf16", (1, 5, 7)): 1, (FLOW, "f16", (1, 5, 7)): 2}
@@ -80,6 +91,30 @@ def forward(sd, kind: int, net, inp, dt: torch.dtype, acc: torch.dtype = torch.f
         delta = rnd(conv(c1, "flow_head.2", 1))
         mask = rnd(conv(m0, "mask.2", 0))
     return h, delta, mask
+
+
+def finite_scale(t) -> float:
+    """max |t| over the finite elements of t (0 when there are none)."""
+    f = t[torch.isfinite(t)]
+    return float(f.abs().max()) if f.numel() else 0.0
+
+
+def twin_outputs(sd, kind: int, net, inp, dt: torch.dtype, acc: torch.dtype = torch.float32):
+    """The twin on arbitrary (sd, net, inp): its three outputs and, per output, the scale taken over the finite elements only."""
+    with torch.no_grad():
+        out = forward(sd, kind, net, inp, dt, acc)
+    return out, [finite_scale(t) for t in out]
+
+
+@functools.lru_cache(maxsize=None)
+def nan_case(kind: int, dtname: str):
+    """The seeded (2, 9, 18) case with one NaN in net at the last pixel of image 0: (net, twin outputs, finite scales)."""
+    shape, at = NAN_CASE
+    c = case(kind, dtname, shape)
+    net = c.net.clone()
+    net[at] = float("nan")
+    out, scale = twin_outputs(c.sd, kind, net, c.inp, c.dt)
+    return net, out, scale
 
 
 def rel_err(got, ref) -> float:
