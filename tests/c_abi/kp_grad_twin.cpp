@@ -87,9 +87,9 @@ extern "C" int kp_grad_twin(const float* image, int H, int W, int mask_width, in
 
 #ifdef KP_GRAD_TWIN_MAIN
 #include <stdio.h>
-int main() {
-    // odd sizes: ragged tiles in both directions, more than one tile each way; values are multiples of 1 / 256
-    const int H = 37, W = 131;
+// one image of H x W (values are multiples of 1 / 256) through every window size with no border, a border of 4 and one of m_all >= min(H, W) / 2;
+// 0: consistent, the candidates added to *total and the last threshold left in *thr
+static int check_shape(int H, int W, int m_all, int* total, float* thr) {
     std::vector<float> img((size_t)3 * H * W), grad((size_t)H * W);
     uint32_t s = 12345u;
     for (auto& v : img) {
@@ -100,16 +100,34 @@ int main() {
     int32_t count[2];
     float stats[3];
     double sums[2];
-    int total = 0;
+    if (2 * m_all < H && 2 * m_all < W) return 5;
     for (int nms : {0, 1, 3, 15})
-        for (int m : {0, 4, 20}) {
+        for (int m : {0, 4, m_all}) {
             if (kp_grad_twin(img.data(), H, W, m, nms, 1.f, grad.data(), cand.data(), count, stats, sums) != 0) return 1;
             if (count[0] < 0 || count[0] > count[1] || count[1] > H * W) return 2;
-            if ((m == 0 || m == 20) && count[0] != 0) return 3;
-            total += count[0];
+            if ((m == 0 || m == m_all) && count[0] != 0) return 3;
+            if (m == 4 && nms == 0 && (count[0] == 0 || count[0] != count[1])) return 6;
+            for (int i = 0; i < count[0]; ++i)
+                if (cand[i] < 0 || cand[i] >= H * W || (i && cand[i] <= cand[i - 1])) return 7;   // row-major, ascending, inside the image
+            *total += count[0];
         }
     if (kp_grad_twin(img.data(), H, W, 4, 2, 1.f, grad.data(), cand.data(), count, stats, sums) != -1) return 4;
-    printf("kp_grad_twin OK %d %.6f\n", total, (double)stats[2]);
+    *thr = stats[2];
+    return 0;
+}
+
+int main() {
+    // 37 x 131: odd sizes, ragged tiles in both directions, more than one tile each way.  130 x 513: more than 1024 candidate words (two per compaction
+    // thread, a row's last word of one pixel).  3841 x 65: 482 tiles, more than one chunk of the kernels' tile sum, a last tile row of one pixel.
+    int total = 0;
+    float thr = 0.f, thr_first = 0.f;
+    const int shapes[3][3] = {{37, 131, 20}, {130, 513, 65}, {3841, 65, 33}};
+    for (int i = 0; i < 3; ++i) {
+        const int rc = check_shape(shapes[i][0], shapes[i][1], shapes[i][2], &total, &thr);
+        if (rc) return 10 * (i + 1) + rc;
+        if (i == 0) thr_first = thr;
+    }
+    printf("kp_grad_twin OK %d %.6f %.6f\n", total, (double)thr_first, (double)thr);
     return 0;
 }
 #endif

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import grad_selectors_ref as GR
+from tests import grad_sizes as GS
 from tests import kp_grad_twin as TW
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -76,6 +77,37 @@ def test_twin_lists_the_restatements_candidates(H, W):
     assert np.array_equal(tw.cand, want.numpy().astype(np.int32)) and want.numel() > 0
     g = GR.image_grad(blk)[0].flatten()[want]
     assert g.unique().numel() < want.numel(), "the block-constant image has tied maxima, and all of them are kept"
+
+
+@pytest.mark.parametrize("seed", [3, 5, 7])
+@pytest.mark.parametrize("H,W", list(GS.TABLE))
+def test_twin_lists_the_restatements_candidates_at_the_path_sizes(H, W, seed):
+    """The sizes of tests/grad_sizes.py (past one compaction pass, past one tile-sum chunk, below one tile): the twin is pinned to the restatement there
+    before tests/test_gpu_grad_selectors_sizes.py compares the kernels with it."""
+    GS.check_path(H, W)
+    img = GR.quantised_image(H, W, seed)
+    want_grad = GR.image_grad(img)[0].numpy().view(np.int32)
+    for m in ((8, 1) if (H, W) in GS.TINY else (GS.mask_width_for(H, W),)):
+        for gs in (1.0, 2.0, 3.0):
+            if H * W > 1:           # (1 x 1: n - 1 = 0, the threshold is NaN on both sides and there is nothing to guard)
+                dist = GR.guard_distance(img, gs)
+                assert dist > GUARD, (H, W, seed, gs, dist)
+                thr64 = GR.threshold_f64(img, gs)[1]
+            n_above = GR.candidates(img, m, gs).numel()
+            for nms in (None, 3, 15):
+                want = GR.candidates(img, m, gs, nms).numpy().astype(np.int32)
+                tw = TW.select(img, m, gs, nms)
+                assert np.array_equal(tw.cand, want), (H, W, seed, m, gs, nms)
+                assert tw.n_above == n_above
+                assert np.array_equal(tw.grad.view(np.int32), want_grad)
+                if H * W > 1:
+                    assert abs(float(tw.stats[2]) - thr64) <= 4.8e-7
+                else:
+                    assert np.isfinite(tw.stats[0]) and np.isnan(tw.stats[1:]).all() and torch.isnan(GR.threshold(GR.image_grad(img), gs)).all()
+                if (H, W) in GS.TINY and (m == 8 or H < 3):
+                    assert want.size == 0 and tw.n_above == 0
+            if (H, W) in GS.LARGE:
+                assert n_above > 0
 
 
 def test_twin_standalone_under_sanitizers():
@@ -154,6 +186,9 @@ def test_entry_points_refuse_bad_arguments_on_the_host():
                dict(grad_std=float("nan")), dict(nms_size=2), dict(nms_size=8), dict(nms_size=-1), dict(ws=P + 4)):
         assert grad(**kw) == INVALID, kw
     assert grad(nms_size=17) == UNSUPPORTED and grad(nms_size=16) == INVALID
+    # sizes past the launch's limits: more tile rows than grid y takes, and v * W + u past an int32
+    assert grad(H=16 * 65535 + 1, W=1) == INVALID and grad(H=65536, W=32768) == INVALID and grad(H=32768, W=65536, lanes=1) == INVALID
+    assert grad(H=16 * 65535, W=1) == WORKSPACE and grad(H=65536, W=32767) == WORKSPACE      # the last sizes inside: refused for the workspace alone
     assert grad(ws_bytes=need * 2 - 1) == WORKSPACE and grad(ws_bytes=need, lanes=2) == WORKSPACE
 
     def fin(state=P, cand=P, stride=4800, count=P, count_stride=4, lanes=2, k=100, cap=100, W=100, out=P, nsel=P):
