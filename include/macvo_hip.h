@@ -1434,6 +1434,31 @@ size_t mv_update_block_workspace_bytes(int kind, int B, int H, int W);
 int mv_update_block_forward(int kind, int operand, const void* packed, const void* net, const void* inp, int B, int H, int W, int channels_last,
                             void* net_out, void* delta, void* mask, void* workspace, mvStream_t stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The decoder's motion encoder in 16-bit operands, one call per decoder iteration (csrc/motion_encoder.hip, csrc/motion_encoder_math.h):
+ * GMAUpdateBlock.encoder as called at covhead.py:106,
+ *   out = cat([relu(conv(cat([relu(convc2(relu(convc1(corr)))), relu(convf2(relu(convf1(flow))))]))), flow])
+ * with convc1 145 -> 256 (1x1), convc2 256 -> 192 (3x3), convf1 2 -> 128 (7x7), convf2 128 -> 64 (3x3), conv 256 -> 126 (3x3).
+ * operand: MV_F16 or MV_BF16 - the type of flow, corr, out and the MFMA operands; accumulation, bias and ReLU are fp32, a value is rounded once where
+ * it is stored; flow reaches channels 126..127 of out bit for bit.  Not bit-equal to the eager 16-bit module, which rounds after every operator.
+ *
+ * mv_motion_encoder_tensor_count / _tensor_info: the module's 10 tensors in state_dict() order ("convc1.weight", ..., "conv.bias"); name_buf holds at
+ *   least 64 bytes, shape[ndim..3] = 0.
+ * mv_motion_encoder_pack: device.  tensors[i] (host array of DEVICE pointers) = tensor i, contiguous fp32; packed = mv_motion_encoder_packed_bytes(operand)
+ *   bytes, 16-byte aligned: per launch the weights in MFMA fragment order, rounded to the operand type, and the fp32 biases.  Pack once.
+ * mv_motion_encoder_forward: flow [B,2,H,W], corr [B,145,H,W] (NCHW-contiguous, or both channels-last memory when channels_last = 1) ->
+ *   out [B,128,H,W], NCHW-contiguous.  B, H, W >= 1, B * H * W <= 2^20.  workspace: mv_motion_encoder_workspace_bytes(B, H, W) bytes (1 920 per pixel; 0
+ *   for sizes out of range), 16-byte aligned, contents irrelevant.  6 launches on `stream`; no atomics, host synchronisation or allocation; two calls
+ *   and both layouts give the same bits; NaN propagates as in torch (ReLU keeps it).
+ * Arguments are checked before anything touches the device: MV_ERR_INVALID_ARG for a null pointer, an unknown operand, a size out of range. */
+int mv_motion_encoder_tensor_count(void);
+int mv_motion_encoder_tensor_info(int i, char* name_buf, int32_t* shape /* [4] */, int32_t* ndim);
+size_t mv_motion_encoder_packed_bytes(int operand);
+int mv_motion_encoder_pack(int operand, const float* const* tensors /* host [10] of device pointers */, void* packed, mvStream_t stream);
+size_t mv_motion_encoder_workspace_bytes(int B, int H, int W);
+int mv_motion_encoder_forward(int operand, const void* packed, const void* flow, const void* corr, int B, int H, int W, int channels_last, void* out,
+                              void* workspace, mvStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

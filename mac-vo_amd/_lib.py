@@ -365,6 +365,14 @@ SIGNATURES = {
     "mv_update_block_pack": (C.c_int, [C.c_int, C.c_int, C.POINTER(_P), _P, _P]),
     "mv_update_block_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mv_update_block_forward": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    # the decoder's motion encoder (operand MV_F16 / MV_BF16): tensor table, device packer (operand, tensors, packed, stream), forward (operand, packed, flow,
+    # corr, B, H, W, channels_last, out, workspace, stream)
+    "mv_motion_encoder_tensor_count": (C.c_int, []),
+    "mv_motion_encoder_tensor_info": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mv_motion_encoder_packed_bytes": (C.c_size_t, [C.c_int]),
+    "mv_motion_encoder_pack": (C.c_int, [C.c_int, C.POINTER(_P), _P, _P]),
+    "mv_motion_encoder_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mv_motion_encoder_forward": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
 }
 
 _lib = None

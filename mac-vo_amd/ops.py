@@ -1280,6 +1280,88 @@ def update_block(net: torch.Tensor, inp: torch.Tensor, weights: UpdateBlockWeigh
     return net_out, delta, mask
 
 
+# ---------------------------------------------------------------------------------------------- the decoder's motion encoder
+def motion_encoder_tensor_table() -> "list[tuple[str, tuple[int, ...]]]":
+    """(state-dict key, shape) of the motion encoder's 10 tensors in the module's order (``convc1.weight`` ... ``conv.bias``), as the library lists them."""
+    lib = L.load()
+    table = []
+    name, shape, ndim = C.create_string_buffer(64), (C.c_int32 * 4)(), C.c_int32()
+    for i in range(lib.mv_motion_encoder_tensor_count()):
+        L.check(lib.mv_motion_encoder_tensor_info(i, name, shape, C.byref(ndim)), "mv_motion_encoder_tensor_info")
+        table.append((name.value.decode(), tuple(shape[d] for d in range(ndim.value))))
+    return table
+
+
+class MotionEncoderWeights:
+    """The weights of the FlowFormerCov decoder's motion encoder (``GMAUpdateBlock.encoder``), packed once into the fragment order of
+    ``mv_motion_encoder_forward`` (16-bit weights in ``operand``, fp32 biases holding 16-bit values; ``convc1`` and ``convf1`` zero-padded to whole
+    64-channel chunks).  ``operand``: ``"bf16"`` / ``"f16"``; None: bf16 for bf16 tensors, f16 for fp16 and fp32 ones.  A missing or mis-shaped tensor is
+    named in the error, before anything touches the device."""
+
+    def __init__(self, state_dict, operand: str | None = None, device=None):
+        lib = L.load()
+        tensors = []
+        for key, shape in motion_encoder_tensor_table():
+            if key not in state_dict:
+                raise L.MacvoHipError(f"MotionEncoderWeights: the state dict has no tensor '{key}'")
+            t = state_dict[key]
+            if tuple(t.shape) != shape:
+                raise L.MacvoHipError(f"MotionEncoderWeights: tensor '{key}' has shape {tuple(t.shape)}, expected {shape}")
+            tensors.append(t)
+        if operand is None:
+            operand = "bf16" if tensors[0].dtype == torch.bfloat16 else "f16"
+        if operand not in _UPDATE_OPERANDS:
+            raise L.MacvoHipError(f"MotionEncoderWeights: operand must be 'f16' or 'bf16', got {operand!r}")
+        self.operand = operand
+        self.operand_type, self.dtype = _UPDATE_OPERANDS[operand]
+        device = torch.device(device) if device is not None else tensors[0].device
+        ts = [_req(t.detach().to(device, torch.float32), torch.float32, "motion-encoder weight") for t in tensors]
+        with torch.cuda.device(device):
+            self.packed = torch.empty(int(lib.mv_motion_encoder_packed_bytes(self.operand_type)), dtype=torch.uint8, device=device)
+            ptrs = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+            L.check(lib.mv_motion_encoder_pack(self.operand_type, ptrs, self.packed.data_ptr(), _stream()), "mv_motion_encoder_pack")
+        self._keep = ts          # (the pack kernels read them on the stream)
+
+    @classmethod
+    def from_module(cls, encoder, operand: str | None = None, device=None) -> "MotionEncoderWeights":
+        """``encoder``: the ``MotionEncoder`` module, or any state dict that holds its ten tensors; other entries are ignored."""
+        sd = encoder if isinstance(encoder, dict) else encoder.state_dict()
+        return cls(sd, operand, device)
+
+
+def motion_encoder(flow: torch.Tensor, corr: torch.Tensor, weights: MotionEncoderWeights, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """``MotionEncoder.forward(flow, corr)`` (covhead.py:106): ``flow [B,2,H,W]``, ``corr [B,145,H,W]`` in ``weights.dtype`` (``corr`` NCHW or
+    channels-last, read as it lies; ``flow`` is brought to ``corr``'s layout when it has the other one, a copy of two channels) -> ``[B,128,H,W]``, NCHW-contiguous, in that dtype: channels 0..125 the features, 126..127 ``flow`` bit for bit.  fp32 accumulation, one
+    rounding per stored tensor; allocates the output and — unless ``workspace`` (uint8, at least ``mv_motion_encoder_workspace_bytes``; its contents do
+    not matter) is handed in — a workspace from torch's caching allocator, copies nothing from the host, does not synchronise."""
+    lib = L.load()
+    for t, c, name in ((flow, 2, "flow"), (corr, 145, "corr")):
+        if not t.is_cuda or t.dtype != weights.dtype or t.dim() != 4 or t.shape[1] != c:
+            raise L.MacvoHipError(f"motion_encoder: {name} must be a [B,{c},H,W] {weights.dtype} GPU tensor (got {tuple(t.shape)} {t.dtype} on {t.device})")
+    if flow.shape[0] != corr.shape[0] or flow.shape[2:] != corr.shape[2:] or flow.device != weights.packed.device or corr.device != flow.device:
+        raise L.MacvoHipError(f"motion_encoder: flow {tuple(flow.shape)} on {flow.device} and corr {tuple(corr.shape)} on {corr.device} do not belong together")
+    B, _, H, W = flow.shape
+    nws = lib.mv_motion_encoder_workspace_bytes(B, H, W)
+    if nws == 0:
+        raise L.MacvoHipError(f"motion_encoder: B x H x W = {B} x {H} x {W} is out of range (1 <= B * H * W <= 2^20)")
+    cl = torch.channels_last
+    # corr decides the layout and is read where it lies (a copy only when it is neither NCHW-contiguous nor channels-last); the two-channel flow follows it
+    channels_last = corr.is_contiguous(memory_format=cl) and not corr.is_contiguous()
+    if channels_last:
+        flow = flow.contiguous(memory_format=cl)
+    else:
+        flow, corr = flow.contiguous(), corr.contiguous()
+    if workspace is None:
+        workspace = torch.empty((nws,), dtype=torch.uint8, device=flow.device)
+    elif workspace.dtype != torch.uint8 or workspace.device != flow.device or not workspace.is_contiguous() or workspace.numel() < nws or workspace.data_ptr() % 16:
+        raise L.MacvoHipError(f"motion_encoder: workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {nws} bytes on {flow.device}")
+    out = torch.empty((B, 128, H, W), dtype=weights.dtype, device=flow.device)
+    with torch.cuda.device(flow.device):
+        L.check(lib.mv_motion_encoder_forward(weights.operand_type, weights.packed.data_ptr(), flow.data_ptr(), corr.data_ptr(), B, H, W, int(channels_last),
+                                              out.data_ptr(), workspace.data_ptr(), _stream()), "mv_motion_encoder_forward")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- frontend evaluation
 @dataclass
 class EvalResult:

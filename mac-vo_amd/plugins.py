@@ -1068,8 +1068,65 @@ class _FusedUpdateBlock:
         return type(self.holder.mask).forward(self.holder.mask, x)
 
 
+class _FusedMotionEncoder:
+    """The decoder's motion encoder (``memory_decoder.update_block.encoder``, covhead.py:106) through ``ops.motion_encoder`` (``mv_motion_encoder_forward``).
+
+    * The module stays in place (only its ``forward`` attribute is rebound): ``state_dict`` keys, ``.to()`` and ``load_state_dict`` keep working, and the
+      packed weights are rebuilt whenever a parameter's storage, dtype or version counter changes.
+    * Numerics policy as ``_FusedUpdateBlock``: the kernels run in the decoder's own 16-bit type with fp32 accumulation and round once per stored tensor.
+      An fp32 decoder, inputs whose dtype is not the parameters', CPU tensors, a correlation input that does not have 145 channels, other shapes,
+      anything that could require a gradient and anything the library refuses fall through to the original layers."""
+
+    def __init__(self, encoder):
+        self.encoder = encoder
+        self._packed: dict = {}                        # operand -> (key, MotionEncoderWeights)
+        self.fused_calls = 0
+
+    def shapes_ok(self) -> bool:
+        sd = self.encoder.state_dict()
+        return all(k in sd and tuple(sd[k].shape) == s for k, s in ops.motion_encoder_tensor_table())
+
+    def repack(self, operand: str):
+        def version(p):
+            try:
+                return p._version
+            except RuntimeError:        # inference tensors carry no version counter (and cannot be updated in place)
+                return -1
+        key = tuple((p.data_ptr(), version(p), p.dtype) for p in self.encoder.parameters())
+        hit = self._packed.get(operand)
+        if hit is None or hit[0] != key:
+            hit = (key, ops.MotionEncoderWeights(self.encoder.state_dict(), operand))
+            self._packed[operand] = hit
+        return hit[1]
+
+    def fused(self, flow, corr):
+        """The [B,128,H,W] block from the kernels, or None when the call has to run the original layers."""
+        if not (isinstance(flow, torch.Tensor) and isinstance(corr, torch.Tensor)):
+            return None
+        operand = {torch.bfloat16: "bf16", torch.float16: "f16"}.get(flow.dtype)
+        if operand is None or not (flow.is_cuda and corr.is_cuda) or corr.dtype != flow.dtype or flow.dim() != 4 or corr.dim() != 4:
+            return None
+        if flow.shape[1] != 2 or corr.shape[1] != 145 or flow.shape[0] != corr.shape[0] or flow.shape[2:] != corr.shape[2:]:
+            return None
+        params = list(self.encoder.parameters())
+        if any(p.dtype != flow.dtype or p.device != flow.device for p in params) or corr.device != flow.device:
+            return None
+        if torch.is_grad_enabled() and (flow.requires_grad or corr.requires_grad or any(p.requires_grad for p in params)):
+            return None
+        try:
+            out = ops.motion_encoder(flow, corr, self.repack(operand))
+        except ops.L.MacvoHipError:                      # anything the kernels refuse falls through to the layers
+            return None
+        self.fused_calls += 1
+        return out
+
+    def forward(self, flow, corr):
+        out = self.fused(flow, corr)
+        return out if out is not None else type(self.encoder).forward(self.encoder, flow, corr)
+
+
 def install_flowformer_hooks(model, volume_precision: str | None = None, fuse_patch_embed: bool | None = None,
-                             fuse_update_blocks: bool | None = None) -> list[str]:
+                             fuse_update_blocks: bool | None = None, fuse_motion_encoder: bool | None = None) -> list[str]:
     """Route the three frontend kernels of ``FlowFormerCov`` through the HIP library by rebinding bound methods on the model
     instance — signatures and result layouts are those of the methods they replace, the network's own code is untouched:
 
@@ -1093,6 +1150,11 @@ def install_flowformer_hooks(model, volume_precision: str | None = None, fuse_pa
       blocks, once each per decoder iteration (covhead.py:112-117) -> ``ops.update_block`` (``_FusedUpdateBlock``).  Opt-in: ``fuse_update_blocks``
       None = the environment variable ``MACVO_HIP_UPDATE_BLOCK`` (``1`` / ``on`` / ``true``; default off), True / False decide here.  Only 16-bit
       decoders take the kernels (an fp32 decoder keeps its layers, bit for bit); a block whose tensors do not have the published shapes is left alone.
+
+    * ``memory_decoder.update_block.encoder`` — the motion encoder, once per decoder iteration (covhead.py:106) -> ``ops.motion_encoder``
+      (``_FusedMotionEncoder``).  Opt-in: ``fuse_motion_encoder`` None = the environment variable ``MACVO_HIP_MOTION_ENCODER`` (``1`` / ``on`` / ``true``;
+      default off), True / False decide here.  Same policy: 16-bit decoders only, an encoder whose tensors do not have the published shapes (a
+      correlation input that is not 145 channels wide) is left alone.
 
     Every attribute that exists is rebound (the FlowFormer submodule is absent from some checkouts, and a stand-in model may
     carry only part of them); the names of the rebound methods are returned so that a caller can insist on all three."""
@@ -1167,6 +1229,15 @@ def install_flowformer_hooks(model, volume_precision: str | None = None, fuse_pa
             if fused.shapes_ok():
                 ub.gru.forward, ub.flow_head.forward, ub.mask.forward = fused.gru_forward, fused.flow_head_forward, fused.mask_forward
                 done += [f"memory_decoder.update_block.{n}" for n in ("gru", "flow_head", "mask")]
+    if fuse_motion_encoder is None:
+        fuse_motion_encoder = os.environ.get("MACVO_HIP_MOTION_ENCODER", "0").lower() in ("1", "on", "true")
+    if fuse_motion_encoder and dec is not None:
+        menc = getattr(getattr(dec, "update_block", None), "encoder", None)
+        if isinstance(menc, torch.nn.Module):
+            fused = _FusedMotionEncoder(menc)
+            if fused.shapes_ok():
+                menc.forward = fused.forward           # an instance attribute shadows the class's forward: the module and its keys stay where they were
+                done.append("memory_decoder.update_block.encoder")
     if not done:
         raise ops.L.MacvoHipError("install_flowformer_hooks: the model has none of memory_decoder.encode_flow_token / "
                                   "upsample_flow / memory_encoder.corr")

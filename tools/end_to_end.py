@@ -7,7 +7,8 @@
     released checkpoint are absent from the reference checkout), behind ``HIP_FlowFormerCovFrontend(config.model = ...)``;
   * ``--variant hooked``: ``plugins.install_flowformer_hooks`` routes the all-pairs volume, the 12 window lookups, the 24 convex upsamplings
     and the cost patch embedding of that network through the HIP library; ``--variant hooked_update``: also the two recurrent update blocks of the
-    decoder (``fuse_update_blocks=True``: 24 fused calls per pair batch); ``--variant unhooked``: the same network as plain PyTorch ops
+    decoder (``fuse_update_blocks=True``: 24 fused calls per pair batch); ``--variant hooked_update_motion``: also the decoder's motion encoder
+    (``fuse_motion_encoder=True``: 12 more fused calls); ``--variant unhooked``: the same network as plain PyTorch ops
     (einsum / grid_sample / softmax-unfold / MIOpen convolutions) — the "before";
   * selector, covariance model and pose-graph solve = the ``HIP_*`` plugins; map, motion model, keyframes, filters, writers = the reference's code.
 
@@ -87,7 +88,8 @@ def run_variant(ref, refrun, variant: str, args) -> dict:
     host = fh.FlowFormerCovHost(fh.demo_cfg(decoder_depth=args.decoder_depth), DT[args.enc], DT[args.dec]).to(dev).eval()
     if args.channels_last:      # NHWC weights (and, through them, activations): MIOpen's bf16 / fp16 convolutions run in NHWC and otherwise transpose around every call
         host = host.to(memory_format=torch.channels_last)
-    hooks = plugins.install_flowformer_hooks(host, fuse_update_blocks=variant == "hooked_update") if variant in ("hooked", "hooked_update") else []
+    hooked = ("hooked", "hooked_update", "hooked_update_motion")
+    hooks = plugins.install_flowformer_hooks(host, fuse_update_blocks=variant in hooked[1:], fuse_motion_encoder=variant == hooked[2]) if variant in hooked else []
     out = {"hooks": hooks, "network_ms_per_pair_batch": round(network_ms(host, args.height, args.width), 3)}
 
     cam, maps, poses = refrun.synthetic_maps(args.frames)
@@ -176,6 +178,9 @@ def main():
     if "fps" in res.get("hooked", {}) and "fps" in res.get("hooked_update", {}):
         res["hooked_update_over_hooked"] = round(res["hooked_update"]["fps"] / res["hooked"]["fps"], 3)
         res["hooked_update_over_hooked_median"] = round(res["hooked_update"]["fps_median"] / res["hooked"]["fps_median"], 3)
+    if "fps" in res.get("hooked_update", {}) and "fps" in res.get("hooked_update_motion", {}):
+        res["hooked_update_motion_over_hooked_update"] = round(res["hooked_update_motion"]["fps"] / res["hooked_update"]["fps"], 3)
+        res["hooked_update_motion_over_hooked_update_median"] = round(res["hooked_update_motion"]["fps_median"] / res["hooked_update"]["fps_median"], 3)
     print(json.dumps({"end_to_end": res}))
 
 

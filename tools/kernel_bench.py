@@ -89,12 +89,68 @@ def update_block_case(a, dev, B, h8, w8):
             per = len(launches) + 1
             first = next(i for i, r in enumerate(rows) if "update_to_nhwc" in r["Kernel_Name"])
             calls = [rows[i:i + per] for i in range(first, len(rows) - per + 1, per)]
-            calls = [c for c in calls if "update_to_nhwc" in c[0]["Kernel_Name"] and all("update_conv" in r["Kernel_Name"] for r in c[1:])][len(calls) // 2:]
+            calls = [c for c in calls if "update_to_nhwc" in c[0]["Kernel_Name"] and all("update_conv" in r["Kernel_Name"] for r in c[1:])]
+            calls = calls[len(calls) // 2:]                    # the second half of the whole calls: past the warm-up
             print(f"per launch, mean of {len(calls)} traced calls: us, executed GFLOP, % of the 16-bit MFMA rate")
             for j, name in enumerate(["to_nhwc"] + [n for n, *_ in launches]):
                 us = statistics.mean((int(c[j]["End_Timestamp"]) - int(c[j]["Start_Timestamp"])) / 1e3 for c in calls)
                 fl = 0.0 if j == 0 else 2.0 * M * launches[j - 1][1] * launches[j - 1][2] * launches[j - 1][3]
                 print(f"  {name:24s} {us:8.1f} us {fl / 1e9:7.2f} GFLOP {fl / us / 1e6 / MFMA16_PEAK_TFLOPS * 100:6.1f}%")
+
+
+# one call of the motion encoder (csrc/motion_encoder_math.h): (launch, kh * kw of the launch, cin of the launch, rows executed, useful MACs per pixel)
+MOTION_LAUNCHES = [("convc1 1x1", 1, 192, 256, 256 * 145), ("convc2 3x3", 9, 256, 192, 192 * 9 * 256), ("convf1 as 1x1", 1, 128, 128, 128 * 98),
+                   ("convf2 3x3", 9, 128, 64, 64 * 9 * 128), ("conv 3x3", 9, 256, 128, 126 * 9 * 256)]
+
+
+def motion_encoder_case(a, dev, B, h8, w8):
+    """The HIP motion encoder against the eager PyTorch-ROCm module with the same bf16 weights and inputs, in this process: median, min and the 10th-90th
+    percentile spread of each (the update_block case's method), the useful FLOP of the module, and — with --launch-trace FILE, a rocprofv3 --kernel-trace
+    CSV of THIS case — the measured time and achieved fraction of the 16-bit MFMA rate per launch."""
+    from tests import motion_encoder_twin as T
+
+    M = B * h8 * w8
+    module = T.make_module(0).to(dev, torch.bfloat16)
+    flow, corr = (t.to(dev, torch.bfloat16) for t in T.make_inputs((B, h8, w8), 0))
+    wts = ops.MotionEncoderWeights.from_module(module, "bf16")
+    useful = sum(2.0 * M * macs for *_, macs in MOTION_LAUNCHES)
+
+    def spread(fn):
+        for _ in range(10):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(max(a.iters, 20)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3)
+        ts.sort()
+        return statistics.median(ts), ts[0], ts[len(ts) // 10], ts[len(ts) * 9 // 10]
+    with torch.inference_mode():
+        hip = spread(lambda: ops.motion_encoder(flow, corr, wts))
+        eager = spread(lambda: module(flow, corr))
+    faster = eager[0] - hip[0] > eager[3] - eager[2]
+    print(f"motion_encoder bf16 B={B} {h8}x{w8} (M = {M}, {useful / 1e9:.2f} GFLOP): HIP {hip[0]:.1f} us (min {hip[1]:.1f}, p10-p90 {hip[2]:.1f}-{hip[3]:.1f}) = "
+          f"{useful / hip[0] / 1e6 / MFMA16_PEAK_TFLOPS * 100:.1f}% of the 16-bit MFMA rate; eager {eager[0]:.1f} us (min {eager[1]:.1f}, p10-p90 "
+          f"{eager[2]:.1f}-{eager[3]:.1f}); eager / HIP = {eager[0] / hip[0]:.2f}; difference of medians {eager[0] - hip[0]:.1f} us "
+          f"{'exceeds' if faster else 'does NOT exceed'} the eager p10-p90 spread of {eager[3] - eager[2]:.1f} us")
+    if a.launch_trace:
+        import csv
+        rows = [r for r in csv.DictReader(open(a.launch_trace)) if "update_conv_kernel" in r["Kernel_Name"] or "motion_stage" in r["Kernel_Name"]]
+        rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+        per = len(MOTION_LAUNCHES) + 1
+        first = next(i for i, r in enumerate(rows) if "motion_stage" in r["Kernel_Name"])
+        calls = [rows[i:i + per] for i in range(first, len(rows) - per + 1, per)]
+        calls = [c for c in calls if "motion_stage" in c[0]["Kernel_Name"] and all("update_conv" in r["Kernel_Name"] for r in c[1:])]
+        calls = calls[len(calls) // 2:]                        # the second half of the whole calls: past the warm-up
+        print(f"per launch, mean of {len(calls)} traced calls: us, executed GFLOP, % of the 16-bit MFMA rate")
+        for j, name in enumerate(["motion_stage"] + [n for n, *_ in MOTION_LAUNCHES]):
+            us = statistics.mean((int(c[j]["End_Timestamp"]) - int(c[j]["Start_Timestamp"])) / 1e3 for c in calls)
+            fl = 0.0 if j == 0 else 2.0 * M * MOTION_LAUNCHES[j - 1][1] * MOTION_LAUNCHES[j - 1][2] * MOTION_LAUNCHES[j - 1][3]
+            print(f"  {name:24s} {us:8.1f} us {fl / 1e9:7.2f} GFLOP {fl / us / 1e6 / MFMA16_PEAK_TFLOPS * 100:6.1f}%")
 
 
 def main():
@@ -105,7 +161,7 @@ def main():
     ap.add_argument("--W", type=int, default=640)
     ap.add_argument("--B", type=int, default=2)
     ap.add_argument("--zeros", action="store_true", help="volume_split: all-zero operands (DVFS probe: same instruction stream, less switching power)")
-    ap.add_argument("--launch-trace", default="", help="update_block: a rocprofv3 --kernel-trace CSV of this case, for the per-launch table")
+    ap.add_argument("--launch-trace", default="", help="update_block, motion_encoder: a rocprofv3 --kernel-trace CSV of this case, for the per-launch table")
     ap.add_argument("--update-kinds", default="cov,flow", help="update_block: the kinds to time (a trace for --launch-trace holds one kind only)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -140,6 +196,8 @@ def main():
                       f"16-bit MFMA peak executed ({'zero' if a.zeros else 'random'} operands)")
         elif w == "update_block":
             update_block_case(a, dev, B, h8, w8)
+        elif w == "motion_encoder":
+            motion_encoder_case(a, dev, B, h8, w8)
         elif w == "patch_embed":
             # (f)2: both volumes of a frame (S = B n slices) through the fused conv stack; 2 x (36 + 16*36*... ) MAC per output, see DESIGN
             from tools.synth import patch_embed_weights

@@ -140,6 +140,10 @@ CHECKS = [
      "thread) in registers indexed by unrolled constants: no scratch, no spills, at most 256 registers (two waves per SIMD; LDS "
      "bounds the 64-pixel tile at three workgroups = three waves per SIMD, which its 140 registers allow); LDS = the staged strips, 5 x 64 pixels x 144 B = 46 080 B for the 64-pixel tile (three workgroups per CU), 23 040 B for "
      "the 32-pixel tiles, 8 448 B for the layout transpose"),
+    (r"^motion_stage_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and
+     regs(r) <= 128 and r.get("group_segment_fixed_size", 0) <= 8448,
+     "motion encoder, launch 0: the eight 16-bit values of a 16-byte store sit in registers indexed by unrolled constants (no scratch, no spills), four "
+     "waves per SIMD, LDS = the 64 x 66 transpose tile (8 448 B); its convolutions are the update blocks' kernels and fall under their budget"),
     (r"^kg_(grad|select|compact)_kernel|^kp_finish_device_kernel", lambda r: r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and
      r["sgpr_spill_count"] == 0 and regs(r) <= 64 and r.get("group_segment_fixed_size", 0) <= 20 * 1024,
      "image-gradient selectors and the device finish: the staged loads of a thread sit in registers indexed by unrolled constants (no scratch, no spills), "
